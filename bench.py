@@ -10,16 +10,25 @@ stream after its K1, rsv_set_resolve_stream: measured slower, off by default.)  
 split by index range (each rank seeks to its offset, weak scaling) and the per-rank reservoirs are
 combined with one all_gather + merge kernel inside the step.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 --gpus N > 1 without a torch.distributed environment (WORLD_SIZE unset) launches N ranks itself
 (a torch.distributed.run child process; this process never touches the GPU).  Inside a launched
 job WORLD_SIZE must equal N.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0: the headline
+(`value`, `ms_per_step`) and
   roofline      -- K1's VALU roofline (tools/roofline.py): algorithmic Philox calls per launch over
                    the fused kernel's average launch time, measured with HIP events on the
-                   sampler's stream, against the gfx950 issue peak; HBM traffic from PMC
+                   sampler's stream inside the timed steps, against the gfx950 issue peak; HBM
+                   traffic from PMC
+--dump-outputs DIR then writes the last timed step's reservoir (what result() returned to the
+caller; the keys and the seed are fixed, so it is the same from run to run) as float64 .npy files:
+reservoir.npy (the int64 keys rounded to float64) and reservoir_hi32.npy / reservoir_lo32.npy (the
+keys' upper and lower 32 bits as unsigned values, exact).
+
+--full adds the measurements that take runs of their own:
+  serial        -- the same steps one at a time (nothing in flight)
   cpu_baseline  -- the oracle's C restatement of the reference (Algorithm L / RandomValues) on the
                    host cores, median of 5 runs per leg (C2 headline leg on one core; C1, C3 on
                    all cores, C4 prefix)
@@ -323,6 +332,18 @@ def load_traffic(n: int):
     return None
 
 
+def dump_outputs(path: str, res) -> None:
+    """--dump-outputs: the last timed step's reservoir (the k int64 keys result() returned, slot
+    order) as float64 .npy files.  A 64-bit key does not fit a float64, so beside the rounded value
+    the two 32-bit halves are written, each exact, for a key-for-key comparison of two builds."""
+    os.makedirs(path, exist_ok=True)
+    keys = np.ascontiguousarray(res, dtype=np.int64)
+    bits = keys.view(np.uint64)
+    np.save(os.path.join(path, "reservoir.npy"), keys.astype(np.float64))
+    np.save(os.path.join(path, "reservoir_hi32.npy"), (bits >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(path, "reservoir_lo32.npy"), (bits & np.uint64(0xFFFFFFFF)).astype(np.float64))
+
+
 def _free_port() -> int:
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -363,13 +384,19 @@ def main() -> None:
                     help="one step at a time (no second sampler in flight) for the timed steps")
     ap.add_argument("--depth", type=int, default=int(os.environ.get("RSV_BENCH_DEPTH", "2")),
                     help="samplers in flight (each step still creates, samples, reads and closes its own)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's reservoir as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the serial figure, the secondary configs, "
+                         "the CPU baseline, and at N > 1 the C4 leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the other hot-path configs (C3 segmented, C4 distinct, C2 on java_l, C5)")
+                    help="with --full: skip the other hot-path configs (C3 segmented, C4 distinct, C2 on "
+                         "java_l, C5)")
     ap.add_argument("--c4-keys", type=int, default=500_000_000, help="C4 keys per rank (N > 1 leg)")
     ap.add_argument("--c4-steps", type=int, default=10)
     ap.add_argument("--c4-warmup", type=int, default=2)
-    ap.add_argument("--no-c4", action="store_true", help="skip the C4 leg at N > 1")
+    ap.add_argument("--no-c4", action="store_true", help="with --full: skip the C4 leg at N > 1")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -504,9 +531,11 @@ def main() -> None:
     elapsed = time.perf_counter() - t0
     _native.check(L.rsv_profile_global(0))
     k1_ms, k1_launches = profile_read()
-    # the same steps one at a time (issue -> result -> close, nothing in flight): reported beside
-    # the pipelined figure, same barrier / synchronize bracketing, not the headline
-    serial_steps = min(args.steps, 40)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
+    # --full: the same steps one at a time (issue -> result -> close, nothing in flight): reported
+    # beside the pipelined figure, same barrier / synchronize bracketing, not the headline
+    serial_steps = min(args.steps, 40) if args.full else 0
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -526,7 +555,7 @@ def main() -> None:
     assert res is not None and res.size == k
 
     c4 = None
-    if world > 1 and not args.no_c4:
+    if args.full and world > 1 and not args.no_c4:
         del keys
         torch.cuda.empty_cache()
         c4 = c4_leg(args, rank, world, dev, backend)
@@ -572,15 +601,17 @@ def main() -> None:
             "ranks_seen": dist.get_world_size() if world > 1 else 1,
             "steps_in_flight": depth,
             "resolve_stream": rstream is not None,
-            "serial": {"steps": serial_steps, "ms_per_step": round(elapsed_serial / serial_steps * 1e3, 4),
-                       "value": round(n * world * serial_steps / elapsed_serial / 1e9, 3),
-                       "what": "the same step run one at a time (result read and sampler closed before the "
-                               "next is created): the host turnaround between steps idles the GPU"},
         }
+        if args.full:
+            line["serial"] = {
+                "steps": serial_steps, "ms_per_step": round(elapsed_serial / serial_steps * 1e3, 4),
+                "value": round(n * world * serial_steps / elapsed_serial / 1e9, 3),
+                "what": "the same step run one at a time (result read and sampler closed before the "
+                        "next is created): the host turnaround between steps idles the GPU"}
         if c4 is not None:
             line["c4"] = c4
         c4_host = None
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             del keys
             torch.cuda.empty_cache()
             line["secondary"] = secondary(dev)
@@ -588,7 +619,7 @@ def main() -> None:
                 line["secondary"] += c5_legs()
             except Exception as ex:  # noqa: BLE001 -- reported, not raised
                 line["secondary"].append({"config": "C5", "error": f"{type(ex).__name__}: {ex}"})
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             import workloads
 
             c4 = workloads.c4_data(500_000_000, dev)

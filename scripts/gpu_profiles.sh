@@ -18,7 +18,7 @@ step() {  # name, limit, command...
     echo "$name rc=$rc"
     [ $rc -eq 0 ] || { tail -20 "$O/$name.log"; exit $rc; }
 }
-step bench 400 python bench.py
+step bench 400 python bench.py --full
 tail -1 "$O/bench.log" > "$O/bench.json"
 step k1_trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/k1" -o k1 -- \
     python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary

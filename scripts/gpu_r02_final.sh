@@ -11,7 +11,7 @@ D=gpurun_out/$OUT
 exec scripts/gpu_run.sh $OUT \
   pytest 700 python3 -u -m pytest tests -m gpu -q -rfE -x --timeout 300 --timeout-method thread :: \
   smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" :: \
-  bench 500 python3 bench.py --steps 50 --warmup 5 :: \
+  bench 500 python3 bench.py --full --steps 50 --warmup 5 :: \
   k1_trace 200 $P --kernel-trace --stats -d $D/k1 -o k1 -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary :: \
   k1_pmc_sq 120 $P --pmc $SQ --kernel-trace -d $D/k1_sq -o pmc -- $B :: \
   k1_pmc_fetch 120 $P --pmc FETCH_SIZE --kernel-trace -d $D/k1_fetch -o pmc -- $B :: \

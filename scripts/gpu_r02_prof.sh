@@ -9,7 +9,7 @@ B="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary"
 D=gpurun_out/$OUT
 exec scripts/gpu_run.sh $OUT \
   valu_pmc 90 $P --pmc $SQ --kernel-trace -d $D/valu_pmc -o pmc -- tools/micro_valu :: \
-  bench 500 python3 bench.py --steps 50 --warmup 5 :: \
+  bench 500 python3 bench.py --full --steps 50 --warmup 5 :: \
   k1_trace 200 $P --kernel-trace --stats -d $D/k1 -o k1 -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary :: \
   k1_pmc_sq 120 $P --pmc $SQ --kernel-trace -d $D/k1_sq -o pmc -- $B :: \
   k1_pmc_fetch 120 $P --pmc FETCH_SIZE --kernel-trace -d $D/k1_fetch -o pmc -- $B :: \

@@ -8,4 +8,4 @@ exec scripts/gpu_run.sh $OUT \
   k2r 300 tools/micro_k2 r :: \
   c3 200 python3 tools/bench_paths.py --only c3 :: \
   rehearse 500 env RSV_BENCH_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node=2 \
-      --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 2 --c4-steps 2 --no-cpu-baseline
+      --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 20 --warmup 2 --c4-steps 2 --no-cpu-baseline

@@ -22,6 +22,6 @@ done
 for f in $O/ab_*.json; do python3 -c "
 import json,sys; d=json.loads(open('$f').read().strip().split('\n')[-1]); r=d['roofline']
 print('$f', d['value'], d['ms_per_step'], r['launch_avg_us'], r['frac'], r.get('launches_timed'))"; done
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 cut -c1-600 $O/bench.json
 echo done

@@ -10,8 +10,8 @@ D=gpurun_out/$OUT
 exec scripts/gpu_run.sh $OUT \
   suite 700 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread :: \
   smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" :: \
-  bench20 300 python3 bench.py --steps 20 --warmup 5 :: \
-  bench 600 python3 bench.py :: \
+  bench20 300 python3 bench.py --full --steps 20 --warmup 5 :: \
+  bench 600 python3 bench.py --full :: \
   k1_trace 200 $P --kernel-trace --stats -d $D/k1 -o k1 -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-secondary :: \
   k1_pmc_sq 120 $P --pmc $SQ --kernel-trace -d $D/k1_sq -o pmc -- $B :: \
   k1_pmc_fetch 120 $P --pmc FETCH_SIZE --kernel-trace -d $D/k1_fetch -o pmc -- $B :: \

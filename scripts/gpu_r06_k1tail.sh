@@ -22,6 +22,6 @@ timeout -k 10 200 $P -d $O/wu -o wu -- python3 tools/bench_paths.py --only c4wu 
 python3 tools/trace_window.py $O/wu/wu_kernel_trace.csv wide_hash_all 1 > $O/wu_timeline.txt || exit $?
 find $O -name "*_kernel_trace.csv" -delete
 grep -h '^{' $O/w_*.log | cut -c1-250
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 cut -c1-400 $O/bench.json
 echo done

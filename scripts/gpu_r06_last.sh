@@ -9,8 +9,8 @@ timeout -k 10 700 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeou
 tail -2 $O/suite.log
 timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench20.json 2> $O/bench20.err || { tail $O/bench20.err; exit 1; }
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench20.json 2> $O/bench20.err || { tail $O/bench20.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 for f in $O/bench20.json $O/bench.json; do python3 -c "
 import json; d=json.loads(open('$f').read().strip().split('\n')[-1]); r=d['roofline']
 print('$f', d['steps'], d['value'], d['ms_per_step'], r['launch_avg_us'], r['frac'], r['launches_timed'])"; done
