@@ -280,3 +280,64 @@ JNIEXPORT void JNICALL JNI_FN(abortIndexed)(JNIEnv* env, jobject self, jlong s) 
     rsv_status st = rsv_jvm_abort_indexed(session(s));
     if (st != RSV_OK) throw_status(env, st);
 }
+
+/* ObjectDistinct (any B): the hash-only candidate pass over the first n hashes of `hashes`
+ * (hash(map(x)) per element); returns the candidate count.  The hashes are copied out with
+ * GetLongArrayRegion: no array stays pinned while the engine works. */
+JNIEXPORT jint JNICALL JNI_FN(distinctCandidates)(JNIEnv* env, jobject self, jlong s, jlongArray hashes, jint n) {
+    (void)self;
+    if (n < 0 || !hashes) {
+        throw_status(env, n < 0 ? RSV_E_ILLEGAL_ARGUMENT : RSV_E_NULL_POINTER);
+        return 0;
+    }
+    jlong* buf = (jlong*)malloc((size_t)(n > 0 ? n : 1) * sizeof(jlong));
+    if (!buf) {
+        throw_status(env, RSV_E_OUT_OF_MEMORY);
+        return 0;
+    }
+    (*env)->GetLongArrayRegion(env, hashes, 0, n, buf);
+    if ((*env)->ExceptionCheck(env)) { /* bounds: nothing was sent */
+        free(buf);
+        return 0;
+    }
+    int64_t c = 0;
+    rsv_status st = rsv_jvm_distinct_candidates(session(s), (const int64_t*)buf, n, &c);
+    free(buf);
+    if (st != RSV_OK) throw_status(env, st);
+    return (jint)c;
+}
+
+/* the pending batch's c candidates into offsets / scrambled (each of length >= c) */
+JNIEXPORT void JNICALL JNI_FN(candidatesRead)(JNIEnv* env, jobject self, jlong s, jlongArray offsets,
+                                              jlongArray scrambled, jint c) {
+    (void)self;
+    if (c < 0 || (*env)->GetArrayLength(env, offsets) < c || (*env)->GetArrayLength(env, scrambled) < c) {
+        throw_status(env, RSV_E_ILLEGAL_ARGUMENT);
+        return;
+    }
+    jlong* buf = (jlong*)malloc((size_t)(c > 0 ? c : 1) * 2 * sizeof(jlong));
+    if (!buf) {
+        throw_status(env, RSV_E_OUT_OF_MEMORY);
+        return;
+    }
+    rsv_status st = rsv_jvm_candidates_read(session(s), (int64_t*)buf, (int64_t*)buf + (c > 0 ? c : 1), c);
+    if (st == RSV_OK) {
+        (*env)->SetLongArrayRegion(env, offsets, 0, c, buf);
+        (*env)->SetLongArrayRegion(env, scrambled, 0, c, buf + (c > 0 ? c : 1));
+    }
+    free(buf);
+    if (st != RSV_OK) throw_status(env, st);
+}
+
+JNIEXPORT void JNICALL JNI_FN(candidatesCommit)(JNIEnv* env, jobject self, jlong s, jint set_size, jlong max_hash) {
+    (void)self;
+    rsv_status st = rsv_jvm_candidates_commit(session(s), set_size, max_hash);
+    if (st != RSV_OK) throw_status(env, st);
+}
+
+/* drop the pending batch (a failure between the candidate pass and its commit; the JVM rethrows) */
+JNIEXPORT void JNICALL JNI_FN(candidatesAbort)(JNIEnv* env, jobject self, jlong s) {
+    (void)self;
+    rsv_status st = rsv_jvm_candidates_abort(session(s));
+    if (st != RSV_OK) throw_status(env, st);
+}

@@ -145,6 +145,30 @@ rsv_status rsv_jvm_commit_indexed(rsv_jvm* s) {
     return rsv_commit_indexed(s->h);
 }
 
+rsv_status rsv_jvm_distinct_candidates(rsv_jvm* s, const int64_t* hashes, int64_t n, int64_t* n_cand) {
+    g_local_error = 0;
+    if (!s->open) return closed();
+    return rsv_distinct_candidates(s->h, hashes, n, RSV_MEM_HOST, n_cand);
+}
+
+rsv_status rsv_jvm_candidates_read(rsv_jvm* s, int64_t* offsets, int64_t* hashes, int64_t cap) {
+    g_local_error = 0;
+    if (!s->open) return closed();
+    return rsv_candidates_read(s->h, offsets, hashes, cap);
+}
+
+rsv_status rsv_jvm_candidates_commit(rsv_jvm* s, int64_t set_size, int64_t max_hash) {
+    g_local_error = 0;
+    if (!s->open) return closed();
+    return rsv_candidates_commit(s->h, set_size, max_hash);
+}
+
+rsv_status rsv_jvm_candidates_abort(rsv_jvm* s) {
+    g_local_error = 0;
+    if (!s->open) return closed();
+    return rsv_candidates_abort(s->h);
+}
+
 rsv_status rsv_jvm_result(rsv_jvm* s, void* out, int64_t cap, int64_t* out_n) {
     g_local_error = 0;
     if (!s->open) return closed();

@@ -60,6 +60,14 @@ rsv_status rsv_jvm_abort_indexed(rsv_jvm* s);
 /* a `Sampler[A, B]` for any other B (ObjectSampler.scala): accept the pending index-only batch
  * without keys -- the binding keeps the B values in its own slot array (rsv_commit_indexed) */
 rsv_status rsv_jvm_commit_indexed(rsv_jvm* s);
+/* a `Sampler.distinct[A, B]` for any other B (ObjectDistinct.scala): the hash-only candidate pass over
+ * n host hashes (rsv_distinct_candidates), its candidates, and the batch's commit (the binding's
+ * replica: set size and maxHash) or abort.  The binding destroys the session itself (rsv_jvm_destroy):
+ * the set lives on the JVM, so rsv_jvm_result is not used on such a session. */
+rsv_status rsv_jvm_distinct_candidates(rsv_jvm* s, const int64_t* hashes, int64_t n, int64_t* n_cand);
+rsv_status rsv_jvm_candidates_read(rsv_jvm* s, int64_t* offsets, int64_t* hashes, int64_t cap);
+rsv_status rsv_jvm_candidates_commit(rsv_jvm* s, int64_t set_size, int64_t max_hash);
+rsv_status rsv_jvm_candidates_abort(rsv_jvm* s);
 /* Sampler.result (S:59-60): writes min(count, k) keys; a single-use sampler closes (S:345-350) */
 rsv_status rsv_jvm_result(rsv_jvm* s, void* out, int64_t cap, int64_t* out_n);
 /* zero-copy form for a producer that writes keys itself (keys-only samplers): the free tail of

@@ -31,6 +31,7 @@ private[reservoir] object Abi {
   final val HashPrecomputed = 4 // any other JVM `hash`: evaluated per element here, shipped beside the key
   // rsv_distinct_order
   final val OrderAuto = 0
+  final val MemHost = 0 // rsv_mem: the hashes of rsv_distinct_candidates live in host memory
 
   val ClosedMessage = "use of sampler after calling `result()`" // Sampler.scala:186
 

@@ -20,6 +20,10 @@ private[reservoir] trait SamplerFactory {
   /** Sampler.apply for a `B` with no fixed-width key: index-only batches, the elements kept on the
     * JVM ([[ObjectSampler]]) */
   def makeObjects[A, B: ClassTag](k: Int, reusable: Boolean, engine: Int, seed: Long)(map: A => B): Sampler[A, B]
+
+  /** Sampler.distinct for a `B` with no fixed-width key: the engine filters by hash alone, the
+    * elements, the heap and the set stay on the JVM ([[ObjectDistinct]]) */
+  def makeObjectDistinct[A, B: ClassTag](k: Int, reusable: Boolean, seed: Long)(map: A => B, hash: B => Long): Sampler[A, B]
 }
 
 private[reservoir] object JniFactory extends SamplerFactory {
@@ -30,6 +34,9 @@ private[reservoir] object JniFactory extends SamplerFactory {
 
   def makeObjects[A, B: ClassTag](k: Int, reusable: Boolean, engine: Int, seed: Long)(map: A => B): Sampler[A, B] =
     new ObjectSampler[A, B](k, reusable, new JniIndexOps(k, reusable, engine, seed))(map)
+
+  def makeObjectDistinct[A, B: ClassTag](k: Int, reusable: Boolean, seed: Long)(map: A => B, hash: B => Long): Sampler[A, B] =
+    new ObjectDistinct[A, B](k, reusable, new JniCandidateOps(k, reusable, seed))(map, hash)
 }
 
 /** Backend selection behind the unchanged factories `Sampler.apply` / `Sampler.distinct`
@@ -38,7 +45,8 @@ private[reservoir] object JniFactory extends SamplerFactory {
   *   -Dreservoir.backend=gpu        use the MI355X engine: Sampler.apply for every B (Long, Int and
   *                                  java.util.UUID keys live on the GPU; any other B is sampled by
   *                                  index and its elements stay on the JVM, ObjectSampler);
-  *                                  Sampler.distinct for B = Long, Int or UUID (else the JVM classes)
+  *                                  Sampler.distinct likewise: any other B is filtered on the GPU by
+  *                                  hash alone and replayed on the JVM (ObjectDistinct)
   *   -Dreservoir.binding=ffm|jni    default: FFM when the JDK is 22+ and the reservoir-gpu-ffm jar is
   *                                  on the class path, JNI otherwise
   *   -Dreservoir.engine=java_l      the reference's Algorithm L over java.util.Random, bit-identical
@@ -93,17 +101,21 @@ private[reservoir] object Backend {
       }
 
   /** Sampler.distinct: the default `hashCode` and the identity hash run on the GPU; any other `hash`
-    * is evaluated here per element and shipped beside the key (RSV_HASH_PRECOMPUTED). */
+    * is evaluated here per element and shipped beside the key (RSV_HASH_PRECOMPUTED).  A `B` without
+    * a fixed-width key ships its hashes only (ObjectDistinct). */
   def distinct[A, B: ClassTag](maxSampleSize: Int, reusable: Boolean)(map: A => B, hash: B => Long)(
       defaultHash: Any => Long
   ): Option[Sampler[A, B]] =
     if (!enabled) None
     else
-      KeyKind.of[B].map { kk =>
-        val hashKind =
-          if (hash eq defaultHash) Abi.HashDefault
-          else if (kk == KeyKind.LongKey && (hash eq Hashes.identity)) Abi.HashIdentity
-          else Abi.HashPrecomputed
-        make[A, B](Abi.KindDistinct, maxSampleSize, reusable, kk, hashKind)(map, hash)
+      KeyKind.of[B] match {
+        case Some(kk) =>
+          val hashKind =
+            if (hash eq defaultHash) Abi.HashDefault
+            else if (kk == KeyKind.LongKey && (hash eq Hashes.identity)) Abi.HashIdentity
+            else Abi.HashPrecomputed
+          Some(make[A, B](Abi.KindDistinct, maxSampleSize, reusable, kk, hashKind)(map, hash))
+        case None => // any other B: candidates by hash on the GPU, RandomValues replayed over them here
+          Some(factory.makeObjectDistinct[A, B](maxSampleSize, reusable, seeds.nextLong())(map, hash))
       }
 }

@@ -47,6 +47,11 @@ private[reservoir] object Jni {
   @native def fillWords(session: Long, words: Array[Long]): Unit
   @native def abortIndexed(session: Long): Unit
   @native def commitIndexed(session: Long): Unit
+  // ObjectDistinct (any B): the hash-only candidate pass
+  @native def distinctCandidates(session: Long, hashes: Array[Long], n: Int): Int
+  @native def candidatesRead(session: Long, offsets: Array[Long], scrambled: Array[Long], c: Int): Unit
+  @native def candidatesCommit(session: Long, setSize: Int, maxHash: Long): Unit
+  @native def candidatesAbort(session: Long): Unit
 }
 
 /** One native session (a malloc'd rsv_jvm, reservoir_jni.c) released exactly once: by a single-use
@@ -232,4 +237,24 @@ private[reservoir] final class JniIndexOps(k: Int, reusable: Boolean, engine: In
   def commitIndexed(): Unit                              = { Jni.commitIndexed(session.get); fence = 1 }
   def abortIndexed(): Unit                               = { Jni.abortIndexed(session.get); fence = 1 }
   def release(): Unit                                    = session.release()
+}
+
+/** [[CandidateOps]] over JNI: a DISTINCT session with precomputed hashes that turns index-only at its
+  * first batch (rsv_distinct_candidates); the B values, the heap and the set live in the
+  * [[ObjectDistinct]]. */
+private[reservoir] final class JniCandidateOps(k: Int, reusable: Boolean, seed: Long) extends CandidateOps {
+  private[this] val session =
+    new JniSession(Jni.create(Abi.KindDistinct, k, 8, reusable, Abi.EnginePhiloxR, Abi.HashPrecomputed, Abi.OrderAuto, seed, 0L, -1))
+  JniCleaner.register(this, session)
+  @volatile private[this] var fence = 0 // keeps `this` reachable across each native call (JniSampler)
+
+  def candidates(hashes: Array[Long], n: Int): Int = {
+    val c = Jni.distinctCandidates(session.get, hashes, n); fence = 1; c
+  }
+  def read(offsets: Array[Long], scrambled: Array[Long], c: Int): Unit = {
+    Jni.candidatesRead(session.get, offsets, scrambled, c); fence = 1
+  }
+  def commit(setSize: Int, maxHash: Long): Unit = { Jni.candidatesCommit(session.get, setSize, maxHash); fence = 1 }
+  def abort(): Unit                             = { Jni.candidatesAbort(session.get); fence = 1 }
+  def release(): Unit                           = session.release()
 }

@@ -12,7 +12,7 @@ import scala.collection.immutable.ArraySeq
 import scala.reflect.ClassTag
 
 import lgbt.princess.reservoir.Sampler
-import lgbt.princess.reservoir.gpu.{Abi, IndexOps, KeyKind, ObjectSampler, SamplerFactory}
+import lgbt.princess.reservoir.gpu.{Abi, CandidateOps, IndexOps, KeyKind, ObjectDistinct, ObjectSampler, SamplerFactory}
 
 /** Panama FFM downcall handles of libreservoir_hip.so (JDK 22+, run with --enable-native-access).
   * Names carry an `rsv` prefix so nothing here shadows a Sampler member (e.g. `isOpen`). */
@@ -53,6 +53,13 @@ private[reservoir] object Native {
   val rsvFillSlots: MethodHandle = downcall("rsv_fill_slots", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS))
   val rsvAbortIndexed: MethodHandle = downcall("rsv_abort_indexed", FunctionDescriptor.of(JAVA_INT, ADDRESS))
   val rsvCommitIndexed: MethodHandle = downcall("rsv_commit_indexed", FunctionDescriptor.of(JAVA_INT, ADDRESS))
+  val rsvDistinctCandidates: MethodHandle =
+    downcall("rsv_distinct_candidates", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, JAVA_INT, ADDRESS))
+  val rsvCandidatesRead: MethodHandle =
+    downcall("rsv_candidates_read", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_LONG))
+  val rsvCandidatesCommit: MethodHandle =
+    downcall("rsv_candidates_commit", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_LONG, JAVA_LONG))
+  val rsvCandidatesAbort: MethodHandle = downcall("rsv_candidates_abort", FunctionDescriptor.of(JAVA_INT, ADDRESS))
 
   val cleaner: Cleaner = Cleaner.create()
 
@@ -238,6 +245,9 @@ private[reservoir] final class FfmFactory extends SamplerFactory {
 
   def makeObjects[A, B: ClassTag](k: Int, reusable: Boolean, engine: Int, seed: Long)(map: A => B): Sampler[A, B] =
     new ObjectSampler[A, B](k, reusable, new FfmIndexOps(k, reusable, engine, seed))(map)
+
+  def makeObjectDistinct[A, B: ClassTag](k: Int, reusable: Boolean, seed: Long)(map: A => B, hash: B => Long): Sampler[A, B] =
+    new ObjectDistinct[A, B](k, reusable, new FfmCandidateOps(k, reusable, seed))(map, hash)
 }
 
 /** [[IndexOps]] over the FFM downcalls: an ELEMENTS handle (8-byte key width, never used for keys)
@@ -273,4 +283,57 @@ private[reservoir] final class FfmIndexOps(k: Int, reusable: Boolean, engine: In
   def commitIndexed(): Unit = check(rsvCommitIndexed.invoke(handle).asInstanceOf[Int])
   def abortIndexed(): Unit  = check(rsvAbortIndexed.invoke(handle).asInstanceOf[Int])
   def release(): Unit       = cleanable.clean()
+}
+
+/** [[CandidateOps]] over the FFM downcalls: a DISTINCT handle with precomputed hashes (8-byte key
+  * width, never used for keys) that turns index-only at its first rsv_distinct_candidates; the B
+  * values, the heap and the set live in the [[ObjectDistinct]].  Hashes go down and candidates come
+  * back through native buffers of this arena (the engine stages host hashes through pinned memory). */
+private[reservoir] final class FfmCandidateOps(k: Int, reusable: Boolean, seed: Long) extends CandidateOps {
+  import Native._
+
+  private[this] val arena = Arena.ofShared()
+  private[this] val handle: MemorySegment = {
+    val cfg = arena.allocate(Config)
+    check(rsvConfigInit.invoke(cfg).asInstanceOf[Int])
+    cfg.set(JAVA_INT, 4L, Abi.KindDistinct)
+    cfg.set(JAVA_INT, 8L, k)
+    cfg.set(JAVA_INT, 16L, if (reusable) 1 else 0)
+    cfg.set(JAVA_INT, 28L, Abi.HashPrecomputed)
+    cfg.set(JAVA_LONG, 40L, seed)
+    val out = arena.allocate(ADDRESS)
+    check(rsvCreate.invoke(cfg, out).asInstanceOf[Int])
+    out.get(ADDRESS, 0L)
+  }
+  private[this] val nCand = arena.allocate(JAVA_LONG)
+  private[this] val bufArena = Arena.ofAuto() // the hash and candidate buffers, regrown on demand (GC-managed)
+  private[this] var hashBuf  = bufArena.allocate(8L * 65536, 8L)
+  private[this] var candBuf  = bufArena.allocate(16L * 1024, 8L) // offsets, then scrambled hashes
+  private[this] var candCap  = 1024L
+  private[this] val cleanable = {
+    val h = handle
+    val a = arena
+    cleaner.register(this, () => { rsvDestroy.invoke(h); a.close() })
+  }
+
+  def candidates(hashes: Array[Long], n: Int): Int = {
+    if (hashBuf.byteSize() < 8L * n) hashBuf = bufArena.allocate(8L * n, 8L)
+    MemorySegment.copy(hashes, 0, hashBuf, JAVA_LONG, 0L, n)
+    check(rsvDistinctCandidates.invoke(handle, hashBuf, n.toLong, Abi.MemHost, nCand).asInstanceOf[Int])
+    nCand.get(JAVA_LONG, 0L).toInt
+  }
+  def read(offsets: Array[Long], scrambled: Array[Long], c: Int): Unit = {
+    if (candCap < c) {
+      candCap = math.max(2 * candCap, c.toLong)
+      candBuf = bufArena.allocate(16L * candCap, 8L)
+    }
+    val hs = candBuf.asSlice(8L * candCap)
+    check(rsvCandidatesRead.invoke(handle, candBuf, hs, candCap).asInstanceOf[Int])
+    MemorySegment.copy(candBuf, JAVA_LONG, 0L, offsets, 0, c)
+    MemorySegment.copy(hs, JAVA_LONG, 0L, scrambled, 0, c)
+  }
+  def commit(setSize: Int, maxHash: Long): Unit =
+    check(rsvCandidatesCommit.invoke(handle, setSize.toLong, maxHash).asInstanceOf[Int])
+  def abort(): Unit = check(rsvCandidatesAbort.invoke(handle).asInstanceOf[Int])
+  def release(): Unit = cleanable.clean()
 }

@@ -174,6 +174,43 @@ rsv_status rsv_abort_indexed(rsv_sampler* s);
  * ELEMENTS samplers; RSV_E_ILLEGAL_STATE without a pending rsv_sample_indexed. */
 rsv_status rsv_commit_indexed(rsv_sampler* s);
 
+/* Sampler.distinct for ANY B (S:171-180; RandomValues S:383-412) WITHOUT the elements: the hash-only
+ * candidate pass.  RandomValues.sample needs the element itself only for `elements.contains` (S:398,
+ * S:403); the admission test `elemHash < maxHash` (S:403) needs only the hash.  The caller passes
+ * hash(map(x)) of the next n elements, 8 B each, and keeps the reference's heap and Set[B] itself; the
+ * engine returns the batch offsets the reference could still admit -- a superset of its admissions,
+ * in arrival order, with their scrambled hashes (S:396) -- and the caller replays RandomValues.sample
+ * over those elements only.  The engine never sees a B: it bounds maxHash by the k-th smallest
+ * DISTINCT scrambled hash seen so far (k distinct hashes mean k distinct elements, so the reference's
+ * set is full and its maxHash is no larger; DESIGN.md has the proof) and by the caller's own maxHash
+ * as of the last commit.  Every repeat of a current member comes back as a candidate (its hash is
+ * under the bound; the caller's `contains` rejects it), and while fewer than k distinct hash values
+ * were seen and the caller's set is not full every element is a candidate: then the cost is the
+ * reference's plus a copy.
+ * A DISTINCT handle with RSV_HASH_PRECOMPUTED (key_width is ignored; another hash kind returns
+ * RSV_E_UNSUPPORTED).  The first call on a handle that has sampled nothing makes it index-only, as
+ * rsv_commit_indexed does: keyed calls, rsv_result*, rsv_export_*, rsv_merge_*, rsv_get_distinct_info
+ * and the log calls then return RSV_E_ILLEGAL_STATE; on a handle that already holds keys this call
+ * returns RSV_E_ILLEGAL_STATE.  mem says where `hashes` live (host hashes travel through pinned
+ * staging); n == 0 is a valid empty batch; *n_cand receives the candidate count.  The call returns
+ * with its device work done, on a caller stream too.  Until rsv_candidates_commit or
+ * rsv_candidates_abort every call but those two, rsv_candidates_read, rsv_is_open, rsv_count and
+ * rsv_destroy returns RSV_E_ILLEGAL_STATE.  Multi-GPU merging of such samplers is not provided. */
+rsv_status rsv_distinct_candidates(rsv_sampler* s, const int64_t* hashes, int64_t n, int32_t mem, int64_t* n_cand);
+/* The pending batch's candidates into host buffers of cap entries: offsets strictly ascending in
+ * [0, n), the scrambled hash of each beside it (the elemHash of S:396).  The same for any order the
+ * device found them in.  RSV_E_ILLEGAL_ARGUMENT when cap is below the count; may be repeated. */
+rsv_status rsv_candidates_read(rsv_sampler* s, int64_t* offsets_host, int64_t* hashes_host, int64_t cap);
+/* Accept the pending batch: rsv_count grows by its n.  set_size and max_hash are the caller's
+ * replica after replaying the candidates (samples.size and maxHash, S:389-392): with set_size == k
+ * the next batch is filtered against min(the engine's bound, max_hash), which keeps a hash with
+ * fewer than k distinct values efficient across batches; max_hash is not read otherwise. */
+rsv_status rsv_candidates_commit(rsv_sampler* s, int64_t set_size, int64_t max_hash);
+/* Drop the pending batch (the caller's `map` or `hash` threw): count, the engine's hash shadow and
+ * its bound are as before the batch, and the next batch's candidates are what they would have been
+ * without it.  A binding then rethrows, as the reference's sample propagates it (S:394-395). */
+rsv_status rsv_candidates_abort(rsv_sampler* s);
+
 /* Sampler.result() (S:59-60; resultImpl S:318-331; RandomValues.result S:411).  Writes
  * min(count, k) keys (ELEMENTS: slot order, which is part of the reference result) or the distinct
  * set (DISTINCT: ascending scrambled hash; the reference's order is HashSet order) into host
@@ -213,7 +250,8 @@ rsv_status rsv_set_resolve_stream(rsv_sampler* s, void* hip_stream);
 rsv_status rsv_synchronize(rsv_sampler* s);
 
 /* Kernel timing: while enabled, HIP events bracket every launch of the handle's hot kernel (K1
- * for PHILOX_R, the event replay K1' for JAVA_L, the K3 filter for DISTINCT) on its stream.
+ * for PHILOX_R, the event replay K1' for JAVA_L, the K3 filter for DISTINCT, the hash-only filter
+ * of rsv_distinct_candidates) on its stream.
  * rsv_profile_read synchronizes and returns the summed kernel time and the launch count. */
 rsv_status rsv_profile_enable(rsv_sampler* s, int32_t on);
 rsv_status rsv_profile_read(rsv_sampler* s, double* total_ms, int64_t* launches);

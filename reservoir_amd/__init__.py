@@ -13,11 +13,13 @@ from ._native import (  # noqa: F401
     NullPointerException,
     ReservoirError,
 )
+from .object_distinct import ObjectDistinct  # noqa: F401
 from .sampler import GpuSampler, Sampler, identity  # noqa: F401
+from .values import RandomValues  # noqa: F401
 from .stream import AbruptStageTerminationException, Sample  # noqa: F401
 
 __all__ = [
-    "Sampler", "GpuSampler", "Sample", "identity", "IllegalArgumentException",
+    "Sampler", "GpuSampler", "ObjectDistinct", "RandomValues", "Sample", "identity", "IllegalArgumentException",
     "IllegalStateException", "NullPointerException", "ReservoirError",
     "AbruptStageTerminationException",
 ]

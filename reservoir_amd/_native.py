@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "rsv_merge_packed", "rsv_profile_global", "rsv_profile_global_read", "rsv_stage_acquire",
     "rsv_stage_commit", "rsv_get_distinct_info", "rsv_export_log", "rsv_merge_log",
     "rsv_sample_indexed", "rsv_fill_slots", "rsv_abort_indexed", "rsv_retain_log", "rsv_commit_indexed",
+    "rsv_distinct_candidates", "rsv_candidates_read", "rsv_candidates_commit", "rsv_candidates_abort",
 )
 
 
@@ -144,6 +145,10 @@ def load():
     L.rsv_abort_indexed.argtypes = [vp]
     L.rsv_commit_indexed.argtypes = [vp]
     L.rsv_retain_log.argtypes = [vp, i32]
+    L.rsv_distinct_candidates.argtypes = [vp, vp, i64, i32, C.POINTER(i64)]
+    L.rsv_candidates_read.argtypes = [vp, vp, vp, i64]
+    L.rsv_candidates_commit.argtypes = [vp, i64, i64]
+    L.rsv_candidates_abort.argtypes = [vp]
     for name in ("rsv_config_init", "rsv_create", "rsv_sample", "rsv_sample_batch", "rsv_result",
                  "rsv_result_device", "rsv_result_take", "rsv_set_stream", "rsv_set_resolve_stream",
                  "rsv_synchronize", "rsv_seek",
@@ -152,7 +157,8 @@ def load():
                  "rsv_merge_packed", "rsv_profile_global", "rsv_profile_global_read", "rsv_stage_acquire",
                  "rsv_stage_commit", "rsv_get_distinct_info", "rsv_export_log", "rsv_merge_log",
                  "rsv_sample_indexed", "rsv_fill_slots", "rsv_abort_indexed", "rsv_retain_log",
-                 "rsv_commit_indexed"):
+                 "rsv_commit_indexed", "rsv_distinct_candidates", "rsv_candidates_read",
+                 "rsv_candidates_commit", "rsv_candidates_abort"):
         getattr(L, name).restype = i32
     if L.rsv_abi_version() != 1:
         raise ImportError("libreservoir_hip.so ABI version mismatch")

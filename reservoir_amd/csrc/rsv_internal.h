@@ -229,4 +229,21 @@ int wide_log_export(WideDistinct* d, int64_t bound, int64_t* out_h, void* out_k,
                     hipStream_t st);
 int wide_log_merge(WideDistinct* d, const int64_t* h, const void* keys, int64_t n, int64_t seen, hipStream_t st);
 
+// ---- distinct for any B: the hash-only candidate pass (rsv_objects.hip) ---------------------------
+// The engine sees scrambled-hash inputs only; the caller keeps the elements and replays RandomValues
+// over the returned candidates.  hashes: device (on_device) or host memory; seen = the elements
+// before the batch.  Every call completes its device work before it returns.
+struct ObjDistinct;
+ObjDistinct* obj_create(int32_t k, int64_t r0, int64_t r1, int* status);
+void obj_destroy(ObjDistinct* d);
+void obj_set_timer(ObjDistinct* d, KernelTimer* t);  // brackets obj_filter
+int obj_candidates(ObjDistinct* d, const int64_t* hashes, int64_t n, bool on_device, int64_t seen, hipStream_t st,
+                   int64_t* n_cand);
+int64_t obj_pending_candidates(const ObjDistinct* d);
+// the pending batch's candidates (offsets ascending, scrambled hashes) into host buffers
+int obj_read(ObjDistinct* d, int64_t* offsets_host, int64_t* hashes_host, hipStream_t st);
+// accept the pending batch (the caller's replica: its size and largest hash) / drop it
+void obj_commit(ObjDistinct* d, int64_t set_size, int64_t max_hash);
+void obj_abort(ObjDistinct* d);
+
 }  // namespace rsv

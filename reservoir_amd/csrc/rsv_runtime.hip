@@ -149,6 +149,11 @@ struct rsv_sampler {
     // DISTINCT
     DistinctState* distinct = nullptr;
     int hash_kind = kHashIdentity;
+    // distinct for any B (rsv_distinct_candidates): the hash-only candidate pass; the caller keeps the
+    // elements (keys_external) and owes a commit or abort while cand_pending
+    ObjDistinct* obj = nullptr;
+    bool cand_pending = false;
+    int64_t cand_batch = 0;  // the pending batch's element count
     // host staging: per-element calls and host batches
     // per-element sample(): two pinned staging buffers; a full one is flushed asynchronously
     // (H2D + kernels, no host wait) while the other fills; an event says when it is free again
@@ -277,6 +282,16 @@ rsv_status check_open(const rsv_sampler* s) {  // SingleUse.checkOpen, Sampler.s
     if (!s) return fail(RSV_E_NULL_POINTER, "sampler is NULL");
     if (!s->open) return fail(RSV_E_ILLEGAL_STATE, "use of sampler after calling `result()`");
     if (s->keys_owed) return fail(RSV_E_ILLEGAL_STATE, "rsv_fill_slots is pending after rsv_sample_indexed");
+    if (s->cand_pending)
+        return fail(RSV_E_ILLEGAL_STATE, "a candidate batch is pending: rsv_candidates_commit or rsv_candidates_abort");
+    return RSV_OK;
+}
+
+// the calls that skip check_open: none of them while a candidate batch is pending
+rsv_status check_no_batch(const rsv_sampler* s) {
+    if (!s) return fail(RSV_E_NULL_POINTER, "sampler is NULL");
+    if (s->cand_pending)
+        return fail(RSV_E_ILLEGAL_STATE, "a candidate batch is pending: rsv_candidates_commit or rsv_candidates_abort");
     return RSV_OK;
 }
 
@@ -284,7 +299,8 @@ rsv_status check_open(const rsv_sampler* s) {  // SingleUse.checkOpen, Sampler.s
 rsv_status check_keyed(const rsv_sampler* s) {
     if (rsv_status st = check_open(s)) return st;
     if (s->keys_external)
-        return fail(RSV_E_ILLEGAL_STATE, "the slots hold no keys (rsv_commit_indexed): index-only batches only");
+        return fail(RSV_E_ILLEGAL_STATE, s->obj ? "the handle holds no keys (rsv_distinct_candidates): hash-only batches only"
+                                                : "the slots hold no keys (rsv_commit_indexed): index-only batches only");
     return RSV_OK;
 }
 
@@ -783,6 +799,7 @@ void free_all(rsv_sampler* s) {
     if (s->side_fork) pool_release_event(s->device, s->side_fork, hipEventDisableTiming);
     if (s->side_join) pool_release_event(s->device, s->side_join, hipEventDisableTiming);
     if (s->distinct) distinct_destroy(s->distinct);
+    if (s->obj) obj_destroy(s->obj);
     if (s->stream && s->own_stream) pool_release_stream(s->device, s->stream);
 }
 
@@ -1084,6 +1101,67 @@ rsv_status rsv_commit_indexed(rsv_sampler* s) {
     return RSV_OK;
 }
 
+rsv_status rsv_distinct_candidates(rsv_sampler* s, const int64_t* hashes, int64_t n, int32_t mem, int64_t* n_cand) {
+    if (rsv_status st = check_open(s)) return st;
+    if (s->cfg.kind != RSV_KIND_DISTINCT)
+        return fail(RSV_E_UNSUPPORTED, "rsv_distinct_candidates needs a DISTINCT sampler");
+    if (s->cfg.hash_kind != RSV_HASH_PRECOMPUTED)
+        return fail(RSV_E_UNSUPPORTED, "rsv_distinct_candidates needs RSV_HASH_PRECOMPUTED (the caller's hash of each element)");
+    if (n < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative batch size");
+    if (!n_cand) return fail(RSV_E_NULL_POINTER, "n_cand is NULL");
+    if (n > 0 && !hashes) return fail(RSV_E_NULL_POINTER, "hashes is NULL");
+    if (mem != RSV_MEM_HOST && mem != RSV_MEM_DEVICE)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "mem must be RSV_MEM_HOST or RSV_MEM_DEVICE");
+    DeviceGuard g(s->device);
+    if (!s->obj) {
+        // the first hash-only batch of a handle that has sampled nothing makes it index-only
+        if (s->count + s->stage_n > 0)
+            return fail(RSV_E_ILLEGAL_STATE, "rsv_distinct_candidates on a sampler that holds keys");
+        JavaRandom r;  // RandomValues r0, r1 (Sampler.scala:385-388), as rsv_create draws them
+        r.init((int64_t)s->cfg.seed);
+        const int64_t r0 = r.next_long(), r1 = r.next_long();
+        int st = RSV_OK;
+        s->obj = obj_create((int32_t)s->k, r0, r1, &st);
+        if (!s->obj) return (rsv_status)st;
+        obj_set_timer(s->obj, &s->timer);
+        s->keys_external = true;
+    }
+    touch(s);
+    if (int rc = obj_candidates(s->obj, hashes, n, mem == RSV_MEM_DEVICE, s->count, s->stream, n_cand)) return (rsv_status)rc;
+    s->ops_done = s->ops;  // obj_candidates returns with the stream drained
+    s->cand_pending = true;
+    s->cand_batch = n;
+    return RSV_OK;
+}
+
+rsv_status rsv_candidates_read(rsv_sampler* s, int64_t* offsets_host, int64_t* hashes_host, int64_t cap) {
+    if (!s) return fail(RSV_E_NULL_POINTER, "sampler is NULL");
+    if (!s->cand_pending) return fail(RSV_E_ILLEGAL_STATE, "rsv_candidates_read without a pending rsv_distinct_candidates");
+    const int64_t c = obj_pending_candidates(s->obj);
+    if (cap < c) return fail(RSV_E_ILLEGAL_ARGUMENT, "cap is below the batch's candidate count");
+    if (c > 0 && (!offsets_host || !hashes_host)) return fail(RSV_E_NULL_POINTER, "offsets_host/hashes_host is NULL");
+    DeviceGuard g(s->device);
+    return (rsv_status)obj_read(s->obj, offsets_host, hashes_host, s->stream);
+}
+
+rsv_status rsv_candidates_commit(rsv_sampler* s, int64_t set_size, int64_t max_hash) {
+    if (!s) return fail(RSV_E_NULL_POINTER, "sampler is NULL");
+    if (!s->cand_pending) return fail(RSV_E_ILLEGAL_STATE, "rsv_candidates_commit without a pending rsv_distinct_candidates");
+    if (set_size < 0 || set_size > (int64_t)s->k) return fail(RSV_E_ILLEGAL_ARGUMENT, "set_size must be in [0, k]");
+    obj_commit(s->obj, set_size, max_hash);
+    s->count += s->cand_batch;
+    s->cand_pending = false;
+    return RSV_OK;
+}
+
+rsv_status rsv_candidates_abort(rsv_sampler* s) {
+    if (!s) return fail(RSV_E_NULL_POINTER, "sampler is NULL");
+    if (!s->cand_pending) return fail(RSV_E_ILLEGAL_STATE, "rsv_candidates_abort without a pending rsv_distinct_candidates");
+    obj_abort(s->obj);
+    s->cand_pending = false;
+    return RSV_OK;
+}
+
 // Wait until a publication kernel has stored `gen` in the result flag (spin_flag)
 static rsv_status wait_flag(rsv_sampler* s, uint32_t gen) { return spin_flag(s, s->result_flag, gen, "result publish"); }
 
@@ -1211,7 +1289,7 @@ int32_t rsv_is_open(const rsv_sampler* s) { return s && s->open ? 1 : 0; }
 int64_t rsv_count(const rsv_sampler* s) { return s ? s->count + s->stage_n : 0; }
 
 rsv_status rsv_set_stream(rsv_sampler* s, void* hip_stream) {
-    if (!s) return fail(RSV_E_NULL_POINTER, "sampler is NULL");
+    if (rsv_status st = check_no_batch(s)) return st;
     DeviceGuard g(s->device);
     if (s->side_pending) {  // the hand-over covers the forked resolve too
         join_side(s);
@@ -1235,7 +1313,7 @@ rsv_status rsv_set_stream(rsv_sampler* s, void* hip_stream) {
 void* rsv_get_stream(const rsv_sampler* s) { return s ? (void*)s->stream : nullptr; }
 
 rsv_status rsv_set_resolve_stream(rsv_sampler* s, void* hip_stream) {
-    if (!s) return fail(RSV_E_NULL_POINTER, "sampler is NULL");
+    if (rsv_status st = check_no_batch(s)) return st;
     if (s->cfg.kind != RSV_KIND_ELEMENTS) return fail(RSV_E_UNSUPPORTED, "rsv_set_resolve_stream: ELEMENTS samplers only");
     DeviceGuard g(s->device);
     if (s->side_pending) {
@@ -1247,20 +1325,21 @@ rsv_status rsv_set_resolve_stream(rsv_sampler* s, void* hip_stream) {
 }
 
 rsv_status rsv_synchronize(rsv_sampler* s) {
-    if (!s) return fail(RSV_E_NULL_POINTER, "sampler is NULL");
+    if (rsv_status st = check_no_batch(s)) return st;
     DeviceGuard g(s->device);
     RSV_HIP_TRY(sync_stream(s));
     return RSV_OK;
 }
 
 rsv_status rsv_profile_enable(rsv_sampler* s, int32_t on) {
-    if (!s) return fail(RSV_E_NULL_POINTER, "sampler is NULL");
+    if (rsv_status st = check_no_batch(s)) return st;
     s->timer.on = on != 0;
     return RSV_OK;
 }
 
 rsv_status rsv_profile_read(rsv_sampler* s, double* total_ms, int64_t* launches) {
     if (!s || !total_ms || !launches) return fail(RSV_E_NULL_POINTER, "NULL argument");
+    if (rsv_status st = check_no_batch(s)) return st;
     DeviceGuard g(s->device);
     RSV_HIP_TRY(s->timer.drain());
     *total_ms = s->timer.total_ms;
@@ -1380,6 +1459,8 @@ rsv_status rsv_merge_state(rsv_sampler* s, const int64_t* idx_dev, const void* k
 static rsv_status check_distinct(rsv_sampler* s, const char* what) {
     if (rsv_status st = check_open(s)) return st;
     if (s->cfg.kind != RSV_KIND_DISTINCT) return fail(RSV_E_UNSUPPORTED, std::string(what) + " needs a DISTINCT sampler");
+    if (s->obj)  // the set lives with the caller
+        return fail(RSV_E_ILLEGAL_STATE, std::string(what) + ": the handle holds no keys (rsv_distinct_candidates)");
     return RSV_OK;
 }
 

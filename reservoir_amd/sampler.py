@@ -17,7 +17,8 @@ called more than ``maxSampleSize`` times, Sampler.scala:115-116); the extracted 
 to the GPU in batches.  Keys already resident in HBM (a torch CUDA tensor) are sampled in place.
 
 Extensions (keyword-only, defaulted so reference-style calls are unchanged):
-    key_type  "long" (B = Long, 8-byte keys, default), "int" (B = Int, 4-byte keys), or "bytesN"
+    key_type  "long" (B = Long, 8-byte keys, default), "int" (B = Int, 4-byte keys), "object" (any B:
+              the elements stay on the host, see ObjectSampler / object_distinct.py), or "bytesN"
               (fixed-width byte keys with value equality, N a multiple of 8 in 16..256, e.g.
               "bytes16" for java.util.UUID laid out [mostSigBits | leastSigBits] as little-endian
               Longs; numpy arrays of shape (n, N) uint8 or dtype "VN", torch CUDA uint8 tensors of
@@ -646,6 +647,7 @@ def Sampler(max_sample_size: int, pre_allocate: bool = False, reusable: bool = F
 
 
 _DEFAULT_HASH = object()
+builtins_hash = hash  # the counterpart of B#hashCode for a Python object
 
 
 def _resolve_hash(hash):
@@ -669,11 +671,24 @@ def distinct(max_sample_size: int, reusable: bool = False, **ext):
 
     ``hash`` defaults to ``B#hashCode().toLong`` (Sampler.scala:75); pass ``"identity"`` for the
     bijective Long identity hash, or any callable (evaluated on the host, shipped as int64).
+    ``key_type="object"`` takes any hashable ``B`` (reservoir_amd/object_distinct.py): the elements
+    stay on the host, the engine reads their hashes only, ``hash`` defaults to the built-in ``hash``.
     """
 
     def make(map_fn: Callable = identity, hash=_DEFAULT_HASH) -> GpuSampler:
         _validate_shared(max_sample_size, map_fn)  # validateDistinctParams :90-95
         hk, hf = _resolve_hash(hash)
+        if ext.get("key_type") == "object":
+            # any B: the elements stay on the host, the engine filters by hash alone
+            from .object_distinct import ObjectDistinct
+
+            if isinstance(hash, str):
+                raise IllegalArgumentException("key_type 'object' takes a callable hash (default: the built-in hash)")
+            extra = set(ext) - {"key_type", "seed", "device"}
+            if extra:
+                raise IllegalArgumentException(f"key_type 'object' does not take {sorted(extra)}")
+            return ObjectDistinct(max_sample_size, map_fn, hf if hf is not None else builtins_hash,
+                                  reusable=reusable, seed=ext.get("seed"), device=ext.get("device"))
         return GpuSampler(N.KIND_DISTINCT, max_sample_size, map_fn, reusable=reusable,
                           hash_fn=hf, hash_kind=hk, **ext)
 
