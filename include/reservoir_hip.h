@@ -356,6 +356,27 @@ rsv_status rsv_sample_segmented(const void* keys_dev, const int64_t* offsets_dev
                                 int32_t key_width, int32_t k, uint64_t seed, uint64_t stream_base,
                                 void* out_dev, int64_t* counts_dev, void* hip_stream);
 
+/* Segmented distinct: S independent Sampler.distinct samplers (no reference counterpart; = S separate
+ * RandomValues instances, S:383-412).  Stream s covers keys_dev[offsets[s] .. offsets[s+1]) and is
+ * seeded like a single DISTINCT handle with java.util.Random(seed + stream_base + s) (wrapping to a
+ * signed 64-bit value): (r0, r1) are its first two nextLong() (S:385-388) and h = the scrambled hash
+ * (S:396) of hash(key).  The result is the engine's set order (RSV_DISTINCT_SET): the min(k, D_s)
+ * distinct keys with the smallest (h, key) -- the key compared as a signed 64-bit value, 4-byte keys
+ * sign-extended -- written ascending by (h, key) into out_keys_dev[s*k ..] (and their h into
+ * out_hashes_dev when not NULL), counts_dev[s] = min(k, D_s), slots beyond it zero.  That is the
+ * reference's set whenever no two distinct keys share the final maximum hash (always under an
+ * injective hash), whatever the arrival order.  The reference's arrival-order tie replay
+ * (RSV_DISTINCT_ORDERED) is not provided here: such callers keep separate handles.
+ * hash_kind: IDENTITY, JAVA_LONG, JAVA_INT, DEFAULT (JAVA_INT for key_width 4, JAVA_LONG for 8), or
+ * PRECOMPUTED with hashes_dev, one int64 per key, indexed like keys_dev (NULL otherwise).
+ * key_width 4 or 8 (byte keys: RSV_E_UNSUPPORTED); 1 <= k <= 4096 (larger: RSV_E_UNSUPPORTED).
+ * Stateless and stream-ordered on hip_stream: no host wait, no allocation.  All pointers are device
+ * pointers. */
+rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
+                                  int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind, uint64_t seed,
+                                  uint64_t stream_base, void* out_keys_dev, int64_t* out_hashes_dev,
+                                  int64_t* counts_dev, void* hip_stream);
+
 /* Event replay (K1'): apply eviction events (1-based position, slot) -- the
  * `samples(rand.nextInt(k)) = map(element)` writes of S:243-246 -- for elements at global indices
  * [base_index, base_index+n) held in keys_dev, onto reservoir_dev[k] (in/out, device).  Also

@@ -135,6 +135,14 @@ hipError_t launch_export_draws(const DrawParams& dp, uint64_t i0, int64_t n, uin
 hipError_t launch_segmented(const void* keys, int key_width, const int64_t* offsets, int64_t S,
                             uint32_t k, const DrawParams& dp, void* out, int64_t* counts,
                             hipStream_t st);
+// K5: segmented distinct (rsv_segdistinct.hip): per stream the bottom-k by (scrambled hash, key),
+// (r0, r1) from java.util.Random(seed0 + s); hashes only for kHashPrecomputed, out_hashes may be null.
+// k <= kSegDistinctMaxK; one wave per stream up to kSegDistinctWaveMaxK, one workgroup above.
+constexpr uint32_t kSegDistinctWaveMaxK = 256;
+constexpr uint32_t kSegDistinctMaxK = 4096;
+hipError_t launch_segdistinct(const void* keys, int key_width, const int64_t* hashes, const int64_t* offsets, int64_t S,
+                              uint32_t k, int hash_kind, uint64_t seed0, void* out_keys, int64_t* out_hashes,
+                              int64_t* counts, hipStream_t st);
 // merge of exported element states: per slot max index among parts (and current state)
 hipError_t launch_merge_slots(const int64_t* idx_parts, const void* key_parts, int key_width,
                               int32_t parts, int64_t part_len, uint32_t k, int64_t* slot_idx,

@@ -1597,6 +1597,32 @@ rsv_status rsv_sample_segmented(const void* keys_dev, const int64_t* offsets_dev
     return RSV_OK;
 }
 
+rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
+                                  int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind, uint64_t seed,
+                                  uint64_t stream_base, void* out_keys_dev, int64_t* out_hashes_dev,
+                                  int64_t* counts_dev, void* hip_stream) {
+    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
+    if (k > (int32_t)kSegDistinctMaxK)
+        return fail(RSV_E_UNSUPPORTED, "rsv_distinct_segmented holds k <= 4096 per stream; use separate handles beyond");
+    if (key_width > 8 && key_width <= 256 && key_width % 8 == 0)
+        return fail(RSV_E_UNSUPPORTED, "rsv_distinct_segmented takes 4- and 8-byte keys, not byte keys");
+    if (key_width != 4 && key_width != 8) return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be 4 or 8");
+    if (hash_kind < RSV_HASH_DEFAULT || hash_kind > RSV_HASH_PRECOMPUTED)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "unknown hash kind");
+    if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
+    if (num_streams == 0) return RSV_OK;
+    // keys_dev is not checked: a launch whose streams are all empty has no keys
+    if (!offsets_dev || !out_keys_dev || !counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (hash_kind == RSV_HASH_PRECOMPUTED && !hashes_dev)
+        return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
+    int hk = hash_kind;
+    if (hk == RSV_HASH_DEFAULT) hk = key_width == 4 ? RSV_HASH_JAVA_INT : RSV_HASH_JAVA_LONG;
+    RSV_HIP_TRY(launch_segdistinct(keys_dev, key_width, hk == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr, offsets_dev,
+                                   num_streams, (uint32_t)k, hk, seed + stream_base, out_keys_dev, out_hashes_dev,
+                                   counts_dev, (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
 rsv_status rsv_replay_events(const void* keys_dev, int64_t n, int32_t key_width, int64_t base_index,
                              const int64_t* ev_pos_dev, const int32_t* ev_slot_dev, int64_t n_events, int32_t k,
                              void* reservoir_dev, void* hip_stream) {
