@@ -377,6 +377,43 @@ rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_de
                                   uint64_t stream_base, void* out_keys_dev, int64_t* out_hashes_dev,
                                   int64_t* counts_dev, void* hip_stream);
 
+/* Segmented distinct, resumed: long-lived distinct samplers advanced by one launch per batch.  The
+ * state is the caller's device memory: state_keys_dev[num_states*k] (key_width values),
+ * state_hashes_dev[num_states*k] and state_counts_dev[num_states] (int64).  Row r holds counts[r]
+ * entries ascending by (h, key): exactly what rsv_distinct_segmented writes into out_keys_dev /
+ * out_hashes_dev / counts_dev, so a stateless result is a valid state; a row with counts[r] == 0 is
+ * the empty sampler, whatever its slots hold.  Bottom-k by (h, key) over distinct keys is a function
+ * of the key set alone, so a row fed a stream in pieces, in any number of launches, ends bit-identical
+ * to one rsv_distinct_segmented launch over the concatenated stream.
+ * Segment b = keys_dev[offsets[b] .. offsets[b+1]) goes into row r = stream_ids_dev[b], or r = b when
+ * stream_ids_dev is NULL (then num_segments <= num_states).  Row r is seeded as
+ * java.util.Random(seed + stream_base + r); hash kinds, key widths and k as rsv_distinct_segmented.
+ * Afterwards row r holds the bottom-k of (its previous entries u the segment's distinct keys),
+ * ascending, slots beyond the count zero.  The ids of one launch must be distinct (two segments on
+ * one row race: the caller's contract); a segment whose id lies outside [0, num_states) is skipped.
+ * Rows that no segment names, and rows whose segment is empty, are not touched.  A row's count is
+ * clamped into [0, k] before use and nothing else read from the state indexes memory: rows that are
+ * not ascending give an unspecified set, never an out-of-range access.
+ * Stateless and stream-ordered on hip_stream: no host wait, no allocation.  All pointers are device
+ * pointers. */
+rsv_status rsv_distinct_segmented_update(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
+                                         const int64_t* stream_ids_dev, int64_t num_segments, int64_t num_states,
+                                         int32_t key_width, int32_t k, int32_t hash_kind, uint64_t seed,
+                                         uint64_t stream_base, void* state_keys_dev, int64_t* state_hashes_dev,
+                                         int64_t* state_counts_dev, void* hip_stream);
+
+/* Combine of segmented distinct states: part_* are `parts` states laid back to back
+ * ([parts][num_states][k] keys and hashes, [parts][num_states] counts: what an all-gather of every
+ * rank's state tensors gives).  Row r becomes the bottom-k of (row r u the first
+ * clamp(part_counts[p][r], 0, k) entries of row r of every part p); equal (h, key) pairs collapse.
+ * The parts' hashes are final (already scrambled): nothing is hashed again, so all parts and the
+ * state must come from the same seed, stream_base and hash (the caller's contract).  A row whose
+ * parts are all empty is not touched.  Stateless and stream-ordered like the update. */
+rsv_status rsv_distinct_segmented_merge(const void* part_keys_dev, const int64_t* part_hashes_dev,
+                                        const int64_t* part_counts_dev, int32_t parts, int64_t num_states,
+                                        int32_t key_width, int32_t k, void* state_keys_dev, int64_t* state_hashes_dev,
+                                        int64_t* state_counts_dev, void* hip_stream);
+
 /* Event replay (K1'): apply eviction events (1-based position, slot) -- the
  * `samples(rand.nextInt(k)) = map(element)` writes of S:243-246 -- for elements at global indices
  * [base_index, base_index+n) held in keys_dev, onto reservoir_dev[k] (in/out, device).  Also

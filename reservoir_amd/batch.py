@@ -5,6 +5,8 @@ libreservoir_hip.so.  Every function raises if the engine is unavailable.
 
     sample_segmented  -- K2: S independent samplers in one launch (one wave per stream)
     distinct_segmented -- K5: S independent Sampler.distinct streams in one launch (bottom-k per stream)
+    SegmentedDistinct -- K5 resumed: the same S streams as caller-held state, advanced by one launch
+                         per micro-batch (update) and combined across launches, GPUs and ranks (merge)
     replay_events     -- K1': apply the reference's Algorithm-L eviction events on the GPU
     export_draws      -- the per-element draw sequence j_i of draw format R2
 """
@@ -94,6 +96,147 @@ def distinct_segmented(keys, offsets, k: int, seed: int, stream_base: int = 0, h
         stream_base & (2**64 - 1), C.c_void_p(out.data_ptr()), C.c_void_p(out_h.data_ptr()),
         C.c_void_p(counts.data_ptr()), _stream_ptr(torch, keys.device)))
     return out, out_h, counts
+
+
+class SegmentedDistinct:
+    """S long-lived Sampler.distinct streams advanced by one launch per batch (K5 resumed).
+
+    The state is three device tensors in distinct_segmented's layout: keys (S, k), hashes (S, k),
+    counts (S,); row s holds counts[s] entries ascending by (scrambled hash, key) and is seeded like
+    a single Sampler.distinct(k, seed=seed + stream_base + s, order="set").  Fed a stream in any
+    number of update() calls, a row ends bit-identical to distinct_segmented over the whole stream.
+    Only the counts are zero-filled: a row with count 0 is empty whatever its slots hold, and every
+    row an update writes has zeros beyond its count.  hash="precomputed": update(hashes=...).
+    Everything runs on torch's current stream.
+    """
+
+    def __init__(self, num_streams: int, k: int, seed: int, stream_base: int = 0, hash: str = "default",
+                 dtype=None, device=None):
+        import torch
+
+        N.load()
+        dtype = torch.int64 if dtype is None else dtype
+        if dtype not in (torch.int64, torch.int32):
+            raise N.IllegalArgumentException("keys must be int64/int32")
+        if hash == "precomputed":
+            self._kind = N.HASH_PRECOMPUTED
+        elif hash in _SEG_HASH:
+            self._kind = _SEG_HASH[hash]
+        else:
+            raise N.IllegalArgumentException(f"unknown hash {hash!r}")
+        if num_streams < 0:
+            raise N.IllegalArgumentException("negative stream count")
+        if k <= 0:
+            raise N.IllegalArgumentException("k out of range")
+        if k > 4096:
+            raise N.ReservoirError("SegmentedDistinct holds k <= 4096 per stream; use separate handles beyond")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise N.IllegalArgumentException("the state lives on the device")
+        self.num_streams, self.k = int(num_streams), int(k)
+        self.seed, self.stream_base = seed & (2**64 - 1), stream_base & (2**64 - 1)
+        self.keys = torch.empty((self.num_streams, self.k), dtype=dtype, device=dev)
+        self.hashes = torch.empty((self.num_streams, self.k), dtype=torch.int64, device=dev)
+        self.counts = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
+
+    def update(self, keys, offsets, stream_ids=None, hashes=None, check_ids: bool = True):
+        """Segment b = keys[offsets[b]:offsets[b+1]] into row stream_ids[b] (None: row b).
+
+        The ids of one call must be distinct and inside [0, num_streams).  check_ids=True verifies
+        that on the device before the launch (one host wait) and raises IllegalArgumentException;
+        check_ids=False keeps the call stream-ordered and leaves the contract to the caller.
+        Rows that no segment names, or whose segment is empty, are not touched.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        if not (keys.is_cuda and offsets.is_cuda):
+            raise N.IllegalArgumentException("keys and offsets must be device tensors")
+        if keys.dtype != self.keys.dtype or offsets.dtype != torch.int64:
+            raise N.IllegalArgumentException("keys must have the state's dtype and offsets must be int64")
+        if keys.device != self.keys.device or offsets.device != self.keys.device:
+            raise N.IllegalArgumentException("keys and offsets must live on the state's device")
+        if self._kind == N.HASH_PRECOMPUTED:
+            if hashes is None:
+                raise N.NullPointerException("hash='precomputed' needs hashes=")
+        elif hashes is not None:
+            raise N.IllegalArgumentException("hashes= needs hash='precomputed'")
+        if hashes is not None:
+            if not hashes.is_cuda or hashes.dtype != torch.int64 or hashes.numel() != keys.numel():
+                raise N.IllegalArgumentException("hashes must be an int64 device tensor, one per key")
+            # an empty tensor has no address; the engine wants one for precomputed hashes
+            hashes = hashes.contiguous() if hashes.numel() else torch.empty(1, dtype=torch.int64, device=keys.device)
+        keys = keys.contiguous()
+        offsets = offsets.contiguous()
+        B = offsets.numel() - 1
+        if B <= 0:
+            return self
+        if stream_ids is not None:
+            if not stream_ids.is_cuda or stream_ids.dtype != torch.int64 or stream_ids.numel() != B:
+                raise N.IllegalArgumentException("stream_ids must be an int64 device tensor, one per segment")
+            stream_ids = stream_ids.contiguous()
+            if check_ids and self.num_streams > 0:
+                S = self.num_streams
+                outside = (stream_ids < 0) | (stream_ids >= S)
+                seen = torch.zeros(S, dtype=torch.int32, device=stream_ids.device)
+                seen.index_add_(0, stream_ids.clamp(0, S - 1), torch.ones(B, dtype=torch.int32, device=stream_ids.device))
+                bad = torch.stack([outside.any(), (seen > 1).any()]).cpu()  # the one host wait
+                if bool(bad[0]):
+                    raise N.IllegalArgumentException(f"stream_ids outside [0, {S})")
+                if bool(bad[1]):
+                    raise N.IllegalArgumentException("stream_ids repeat a row within one update")
+        N.check(L.rsv_distinct_segmented_update(
+            C.c_void_p(keys.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
+            C.c_void_p(offsets.data_ptr()), C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
+            B, self.num_streams, keys.element_size(), self.k, self._kind, self.seed, self.stream_base,
+            C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.hashes.data_ptr()), C.c_void_p(self.counts.data_ptr()),
+            _stream_ptr(torch, self.keys.device)))
+        return self
+
+    def merge(self, part_keys, part_hashes=None, part_counts=None):
+        """Row s becomes the bottom-k of (row s u row s of every part).
+
+        merge(part_keys, part_hashes, part_counts): tensors (P, S, k), (P, S, k), (P, S) -- or (S, k),
+        (S, k), (S,) for one part -- e.g. an all-gather of every rank's state tensors; or
+        merge(other, ...) with SegmentedDistinct objects.  All parts must come from this state's
+        seed, stream_base and hash: their hashes are taken as stored.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        if isinstance(part_keys, SegmentedDistinct):
+            others = [part_keys] + [o for o in (part_hashes, part_counts) if o is not None]
+            for o in others:
+                if not isinstance(o, SegmentedDistinct) or (o.num_streams, o.k, o.seed, o.stream_base, o._kind) != (
+                        self.num_streams, self.k, self.seed, self.stream_base, self._kind):
+                    raise N.IllegalArgumentException("merge needs states of the same shape, seed, stream_base and hash")
+            if len(others) == 1:
+                part_keys, part_hashes, part_counts = others[0].keys, others[0].hashes, others[0].counts
+            else:
+                part_keys = torch.stack([o.keys for o in others])
+                part_hashes = torch.stack([o.hashes for o in others])
+                part_counts = torch.stack([o.counts for o in others])
+        if part_hashes is None or part_counts is None:
+            raise N.NullPointerException("merge needs part_keys, part_hashes and part_counts")
+        S, k = self.num_streams, self.k
+        if part_keys.dim() == 2:
+            part_keys, part_hashes, part_counts = part_keys[None], part_hashes[None], part_counts[None]
+        P = part_keys.shape[0]
+        if tuple(part_keys.shape) != (P, S, k) or tuple(part_hashes.shape) != (P, S, k) or tuple(part_counts.shape) != (P, S):
+            raise N.IllegalArgumentException(f"parts must be shaped (P, {S}, {k}), (P, {S}, {k}), (P, {S})")
+        if part_keys.dtype != self.keys.dtype or part_hashes.dtype != torch.int64 or part_counts.dtype != torch.int64:
+            raise N.IllegalArgumentException("part keys must have the state's dtype, hashes and counts must be int64")
+        dev = self.keys.device
+        if part_keys.device != dev or part_hashes.device != dev or part_counts.device != dev:
+            raise N.IllegalArgumentException("parts must live on the state's device")
+        if P == 0 or S == 0:
+            return self
+        part_keys, part_hashes, part_counts = part_keys.contiguous(), part_hashes.contiguous(), part_counts.contiguous()
+        N.check(L.rsv_distinct_segmented_merge(
+            C.c_void_p(part_keys.data_ptr()), C.c_void_p(part_hashes.data_ptr()), C.c_void_p(part_counts.data_ptr()),
+            P, S, part_keys.element_size(), k, C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.hashes.data_ptr()),
+            C.c_void_p(self.counts.data_ptr()), _stream_ptr(torch, dev)))
+        return self
 
 
 def replay_events(keys, base_index: int, ev_pos, ev_slot, k: int, reservoir=None):

@@ -143,6 +143,17 @@ constexpr uint32_t kSegDistinctMaxK = 4096;
 hipError_t launch_segdistinct(const void* keys, int key_width, const int64_t* hashes, const int64_t* offsets, int64_t S,
                               uint32_t k, int hash_kind, uint64_t seed0, void* out_keys, int64_t* out_hashes,
                               int64_t* counts, hipStream_t st);
+// K5 resumed (rsv_segdistinct_state.hip): the same teams started from the caller's state rows
+// (keys[num_states*k], hashes, counts; ascending by (h, key) as launch_segdistinct writes them) and
+// written back in place.  update: segment b into row stream_ids[b] (null: row b), seeded seed0 + row;
+// merge: row r takes the valid entries of row r of every part ([parts][num_states][k]), hashes as stored.
+hipError_t launch_segdistinct_update(const void* keys, int key_width, const int64_t* hashes, const int64_t* offsets,
+                                     const int64_t* stream_ids, int64_t num_segments, int64_t num_states, uint32_t k,
+                                     int hash_kind, uint64_t seed0, void* state_keys, int64_t* state_hashes,
+                                     int64_t* state_counts, hipStream_t st);
+hipError_t launch_segdistinct_merge(const void* part_keys, int key_width, const int64_t* part_hashes,
+                                    const int64_t* part_counts, int32_t parts, int64_t num_states, uint32_t k,
+                                    void* state_keys, int64_t* state_hashes, int64_t* state_counts, hipStream_t st);
 // merge of exported element states: per slot max index among parts (and current state)
 hipError_t launch_merge_slots(const int64_t* idx_parts, const void* key_parts, int key_width,
                               int32_t parts, int64_t part_len, uint32_t k, int64_t* slot_idx,

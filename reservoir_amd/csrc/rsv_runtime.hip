@@ -1623,6 +1623,59 @@ rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_de
     return RSV_OK;
 }
 
+// k and key_width of the resumable K5 entry points, in rsv_distinct_segmented's order
+static rsv_status check_segstate_shape(const char* fn, int32_t k, int32_t key_width) {
+    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
+    if (k > (int32_t)kSegDistinctMaxK)
+        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " holds k <= 4096 per stream; use separate handles beyond");
+    if (key_width > 8 && key_width <= 256 && key_width % 8 == 0)
+        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " takes 4- and 8-byte keys, not byte keys");
+    if (key_width != 4 && key_width != 8) return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be 4 or 8");
+    return RSV_OK;
+}
+
+rsv_status rsv_distinct_segmented_update(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
+                                         const int64_t* stream_ids_dev, int64_t num_segments, int64_t num_states,
+                                         int32_t key_width, int32_t k, int32_t hash_kind, uint64_t seed,
+                                         uint64_t stream_base, void* state_keys_dev, int64_t* state_hashes_dev,
+                                         int64_t* state_counts_dev, void* hip_stream) {
+    if (rsv_status st = check_segstate_shape("rsv_distinct_segmented_update", k, key_width)) return st;
+    if (hash_kind < RSV_HASH_DEFAULT || hash_kind > RSV_HASH_PRECOMPUTED)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "unknown hash kind");
+    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
+    if (!stream_ids_dev && num_segments > num_states)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
+    if (num_segments == 0 || num_states == 0) return RSV_OK;
+    // keys_dev is not checked: a launch whose segments are all empty has no keys
+    if (!offsets_dev || !state_keys_dev || !state_hashes_dev || !state_counts_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (hash_kind == RSV_HASH_PRECOMPUTED && !hashes_dev)
+        return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
+    int hk = hash_kind;
+    if (hk == RSV_HASH_DEFAULT) hk = key_width == 4 ? RSV_HASH_JAVA_INT : RSV_HASH_JAVA_LONG;
+    RSV_HIP_TRY(launch_segdistinct_update(keys_dev, key_width, hk == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr,
+                                          offsets_dev, stream_ids_dev, num_segments, num_states, (uint32_t)k, hk,
+                                          seed + stream_base, state_keys_dev, state_hashes_dev, state_counts_dev,
+                                          (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
+rsv_status rsv_distinct_segmented_merge(const void* part_keys_dev, const int64_t* part_hashes_dev,
+                                        const int64_t* part_counts_dev, int32_t parts, int64_t num_states,
+                                        int32_t key_width, int32_t k, void* state_keys_dev, int64_t* state_hashes_dev,
+                                        int64_t* state_counts_dev, void* hip_stream) {
+    if (rsv_status st = check_segstate_shape("rsv_distinct_segmented_merge", k, key_width)) return st;
+    if (parts < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative part or state count");
+    if (parts == 0 || num_states == 0) return RSV_OK;
+    if (!part_keys_dev || !part_hashes_dev || !part_counts_dev || !state_keys_dev || !state_hashes_dev ||
+        !state_counts_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    RSV_HIP_TRY(launch_segdistinct_merge(part_keys_dev, key_width, part_hashes_dev, part_counts_dev, parts, num_states,
+                                         (uint32_t)k, state_keys_dev, state_hashes_dev, state_counts_dev,
+                                         (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
 rsv_status rsv_replay_events(const void* keys_dev, int64_t n, int32_t key_width, int64_t base_index,
                              const int64_t* ev_pos_dev, const int32_t* ev_slot_dev, int64_t n_events, int32_t k,
                              void* reservoir_dev, void* hip_stream) {

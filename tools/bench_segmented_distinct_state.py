@@ -1,0 +1,190 @@
+"""Resumed segmented Sampler.distinct (batch.SegmentedDistinct: rsv_distinct_segmented_update / _merge).
+
+--mode update (default): the streams of tools/bench_segmented_distinct.py (the same key generator:
+S streams x len int64 keys, ~dup repeats inside each stream, identity hash) cut into B equal batches
+and fed as B update launches into one state, against one stateless rsv_distinct_segmented launch over
+the same keys in the same run.  Device events around every launch, --warmup runs then --steps timed
+runs of the B launches (the counts are zeroed before each run, outside the timed windows).  Reports
+
+    launch_ms[B]      median time of each of the B launches
+    sum_ms            median over the runs of the sum of the B launch times (sum_ms_min / _max: the spread)
+    stateless_ms      median of one stateless launch (stateless_ms_min / _max)
+    ratio             sum_ms / stateless_ms
+    state_bytes       B x S x 32 x k: every launch reading and writing every row, an upper bound (a full
+                      row that admits nothing is not written)
+    model_ms          stateless_ms + state_bytes / (8 B x elements / stateless_ms): the state moved at the
+                      rate the stateless launch itself achieved; model_ratio = model_ms / stateless_ms
+    later_over_first  mean of launches 2..B over launch 1: what a known threshold saves
+    check             the state equals the stateless result (keys, hashes, counts)
+
+--mode merge: P parts (the stateless results of P index-split pieces of every stream) merged in one
+launch into an empty state (merge_ms) and once more into the merged state (remerge_ms: every entry
+ties with a member), against a device copy of the same part bytes in the same run (copy_ms);
+merge_over_copy = merge_ms / copy_ms.  check: the merged state equals the stateless result over the
+whole streams.
+
+    python tools/bench_segmented_distinct_state.py [--mode update] [--streams 1048576] [--len 4096] [--k 64]
+                                                   [--batches 8] [--dup 0.3] [--steps 10] [--warmup 3] [--out FILE]
+    python tools/bench_segmented_distinct_state.py --mode merge [--parts 8] [--streams 1048576] [--len 2048] [--k 64]
+prints one JSON line (and appends it to --out).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def make_keys(torch, dev, S, n, dup):
+    """bench_segmented_distinct.py's keys: random int64, ~dup of each stream's positions repeat another."""
+    g = torch.Generator(device=dev)
+    g.manual_seed(0x5EED)
+    keys = torch.empty((S, n), dtype=torch.int64, device=dev)
+    rows = max(1, (1 << 27) // n)
+    for r0 in range(0, S, rows):
+        r1 = min(S, r0 + rows)
+        v = torch.randint(-2**63, 2**63 - 1, (r1 - r0, n), dtype=torch.int64, device=dev, generator=g)
+        src = torch.randint(0, n, (r1 - r0, n), dtype=torch.int64, device=dev, generator=g)
+        rep = torch.rand((r1 - r0, n), device=dev, generator=g) < dup
+        keys[r0:r1] = torch.where(rep, torch.gather(v, 1, src), v)
+        del v, src, rep
+    return keys
+
+
+def timed(torch, fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1), out
+
+
+def pieces(torch, keys, B):
+    """B contiguous (S, len / B) column slices with their offsets."""
+    S, n = keys.shape
+    w = n // B
+    offs = torch.arange(0, S * w + 1, w, dtype=torch.int64, device=keys.device)
+    return [keys[:, t * w:(t + 1) * w].contiguous().view(-1) for t in range(B)], offs
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["update", "merge"], default="update")
+    ap.add_argument("--streams", type=int, default=1 << 20)
+    ap.add_argument("--len", type=int, default=None)
+    ap.add_argument("--k", type=int, default=64)
+    ap.add_argument("--batches", type=int, default=8)
+    ap.add_argument("--parts", type=int, default=8)
+    ap.add_argument("--dup", type=float, default=0.3)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+
+    import torch
+
+    from reservoir_amd import batch
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_segmented_distinct_state needs a GPU")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    S, k = a.streams, a.k
+    n = a.len if a.len is not None else (4096 if a.mode == "update" else 2048)
+    B = a.batches if a.mode == "update" else a.parts
+    if n % B:
+        raise SystemExit("--len must be a multiple of the number of pieces")
+    keys = make_keys(torch, dev, S, n, a.dup)
+    flat = keys.view(-1)
+    offs = torch.arange(0, S * n + 1, n, dtype=torch.int64, device=dev)
+    parts, poffs = pieces(torch, keys, B)
+    torch.cuda.synchronize()
+
+    def stateless():
+        return batch.distinct_segmented(flat, offs, k, seed=11, hash="identity")
+
+    def same(sd, ref):
+        return bool(torch.equal(sd.keys, ref[0]) and torch.equal(sd.hashes, ref[1]) and torch.equal(sd.counts, ref[2]))
+
+    base = {"bench": "segmented_distinct_state", "mode": a.mode, "streams": S, "len": n, "k": k, "dup": a.dup,
+            "hash": "identity", "form": "wave" if k <= 256 else "workgroup", "steps": a.steps, "warmup": a.warmup,
+            "device": torch.cuda.get_device_name(0)}
+    sd = batch.SegmentedDistinct(S, k, seed=11, hash="identity", device=dev)
+
+    if a.mode == "update":
+        sl = []
+        for step in range(a.warmup + a.steps):
+            ms, ref = timed(torch, stateless)
+            if step >= a.warmup:
+                sl.append(ms)
+            if step < a.warmup + a.steps - 1:
+                del ref
+        runs = []
+        for step in range(a.warmup + a.steps):
+            sd.counts.zero_()
+            per = [timed(torch, lambda t=t: sd.update(parts[t], poffs))[0] for t in range(B)]
+            if step >= a.warmup:
+                runs.append(per)
+        sums = [sum(r) for r in runs]
+        launch = [statistics.median(r[t] for r in runs) for t in range(B)]
+        sl_ms, sum_ms = statistics.median(sl), statistics.median(sums)
+        state_bytes = B * S * 32 * k
+        rate = S * n * 8 / sl_ms  # bytes per ms of the stateless launch
+        model = sl_ms + state_bytes / rate
+        out = dict(base, batches=B, launch_ms=launch, sum_ms=sum_ms, sum_ms_min=min(sums), sum_ms_max=max(sums),
+                   stateless_ms=sl_ms, stateless_ms_min=min(sl), stateless_ms_max=max(sl), ratio=sum_ms / sl_ms,
+                   state_bytes=state_bytes, stateless_GBps=rate / 1e6, model_ms=model, model_ratio=model / sl_ms,
+                   sum_over_model=sum_ms / model,
+                   later_over_first=(statistics.mean(launch[1:]) / launch[0]) if B > 1 else None,
+                   check=same(sd, ref))
+    else:
+        ref = stateless()
+        pk, ph, pc = [], [], []
+        for t in range(B):
+            r = batch.distinct_segmented(parts[t], poffs, k, seed=11, hash="identity")
+            pk.append(r[0]), ph.append(r[1]), pc.append(r[2])
+        pk, ph, pc = torch.stack(pk), torch.stack(ph), torch.stack(pc)
+        ck, ch, cc = torch.empty_like(pk), torch.empty_like(ph), torch.empty_like(pc)
+        del parts, keys, flat
+        torch.cuda.synchronize()
+
+        def copy():
+            ck.copy_(pk)
+            ch.copy_(ph)
+            cc.copy_(pc)
+
+        mg, rm, cp = [], [], []
+        for step in range(a.warmup + a.steps):
+            sd.counts.zero_()
+            t0 = timed(torch, lambda: sd.merge(pk, ph, pc))[0]
+            ok = same(sd, ref) if step == 0 else True
+            if not ok:
+                raise SystemExit("the merged state and the stateless launch disagree")
+            t1 = timed(torch, lambda: sd.merge(pk, ph, pc))[0]
+            t2 = timed(torch, copy)[0]
+            if step >= a.warmup:
+                mg.append(t0), rm.append(t1), cp.append(t2)
+        nbytes = pk.numel() * 8 + ph.numel() * 8 + pc.numel() * 8
+        m, c = statistics.median(mg), statistics.median(cp)
+        out = dict(base, parts=B, part_bytes=nbytes, merge_ms=m, merge_ms_min=min(mg), merge_ms_max=max(mg),
+                   remerge_ms=statistics.median(rm), copy_ms=c, copy_ms_min=min(cp), copy_ms_max=max(cp),
+                   merge_GBps=nbytes / m / 1e6, copy_GBps=nbytes / c / 1e6, merge_over_copy=m / c,
+                   check=same(sd, ref))
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+    if not out["check"]:
+        raise SystemExit("the state and the stateless launch disagree")
+
+
+if __name__ == "__main__":
+    main()
