@@ -384,7 +384,9 @@ rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_de
  * out_hashes_dev / counts_dev, so a stateless result is a valid state; a row with counts[r] == 0 is
  * the empty sampler, whatever its slots hold.  Bottom-k by (h, key) over distinct keys is a function
  * of the key set alone, so a row fed a stream in pieces, in any number of launches, ends bit-identical
- * to one rsv_distinct_segmented launch over the concatenated stream.
+ * to one rsv_distinct_segmented launch over the concatenated stream (the three entry points run one
+ * element loop with one table of thread counts and buffer sizes per k, and share their k, key_width
+ * and hash_kind checks).
  * Segment b = keys_dev[offsets[b] .. offsets[b+1]) goes into row r = stream_ids_dev[b], or r = b when
  * stream_ids_dev is NULL (then num_segments <= num_states).  Row r is seeded as
  * java.util.Random(seed + stream_base + r); hash kinds, key widths and k as rsv_distinct_segmented.

@@ -52,6 +52,32 @@ def sample_segmented(keys, offsets, k: int, seed: int, stream_base: int = 0):
 
 _SEG_HASH = {"default": N.HASH_DEFAULT, "identity": N.HASH_IDENTITY, "java_long": N.HASH_JAVA_LONG,
              "java_int": N.HASH_JAVA_INT}
+_SEG_DISTINCT_MAX_K = 4096  # rsv_internal.h kSegDistinctMaxK
+
+
+def _segd_inputs(torch, keys, offsets, hashes, state=None):
+    """keys / offsets / hashes of a K5 call, checked and contiguous (state: the SegmentedDistinct they feed)."""
+    if not (keys.is_cuda and offsets.is_cuda):
+        raise N.IllegalArgumentException("keys and offsets must be device tensors")
+    if state is None:
+        if keys.dtype not in (torch.int64, torch.int32) or offsets.dtype != torch.int64:
+            raise N.IllegalArgumentException("keys must be int64/int32 and offsets int64")
+    else:
+        if keys.dtype != state.keys.dtype or offsets.dtype != torch.int64:
+            raise N.IllegalArgumentException("keys must have the state's dtype and offsets must be int64")
+        if keys.device != state.keys.device or offsets.device != state.keys.device:
+            raise N.IllegalArgumentException("keys and offsets must live on the state's device")
+        if state._kind == N.HASH_PRECOMPUTED:
+            if hashes is None:
+                raise N.NullPointerException("hash='precomputed' needs hashes=")
+        elif hashes is not None:
+            raise N.IllegalArgumentException("hashes= needs hash='precomputed'")
+    if hashes is not None:
+        if not hashes.is_cuda or hashes.dtype != torch.int64 or hashes.numel() != keys.numel():
+            raise N.IllegalArgumentException("hashes must be an int64 device tensor, one per key")
+        # an empty tensor has no address; the engine wants one for precomputed hashes
+        hashes = hashes.contiguous() if hashes.numel() else torch.empty(1, dtype=torch.int64, device=keys.device)
+    return keys.contiguous(), offsets.contiguous(), hashes
 
 
 def distinct_segmented(keys, offsets, k: int, seed: int, stream_base: int = 0, hash: str = "default", hashes=None):
@@ -66,22 +92,13 @@ def distinct_segmented(keys, offsets, k: int, seed: int, stream_base: int = 0, h
     import torch
 
     L = N.load()
-    if not (keys.is_cuda and offsets.is_cuda):
-        raise N.IllegalArgumentException("keys and offsets must be device tensors")
-    if keys.dtype not in (torch.int64, torch.int32) or offsets.dtype != torch.int64:
-        raise N.IllegalArgumentException("keys must be int64/int32 and offsets int64")
+    keys, offsets, hashes = _segd_inputs(torch, keys, offsets, hashes)
     if hashes is not None:
-        if not hashes.is_cuda or hashes.dtype != torch.int64 or hashes.numel() != keys.numel():
-            raise N.IllegalArgumentException("hashes must be an int64 device tensor, one per key")
         kind = N.HASH_PRECOMPUTED
-        # an empty tensor has no address; the engine wants one for precomputed hashes
-        hashes = hashes.contiguous() if hashes.numel() else torch.empty(1, dtype=torch.int64, device=keys.device)
     elif hash in _SEG_HASH:
         kind = _SEG_HASH[hash]
     else:
         raise N.IllegalArgumentException(f"unknown hash {hash!r}")
-    keys = keys.contiguous()
-    offsets = offsets.contiguous()
     S = offsets.numel() - 1
     # the kernel writes every slot (empty ones as 0) and every count: no zero-fill
     kk = max(int(k), 0)
@@ -128,8 +145,9 @@ class SegmentedDistinct:
             raise N.IllegalArgumentException("negative stream count")
         if k <= 0:
             raise N.IllegalArgumentException("k out of range")
-        if k > 4096:
-            raise N.ReservoirError("SegmentedDistinct holds k <= 4096 per stream; use separate handles beyond")
+        if k > _SEG_DISTINCT_MAX_K:
+            raise N.ReservoirError(
+                f"SegmentedDistinct holds k <= {_SEG_DISTINCT_MAX_K} per stream; use separate handles beyond")
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if dev.type != "cuda":
             raise N.IllegalArgumentException("the state lives on the device")
@@ -150,24 +168,7 @@ class SegmentedDistinct:
         import torch
 
         L = N.load()
-        if not (keys.is_cuda and offsets.is_cuda):
-            raise N.IllegalArgumentException("keys and offsets must be device tensors")
-        if keys.dtype != self.keys.dtype or offsets.dtype != torch.int64:
-            raise N.IllegalArgumentException("keys must have the state's dtype and offsets must be int64")
-        if keys.device != self.keys.device or offsets.device != self.keys.device:
-            raise N.IllegalArgumentException("keys and offsets must live on the state's device")
-        if self._kind == N.HASH_PRECOMPUTED:
-            if hashes is None:
-                raise N.NullPointerException("hash='precomputed' needs hashes=")
-        elif hashes is not None:
-            raise N.IllegalArgumentException("hashes= needs hash='precomputed'")
-        if hashes is not None:
-            if not hashes.is_cuda or hashes.dtype != torch.int64 or hashes.numel() != keys.numel():
-                raise N.IllegalArgumentException("hashes must be an int64 device tensor, one per key")
-            # an empty tensor has no address; the engine wants one for precomputed hashes
-            hashes = hashes.contiguous() if hashes.numel() else torch.empty(1, dtype=torch.int64, device=keys.device)
-        keys = keys.contiguous()
-        offsets = offsets.contiguous()
+        keys, offsets, hashes = _segd_inputs(torch, keys, offsets, hashes, state=self)
         B = offsets.numel() - 1
         if B <= 0:
             return self

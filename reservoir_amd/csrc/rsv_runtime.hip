@@ -1597,40 +1597,41 @@ rsv_status rsv_sample_segmented(const void* keys_dev, const int64_t* offsets_dev
     return RSV_OK;
 }
 
+// k and key_width of the three K5 entry points (fn: the entry point's name, for the messages)
+static rsv_status check_segdistinct_shape(const char* fn, int32_t k, int32_t key_width) {
+    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
+    if (k > (int32_t)kSegDistinctMaxK)
+        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " holds k <= " + std::to_string(kSegDistinctMaxK) +
+                                           " per stream; use separate handles beyond");
+    if (key_width > 8 && key_width <= 256 && key_width % 8 == 0)
+        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " takes 4- and 8-byte keys, not byte keys");
+    if (key_width != 4 && key_width != 8) return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be 4 or 8");
+    return RSV_OK;
+}
+
+// the hash kind of the two K5 entry points that hash: its range, and RSV_HASH_DEFAULT resolved by key width
+static rsv_status resolve_segdistinct_hash(int32_t hash_kind, int32_t key_width, int& hk) {
+    if (hash_kind < RSV_HASH_DEFAULT || hash_kind > RSV_HASH_PRECOMPUTED)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "unknown hash kind");
+    hk = hash_kind != RSV_HASH_DEFAULT ? hash_kind : key_width == 4 ? RSV_HASH_JAVA_INT : RSV_HASH_JAVA_LONG;
+    return RSV_OK;
+}
+
 rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
                                   int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind, uint64_t seed,
                                   uint64_t stream_base, void* out_keys_dev, int64_t* out_hashes_dev,
                                   int64_t* counts_dev, void* hip_stream) {
-    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
-    if (k > (int32_t)kSegDistinctMaxK)
-        return fail(RSV_E_UNSUPPORTED, "rsv_distinct_segmented holds k <= 4096 per stream; use separate handles beyond");
-    if (key_width > 8 && key_width <= 256 && key_width % 8 == 0)
-        return fail(RSV_E_UNSUPPORTED, "rsv_distinct_segmented takes 4- and 8-byte keys, not byte keys");
-    if (key_width != 4 && key_width != 8) return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be 4 or 8");
-    if (hash_kind < RSV_HASH_DEFAULT || hash_kind > RSV_HASH_PRECOMPUTED)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "unknown hash kind");
+    int hk;
+    if (rsv_status st = check_segdistinct_shape("rsv_distinct_segmented", k, key_width)) return st;
+    if (rsv_status st = resolve_segdistinct_hash(hash_kind, key_width, hk)) return st;
     if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
     if (num_streams == 0) return RSV_OK;
     // keys_dev is not checked: a launch whose streams are all empty has no keys
     if (!offsets_dev || !out_keys_dev || !counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
-    if (hash_kind == RSV_HASH_PRECOMPUTED && !hashes_dev)
-        return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
-    int hk = hash_kind;
-    if (hk == RSV_HASH_DEFAULT) hk = key_width == 4 ? RSV_HASH_JAVA_INT : RSV_HASH_JAVA_LONG;
+    if (hk == RSV_HASH_PRECOMPUTED && !hashes_dev) return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
     RSV_HIP_TRY(launch_segdistinct(keys_dev, key_width, hk == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr, offsets_dev,
                                    num_streams, (uint32_t)k, hk, seed + stream_base, out_keys_dev, out_hashes_dev,
                                    counts_dev, (hipStream_t)hip_stream));
-    return RSV_OK;
-}
-
-// k and key_width of the resumable K5 entry points, in rsv_distinct_segmented's order
-static rsv_status check_segstate_shape(const char* fn, int32_t k, int32_t key_width) {
-    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
-    if (k > (int32_t)kSegDistinctMaxK)
-        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " holds k <= 4096 per stream; use separate handles beyond");
-    if (key_width > 8 && key_width <= 256 && key_width % 8 == 0)
-        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " takes 4- and 8-byte keys, not byte keys");
-    if (key_width != 4 && key_width != 8) return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be 4 or 8");
     return RSV_OK;
 }
 
@@ -1639,9 +1640,9 @@ rsv_status rsv_distinct_segmented_update(const void* keys_dev, const int64_t* ha
                                          int32_t key_width, int32_t k, int32_t hash_kind, uint64_t seed,
                                          uint64_t stream_base, void* state_keys_dev, int64_t* state_hashes_dev,
                                          int64_t* state_counts_dev, void* hip_stream) {
-    if (rsv_status st = check_segstate_shape("rsv_distinct_segmented_update", k, key_width)) return st;
-    if (hash_kind < RSV_HASH_DEFAULT || hash_kind > RSV_HASH_PRECOMPUTED)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "unknown hash kind");
+    int hk;
+    if (rsv_status st = check_segdistinct_shape("rsv_distinct_segmented_update", k, key_width)) return st;
+    if (rsv_status st = resolve_segdistinct_hash(hash_kind, key_width, hk)) return st;
     if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
     if (!stream_ids_dev && num_segments > num_states)
         return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
@@ -1649,10 +1650,7 @@ rsv_status rsv_distinct_segmented_update(const void* keys_dev, const int64_t* ha
     // keys_dev is not checked: a launch whose segments are all empty has no keys
     if (!offsets_dev || !state_keys_dev || !state_hashes_dev || !state_counts_dev)
         return fail(RSV_E_NULL_POINTER, "NULL buffer");
-    if (hash_kind == RSV_HASH_PRECOMPUTED && !hashes_dev)
-        return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
-    int hk = hash_kind;
-    if (hk == RSV_HASH_DEFAULT) hk = key_width == 4 ? RSV_HASH_JAVA_INT : RSV_HASH_JAVA_LONG;
+    if (hk == RSV_HASH_PRECOMPUTED && !hashes_dev) return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
     RSV_HIP_TRY(launch_segdistinct_update(keys_dev, key_width, hk == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr,
                                           offsets_dev, stream_ids_dev, num_segments, num_states, (uint32_t)k, hk,
                                           seed + stream_base, state_keys_dev, state_hashes_dev, state_counts_dev,
@@ -1664,7 +1662,7 @@ rsv_status rsv_distinct_segmented_merge(const void* part_keys_dev, const int64_t
                                         const int64_t* part_counts_dev, int32_t parts, int64_t num_states,
                                         int32_t key_width, int32_t k, void* state_keys_dev, int64_t* state_hashes_dev,
                                         int64_t* state_counts_dev, void* hip_stream) {
-    if (rsv_status st = check_segstate_shape("rsv_distinct_segmented_merge", k, key_width)) return st;
+    if (rsv_status st = check_segdistinct_shape("rsv_distinct_segmented_merge", k, key_width)) return st;
     if (parts < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative part or state count");
     if (parts == 0 || num_states == 0) return RSV_OK;
     if (!part_keys_dev || !part_hashes_dev || !part_counts_dev || !state_keys_dev || !state_hashes_dev ||

@@ -1,4 +1,5 @@
-// rsv_segdistinct.hip -- K5: S independent Sampler.distinct streams per launch (rsv_distinct_segmented).
+// rsv_segdistinct.hip -- K5: S independent Sampler.distinct streams per launch, stateless
+// (rsv_distinct_segmented) and resumed from caller-held state (rsv_distinct_segmented_update / _merge).
 // No reference counterpart; = S separate RandomValues instances (Sampler.scala:383-412), each seeded
 // with java.util.Random(seed + stream_base + s), in the engine's set order (RSV_DISTINCT_SET): stream
 // s keeps the min(k, D_s) distinct keys with the smallest (scrambled hash, key), written ascending.
@@ -22,26 +23,227 @@
 // entry equal to the pad sorts among the pads and is still inside the first m + c), drop of adjacent
 // equals with an in-place block scan, keep the first k, reload T.
 //
-// Forms (DESIGN.md "Segmented distinct"):
+// Forms (DESIGN.md "Segmented distinct"; with_form below is the only place that names them):
 //   k <= 64    NT = 64 (one wave per stream), P = 256: 4 KB of LDS, 32 streams resident per CU
 //   k <= 256   NT = 64, P = 512: 8 KB, 19 streams per CU
 //   k <= 1024  NT = 256, P = 2048: 32 KB, 4 workgroups per CU
 //   k <= 4096  NT = 1024, P = 8192: 128 KB, one workgroup per CU
 // The smaller P for k <= 64 is deliberate: a buffer that fills sooner gives a fresher T, so fewer
 // entries are admitted, and a sort of 256 costs 0.4 of a sort of 512.
+//
+// Resumed: the state is the caller's: per row r counts[r] entries (h, key) ascending, in the layout
+// the stateless launch writes.  Bottom-k by (h, key) over distinct keys is a function of the key set
+// alone, so bottomk(A u B) = bottomk(bottomk(A) u B): a row resumed from its stored set and fed the
+// next piece ends where one stateless launch over the concatenation ends.  The
+// element loop (take_piece), the forms, the grid and the row's epilogue (finish_row) are the
+// stateless kernel's own; segstate_kernel adds
+//   prologue   m0 = clamp(counts[r], 0, k); the row's pairs into se[0, m0) (coalesced global loads,
+//              one 16-byte LDS write per entry); s_cnt = n_tot = m = m0; T = se[k-1] when m0 == k,
+//              so a full row rejects from its first element on.
+//   input      UPDATE: segment b = keys[offsets[b], offsets[b+1]) hashed and scrambled with the
+//              row's (r0, r1), row r = stream_ids[b] (or b).  MERGE: for every part p the first
+//              clamp(part_counts[p][r], 0, k) slots of its row r, h taken as stored.
+//   epilogue   in place, behind the barrier after the last LDS read of the team; a row with no
+//              input, and a row whose input admitted nothing, writes nothing (a full row in steady
+//              state moves no state bytes out).
+// Nothing read from the state or from the ids indexes memory unclamped: the count is clamped into
+// [0, k], an id outside [0, num_states) skips the segment.
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/reservoir_hip.h"
 #include "rsv_device.h"
 #include "rsv_internal.h"
-#include "rsv_segdistinct.h"
 
 namespace rsv {
 
 namespace {
 
-using namespace segd;
+constexpr int kU = 4;  // elements per lane and iteration
+constexpr int64_t kMaxI64 = INT64_MAX;
 
+// java.util.Random(seed): the first two nextLong() (RandomValues r0, r1, Sampler.scala:385-388)
+__device__ __forceinline__ void java_r0r1(uint64_t seed, int64_t& r0, int64_t& r1) {
+    constexpr uint64_t kMul = 0x5DEECE66DULL, kMask = (1ULL << 48) - 1;
+    uint64_t st = (seed ^ kMul) & kMask;
+    int64_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        st = (st * kMul + 0xBULL) & kMask;
+        w[i] = (int64_t)(int32_t)(uint32_t)(st >> 16);
+    }
+    r0 = (int64_t)(((uint64_t)w[0] << 32) + (uint64_t)w[1]);
+    r1 = (int64_t)(((uint64_t)w[2] << 32) + (uint64_t)w[3]);
+}
+
+// one LDS entry: 16 bytes, moved with one ds_read_b128 / ds_write_b128
+struct alignas(16) Ent {
+    int64_t h, key;
+};
+
+__device__ __forceinline__ bool ent_less(const Ent& a, const Ent& b) { return a.h < b.h || (a.h == b.h && a.key < b.key); }
+__device__ __forceinline__ bool ent_eq(const Ent& a, const Ent& b) { return a.h == b.h && a.key == b.key; }
+
+// Sort + dedup + trim of the team's first n entries; returns the new set size min(k, distinct).
+template <int NT>
+__device__ __forceinline__ uint32_t merge_set(Ent* __restrict__ se, uint32_t n, uint32_t k, uint32_t* __restrict__ s_scan) {
+    const uint32_t tid = threadIdx.x;
+    if (n == 0) return 0;
+    uint32_t sz2 = 2;
+    while (sz2 < n) sz2 <<= 1;
+    for (uint32_t i = n + tid; i < sz2; i += NT) se[i] = Ent{kMaxI64, kMaxI64};
+    __syncthreads();
+    for (uint32_t sz = 2; sz <= sz2; sz <<= 1) {
+        for (uint32_t j = sz >> 1; j > 0; j >>= 1) {
+            for (uint32_t t = tid; t < (sz2 >> 1); t += NT) {
+                const uint32_t l = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const bool asc = (l & sz) == 0;
+                const Ent a = se[l], b = se[l + j];
+                if (ent_less(b, a) == asc && !ent_eq(a, b)) {
+                    se[l] = b;
+                    se[l + j] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // in-place compaction of the first occurrences, NT entries per round.  An entry moves to a
+    // position <= its own, and entry base - 1 is only ever overwritten by itself, so the next
+    // round's look-behind reads what the sort left.
+    constexpr uint32_t kWavesT = NT / 64;
+    uint32_t run = 0;
+    for (uint32_t base = 0; base < n && run < k; base += NT) {
+        const uint32_t i = base + tid;
+        Ent e{0, 0};
+        bool first = false;
+        if (i < n) {
+            e = se[i];
+            first = i == 0 || !ent_eq(e, se[i - 1]);
+        }
+        const uint64_t mask = __ballot(first);
+        uint32_t pre = (uint32_t)__popcll(mask & ((1ULL << (tid & 63)) - 1));
+        uint32_t total = (uint32_t)__popcll(mask);
+        if constexpr (kWavesT > 1) {
+            if ((tid & 63) == 0) s_scan[tid >> 6] = total;
+            __syncthreads();  // also: every read of this round is done
+            uint32_t before = 0;
+            total = 0;
+            for (uint32_t w = 0; w < kWavesT; ++w) {
+                const uint32_t c = s_scan[w];
+                if (w < (tid >> 6)) before += c;
+                total += c;
+            }
+            pre += before;
+        } else {
+            __syncthreads();
+        }
+        const uint32_t pos = run + pre;
+        if (first && pos < k) se[pos] = e;
+        run += total;
+        __syncthreads();
+    }
+    return run < k ? run : k;
+}
+
+// the team's registers across the pieces of one row (uniform over the team)
+struct Team {
+    uint32_t m;      // set size
+    uint32_t n_tot;  // set + waiting candidates (= s_cnt, read between two barriers)
+    int64_t Th, Tk;  // admission threshold: the k-th entry, or (max, max) below k entries
+    bool dirty;      // something was appended since the team started on the row
+};
+
+// The element loop over one piece [lo, hi) of keys (and hashes).  SCRAMBLE: h = scramble(r0, r1,
+// hash(key)); otherwise h = hashes[i] as stored.
+template <typename KeyT, int NT, bool SCRAMBLE>
+__device__ __forceinline__ void take_piece(Ent* __restrict__ se, uint32_t* __restrict__ s_cnt, uint32_t* __restrict__ s_scan,
+                                           const KeyT* __restrict__ keys, const int64_t* __restrict__ hashes, int64_t lo,
+                                           int64_t hi, uint32_t k, uint32_t P, int hash_kind, int64_t r0, int64_t r1,
+                                           Team& t) {
+    const uint32_t tid = threadIdx.x;
+    constexpr int64_t kChunk = (int64_t)NT * kU;
+    for (int64_t base = lo; base < hi; base += kChunk) {
+        // the loads first: kU in flight per lane
+        int64_t key[kU], hv[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int64_t i = base + (int64_t)u * NT + tid;
+            key[u] = 0;
+            hv[u] = 0;
+            if (i < hi) {
+                key[u] = (int64_t)keys[i];
+                if (!SCRAMBLE || hash_kind == kHashPrecomputed) hv[u] = hashes[i];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int64_t i = base + (int64_t)u * NT + tid;
+            if (base + (int64_t)u * NT >= hi) break;  // uniform: the tail chunk's empty steps
+            if (t.n_tot + NT > P || (t.m < k && t.n_tot >= 4 * k)) {
+                t.m = merge_set<NT>(se, t.n_tot, k, s_scan);
+                if (t.m == k) {
+                    t.Th = se[k - 1].h;
+                    t.Tk = se[k - 1].key;
+                }
+                __syncthreads();  // T is read before the appends below overwrite anything
+                if (tid == 0) *s_cnt = t.m;
+                t.n_tot = t.m;
+                __syncthreads();
+            }
+            int64_t h;
+            if constexpr (SCRAMBLE) {
+                int64_t hashed;
+                if (hash_kind == kHashPrecomputed)
+                    hashed = hv[u];
+                else if (hash_kind == kHashJavaLong)
+                    hashed = hash_of<int64_t, kHashJavaLong>(key[u]);
+                else if (hash_kind == kHashJavaInt)
+                    hashed = hash_of<int64_t, kHashJavaInt>(key[u]);
+                else
+                    hashed = key[u];  // identity: the sign-extended key
+                h = scramble(r0, r1, hashed);
+            } else {
+                h = hv[u];
+            }
+            const bool pass = i < hi && (h < t.Th || (h == t.Th && key[u] <= t.Tk));
+            const uint64_t mask = __ballot(pass);
+            if (mask) {
+                const uint32_t lead = (uint32_t)(__ffsll((long long)mask) - 1);  // the wave's first admitting lane
+                uint32_t b = 0;
+                if ((tid & 63) == lead) b = atomicAdd(s_cnt, (uint32_t)__popcll(mask));
+                b = (uint32_t)__shfl((int)b, (int)lead);
+                if (pass) se[b + (uint32_t)__popcll(mask & ((1ULL << (tid & 63)) - 1))] = Ent{h, key[u]};
+            }
+            // every wave reads the same count: no append of the next step runs before the
+            // second barrier
+            __syncthreads();
+            const uint32_t c = *s_cnt;
+            t.dirty |= c != t.n_tot;
+            t.n_tot = c;
+            __syncthreads();
+        }
+    }
+}
+
+// The row's epilogue: the last merge (merge_set of nothing is 0, an empty row needs no case of its
+// own), then se[0, m) and zeros up to k, then the count.  HASHES_OPTIONAL: hashes may be null (the
+// stateless launch's out_hashes; a state always has them, and its kernels carry no test).
+template <typename KeyT, int NT, bool HASHES_OPTIONAL>
+__device__ __forceinline__ void finish_row(Ent* se, uint32_t* s_scan, Team& t, uint32_t k, int64_t row, KeyT* keys,
+                                           int64_t* hashes, int64_t* counts) {
+    const uint32_t tid = threadIdx.x;
+    if (t.n_tot != t.m) t.m = merge_set<NT>(se, t.n_tot, k, s_scan);
+    __syncthreads();
+    const int64_t ob = row * (int64_t)k;
+    for (uint32_t i = tid; i < k; i += NT) {
+        const Ent e = i < t.m ? se[i] : Ent{0, 0};
+        keys[ob + i] = (KeyT)e.key;
+        if (!HASHES_OPTIONAL || hashes) hashes[ob + i] = e.h;
+    }
+    if (tid == 0) counts[row] = t.m;
+}
+
+// Stateless: no prologue, row = stream index, every row is written.
 template <typename KeyT, int NT>
 __global__ __launch_bounds__(NT) void segdistinct_kernel(const KeyT* __restrict__ keys, const int64_t* __restrict__ hashes,
                                                          const int64_t* __restrict__ offsets, int64_t S, uint32_t k,
@@ -52,112 +254,103 @@ __global__ __launch_bounds__(NT) void segdistinct_kernel(const KeyT* __restrict_
     Ent* const se = (Ent*)seg_lds;
     __shared__ uint32_t s_cnt;
     __shared__ uint32_t s_scan[NT / 64 > 1 ? NT / 64 : 1];
-    const uint32_t tid = threadIdx.x;
-    constexpr int64_t kChunk = (int64_t)NT * kU;
 
     for (int64_t s = blockIdx.x; s < S; s += gridDim.x) {
-        const int64_t lo = offsets[s], hi = offsets[s + 1];
         int64_t r0, r1;
         java_r0r1(seed0 + (uint64_t)s, r0, r1);
-        uint32_t m = 0;      // set size
-        uint32_t n_tot = 0;  // set + waiting candidates (= s_cnt, read between two barriers)
-        int64_t Th = kMaxI64, Tk = kMaxI64;
         __syncthreads();  // the previous stream's output reads are done
-        if (tid == 0) s_cnt = 0;
+        if (threadIdx.x == 0) s_cnt = 0;
         __syncthreads();
-        for (int64_t base = lo; base < hi; base += kChunk) {
-            // the loads first: kU in flight per lane
-            int64_t key[kU], hv[kU];
-#pragma unroll
-            for (int u = 0; u < kU; ++u) {
-                const int64_t i = base + (int64_t)u * NT + tid;
-                key[u] = 0;
-                hv[u] = 0;
-                if (i < hi) {
-                    key[u] = (int64_t)keys[i];
-                    if (hash_kind == kHashPrecomputed) hv[u] = hashes[i];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < kU; ++u) {
-                const int64_t i = base + (int64_t)u * NT + tid;
-                if (base + (int64_t)u * NT >= hi) break;  // uniform: the tail chunk's empty steps
-                if (n_tot + NT > P || (m < k && n_tot >= 4 * k)) {
-                    m = merge_set<NT>(se, n_tot, k, s_scan);
-                    if (m == k) {
-                        Th = se[k - 1].h;
-                        Tk = se[k - 1].key;
-                    }
-                    __syncthreads();  // T is read before the appends below overwrite anything
-                    if (tid == 0) s_cnt = m;
-                    n_tot = m;
-                    __syncthreads();
-                }
-                int64_t hashed;
-                if (hash_kind == kHashPrecomputed)
-                    hashed = hv[u];
-                else if (hash_kind == kHashJavaLong)
-                    hashed = hash_of<int64_t, kHashJavaLong>(key[u]);
-                else if (hash_kind == kHashJavaInt)
-                    hashed = hash_of<int64_t, kHashJavaInt>(key[u]);
-                else
-                    hashed = key[u];  // identity: the sign-extended key
-                const int64_t h = scramble(r0, r1, hashed);
-                const bool pass = i < hi && (h < Th || (h == Th && key[u] <= Tk));
-                const uint64_t mask = __ballot(pass);
-                if (mask) {
-                    uint32_t b = 0;
-                    if ((tid & 63) == (uint32_t)(__ffsll((long long)mask) - 1)) b = atomicAdd(&s_cnt, (uint32_t)__popcll(mask));
-                    b = (uint32_t)__shfl((int)b, __ffsll((long long)mask) - 1);
-                    if (pass) se[b + (uint32_t)__popcll(mask & ((1ULL << (tid & 63)) - 1))] = Ent{h, key[u]};
-                }
-                // every wave reads the same count: no append of the next step runs before the
-                // second barrier
-                __syncthreads();
-                n_tot = s_cnt;
-                __syncthreads();
-            }
-        }
-        if (n_tot != m || m == 0) m = merge_set<NT>(se, n_tot, k, s_scan);
-        __syncthreads();
-        const int64_t ob = s * (int64_t)k;
-        for (uint32_t i = tid; i < k; i += NT) {
-            const Ent e = i < m ? se[i] : Ent{0, 0};
-            out_keys[ob + i] = (KeyT)e.key;
-            if (out_hashes) out_hashes[ob + i] = e.h;
-        }
-        if (tid == 0) counts[s] = m;
+        Team t{0, 0, kMaxI64, kMaxI64, false};
+        take_piece<KeyT, NT, true>(se, &s_cnt, s_scan, keys, hashes, offsets[s], offsets[s + 1], k, P, hash_kind, r0, r1, t);
+        finish_row<KeyT, NT, true>(se, s_scan, t, k, s, out_keys, out_hashes, counts);
     }
 }
 
-template <typename KeyT, int NT>
-hipError_t launch_form(const void* keys, const int64_t* hashes, const int64_t* offsets, int64_t S, uint32_t k, uint32_t P,
-                       int hash_kind, uint64_t seed0, void* out_keys, int64_t* out_hashes, int64_t* counts,
-                       hipStream_t st) {
+// MERGE = false: in = the batch's keys / hashes / offsets, ids = stream ids or null, teams = segments.
+// MERGE = true:  in = the parts' keys / hashes, part_counts, teams = num_states (row r = team index).
+template <typename KeyT, int NT, bool MERGE>
+__global__ __launch_bounds__(NT) void segstate_kernel(const KeyT* in_keys, const int64_t* in_hashes,
+                                                      const int64_t* __restrict__ offsets,
+                                                      const int64_t* __restrict__ ids, const int64_t* part_counts,
+                                                      int64_t teams, int64_t num_states, int32_t parts, uint32_t k,
+                                                      uint32_t P, int hash_kind, uint64_t seed0, KeyT* state_keys,
+                                                      int64_t* state_hashes, int64_t* state_counts) {
+    extern __shared__ __align__(16) unsigned char seg_lds[];
+    Ent* const se = (Ent*)seg_lds;
+    __shared__ uint32_t s_cnt;
+    __shared__ uint32_t s_scan[NT / 64 > 1 ? NT / 64 : 1];
+    const uint32_t tid = threadIdx.x;
+
+    for (int64_t b = blockIdx.x; b < teams; b += gridDim.x) {
+        // everything that decides the control flow below is uniform over the team
+        int64_t r = b, lo = 0, hi = 0;
+        if constexpr (!MERGE) {
+            if (ids) r = ids[b];
+            if (r < 0 || r >= num_states) continue;  // an id outside the state: no row is addressed
+            lo = offsets[b];
+            hi = offsets[b + 1];
+            if (hi <= lo) continue;  // an empty segment leaves its row as it is
+        }
+        const int64_t ob = r * (int64_t)k;
+        const int64_t c0 = state_counts[r];
+        const uint32_t m0 = c0 <= 0 ? 0u : (c0 >= (int64_t)k ? k : (uint32_t)c0);
+        __syncthreads();  // the previous row's output reads are done
+        for (uint32_t i = tid; i < m0; i += NT) se[i] = Ent{state_hashes[ob + i], (int64_t)state_keys[ob + i]};
+        if (tid == 0) s_cnt = m0;
+        __syncthreads();
+        Team t{m0, m0, kMaxI64, kMaxI64, false};
+        if (m0 == k) {
+            t.Th = se[k - 1].h;
+            t.Tk = se[k - 1].key;
+        }
+        // (no barrier needed before the first append: it lands at se[m0] or behind, and a merge
+        // has its own)
+        if constexpr (MERGE) {
+            for (int32_t p = 0; p < parts; ++p) {
+                const int64_t row = (int64_t)p * num_states + r;
+                const int64_t pc = part_counts[row];
+                const int64_t n = pc <= 0 ? 0 : (pc >= (int64_t)k ? (int64_t)k : pc);
+                const int64_t pb = row * (int64_t)k;
+                take_piece<KeyT, NT, false>(se, &s_cnt, s_scan, in_keys, in_hashes, pb, pb + n, k, P, hash_kind, 0, 0, t);
+            }
+        } else {
+            int64_t r0, r1;
+            java_r0r1(seed0 + (uint64_t)r, r0, r1);
+            take_piece<KeyT, NT, true>(se, &s_cnt, s_scan, in_keys, in_hashes, lo, hi, k, P, hash_kind, r0, r1, t);
+        }
+        if (!t.dirty) continue;  // nothing admitted: the row stands as it is
+        finish_row<KeyT, NT, false>(se, s_scan, t, k, r, state_keys, state_hashes, state_counts);
+    }
+}
+
+// The forms: f(KeyT{}, NT as an integral_constant, P) for the key width and k of a launch.
+template <typename KeyT, typename F>
+hipError_t with_form_of(uint32_t k, F& f) {
+    if (k <= kSegDistinctWaveMaxK)  // P >= k + 192: three steps of 64 fit behind a full set
+        return f(KeyT{}, std::integral_constant<int, 64>{}, k <= 64 ? 256u : 512u);
+    if (k <= 1024) return f(KeyT{}, std::integral_constant<int, 256>{}, 2048u);
+    return f(KeyT{}, std::integral_constant<int, 1024>{}, 8192u);
+}
+
+template <typename F>
+hipError_t with_form(int key_width, uint32_t k, F f) {
+    return key_width == 8 ? with_form_of<int64_t>(k, f) : with_form_of<int32_t>(k, f);
+}
+
+// One team of nt threads with P entries of LDS per item, grid-stride.
+template <typename... Params, typename... Args>
+hipError_t launch_teams(void (*kernel)(Params...), int nt, int64_t teams, uint32_t P, hipStream_t st, Args... args) {
     const size_t lds = (size_t)P * 16;
     if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)segdistinct_kernel<KeyT, NT>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     // the teams the 256 CUs hold at once (LDS and 32 waves per CU), four times over
-    const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>((160 * 1024) / (lds + 256), 32 / (NT / 64)));
-    const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)S, 256ull * per_cu * 4);
-    hipLaunchKernelGGL((segdistinct_kernel<KeyT, NT>), dim3(grid), dim3(NT), lds, st, (const KeyT*)keys, hashes, offsets,
-                       S, k, P, hash_kind, seed0, (KeyT*)out_keys, out_hashes, counts);
+    const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>((160 * 1024) / (lds + 256), 32 / (nt / 64)));
+    const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)teams, 256ull * per_cu * 4);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(nt), lds, st, args...);
     return hipGetLastError();
-}
-
-template <typename KeyT>
-hipError_t launch_keyed(const void* keys, const int64_t* hashes, const int64_t* offsets, int64_t S, uint32_t k,
-                        int hash_kind, uint64_t seed0, void* out_keys, int64_t* out_hashes, int64_t* counts,
-                        hipStream_t st) {
-    if (k <= kSegDistinctWaveMaxK)  // P >= k + 192: three steps of 64 fit behind a full set
-        return launch_form<KeyT, 64>(keys, hashes, offsets, S, k, k <= 64 ? 256 : 512, hash_kind, seed0, out_keys,
-                                     out_hashes, counts, st);
-    if (k <= 1024)
-        return launch_form<KeyT, 256>(keys, hashes, offsets, S, k, 2048, hash_kind, seed0, out_keys, out_hashes, counts, st);
-    return launch_form<KeyT, 1024>(keys, hashes, offsets, S, k, 8192, hash_kind, seed0, out_keys, out_hashes, counts, st);
 }
 
 }  // namespace
@@ -166,9 +359,40 @@ hipError_t launch_segdistinct(const void* keys, int key_width, const int64_t* ha
                               uint32_t k, int hash_kind, uint64_t seed0, void* out_keys, int64_t* out_hashes,
                               int64_t* counts, hipStream_t st) {
     if (S <= 0) return hipSuccess;
-    if (key_width == 8)
-        return launch_keyed<int64_t>(keys, hashes, offsets, S, k, hash_kind, seed0, out_keys, out_hashes, counts, st);
-    return launch_keyed<int32_t>(keys, hashes, offsets, S, k, hash_kind, seed0, out_keys, out_hashes, counts, st);
+    return with_form(key_width, k, [&](auto key, auto nt, uint32_t P) {
+        using KeyT = decltype(key);
+        constexpr int NT = decltype(nt)::value;
+        return launch_teams(segdistinct_kernel<KeyT, NT>, NT, S, P, st, (const KeyT*)keys, hashes, offsets, S, k, P,
+                            hash_kind, seed0, (KeyT*)out_keys, out_hashes, counts);
+    });
+}
+
+hipError_t launch_segdistinct_update(const void* keys, int key_width, const int64_t* hashes, const int64_t* offsets,
+                                     const int64_t* stream_ids, int64_t num_segments, int64_t num_states, uint32_t k,
+                                     int hash_kind, uint64_t seed0, void* state_keys, int64_t* state_hashes,
+                                     int64_t* state_counts, hipStream_t st) {
+    if (num_segments <= 0 || num_states <= 0) return hipSuccess;
+    return with_form(key_width, k, [&](auto key, auto nt, uint32_t P) {
+        using KeyT = decltype(key);
+        constexpr int NT = decltype(nt)::value;
+        return launch_teams(segstate_kernel<KeyT, NT, false>, NT, num_segments, P, st, (const KeyT*)keys, hashes,
+                            offsets, stream_ids, (const int64_t*)nullptr, num_segments, num_states, (int32_t)0, k, P,
+                            hash_kind, seed0, (KeyT*)state_keys, state_hashes, state_counts);
+    });
+}
+
+hipError_t launch_segdistinct_merge(const void* part_keys, int key_width, const int64_t* part_hashes,
+                                    const int64_t* part_counts, int32_t parts, int64_t num_states, uint32_t k,
+                                    void* state_keys, int64_t* state_hashes, int64_t* state_counts, hipStream_t st) {
+    if (parts <= 0 || num_states <= 0) return hipSuccess;
+    return with_form(key_width, k, [&](auto key, auto nt, uint32_t P) {
+        using KeyT = decltype(key);
+        constexpr int NT = decltype(nt)::value;
+        return launch_teams(segstate_kernel<KeyT, NT, true>, NT, num_states, P, st, (const KeyT*)part_keys,
+                            part_hashes, (const int64_t*)nullptr, (const int64_t*)nullptr, part_counts, num_states,
+                            num_states, parts, k, P, (int)kHashPrecomputed, (uint64_t)0, (KeyT*)state_keys, state_hashes,
+                            state_counts);
+    });
 }
 
 }  // namespace rsv

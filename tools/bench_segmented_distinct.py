@@ -33,6 +33,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def make_keys(torch, dev, S, n, dup):
+    """(S, n) random int64 keys; ~dup of each stream's positions repeat another position of that stream."""
+    g = torch.Generator(device=dev)
+    g.manual_seed(0x5EED)
+    keys = torch.empty((S, n), dtype=torch.int64, device=dev)
+    rows = max(1, (1 << 27) // n)
+    for r0 in range(0, S, rows):
+        r1 = min(S, r0 + rows)
+        v = torch.randint(-2**63, 2**63 - 1, (r1 - r0, n), dtype=torch.int64, device=dev, generator=g)
+        src = torch.randint(0, n, (r1 - r0, n), dtype=torch.int64, device=dev, generator=g)
+        rep = torch.rand((r1 - r0, n), device=dev, generator=g) < dup
+        keys[r0:r1] = torch.where(rep, torch.gather(v, 1, src), v)
+        del v, src, rep
+    return keys
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=1 << 20)
@@ -59,18 +75,7 @@ def main() -> None:
     S, n, k = a.streams, a.len, a.k
     total = S * n
 
-    # keys: random int64, then ~dup of each stream's positions repeat another position of that stream
-    g = torch.Generator(device=dev)
-    g.manual_seed(0x5EED)
-    keys = torch.empty((S, n), dtype=torch.int64, device=dev)
-    rows = max(1, (1 << 27) // n)
-    for r0 in range(0, S, rows):
-        r1 = min(S, r0 + rows)
-        v = torch.randint(-2**63, 2**63 - 1, (r1 - r0, n), dtype=torch.int64, device=dev, generator=g)
-        src = torch.randint(0, n, (r1 - r0, n), dtype=torch.int64, device=dev, generator=g)
-        rep = torch.rand((r1 - r0, n), device=dev, generator=g) < a.dup
-        keys[r0:r1] = torch.where(rep, torch.gather(v, 1, src), v)
-        del v, src, rep
+    keys = make_keys(torch, dev, S, n, a.dup)
     flat = keys.view(-1)
     offs = torch.arange(0, total + 1, n, dtype=torch.int64, device=dev)
     torch.cuda.synchronize()

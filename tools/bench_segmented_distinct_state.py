@@ -1,6 +1,6 @@
 """Resumed segmented Sampler.distinct (batch.SegmentedDistinct: rsv_distinct_segmented_update / _merge).
 
---mode update (default): the streams of tools/bench_segmented_distinct.py (the same key generator:
+--mode update (default): the streams of tools/bench_segmented_distinct.py (its make_keys:
 S streams x len int64 keys, ~dup repeats inside each stream, identity hash) cut into B equal batches
 and fed as B update launches into one state, against one stateless rsv_distinct_segmented launch over
 the same keys in the same run.  Device events around every launch, --warmup runs then --steps timed
@@ -38,22 +38,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-
-def make_keys(torch, dev, S, n, dup):
-    """bench_segmented_distinct.py's keys: random int64, ~dup of each stream's positions repeat another."""
-    g = torch.Generator(device=dev)
-    g.manual_seed(0x5EED)
-    keys = torch.empty((S, n), dtype=torch.int64, device=dev)
-    rows = max(1, (1 << 27) // n)
-    for r0 in range(0, S, rows):
-        r1 = min(S, r0 + rows)
-        v = torch.randint(-2**63, 2**63 - 1, (r1 - r0, n), dtype=torch.int64, device=dev, generator=g)
-        src = torch.randint(0, n, (r1 - r0, n), dtype=torch.int64, device=dev, generator=g)
-        rep = torch.rand((r1 - r0, n), device=dev, generator=g) < dup
-        keys[r0:r1] = torch.where(rep, torch.gather(v, 1, src), v)
-        del v, src, rep
-    return keys
+from bench_segmented_distinct import make_keys  # noqa: E402
 
 
 def timed(torch, fn):
