@@ -356,6 +356,42 @@ rsv_status rsv_sample_segmented(const void* keys_dev, const int64_t* offsets_dev
                                 int32_t key_width, int32_t k, uint64_t seed, uint64_t stream_base,
                                 void* out_dev, int64_t* counts_dev, void* hip_stream);
 
+/* Segmented sampling, resumed: long-lived Algorithm-R samplers advanced by one launch per batch.  The
+ * state is the caller's device memory: state_keys_dev[num_states*k] (key_width values),
+ * state_idx_dev[num_states*k] (int64: the global index of each slot's last writer, -1 = empty slot,
+ * the convention of rsv_export_state) and state_next_dev[num_states] (int64: one past the highest
+ * index the row has consumed).  A fresh state is idx = -1, next = 0, keys anything.
+ * For stream (seed, stream id) let slot(i) = i for i < k, else the draw j_i (format R2) if j_i < k;
+ * slot j of a row that has consumed the index set I holds the key of max{i in I : slot(i) = j}.
+ * That max is associative and commutative: any sequence of updates and merges whose pieces cover
+ * [0, n) leaves keys and idx exactly as one rsv_sample_segmented launch over the whole stream does.
+ * Segment b = keys_dev[offsets[b] .. offsets[b+1]) goes into row r = stream_ids_dev[b], or r = b when
+ * stream_ids_dev is NULL (then num_segments <= num_states), with Philox stream id stream_base + r.
+ * Its first element has global index bases_dev[b], or state_next_dev[r] when bases_dev is NULL.  A slot
+ * is written (key and idx) only where the segment's last writer w -- fill indices < k included -- has
+ * state_idx < w; state_next[r] = max(state_next[r], base + len).  A segment whose id lies outside
+ * [0, num_states), whose base is negative or that is empty is skipped; rows that no segment names
+ * are not touched.  The ids of one launch must be distinct (the caller's contract).
+ * key_width 4 or 8; 1 <= k <= 15104 (the 64-bit winner table of the one-workgroup-per-stream form
+ * has to fit LDS; larger: RSV_E_UNSUPPORTED).  Stateless and stream-ordered on hip_stream: no host
+ * wait, no allocation.  All pointers are device pointers. */
+rsv_status rsv_sample_segmented_update(const void* keys_dev, const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                       const int64_t* bases_dev, int64_t num_segments, int64_t num_states,
+                                       int32_t key_width, int32_t k, uint64_t seed, uint64_t stream_base,
+                                       void* state_keys_dev, int64_t* state_idx_dev, int64_t* state_next_dev,
+                                       void* hip_stream);
+
+/* Combine of segmented sampler states: part_* are `parts` states laid back to back
+ * ([parts][num_states][k] keys and idx, [parts][num_states] next: what an all-gather of every rank's
+ * state tensors gives).  Per slot the largest idx among the row and the parts wins (a slot that no
+ * part beats is not written); next becomes the max over the row and the parts.  All parts and the
+ * state must come from the same seed and stream_base (the caller's contract).  Stateless and
+ * stream-ordered like the update. */
+rsv_status rsv_sample_segmented_merge(const void* part_keys_dev, const int64_t* part_idx_dev,
+                                      const int64_t* part_next_dev, int32_t parts, int64_t num_states,
+                                      int32_t key_width, int32_t k, void* state_keys_dev, int64_t* state_idx_dev,
+                                      int64_t* state_next_dev, void* hip_stream);
+
 /* Segmented distinct: S independent Sampler.distinct samplers (no reference counterpart; = S separate
  * RandomValues instances, S:383-412).  Stream s covers keys_dev[offsets[s] .. offsets[s+1]) and is
  * seeded like a single DISTINCT handle with java.util.Random(seed + stream_base + s) (wrapping to a

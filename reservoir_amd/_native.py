@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "rsv_sample_indexed", "rsv_fill_slots", "rsv_abort_indexed", "rsv_retain_log", "rsv_commit_indexed",
     "rsv_distinct_candidates", "rsv_candidates_read", "rsv_candidates_commit", "rsv_candidates_abort",
     "rsv_distinct_segmented", "rsv_distinct_segmented_update", "rsv_distinct_segmented_merge",
+    "rsv_sample_segmented_update", "rsv_sample_segmented_merge",
 )
 
 
@@ -130,6 +131,8 @@ def load():
     L.rsv_export_packed.argtypes = [vp, vp]
     L.rsv_merge_packed.argtypes = [vp, vp, i32, i64, i64]
     L.rsv_sample_segmented.argtypes = [vp, vp, i64, i32, i32, u64, u64, vp, vp, vp]
+    L.rsv_sample_segmented_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, u64, u64, vp, vp, vp, vp]
+    L.rsv_sample_segmented_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
     L.rsv_distinct_segmented.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_distinct_segmented_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_distinct_segmented_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
@@ -163,7 +166,8 @@ def load():
                  "rsv_sample_indexed", "rsv_fill_slots", "rsv_abort_indexed", "rsv_retain_log",
                  "rsv_commit_indexed", "rsv_distinct_candidates", "rsv_candidates_read",
                  "rsv_candidates_commit", "rsv_candidates_abort", "rsv_distinct_segmented",
-                 "rsv_distinct_segmented_update", "rsv_distinct_segmented_merge"):
+                 "rsv_distinct_segmented_update", "rsv_distinct_segmented_merge",
+                 "rsv_sample_segmented_update", "rsv_sample_segmented_merge"):
         getattr(L, name).restype = i32
     if L.rsv_abi_version() != 1:
         raise ImportError("libreservoir_hip.so ABI version mismatch")

@@ -7,6 +7,8 @@ libreservoir_hip.so.  Every function raises if the engine is unavailable.
     distinct_segmented -- K5: S independent Sampler.distinct streams in one launch (bottom-k per stream)
     SegmentedDistinct -- K5 resumed: the same S streams as caller-held state, advanced by one launch
                          per micro-batch (update) and combined across launches, GPUs and ranks (merge)
+    SegmentedSampler  -- K2 resumed: S Sampler.apply streams as caller-held state (keys, idx, next), fed in
+                         pieces from any start index (update) and combined per slot by largest index (merge)
     replay_events     -- K1': apply the reference's Algorithm-L eviction events on the GPU
     export_draws      -- the per-element draw sequence j_i of draw format R2
 """
@@ -78,6 +80,21 @@ def _segd_inputs(torch, keys, offsets, hashes, state=None):
         # an empty tensor has no address; the engine wants one for precomputed hashes
         hashes = hashes.contiguous() if hashes.numel() else torch.empty(1, dtype=torch.int64, device=keys.device)
     return keys.contiguous(), offsets.contiguous(), hashes
+
+
+def _check_stream_ids(torch, stream_ids, S: int) -> None:
+    """The row ids of one update: inside [0, S) and distinct, verified on the device (one host wait)."""
+    if S <= 0:
+        return
+    B = stream_ids.numel()
+    outside = (stream_ids < 0) | (stream_ids >= S)
+    seen = torch.zeros(S, dtype=torch.int32, device=stream_ids.device)
+    seen.index_add_(0, stream_ids.clamp(0, S - 1), torch.ones(B, dtype=torch.int32, device=stream_ids.device))
+    bad = torch.stack([outside.any(), (seen > 1).any()]).cpu()  # the one host wait
+    if bool(bad[0]):
+        raise N.IllegalArgumentException(f"stream_ids outside [0, {S})")
+    if bool(bad[1]):
+        raise N.IllegalArgumentException("stream_ids repeat a row within one update")
 
 
 def distinct_segmented(keys, offsets, k: int, seed: int, stream_base: int = 0, hash: str = "default", hashes=None):
@@ -176,16 +193,8 @@ class SegmentedDistinct:
             if not stream_ids.is_cuda or stream_ids.dtype != torch.int64 or stream_ids.numel() != B:
                 raise N.IllegalArgumentException("stream_ids must be an int64 device tensor, one per segment")
             stream_ids = stream_ids.contiguous()
-            if check_ids and self.num_streams > 0:
-                S = self.num_streams
-                outside = (stream_ids < 0) | (stream_ids >= S)
-                seen = torch.zeros(S, dtype=torch.int32, device=stream_ids.device)
-                seen.index_add_(0, stream_ids.clamp(0, S - 1), torch.ones(B, dtype=torch.int32, device=stream_ids.device))
-                bad = torch.stack([outside.any(), (seen > 1).any()]).cpu()  # the one host wait
-                if bool(bad[0]):
-                    raise N.IllegalArgumentException(f"stream_ids outside [0, {S})")
-                if bool(bad[1]):
-                    raise N.IllegalArgumentException("stream_ids repeat a row within one update")
+            if check_ids:
+                _check_stream_ids(torch, stream_ids, self.num_streams)
         N.check(L.rsv_distinct_segmented_update(
             C.c_void_p(keys.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
             C.c_void_p(offsets.data_ptr()), C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
@@ -237,6 +246,137 @@ class SegmentedDistinct:
             C.c_void_p(part_keys.data_ptr()), C.c_void_p(part_hashes.data_ptr()), C.c_void_p(part_counts.data_ptr()),
             P, S, part_keys.element_size(), k, C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.hashes.data_ptr()),
             C.c_void_p(self.counts.data_ptr()), _stream_ptr(torch, dev)))
+        return self
+
+
+_SEG_SAMPLE_STATE_MAX_K = 15104  # rsv_internal.h kSegSampleStateMaxK
+
+
+class SegmentedSampler:
+    """S long-lived Sampler.apply streams advanced by one launch per batch (K2 resumed).
+
+    The state is three device tensors: keys (S, k); idx (S, k), the global index of each slot's
+    last writer, -1 for an empty slot; next (S,), one past the highest index a row has consumed.
+    Row s draws like a single "philox_r" Sampler with stream_id = stream_base + s.  Per slot the
+    largest index wins, so a row fed its stream in any number of update() calls -- in order, or out
+    of order with bases= -- or assembled by merge() from states that each saw a part of the stream,
+    ends with the keys sample_segmented gives over the whole stream.  Only idx and next are filled:
+    a slot with idx -1 is empty whatever its key holds.  Everything runs on torch's current stream.
+    """
+
+    def __init__(self, num_streams: int, k: int, seed: int, stream_base: int = 0, dtype=None, device=None):
+        import torch
+
+        N.load()
+        dtype = torch.int64 if dtype is None else dtype
+        if dtype not in (torch.int64, torch.int32):
+            raise N.IllegalArgumentException("keys must be int64/int32")
+        if num_streams < 0:
+            raise N.IllegalArgumentException("negative stream count")
+        if k <= 0:
+            raise N.IllegalArgumentException("k out of range")
+        if k > _SEG_SAMPLE_STATE_MAX_K:
+            raise N.ReservoirError(
+                f"SegmentedSampler holds k <= {_SEG_SAMPLE_STATE_MAX_K} per stream; use separate handles beyond")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise N.IllegalArgumentException("the state lives on the device")
+        self.num_streams, self.k = int(num_streams), int(k)
+        self.seed, self.stream_base = seed & (2**64 - 1), stream_base & (2**64 - 1)
+        self.keys = torch.empty((self.num_streams, self.k), dtype=dtype, device=dev)
+        self.idx = torch.full((self.num_streams, self.k), -1, dtype=torch.int64, device=dev)
+        self.next = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
+
+    @property
+    def counts(self):
+        """Filled slots per row: min(k, elements seen) once a row's pieces cover a prefix of its stream."""
+        return (self.idx >= 0).sum(1)
+
+    def update(self, keys, offsets, stream_ids=None, bases=None, check_ids: bool = True):
+        """Segment b = keys[offsets[b]:offsets[b+1]] into row stream_ids[b] (None: row b).
+
+        The segment's first element has global index bases[b] (None: the row's next).  The ids of
+        one call must be distinct and inside [0, num_streams).  check_ids=True verifies that on the
+        device before the launch (one host wait) and raises IllegalArgumentException;
+        check_ids=False keeps the call stream-ordered and leaves the contract to the caller (ids
+        outside the range, negative bases and empty segments are then skipped).  Rows that no
+        segment names are not touched.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        if not (keys.is_cuda and offsets.is_cuda):
+            raise N.IllegalArgumentException("keys and offsets must be device tensors")
+        if keys.dtype != self.keys.dtype or offsets.dtype != torch.int64:
+            raise N.IllegalArgumentException("keys must have the state's dtype and offsets must be int64")
+        dev = self.keys.device
+        if keys.device != dev or offsets.device != dev:
+            raise N.IllegalArgumentException("keys and offsets must live on the state's device")
+        keys, offsets = keys.contiguous(), offsets.contiguous()
+        B = offsets.numel() - 1
+        if B <= 0:
+            return self
+        for name, t in (("stream_ids", stream_ids), ("bases", bases)):
+            if t is not None and (not t.is_cuda or t.dtype != torch.int64 or t.numel() != B or t.device != dev):
+                raise N.IllegalArgumentException(f"{name} must be an int64 device tensor, one per segment")
+        if stream_ids is not None:
+            stream_ids = stream_ids.contiguous()
+            if check_ids:
+                _check_stream_ids(torch, stream_ids, self.num_streams)
+        if bases is not None:
+            bases = bases.contiguous()
+        N.check(L.rsv_sample_segmented_update(
+            C.c_void_p(keys.data_ptr()), C.c_void_p(offsets.data_ptr()),
+            C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
+            C.c_void_p(bases.data_ptr()) if bases is not None else None,
+            B, self.num_streams, keys.element_size(), self.k, self.seed, self.stream_base,
+            C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.idx.data_ptr()), C.c_void_p(self.next.data_ptr()),
+            _stream_ptr(torch, dev)))
+        return self
+
+    def merge(self, part_keys, part_idx=None, part_next=None):
+        """Per slot the largest idx among row s and row s of every part wins; next takes the max.
+
+        merge(part_keys, part_idx, part_next): tensors (P, S, k), (P, S, k), (P, S) -- or (S, k),
+        (S, k), (S,) for one part -- e.g. an all-gather of every rank's state tensors; or
+        merge(other, ...) with SegmentedSampler objects.  All parts must come from this state's
+        seed and stream_base.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        if isinstance(part_keys, SegmentedSampler):
+            others = [part_keys] + [o for o in (part_idx, part_next) if o is not None]
+            for o in others:
+                if not isinstance(o, SegmentedSampler) or (o.num_streams, o.k, o.seed, o.stream_base) != (
+                        self.num_streams, self.k, self.seed, self.stream_base):
+                    raise N.IllegalArgumentException("merge needs states of the same shape, seed and stream_base")
+            if len(others) == 1:
+                part_keys, part_idx, part_next = others[0].keys, others[0].idx, others[0].next
+            else:
+                part_keys = torch.stack([o.keys for o in others])
+                part_idx = torch.stack([o.idx for o in others])
+                part_next = torch.stack([o.next for o in others])
+        if part_idx is None or part_next is None:
+            raise N.NullPointerException("merge needs part_keys, part_idx and part_next")
+        S, k = self.num_streams, self.k
+        if part_keys.dim() == 2:
+            part_keys, part_idx, part_next = part_keys[None], part_idx[None], part_next[None]
+        P = part_keys.shape[0]
+        if tuple(part_keys.shape) != (P, S, k) or tuple(part_idx.shape) != (P, S, k) or tuple(part_next.shape) != (P, S):
+            raise N.IllegalArgumentException(f"parts must be shaped (P, {S}, {k}), (P, {S}, {k}), (P, {S})")
+        if part_keys.dtype != self.keys.dtype or part_idx.dtype != torch.int64 or part_next.dtype != torch.int64:
+            raise N.IllegalArgumentException("part keys must have the state's dtype, idx and next must be int64")
+        dev = self.keys.device
+        if part_keys.device != dev or part_idx.device != dev or part_next.device != dev:
+            raise N.IllegalArgumentException("parts must live on the state's device")
+        if P == 0 or S == 0:
+            return self
+        part_keys, part_idx, part_next = part_keys.contiguous(), part_idx.contiguous(), part_next.contiguous()
+        N.check(L.rsv_sample_segmented_merge(
+            C.c_void_p(part_keys.data_ptr()), C.c_void_p(part_idx.data_ptr()), C.c_void_p(part_next.data_ptr()),
+            P, S, part_keys.element_size(), k, C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.idx.data_ptr()),
+            C.c_void_p(self.next.data_ptr()), _stream_ptr(torch, dev)))
         return self
 
 

@@ -135,6 +135,19 @@ hipError_t launch_export_draws(const DrawParams& dp, uint64_t i0, int64_t n, uin
 hipError_t launch_segmented(const void* keys, int key_width, const int64_t* offsets, int64_t S,
                             uint32_t k, const DrawParams& dp, void* out, int64_t* counts,
                             hipStream_t st);
+// K2 resumed (rsv_segmented.hip): the streams as rows of caller-held state (keys[num_states*k], idx = the
+// global index of each slot's last writer or -1, next[num_states]); per slot the largest index wins.
+// update: segment b holds the indices [bases[b] (null: next[r]), + len) of row r = stream_ids[b] (null: b),
+// Philox stream dp.stream + r; merge: parts laid out [parts][num_states][k], [..][k], [parts][num_states].
+// k <= kSegSampleStateMaxK: the workgroup form's 64-bit winner table has to fit LDS (k2::lds_bytes_wg).
+constexpr uint32_t kSegSampleStateMaxK = 15104;
+hipError_t launch_segmented_update(const void* keys, int key_width, const int64_t* offsets, const int64_t* stream_ids,
+                                   const int64_t* bases, int64_t num_segments, int64_t num_states, uint32_t k,
+                                   const DrawParams& dp, void* state_keys, int64_t* state_idx, int64_t* state_next,
+                                   hipStream_t st);
+hipError_t launch_segmented_merge(const void* part_keys, int key_width, const int64_t* part_idx,
+                                  const int64_t* part_next, int32_t parts, int64_t num_states, uint32_t k,
+                                  void* state_keys, int64_t* state_idx, int64_t* state_next, hipStream_t st);
 // K5: segmented distinct (rsv_segdistinct.hip): per stream the bottom-k by (scrambled hash, key),
 // (r0, r1) from java.util.Random(seed0 + s); hashes only for kHashPrecomputed, out_hashes may be null.
 // k <= kSegDistinctMaxK; one wave per stream up to kSegDistinctWaveMaxK, one workgroup above.

@@ -106,6 +106,19 @@ __device__ __forceinline__ uint64_t draw_j(uint32_t b, uint32_t Lh, uint32_t Ll,
     return __umul64hi(((uint64_t)Uh << 32) | Ul, i1);
 }
 
+// the workgroup's table of T for the first kLut blocks, as k2_segmented and k2_segmented_wg build theirs
+// (the resumed kernels call this; the stateless ones keep their loops so that their code stays as measured)
+__device__ __forceinline__ void build_lut(uint16_t* lut, uint64_t dense_lim) {
+    for (uint32_t g = threadIdx.x; g < kLut; g += blockDim.x) {
+        const uint64_t i0 = (uint64_t)g << 4;
+        uint32_t T;
+        if (i0 + 1 >= dense_lim) T = 0;
+        else if (dense_lim + i0 <= 0xFFFFFFFFull) T = std::min<uint32_t>(256u, (uint32_t)(dense_lim + i0) / (uint32_t)(i0 + 1));
+        else T = block_threshold(i0, dense_lim);
+        lut[g] = (uint16_t)T;
+    }
+}
+
 struct Wave {
     u32x4* stash;
     uint16_t* q;
@@ -121,9 +134,11 @@ struct Wave {
 // DEFER (k <= 64): the lane's winner index is returned (-1: none) and the caller gathers its key
 // after storing the previous stream's, so the random gather's latency overlaps the next stream's draws.
 // (k >= kWGMinK takes the workgroup form below, k2_segmented_wg.)
-template <typename KeyT, bool SMALL, bool DEFER>
+// RES (k2_segmented_update): the segment holds the stream's indices [n0, n0 + len) -- SMALL then means
+// n0 + len < 2^27 -- and only the winner table is built: the caller writes it back into its state row.
+template <typename KeyT, bool SMALL, bool DEFER, bool RES = false>
 __device__ __forceinline__ int64_t k2_stream(const Wave& W, const KeyT* __restrict__ keys, int64_t off, int64_t len,
-                                             uint64_t stream, KeyT* __restrict__ o) {
+                                             uint64_t stream, KeyT* __restrict__ o, int64_t n0 = 0) {
     using IdxT = typename std::conditional<SMALL, uint32_t, uint64_t>::type;
     constexpr uint32_t QC = kQCap, RG = kRing, WIN = RG * 1024;  // WIN: indices in the ring
     const uint32_t lane = W.lane, k = W.k;
@@ -131,12 +146,22 @@ __device__ __forceinline__ int64_t k2_stream(const Wave& W, const KeyT* __restri
     for (uint32_t j = lane; j < k; j += 64) tab[j] = 0;
     const uint32_t s0 = (uint32_t)stream, s1 = (uint32_t)(stream >> 32);
     const DrawKey dk{W.k0, W.k1, s0, s1};
-    const IdxT n_groups = (IdxT)(((uint64_t)len + 15) >> 4);
+    // the draws cover [lo, nend): lo = k and nend = len for a whole stream, max(k, n0) and n0 + len resumed
+    // (the head spells its stateless bound as (IdxT)k, not lo: the same value, but with lo there the
+    // compiler schedules the stateless kernels differently, and their code is to stay as measured)
+    const IdxT lo = RES ? (IdxT)std::max<uint64_t>((uint64_t)k, (uint64_t)n0) : (IdxT)k;
+    const uint64_t nend = RES ? (uint64_t)n0 + (uint64_t)len : (uint64_t)len;
+    const IdxT n_groups = (IdxT)((nend + 15) >> 4);
     uint32_t head = 0, tail = 0;  // FIFO positions (wave-uniform, wrap mod 2^32)
-    // iterations start at a multiple of 64 blocks (the blocks below k >> 4 are clipped: fill), so
-    // block g sits in stash slot g mod 256 (ring = (g / 64) mod 4) and a FIFO entry is i mod 4096
+    // iterations start at a multiple of 64 blocks (the blocks below lo >> 4 are clipped: fill, or an
+    // earlier segment's), so block g sits in stash slot g mod 256 (ring = (g / 64) mod 4) and a FIFO
+    // entry is i mod 4096
     IdxT gb = (IdxT)((k >> 4) & ~63u);
     uint32_t ring = (k >> 10) & (RG - 1);
+    if constexpr (RES) {
+        gb = (lo >> 4) & ~(IdxT)63;
+        ring = (uint32_t)(gb >> 6) & (RG - 1);
+    }
 
     // resolve FIFO entries [head, head + nvalid) (nvalid <= 64), one per lane; last_gb = the most
     // recently stashed iteration: every pending index lies in [16 (last_gb - 192), + 4096)
@@ -174,8 +199,8 @@ __device__ __forceinline__ int64_t k2_stream(const Wave& W, const KeyT* __restri
     // (only where the head holds at least one whole round: below k = 43 the cut would remove it and
     // send the 25-100 % dense region through the FIFO)
     if (hx - k >= 128) hx = k + ((hx - k) & ~(uint64_t)127);
-    const IdxT hend = (IdxT)std::min<uint64_t>((uint64_t)len, hx);
-    const IdxT flo = std::max<IdxT>((IdxT)k, hend);
+    const IdxT hend = (IdxT)std::min<uint64_t>((uint64_t)nend, hx);
+    const IdxT flo = std::max<IdxT>(lo, hend);
     for (; gb < n_groups; gb += 64, ring = (ring + 1) & (RG - 1)) {
         // the oldest pending candidate still refers to the ring slot about to be overwritten
         if (tail != head && ((uint32_t)__builtin_amdgcn_readfirstlane((int)W.q[head & (QC - 1)]) >> 10) == ring) {
@@ -193,13 +218,14 @@ __device__ __forceinline__ int64_t k2_stream(const Wave& W, const KeyT* __restri
         const uint32_t Tmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)T);
         uint32_t mask = valid ? (Tmax <= 16u ? mask_for_small(w, T) : mask_for(w, T)) : 0u;
         bool clip;  // wave-uniform; 32-bit compares for SMALL (scalar: no 64-bit s_cmp_lt)
-        if constexpr (SMALL) clip = ((uint32_t)gb << 4) < (uint32_t)flo || (((uint32_t)gb + 64) << 4) > (uint32_t)len;
-        else clip = ((uint64_t)gb << 4) < (uint64_t)flo || (((uint64_t)gb + 64) << 4) > (uint64_t)len;
-        if (clip) mask &= clip16(i0, (uint64_t)flo, (uint64_t)len);
+        if constexpr (SMALL) clip = ((uint32_t)gb << 4) < (uint32_t)flo || (((uint32_t)gb + 64) << 4) > (uint32_t)nend;
+        else clip = ((uint64_t)gb << 4) < (uint64_t)flo || (((uint64_t)gb + 64) << 4) > (uint64_t)nend;
+        if (clip) mask &= clip16(i0, (uint64_t)flo, (uint64_t)nend);
         W.stash[ring * 64 + lane] = w;
-        if (((uint64_t)gb << 4) < (uint64_t)hend) {  // this iteration holds head indices (uniform)
+        // this iteration holds head indices (uniform; resumed: only a segment that starts inside the head)
+        if (((uint64_t)gb << 4) < (uint64_t)hend && (!RES || lo < hend)) {
             __builtin_amdgcn_wave_barrier();
-            const IdxT ia = std::max<IdxT>((IdxT)k & ~(IdxT)1, gb << 4);
+            const IdxT ia = std::max<IdxT>((RES ? lo : (IdxT)k) & ~(IdxT)1, gb << 4);
             const IdxT ib = std::min<IdxT>(hend, (gb + 64) << 4);
             for (IdxT p0 = ia; p0 < ib; p0 += 128) {
                 const IdxT i = p0 + 2 * lane;  // even
@@ -213,8 +239,8 @@ __device__ __forceinline__ int64_t k2_stream(const Wave& W, const KeyT* __restri
                 asm volatile("" : "+v"(w1.x), "+v"(w1.y), "+v"(w1.z), "+v"(w1.w));
                 const uint64_t j0 = draw_j(b0, w1.x, w1.y, (uint64_t)i + 1, SMALL);
                 const uint64_t j1 = draw_j(b1, w1.z, w1.w, (uint64_t)i + 2, SMALL);
-                if (i < ib && i >= (IdxT)k && j0 < k) atomicMax(&tab[(uint32_t)j0], i);
-                if (i + 1 < ib && i + 1 >= (IdxT)k && j1 < k) atomicMax(&tab[(uint32_t)j1], i + 1);
+                if (i < ib && i >= (RES ? lo : (IdxT)k) && j0 < k) atomicMax(&tab[(uint32_t)j0], i);
+                if (i + 1 < ib && i + 1 >= (RES ? lo : (IdxT)k) && j1 < k) atomicMax(&tab[(uint32_t)j1], i + 1);
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -265,6 +291,7 @@ __device__ __forceinline__ int64_t k2_stream(const Wave& W, const KeyT* __restri
     }
     while (tail != head) resolve_round(std::min<uint32_t>(64u, tail - head), gb - 64);
     __builtin_amdgcn_wave_barrier();
+    if constexpr (RES) return -1;  // the caller merges the table into its state row
     if constexpr (DEFER) {  // the caller gathers (one load site, see k2_segmented)
         int64_t at = -1;
         if (lane < k) {
@@ -399,6 +426,72 @@ __global__ __launch_bounds__(64 * kWaves) void k2_segmented(const KeyT* __restri
     }
 }
 
+// ---- resumed: the streams are rows of caller-held state ------------------------------------------
+// rsv_sample_segmented_update: segment b = keys[offsets[b], offsets[b+1]) holds the indices
+// [n0, n0 + len) of row r = ids[b] (null: b), Philox stream stream_base + r, n0 = bases[b] (null:
+// state_next[r]).  The element loops above run from max(k, n0); the write-back below replaces a slot
+// only where this segment's last writer (or its fill index j in [n0, min(k, n0 + len))) is later than
+// the row's idx -- the largest index per slot wins, whatever order the segments arrive in.  Segments
+// with an id outside [0, S), a negative base or no elements are skipped.
+
+// wave-uniform 64-bit value in scalar registers
+__device__ __forceinline__ int64_t uniform64(int64_t v) {
+    return ((int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v)) |
+           ((int64_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32);
+}
+
+// slot j of a row: winner w (0: none) of the segment [n0, nend) at keys[off ...]
+template <typename KeyT>
+__device__ __forceinline__ void update_slot(const KeyT* __restrict__ keys, int64_t off, int64_t n0, int64_t nend,
+                                            uint32_t j, uint64_t w, KeyT* __restrict__ sk, int64_t* __restrict__ si) {
+    int64_t at = (int64_t)w;
+    if (!w) at = ((int64_t)j >= n0 && (int64_t)j < nend) ? (int64_t)j : -1;  // a fill index of this segment
+    if (at < 0) return;
+    if (si[j] < at) {
+        sk[j] = keys[off + (at - n0)];
+        si[j] = at;
+    }
+}
+
+template <typename KeyT>
+__global__ __launch_bounds__(64 * kWaves) void k2_segmented_update(
+    const KeyT* __restrict__ keys, const int64_t* __restrict__ offsets, const int64_t* __restrict__ ids,
+    const int64_t* __restrict__ bases, int64_t B, int64_t S, uint32_t k, uint32_t k0, uint32_t k1,
+    uint64_t stream_base, KeyT* __restrict__ state_keys, int64_t* __restrict__ state_idx,
+    int64_t* __restrict__ state_next, uint32_t fifo_cap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    uint16_t* lut = (uint16_t*)lds;
+    const uint64_t dense_lim = 256ull * k;
+    build_lut(lut, dense_lim);
+    __syncthreads();
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes + (size_t)k * 8);
+    void* tab = base + kStashBytes + kQueueBytes;
+    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), tab, lut, lane, k,
+                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    const int64_t wave_stride = (int64_t)gridDim.x * kWaves;
+    for (int64_t b = (int64_t)blockIdx.x * kWaves + wave; b < B; b += wave_stride) {
+        const int64_t off = uniform64(offsets[b]), len = uniform64(offsets[b + 1]) - off;
+        const int64_t r = ids ? uniform64(ids[b]) : b;
+        if (len <= 0 || r < 0 || r >= S) continue;
+        const int64_t n0 = uniform64(bases ? bases[b] : state_next[r]);
+        if (n0 < 0) continue;
+        const int64_t nend = n0 + len;
+        const uint64_t stream = stream_base + (uint64_t)r;
+        KeyT* sk = state_keys + r * (int64_t)k;
+        int64_t* si = state_idx + r * (int64_t)k;
+        if (nend < kSmallLen) {
+            k2_stream<KeyT, true, false, true>(W, keys, off, len, stream, nullptr, n0);
+            for (uint32_t j = lane; j < k; j += 64) update_slot(keys, off, n0, nend, j, ((const uint32_t*)tab)[j], sk, si);
+        } else {
+            k2_stream<KeyT, false, false, true>(W, keys, off, len, stream, nullptr, n0);
+            for (uint32_t j = lane; j < k; j += 64) update_slot(keys, off, n0, nend, j, ((const uint64_t*)tab)[j], sk, si);
+        }
+        if (lane == 0 && state_next[r] < nend) state_next[r] = nend;
+        __builtin_amdgcn_wave_barrier();  // the table is read before the next segment zeroes it
+    }
+}
+
 // ---- large k: one WORKGROUP per stream ------------------------------------------------------------
 // Per wave, k2_segmented keeps a k-slot table in LDS: above k ~ 512 the tables cap a CU at one or two
 // workgroups (k = 4096: 150 KB, one wave per SIMD) and above k = 4416 they no longer fit at all --
@@ -412,21 +505,26 @@ __global__ __launch_bounds__(64 * kWaves) void k2_segmented(const KeyT* __restri
 constexpr int kWavesWG = 8;
 constexpr uint32_t kWGMinK = 512;  // smaller k keep one wave per stream (C3: k = 64)
 
-__host__ __device__ inline size_t lds_bytes_wg(uint32_t k, size_t tab_entry, bool GT) {
+__host__ __device__ constexpr size_t lds_bytes_wg(uint32_t k, size_t tab_entry, bool GT) {
     return kLutBytes + (size_t)kWavesWG * (kStashBytes + kQueueBytes) + (GT ? 0 : (size_t)k * tab_entry);
 }
 
-template <typename TabT, bool SMALL, bool GT>
-__device__ __forceinline__ void k2_part(const Wave& W, TabT* tab, int64_t len, uint64_t stream, uint32_t wave) {
+// RES (k2_segmented_update_wg): the segment holds the stream's indices [n0, n0 + len), as in k2_stream.
+template <typename TabT, bool SMALL, bool GT, bool RES = false>
+__device__ __forceinline__ void k2_part(const Wave& W, TabT* tab, int64_t len, uint64_t stream, uint32_t wave,
+                                        int64_t n0 = 0) {
     using IdxT = typename std::conditional<SMALL, uint32_t, uint64_t>::type;
     constexpr uint32_t QC = kQCap, RG = kRing;
     constexpr uint32_t STEP = 64u * kWavesWG;  // blocks between this wave's iterations
     const uint32_t lane = W.lane, k = W.k;
     const uint32_t s0 = (uint32_t)stream, s1 = (uint32_t)(stream >> 32);
     const DrawKey dk{W.k0, W.k1, s0, s1};
-    const IdxT n_groups = (IdxT)(((uint64_t)len + 15) >> 4);
+    const IdxT lo = RES ? (IdxT)std::max<uint64_t>((uint64_t)k, (uint64_t)n0) : (IdxT)k;
+    const uint64_t nend = RES ? (uint64_t)n0 + (uint64_t)len : (uint64_t)len;
+    const IdxT n_groups = (IdxT)((nend + 15) >> 4);
     uint32_t head = 0, tail = 0;
     IdxT gb = (IdxT)(((k >> 4) & ~63u) + 64u * wave);
+    if constexpr (RES) gb = ((lo >> 4) & ~(IdxT)63) + (IdxT)(64u * wave);
     uint32_t ring = 0;
     IdxT slot_gb[RG] = {};  // first block of the iteration each ring slot holds (wave-uniform)
 
@@ -456,8 +554,8 @@ __device__ __forceinline__ void k2_part(const Wave& W, TabT* tab, int64_t len, u
     // the dense head [k, hend) by index pairs, as k2_stream (each wave takes its iterations' share)
     uint64_t hx = 4ull * k;
     if (hx - k >= 128) hx = k + ((hx - k) & ~(uint64_t)127);
-    const IdxT hend = (IdxT)std::min<uint64_t>((uint64_t)len, hx);
-    const IdxT flo = std::max<IdxT>((IdxT)k, hend);
+    const IdxT hend = (IdxT)std::min<uint64_t>((uint64_t)nend, hx);
+    const IdxT flo = std::max<IdxT>(lo, hend);
     for (; gb < n_groups; gb += STEP, ring = (ring + 1) & (RG - 1)) {
         if (tail != head && ((uint32_t)__builtin_amdgcn_readfirstlane((int)W.q[head & (QC - 1)]) >> 10) == ring) {
             while (tail != head) resolve_round(std::min<uint32_t>(64u, tail - head));
@@ -474,12 +572,13 @@ __device__ __forceinline__ void k2_part(const Wave& W, TabT* tab, int64_t len, u
         const uint32_t T = g < kLut ? (uint32_t)W.lut[(uint32_t)g] : block_threshold(i0, W.dense_lim);
         const uint32_t Tmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)T);
         uint32_t mask = valid ? (Tmax <= 16u ? mask_for_small(w, T) : mask_for(w, T)) : 0u;
-        const bool clip = ((uint64_t)gb << 4) < (uint64_t)flo || (((uint64_t)gb + 64) << 4) > (uint64_t)len;
-        if (clip) mask &= clip16(i0, (uint64_t)flo, (uint64_t)len);
+        const bool clip = ((uint64_t)gb << 4) < (uint64_t)flo || (((uint64_t)gb + 64) << 4) > (uint64_t)nend;
+        if (clip) mask &= clip16(i0, (uint64_t)flo, (uint64_t)nend);
         W.stash[ring * 64 + lane] = w;
-        if (((uint64_t)gb << 4) < (uint64_t)hend) {  // this iteration holds head indices (uniform)
+        // this iteration holds head indices (uniform; resumed: only a segment that starts inside the head)
+        if (((uint64_t)gb << 4) < (uint64_t)hend && (!RES || lo < hend)) {
             __builtin_amdgcn_wave_barrier();
-            const IdxT ia = std::max<IdxT>((IdxT)k & ~(IdxT)1, gb << 4);
+            const IdxT ia = std::max<IdxT>((RES ? lo : (IdxT)k) & ~(IdxT)1, gb << 4);
             const IdxT ib = std::min<IdxT>(hend, (gb + 64) << 4);
             for (IdxT p0 = ia; p0 < ib; p0 += 128) {
                 const IdxT i = p0 + 2 * lane;  // even
@@ -493,8 +592,8 @@ __device__ __forceinline__ void k2_part(const Wave& W, TabT* tab, int64_t len, u
                 asm volatile("" : "+v"(w1.x), "+v"(w1.y), "+v"(w1.z), "+v"(w1.w));
                 const uint64_t j0 = draw_j(b0, w1.x, w1.y, (uint64_t)i + 1, SMALL);
                 const uint64_t j1 = draw_j(b1, w1.z, w1.w, (uint64_t)i + 2, SMALL);
-                if (i < ib && i >= (IdxT)k && j0 < k) atomicMax(&tab[(uint32_t)j0], (TabT)i);
-                if (i + 1 < ib && i + 1 >= (IdxT)k && j1 < k) atomicMax(&tab[(uint32_t)j1], (TabT)(i + 1));
+                if (i < ib && i >= (RES ? lo : (IdxT)k) && j0 < k) atomicMax(&tab[(uint32_t)j0], (TabT)i);
+                if (i + 1 < ib && i + 1 >= (RES ? lo : (IdxT)k) && j1 < k) atomicMax(&tab[(uint32_t)j1], (TabT)(i + 1));
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -578,6 +677,81 @@ __global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_wg(const KeyT* __r
         }
         if (threadIdx.x == 0) counts[s] = len < (int64_t)k ? len : (int64_t)k;
         __syncthreads();  // the gather has read the table before the next stream zeroes it
+    }
+}
+
+// the workgroup form of k2_segmented_update (k >= kWGMinK): one shared table in LDS, always 64-bit
+// entries of the absolute index (no launch reads offsets or bases on the host), which bounds k by
+// lds_bytes_wg(k, 8, false) <= kLdsMax
+template <typename KeyT>
+__global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_update_wg(
+    const KeyT* __restrict__ keys, const int64_t* __restrict__ offsets, const int64_t* __restrict__ ids,
+    const int64_t* __restrict__ bases, int64_t B, int64_t S, uint32_t k, uint32_t k0, uint32_t k1,
+    uint64_t stream_base, KeyT* __restrict__ state_keys, int64_t* __restrict__ state_idx,
+    int64_t* __restrict__ state_next, uint32_t fifo_cap) {
+    using TabT = unsigned long long;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    uint16_t* lut = (uint16_t*)lds;
+    const uint64_t dense_lim = 256ull * k;
+    build_lut(lut, dense_lim);
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes);
+    TabT* tab = (TabT*)(lds + kLutBytes + (size_t)kWavesWG * (kStashBytes + kQueueBytes));
+    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), nullptr, lut, lane, k,
+                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    const uint32_t nthr = 64u * kWavesWG;
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        // workgroup-uniform: every thread reads the same words (state_next[r] before anyone writes it)
+        const int64_t off = uniform64(offsets[b]), len = uniform64(offsets[b + 1]) - off;
+        const int64_t r = ids ? uniform64(ids[b]) : b;
+        if (len <= 0 || r < 0 || r >= S) continue;
+        const int64_t n0 = uniform64(bases ? bases[b] : state_next[r]);
+        if (n0 < 0) continue;
+        const int64_t nend = n0 + len;
+        for (uint32_t j = threadIdx.x; j < k; j += nthr) tab[j] = 0;
+        __syncthreads();  // the table is zero, the lut built, and n0 read by every wave
+        const uint64_t stream = stream_base + (uint64_t)r;
+        if (nend < kSmallLen) k2_part<TabT, true, false, true>(W, tab, len, stream, wave, n0);
+        else k2_part<TabT, false, false, true>(W, tab, len, stream, wave, n0);
+        __syncthreads();
+        KeyT* sk = state_keys + r * (int64_t)k;
+        int64_t* si = state_idx + r * (int64_t)k;
+        for (uint32_t j = threadIdx.x; j < k; j += nthr) update_slot(keys, off, n0, nend, j, tab[j], sk, si);
+        if (threadIdx.x == 0 && state_next[r] < nend) state_next[r] = nend;
+        __syncthreads();  // the write-back has read the table before the next segment zeroes it
+    }
+}
+
+// rsv_sample_segmented_merge: per (row, slot) the part with the largest idx, if it beats the row's;
+// next = the max over the row and the parts.  parts: [P][S][k], [P][S][k], [P][S].
+template <typename KeyT>
+__global__ __launch_bounds__(256) void k2_segmented_merge(const KeyT* part_keys, const int64_t* part_idx,
+                                                          const int64_t* part_next, int32_t P, int64_t S, uint32_t k,
+                                                          KeyT* state_keys, int64_t* state_idx, int64_t* state_next) {
+    // (no __restrict__: a state merged into itself names the same memory twice)
+    const int64_t total = S * (int64_t)k;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int64_t cur = state_idx[t];
+    int64_t best = cur;
+    int32_t bp = -1;
+    for (int32_t p = 0; p < P; ++p) {
+        const int64_t pi = part_idx[(int64_t)p * total + t];
+        if (pi > best) {
+            best = pi;
+            bp = p;
+        }
+    }
+    if (bp >= 0) {
+        state_keys[t] = part_keys[(int64_t)bp * total + t];
+        state_idx[t] = best;
+    }
+    if (t % k == 0) {  // the row's first slot also takes its next
+        const int64_t r = t / k;
+        const int64_t cn = state_next[r];
+        int64_t n = cn;
+        for (int32_t p = 0; p < P; ++p) n = std::max<int64_t>(n, part_next[(int64_t)p * S + r]);
+        if (n > cn) state_next[r] = n;
     }
 }
 

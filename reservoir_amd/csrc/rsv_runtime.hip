@@ -1597,6 +1597,51 @@ rsv_status rsv_sample_segmented(const void* keys_dev, const int64_t* offsets_dev
     return RSV_OK;
 }
 
+// k and key_width of the two resumed K2 entry points (fn: the entry point's name, for the messages)
+static rsv_status check_segstate_shape(const char* fn, int32_t k, int32_t key_width) {
+    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
+    if (k > (int32_t)kSegSampleStateMaxK)
+        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " holds k <= " + std::to_string(kSegSampleStateMaxK) +
+                                           " per stream; use separate handles beyond");
+    if (key_width != 4 && key_width != 8) return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be 4 or 8");
+    return RSV_OK;
+}
+
+rsv_status rsv_sample_segmented_update(const void* keys_dev, const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                       const int64_t* bases_dev, int64_t num_segments, int64_t num_states,
+                                       int32_t key_width, int32_t k, uint64_t seed, uint64_t stream_base,
+                                       void* state_keys_dev, int64_t* state_idx_dev, int64_t* state_next_dev,
+                                       void* hip_stream) {
+    if (rsv_status st = check_segstate_shape("rsv_sample_segmented_update", k, key_width)) return st;
+    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
+    if (!stream_ids_dev && num_segments > num_states)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
+    if (num_segments == 0 || num_states == 0) return RSV_OK;
+    // keys_dev is not checked: a launch whose segments are all empty has no keys
+    if (!offsets_dev || !state_keys_dev || !state_idx_dev || !state_next_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    const DrawParams dp{seed, stream_base};
+    RSV_HIP_TRY(launch_segmented_update(keys_dev, key_width, offsets_dev, stream_ids_dev, bases_dev, num_segments,
+                                        num_states, (uint32_t)k, dp, state_keys_dev, state_idx_dev, state_next_dev,
+                                        (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
+rsv_status rsv_sample_segmented_merge(const void* part_keys_dev, const int64_t* part_idx_dev,
+                                      const int64_t* part_next_dev, int32_t parts, int64_t num_states,
+                                      int32_t key_width, int32_t k, void* state_keys_dev, int64_t* state_idx_dev,
+                                      int64_t* state_next_dev, void* hip_stream) {
+    if (rsv_status st = check_segstate_shape("rsv_sample_segmented_merge", k, key_width)) return st;
+    if (parts < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative part or state count");
+    if (parts == 0 || num_states == 0) return RSV_OK;
+    if (!part_keys_dev || !part_idx_dev || !part_next_dev || !state_keys_dev || !state_idx_dev || !state_next_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    RSV_HIP_TRY(launch_segmented_merge(part_keys_dev, key_width, part_idx_dev, part_next_dev, parts, num_states,
+                                       (uint32_t)k, state_keys_dev, state_idx_dev, state_next_dev,
+                                       (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
 // k and key_width of the three K5 entry points (fn: the entry point's name, for the messages)
 static rsv_status check_segdistinct_shape(const char* fn, int32_t k, int32_t key_width) {
     if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");

@@ -23,6 +23,12 @@
 // offsets[0] and offsets[S] once), in LDS while it fits beside the waves' rings (k <= ~29.5k), else
 // the workgroup's slice of a per-device global scratch that is zeroed once and left zero by every
 // launch -- no allocation or fill per call.
+//
+// Resumed (rsv_sample_segmented_update / _merge): the S streams are rows of caller-held
+// state (keys, idx = each slot's last writer, next), a launch feeds each named row one more segment
+// of its stream from any start index, and the largest index per slot wins.  The same two forms
+// (k2_segmented_update, k2_segmented_update_wg) over the same element loops; the workgroup form keeps
+// 64-bit table entries in LDS, so k <= kSegSampleStateMaxK.
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -92,6 +98,16 @@ void gt_release(int dev, hipStream_t st, bool priv, void* p) {
     c.st = st;
 }
 
+// RSV_K2_FIFO_CAP (tests, read once per process): a lower bulk-append limit, so the ballot-
+// round overflow path runs
+uint32_t env_fifo_cap() {
+    static const uint32_t fifo_cap = [] {
+        const char* e = std::getenv("RSV_K2_FIFO_CAP");
+        return e ? (uint32_t)std::atoi(e) : k2::kQCap;
+    }();
+    return fifo_cap;
+}
+
 template <typename KeyT, typename TabT>
 hipError_t launch_wg(const KeyT* keys, const int64_t* offsets, int64_t S, uint32_t k, const DrawParams& dp,
                      KeyT* out, int64_t* counts, hipStream_t st, uint32_t fifo_cap) {
@@ -125,12 +141,7 @@ hipError_t launch_wg(const KeyT* keys, const int64_t* offsets, int64_t S, uint32
 hipError_t launch_segmented(const void* keys, int key_width, const int64_t* offsets, int64_t S, uint32_t k,
                             const DrawParams& dp, void* out, int64_t* counts, hipStream_t st) {
     if (S <= 0) return hipSuccess;
-    // RSV_K2_FIFO_CAP (tests, read once per process): a lower bulk-append limit, so the ballot-
-    // round overflow path runs
-    static const uint32_t fifo_cap = [] {
-        const char* e = std::getenv("RSV_K2_FIFO_CAP");
-        return e ? (uint32_t)std::atoi(e) : k2::kQCap;
-    }();
+    const uint32_t fifo_cap = env_fifo_cap();
     if (k >= k2::kWGMinK) {  // one workgroup per stream
         // every index fits 32 bits when the streams together span < 2^32 elements: u32 tables
         int64_t ends[2] = {0, 0};
@@ -159,6 +170,64 @@ hipError_t launch_segmented(const void* keys, int key_width, const int64_t* offs
     else
         hipLaunchKernelGGL(k2_segmented<int32_t>, dim3(grid), dim3(64 * kWaves), lds, st, (const int32_t*)keys,
                            offsets, S, k, k0, k1, dp.stream, (int32_t*)out, counts, fifo_cap);
+    return hipGetLastError();
+}
+
+// the largest k whose 64-bit winner table fits one workgroup's LDS beside the waves' rings
+static_assert(k2::lds_bytes_wg(kSegSampleStateMaxK, 8, false) <= k2::kLdsMax &&
+                  k2::lds_bytes_wg(kSegSampleStateMaxK + 1, 8, false) > k2::kLdsMax,
+              "kSegSampleStateMaxK is the LDS limit of k2_segmented_update_wg");
+
+namespace {
+template <typename KeyT>
+hipError_t launch_update(const KeyT* keys, const int64_t* offsets, const int64_t* ids, const int64_t* bases, int64_t B,
+                         int64_t S, uint32_t k, const DrawParams& dp, KeyT* state_keys, int64_t* state_idx,
+                         int64_t* state_next, hipStream_t st) {
+    const uint32_t k0 = (uint32_t)dp.seed, k1 = (uint32_t)(dp.seed >> 32);
+    const uint32_t fifo_cap = env_fifo_cap();
+    if (k >= k2::kWGMinK) {  // one workgroup per segment, grids as launch_wg
+        const size_t lds = k2::lds_bytes_wg(k, 8, false);
+        const uint64_t per_cu = std::max<uint64_t>(1, k2::kLdsMax / lds);
+        const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)B, 256ull * per_cu * 2);
+        hipLaunchKernelGGL(k2_segmented_update_wg<KeyT>, dim3(grid), dim3(64 * kWavesWG), lds, st, keys, offsets, ids,
+                           bases, B, S, k, k0, k1, dp.stream, state_keys, state_idx, state_next, fifo_cap);
+        return hipGetLastError();
+    }
+    const uint64_t blocks = ((uint64_t)B + kWaves - 1) / kWaves;  // grids as launch_segmented
+    const unsigned grid = (unsigned)std::min<uint64_t>(blocks, 256ull * 128);
+    hipLaunchKernelGGL(k2_segmented_update<KeyT>, dim3(grid), dim3(64 * kWaves), k2::lds_bytes(k), st, keys, offsets,
+                       ids, bases, B, S, k, k0, k1, dp.stream, state_keys, state_idx, state_next, fifo_cap);
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_segmented_update(const void* keys, int key_width, const int64_t* offsets, const int64_t* stream_ids,
+                                   const int64_t* bases, int64_t num_segments, int64_t num_states, uint32_t k,
+                                   const DrawParams& dp, void* state_keys, int64_t* state_idx, int64_t* state_next,
+                                   hipStream_t st) {
+    if (num_segments <= 0 || num_states <= 0) return hipSuccess;
+    if (k > kSegSampleStateMaxK) return hipErrorInvalidValue;
+    if (key_width == 8)
+        return launch_update<int64_t>((const int64_t*)keys, offsets, stream_ids, bases, num_segments, num_states, k, dp,
+                                      (int64_t*)state_keys, state_idx, state_next, st);
+    return launch_update<int32_t>((const int32_t*)keys, offsets, stream_ids, bases, num_segments, num_states, k, dp,
+                                  (int32_t*)state_keys, state_idx, state_next, st);
+}
+
+hipError_t launch_segmented_merge(const void* part_keys, int key_width, const int64_t* part_idx,
+                                  const int64_t* part_next, int32_t parts, int64_t num_states, uint32_t k,
+                                  void* state_keys, int64_t* state_idx, int64_t* state_next, hipStream_t st) {
+    if (parts <= 0 || num_states <= 0) return hipSuccess;
+    const uint64_t blocks = ((uint64_t)num_states * k + 255) / 256;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (key_width == 8)
+        hipLaunchKernelGGL(k2_segmented_merge<int64_t>, dim3((unsigned)blocks), dim3(256), 0, st,
+                           (const int64_t*)part_keys, part_idx, part_next, parts, num_states, k, (int64_t*)state_keys,
+                           state_idx, state_next);
+    else
+        hipLaunchKernelGGL(k2_segmented_merge<int32_t>, dim3((unsigned)blocks), dim3(256), 0, st,
+                           (const int32_t*)part_keys, part_idx, part_next, parts, num_states, k, (int32_t*)state_keys,
+                           state_idx, state_next);
     return hipGetLastError();
 }
 
