@@ -22,6 +22,45 @@ def test_last_writers_equal_sequential(oracle, k, i0, n):
         assert np.array_equal(got, idx), threads
 
 
+SEED, SID = 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03  # all four 32-bit words nonzero and distinct
+
+
+@pytest.mark.parametrize("k,i0,n,winners", [(1 << 20, 2**40 - (1 << 25) - 7, 1 << 26, 75),
+                                            (1 << 20, 3 * 2**33 - (1 << 21) - 9, 1 << 22, 180),
+                                            (1 << 20, 2**36 - (1 << 22) - 1, 1 << 23, 143),
+                                            (2048, 2**33 - (1 << 26) - 3, 1 << 27, 24)])
+def test_last_writers_equal_sequential_64bit_params(oracle, k, i0, n, winners):
+    """The shapes the GPU K1 index-range tests compare against (tests/test_gpu_k1_forms.py): 64-bit
+    seed and stream, k = 2^20 at high indices, with enough winners in the range to mean something.
+    The winner counts are properties of draw format R2 at (SEED, SID), so they are pinned too."""
+    keys = np.zeros(n, dtype=np.int64)  # or_algo_r's res is not compared, only res_idx
+    res = np.zeros(k, dtype=np.int64)
+    idx = np.full(k, -1, dtype=np.int64)
+    oracle.lib().or_algo_r(SEED, SID, k, i0, keys, n, res, idx.ctypes.data_as(C.c_void_p))
+    assert int((idx >= 0).sum()) == winners
+    assert ((idx[idx >= 0] >= i0) & (idx[idx >= 0] < i0 + n)).all()
+    for threads in (1, 3, 0):
+        got = oracle.algo_r_last_writers(SEED, SID, k, i0, n, threads)
+        assert np.array_equal(got, idx), threads
+
+
+def test_every_seed_and_stream_word_matters(oracle):
+    """The high words of the seed and of the stream enter the draws: dropping either changes the
+    reservoir (a GPU parity test at a 64-bit seed is vacuous if the oracle ignores the high word)."""
+    k, n = 1000, 200_000
+    keys = np.arange(n, dtype=np.int64)
+    full, _ = oracle.algo_r(SEED, SID, k, keys)
+    low_seed, _ = oracle.algo_r(SEED & 0xFFFFFFFF, SID, k, keys)
+    low_sid, _ = oracle.algo_r(SEED, SID & 0xFFFFFFFF, k, keys)
+    hi_seed, _ = oracle.algo_r(SEED & ~0xFFFFFFFF, SID, k, keys)
+    hi_sid, _ = oracle.algo_r(SEED, SID & ~0xFFFFFFFF, k, keys)
+    for other in (low_seed, low_sid, hi_seed, hi_sid):
+        # a slot keeps its fill with probability k / n and holds any later index with probability
+        # 1 / n, so two independent draw sequences agree in a slot with probability (k / n)^2 +
+        # (n - k) / n^2 = 3e-5: 0.03 agreeing slots expected among the 1000, 6 or more never
+        assert int((full != other).sum()) >= k - 5
+
+
 def test_segmented_timer_runs_reference_samplers(oracle):
     """The C3 CPU leg's threaded Algorithm-L samplers equal one AlgoL per stream (seed = stream)."""
     S, L, k = 12, 3000, 20
