@@ -339,6 +339,12 @@ __device__ __forceinline__ T xor_any(T v, int s) {
     }
 }
 
+// the wave's lanes below this one, as a ballot mask
+__device__ __forceinline__ unsigned long long lanemask_lt64() {
+    const uint32_t lane = threadIdx.x & 63;
+    return lane ? (~0ull >> (64 - lane)) : 0ull;
+}
+
 // End of a one-workgroup host publication: every wave waits for its own stores, the workgroup
 // barrier orders them before lane 0, and lane 0 alone runs the system-scope release (L2 write-back)
 // and stores the flag.  (A __threadfence_system() in every wave cost ~4 us more per publication.)

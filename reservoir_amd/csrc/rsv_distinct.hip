@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/reservoir_hip.h"
+#include "rsv_cand.h"
 #include "rsv_device.h"
 #include "rsv_host_values.h"
 #include "rsv_internal.h"
@@ -37,99 +38,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int64_t kSample = 65536;
-
-__device__ __forceinline__ unsigned long long lanemask_lt() {
-    const uint32_t lane = threadIdx.x & 63;
-    return lane ? (~0ull >> (64 - lane)) : 0ull;
-}
-
-// Candidate output: staged per wave in LDS and written B at a time, so the global reservation
-// counter sees one atomic per B candidates (a single contended word sustains ~88 atomics/us:
-// one atomic per candidate cost 1.5 ms at 132k candidates).  IDX: each candidate also carries its
-// pass-relative index (the ordered mode's arrival order); its chunks run at ~3k candidates per
-// pass, so it stages B = 256 (64: ~35 us of atomics per short chunk).
-// Sink (the scheduled pass): also files each written candidate into its merge bucket, so the
-// bucket atomics ride under the HBM-bound stream instead of a scatter kernel after it
-template <typename KeyT, bool IDX = false, typename Sink = void>
-struct CandOut {
-    static constexpr uint32_t B = IDX ? 256 : 64;  // batch; the LDS queue holds B + 64
-    int64_t* qh;  // LDS: B + 64 hashes of this wave
-    KeyT* qk;     // LDS: B + 64 keys
-    uint32_t qn;  // wave-uniform fill
-    int64_t* cand_h;
-    KeyT* cand_k;
-    unsigned long long* counter;
-    int64_t cap;
-    uint32_t* qi = nullptr;      // LDS: B + 64 indices (IDX)
-    uint32_t* cand_i = nullptr;  // (IDX)
-    Sink* sink = nullptr;
-
-    __device__ __forceinline__ void write64(uint32_t from, uint32_t cnt) {
-        const uint32_t lane = threadIdx.x & 63;
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(counter, (unsigned long long)cnt);
-        base = __shfl(base, 0);
-        write_at(base, from, cnt);
-    }
-    __device__ __forceinline__ void write_at(unsigned long long base, uint32_t from, uint32_t cnt) {
-        const uint32_t lane = threadIdx.x & 63;
-#pragma unroll
-        for (uint32_t j0 = 0; j0 < B; j0 += 64) {
-            const uint32_t j = j0 + lane;
-            if (j < cnt) {
-                const unsigned long long pos = base + j;
-                if ((int64_t)pos < cap) {
-                    cand_h[pos] = qh[from + j];
-                    cand_k[pos] = qk[from + j];
-                    if constexpr (IDX) cand_i[pos] = qi[from + j];
-                    if constexpr (!std::is_void<Sink>::value) sink->put(qh[from + j], qk[from + j], qi[from + j] + 1u);
-                }
-            }
-        }
-    }
-    __device__ __forceinline__ void push(bool c, int64_t h, KeyT key, uint32_t idx) {
-        const unsigned long long bal = __ballot(c);
-        if (bal == 0) return;
-        if (c) {
-            const uint32_t pos = qn + __popcll(bal & lanemask_lt());
-            qh[pos] = h;
-            qk[pos] = key;
-            if constexpr (IDX) qi[pos] = idx;
-        }
-        qn += (uint32_t)__popcll(bal);
-        if (qn >= B) {
-            qn -= B;
-            __builtin_amdgcn_wave_barrier();
-            write64(qn, B);
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-    __device__ __forceinline__ void flush() {
-        __builtin_amdgcn_wave_barrier();
-        if (qn) write64(0, qn);
-        qn = 0;
-    }
-    // the final flush of every wave of the workgroup under ONE reservation atomic: the counter is
-    // a single contended word (~88 atomics/us), and a pass whose waves each end with a few staged
-    // candidates (the ordered mode's short chunks) was bound by one atomic per wave
-    template <int WAVES>
-    __device__ __forceinline__ void flush_block(uint32_t* s_q, unsigned long long* s_base) {
-        const uint32_t w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) s_q[w] = qn;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t tot = 0;
-#pragma unroll
-            for (int i = 0; i < WAVES; ++i) tot += s_q[i];
-            *s_base = tot ? atomicAdd(counter, (unsigned long long)tot) : 0ull;
-        }
-        __syncthreads();
-        uint32_t pre = 0;
-        for (uint32_t i = 0; i < w; ++i) pre += s_q[i];
-        if (qn) write_at(*s_base + pre, 0, qn);
-        qn = 0;
-    }
-};
 
 template <typename KeyT, int HASH>
 __device__ __forceinline__ int64_t elem_hash(const KeyT* keys, const int64_t* hashes, int64_t idx,
@@ -227,24 +135,23 @@ __device__ __forceinline__ void k3_tile(const typename Vec<KeyT>::T* x, int64_t 
 }
 
 // IDX (the ordered mode's chunk pass): candidates also carry their index in [0, n < 2^32).
-template <typename KeyT, int HASH, bool IDX, typename Bound, typename Sink = void>
+template <typename KeyT, int HASH, bool IDX, typename Bound>
 __device__ __forceinline__ void k3_filter_body(const KeyT* __restrict__ keys, const int64_t* __restrict__ hashes,
                                                int64_t n, int64_t r0, int64_t r1, Bound bound,
                                                int64_t* __restrict__ cand_h, KeyT* __restrict__ cand_k,
                                                unsigned long long* __restrict__ counter, int64_t cap,
-                                               uint32_t* __restrict__ cand_i, Sink* sink = nullptr) {
+                                               uint32_t* __restrict__ cand_i) {
     using V = Vec<KeyT>;
     constexpr int U = kK3U;  // 8 x 16-B loads in flight per lane (tools/micro_k3: 6.0 -> 6.4 TB/s vs 4)
     constexpr uint32_t Q = CandOut<KeyT, IDX>::B + 64;
     __shared__ int64_t sh_h[kBlock / 64][Q];
     __shared__ KeyT sh_k[kBlock / 64][Q];
     __shared__ uint32_t sh_i[IDX ? kBlock / 64 : 1][IDX ? Q : 1];
-    CandOut<KeyT, IDX, Sink> out{sh_h[threadIdx.x >> 6], sh_k[threadIdx.x >> 6], 0u, cand_h, cand_k, counter, cap};
+    CandOut<KeyT, IDX> out{sh_h[threadIdx.x >> 6], sh_k[threadIdx.x >> 6], 0u, cand_h, cand_k, counter, cap};
     if constexpr (IDX) {
         out.qi = sh_i[threadIdx.x >> 6];
         out.cand_i = cand_i;
     }
-    out.sink = sink;
     const int64_t T = (int64_t)gridDim.x * blockDim.x;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     // the vector loads start at the first 16-B boundary (a batch may begin anywhere in a tensor);
@@ -429,9 +336,10 @@ struct BucketMap {
     }
 };
 
-template <typename KeyT>
-__device__ __forceinline__ bool ent_less(int64_t ha, KeyT ka, int64_t hb, KeyT kb) {
-    return ha < hb || (ha == hb && ka < kb);
+// order of the merge's entries: (h, key), then (TAGGED) the arrival tag
+template <typename KeyT, bool TAGGED>
+__device__ __forceinline__ bool ent_less(int64_t ha, KeyT ka, uint32_t ga, int64_t hb, KeyT kb, uint32_t gb) {
+    return ha < hb || (ha == hb && (ka < kb || (TAGGED && ka == kb && ga < gb)));
 }
 
 template <typename KeyT>
@@ -563,36 +471,36 @@ template <typename KeyT>
 struct PairSrc {
     const int64_t* h;
     const KeyT* k;
-    __device__ __forceinline__ void load(uint32_t i, int64_t& hh, KeyT& kk) const {
+    __device__ __forceinline__ void load(uint32_t i, int64_t& hh, KeyT& kk, uint32_t&) const {
         hh = h[i];
         kk = k[i];
     }
 };
 
-template <typename KeyT, int R, typename Src>
-__device__ __forceinline__ uint32_t wave_sort_bucket(const Src src, int64_t* gh, KeyT* gk, uint32_t n,
-                                                     uint32_t* out_cnt) {
+// Load, pad and sort: entry i = r * 64 + lane of src into slot r (pads: MAX), the packed sort when
+// R == 1 and the hashes allow it, else the bitonic network by ent_less.  g (the tags) is touched only
+// when TAGGED.
+template <typename KeyT, int R, bool TAGGED, typename Src>
+__device__ __forceinline__ void wave_sort_regs(const Src& src, uint32_t n, int64_t (&h)[R], KeyT (&k)[R],
+                                               uint32_t (&g)[R]) {
     const uint32_t lane = threadIdx.x & 63;
     constexpr uint32_t N = 64u * R;
-    int64_t h[R];
-    KeyT k[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const uint32_t i = r * 64u + lane;
         if (i < n) {
-            src.load(i, h[r], k[r]);
+            src.load(i, h[r], k[r], g[r]);
         } else {
             h[r] = INT64_MAX;
             k[r] = std::numeric_limits<KeyT>::max();
+            if constexpr (TAGGED) g[r] = 0xFFFFFFFFu;
         }
     }
-    bool packed = false;
     if constexpr (R == 1) {
-        uint32_t g0 = 0;
-        packed = wave_packed_sort<KeyT, false>(
-            [&](uint32_t i, int64_t& hh, KeyT& kk, uint32_t&) { src.load(i, hh, kk); }, n, h[0], k[0], g0);
+        if (wave_packed_sort<KeyT, TAGGED>(
+                [&](uint32_t i, int64_t& hh, KeyT& kk, uint32_t& gg) { src.load(i, hh, kk, gg); }, n, h[0], k[0], g[0]))
+            return;
     }
-    if (!packed) {
 #pragma unroll
     for (uint32_t size = 2; size <= N; size <<= 1) {
 #pragma unroll
@@ -605,13 +513,18 @@ __device__ __forceinline__ uint32_t wave_sort_bucket(const Src src, int64_t* gh,
                         const uint32_t i = r * 64u + lane;
                         const bool up = (i & size) == 0;
                         const int r2 = r + rs;
-                        if (ent_less<KeyT>(h[r2], k[r2], h[r], k[r]) == up) {
+                        if (ent_less<KeyT, TAGGED>(h[r2], k[r2], g[r2], h[r], k[r], g[r]) == up) {
                             const int64_t th = h[r];
                             const KeyT tk = k[r];
                             h[r] = h[r2];
                             k[r] = k[r2];
                             h[r2] = th;
                             k[r2] = tk;
+                            if constexpr (TAGGED) {
+                                const uint32_t tg = g[r];
+                                g[r] = g[r2];
+                                g[r2] = tg;
+                            }
                         }
                     }
                 }
@@ -621,38 +534,55 @@ __device__ __forceinline__ uint32_t wave_sort_bucket(const Src src, int64_t* gh,
                     const uint32_t i = r * 64u + lane;
                     const int64_t oh = xor_any(h[r], (int)stride);
                     const KeyT ok = xor_any(k[r], (int)stride);
+                    const uint32_t og = TAGGED ? xor_lane32(g[r], (int)stride) : 0u;
                     const bool lower = (lane & stride) == 0;
                     const bool up = (i & size) == 0;
                     // the lower lane keeps the smaller entry in an ascending run, the larger otherwise
-                    const bool other_less = ent_less<KeyT>(oh, ok, h[r], k[r]);
-                    const bool mine_less = ent_less<KeyT>(h[r], k[r], oh, ok);
-                    const bool take = (lower == up) ? other_less : mine_less;
-                    if (take) {
+                    const bool other_less = ent_less<KeyT, TAGGED>(oh, ok, og, h[r], k[r], g[r]);
+                    const bool mine_less = ent_less<KeyT, TAGGED>(h[r], k[r], g[r], oh, ok, og);
+                    if ((lower == up) ? other_less : mine_less) {
                         h[r] = oh;
                         k[r] = ok;
+                        if constexpr (TAGGED) g[r] = og;
                     }
                 }
             }
         }
     }
-    }  // !packed
-    // distinct: entry i differs from entry i - 1
+}
+
+// Row r of the sorted registers: whether this lane's entry i = r * 64 + lane opens a run of equal
+// (h, key), i.e. differs from entry i - 1 (lane 63 of the row before, carried in prev_*_last)
+template <typename KeyT>
+__device__ __forceinline__ bool run_first(int64_t h, KeyT k, uint32_t i, uint32_t n, int64_t prev_h_last,
+                                          KeyT prev_k_last) {
+    const uint32_t lane = threadIdx.x & 63;
+    int64_t ph = shfl_any(h, (int)((lane + 63) & 63));
+    KeyT pk = shfl_any(k, (int)((lane + 63) & 63));
+    if (lane == 0) {
+        ph = prev_h_last;
+        pk = prev_k_last;
+    }
+    return i < n && (i == 0 || ph != h || pk != k);
+}
+
+// the bucket (gh, gk)[0, n) sorted by (h, key) in place, duplicates dropped, *out_cnt = the distinct count
+template <typename KeyT, int R>
+__device__ __forceinline__ uint32_t wave_sort_bucket(int64_t* gh, KeyT* gk, uint32_t n, uint32_t* out_cnt) {
+    const uint32_t lane = threadIdx.x & 63;
+    int64_t h[R];
+    KeyT k[R];
+    uint32_t g[R] = {};
+    wave_sort_regs<KeyT, R, false>(PairSrc<KeyT>{gh, gk}, n, h, k, g);
     uint32_t base = 0;
     int64_t prev_h_last = 0;
     KeyT prev_k_last = 0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const uint32_t i = r * 64u + lane;
-        int64_t ph = shfl_any(h[r], (int)((lane + 63) & 63));
-        KeyT pk = shfl_any(k[r], (int)((lane + 63) & 63));
-        if (lane == 0) {
-            ph = prev_h_last;
-            pk = prev_k_last;
-        }
-        const bool first = i < n && (i == 0 || ph != h[r] || pk != k[r]);
+        const bool first = run_first(h[r], k[r], r * 64u + lane, n, prev_h_last, prev_k_last);
         const unsigned long long bal = __ballot(first);
         if (first) {
-            const uint32_t o = base + (uint32_t)__popcll(bal & lanemask_lt());
+            const uint32_t o = base + (uint32_t)__popcll(bal & lanemask_lt64());
             gh[o] = h[r];
             gk[o] = k[r];
         }
@@ -662,11 +592,6 @@ __device__ __forceinline__ uint32_t wave_sort_bucket(const Src src, int64_t* gh,
     }
     if (lane == 0) *out_cnt = base;
     return base;
-}
-
-template <typename KeyT, int R>
-__device__ __forceinline__ uint32_t wave_sort_bucket(int64_t* gh, KeyT* gk, uint32_t n, uint32_t* out_cnt) {
-    return wave_sort_bucket<KeyT, R>(PairSrc<KeyT>{gh, gk}, gh, gk, n, out_cnt);
 }
 
 template <typename KeyT>
@@ -824,31 +749,10 @@ struct SchedMap {
     }
 };
 
-template <typename KeyT>
-struct SchedSink {
-    SchedMap map;
-    uint32_t* bcnt;
-    int64_t* bh;
-    KeyT* bk;
-    uint32_t* bi;
-    int64_t* ovf;
-    __device__ __forceinline__ void put(int64_t h, KeyT key, uint32_t tag) {
-        const uint32_t b = map(h);
-        const uint32_t at = atomicAdd(&bcnt[(size_t)b * kCountStride], 1u);
-        if (at < kBucketCap) {
-            bh[(size_t)b * kBucketCap + at] = h;
-            bk[(size_t)b * kBucketCap + at] = key;
-            bi[(size_t)b * kBucketCap + at] = tag;
-        } else {
-            *ovf = 1;
-        }
-    }
-};
-
 // the scheduled pass: logs the candidates (with their batch index) for the merge and the replica.
-// The merge buckets are filled by sched_file after it: filed inside the pass, every candidate batch
-// held its wave on the bucket atomics between streaming loads (C4 share: 790 us with the filing,
-// 696 us without, rocprof kernel stats; sched_file takes the filing off the streaming path).
+// The merge buckets are filled by sched_bin_file after it: filed inside the pass, every candidate
+// batch held its wave on the bucket atomics between streaming loads (C4 share: 790 us with the
+// filing, 696 us without, rocprof kernel stats), so the filing stays off the streaming path.
 template <typename KeyT, int HASH>
 __global__ __launch_bounds__(kBlock) void sched_filter(const KeyT* __restrict__ keys, const int64_t* __restrict__ hashes,
                                                        int64_t n, int64_t r0, int64_t r1, const SchedDev* __restrict__ sd,
@@ -883,9 +787,6 @@ __global__ __launch_bounds__(kBlock) void sched_filter(const KeyT* __restrict__ 
                                      cap, cand_i + off);
 }
 
-// the scheduled merge's bucket filing, after the pass: the set's members (tag 0; backed up first,
-// restored if a bound fails verification) and the pass's logged candidates (tag 1 + batch index,
-// their count from the pass's counter ctl[0], at most cap).  Grid-stride over all of them.
 // ---- the plan (host: sched_sample; device: ctl_plan, the fused first chunk + pass) ------------
 __host__ __device__ inline double sched_ufrac(int64_t t) {  // fraction of the hash range at or below t
     return ((double)((uint64_t)t - (uint64_t)INT64_MIN) + 1.0) / 18446744073709551616.0;
@@ -1065,27 +966,6 @@ __global__ __launch_bounds__(256) void sched_plan_store(const SchedDev plan, Sch
     for (uint32_t i = threadIdx.x; i < sizeof(SchedDev) / 4; i += blockDim.x) ((uint32_t*)out)[i] = src[i];
 }
 
-template <typename KeyT>
-__device__ __forceinline__ bool ent_less3(int64_t ha, KeyT ka, uint32_t ia, int64_t hb, KeyT kb, uint32_t ib) {
-    return ha < hb || (ha == hb && (ka < kb || (ka == kb && ia < ib)));
-}
-
-// one wave per bucket: sort by (h, key, tag), keep the first of each (h, key) run (its earliest
-// arrival), write them back compacted; each kept element adds +1 / -1 at ranges r_a / r_h + 1 of
-// the block's difference array (sdiff, LDS)
-// a bucket's entries in place in global memory (sched_sort)
-template <typename KeyT>
-struct BucketSrc {
-    const int64_t* h;
-    const KeyT* k;
-    const uint32_t* g;
-    __device__ __forceinline__ void load(uint32_t i, int64_t& hh, KeyT& kk, uint32_t& gg) const {
-        hh = h[i];
-        kk = k[i];
-        gg = g[i];
-    }
-};
-
 // a fine bucket of a coarse bin staged in LDS, through the bin's permutation (sched_bin_sort)
 template <typename KeyT>
 struct LdsBinSrc {
@@ -1101,94 +981,28 @@ struct LdsBinSrc {
     }
 };
 
+// one wave per bucket: sort by (h, key, tag), keep the first of each (h, key) run (its earliest
+// arrival), write them back compacted; each kept element adds +1 / -1 at ranges r_a / r_h + 1 of
+// the block's difference array (sdiff, LDS)
 template <typename KeyT, int R, typename Src>
 __device__ __forceinline__ uint32_t wave_sort_bucket_tagged(const Src src, int64_t* gh, KeyT* gk, uint32_t n,
                                                             const int64_t* sb, const int64_t* stt, int nr,
                                                             int* sdiff) {
     const uint32_t lane = threadIdx.x & 63;
-    constexpr uint32_t N = 64u * R;
     int64_t h[R];
     KeyT k[R];
     uint32_t g[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint32_t i = r * 64u + lane;
-        if (i < n) {
-            src.load(i, h[r], k[r], g[r]);
-        } else {
-            h[r] = INT64_MAX;
-            k[r] = std::numeric_limits<KeyT>::max();
-            g[r] = 0xFFFFFFFFu;
-        }
-    }
-    bool packed = false;
-    if constexpr (R == 1)
-        packed = wave_packed_sort<KeyT, true>(
-            [&](uint32_t i, int64_t& hh, KeyT& kk, uint32_t& gg) { src.load(i, hh, kk, gg); }, n, h[0], k[0], g[0]);
-    if (!packed) {
-#pragma unroll
-    for (uint32_t size = 2; size <= N; size <<= 1) {
-#pragma unroll
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            if (stride >= 64) {
-                const uint32_t rs = stride / 64;
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    if ((r & rs) == 0) {
-                        const uint32_t i = r * 64u + lane;
-                        const bool up = (i & size) == 0;
-                        const int r2 = r + rs;
-                        if (ent_less3<KeyT>(h[r2], k[r2], g[r2], h[r], k[r], g[r]) == up) {
-                            const int64_t th = h[r];
-                            const KeyT tk = k[r];
-                            const uint32_t tg = g[r];
-                            h[r] = h[r2];
-                            k[r] = k[r2];
-                            g[r] = g[r2];
-                            h[r2] = th;
-                            k[r2] = tk;
-                            g[r2] = tg;
-                        }
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const uint32_t i = r * 64u + lane;
-                    const int64_t oh = xor_any(h[r], (int)stride);
-                    const KeyT ok = xor_any(k[r], (int)stride);
-                    const uint32_t og = xor_lane32(g[r], (int)stride);
-                    const bool lower = (lane & stride) == 0;
-                    const bool up = (i & size) == 0;
-                    const bool other_less = ent_less3<KeyT>(oh, ok, og, h[r], k[r], g[r]);
-                    const bool mine_less = ent_less3<KeyT>(h[r], k[r], g[r], oh, ok, og);
-                    if ((lower == up) ? other_less : mine_less) {
-                        h[r] = oh;
-                        k[r] = ok;
-                        g[r] = og;
-                    }
-                }
-            }
-        }
-    }
-    }  // !packed
+    wave_sort_regs<KeyT, R, true>(src, n, h, k, g);
     uint32_t base = 0;
     int64_t prev_h_last = 0;
     KeyT prev_k_last = 0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const uint32_t i = r * 64u + lane;
-        int64_t ph = shfl_any(h[r], (int)((lane + 63) & 63));
-        KeyT pk = shfl_any(k[r], (int)((lane + 63) & 63));
-        if (lane == 0) {
-            ph = prev_h_last;
-            pk = prev_k_last;
-        }
-        const bool first = i < n && (i == 0 || ph != h[r] || pk != k[r]);
+        const bool first = run_first(h[r], k[r], r * 64u + lane, n, prev_h_last, prev_k_last);
         const unsigned long long bal = __ballot(first);
         int ra = 1, rh = -1;
         if (first) {
-            const uint32_t o = base + (uint32_t)__popcll(bal & lanemask_lt());
+            const uint32_t o = base + (uint32_t)__popcll(bal & lanemask_lt64());
             gh[o] = h[r];
             gk[o] = k[r];
             // ranges this element verifies: r_a = first r >= 1 with b[r] >= tag (arrived before b[r]),
@@ -1234,14 +1048,17 @@ __device__ __forceinline__ uint32_t wave_sort_bucket_tagged(const Src src, int64
 
 // ---- the scheduled merge by coarse bins (sched_bin_file -> sched_bin_sort) -------------------
 // The merge's 2^lb fine buckets grouped 2^kBinLog to a coarse bin.  sched_bin_file files every
-// entry into its bin: a workgroup's 4096 entries are counted per bin in LDS, ONE global atomic per
-// (workgroup, bin) reserves their places (~4 entries per atomic at 1024 bins, where sched_file paid
-// one returning atomic per entry on 128-B count lines), and they are stored in runs.  sched_bin_sort
-// then stages one bin in LDS (one workgroup per bin), splits it into its fine buckets by a counting
-// sort there, and sorts / dedups / verifies each fine bucket with the same wave network as
-// sched_sort, reading LDS instead of global memory; the bin's group sums are plain stores and its
-// verification columns one set of atomics per bin.  Bin capacity kBinCap (LDS): ~2.3x the plan's
-// expected fill; more (like a fine bucket over kBucketCap) is the overflow the host falls back on.
+// entry into its bin -- the set's members (tag 0; backed up first, restored if a bound fails
+// verification) and the pass's logged candidates (tag 1 + batch index, their count from the pass's
+// counter ctl[0], at most cap): a workgroup's 4096 entries are counted per bin in LDS, ONE global
+// atomic per (workgroup, bin) reserves their places (~4 entries per atomic at 1024 bins, instead of
+// one returning atomic per entry on the fine buckets' 128-B count lines), and they are stored in
+// runs.  sched_bin_sort then stages one bin in LDS (one workgroup per bin), splits it into its fine
+// buckets by a counting sort there, and sorts / dedups / verifies each fine bucket with the wave
+// network of the set merge (wave_sort_regs) carrying the tags, reading LDS instead of global memory;
+// the bin's group sums are plain stores and its verification columns one set of atomics per bin.
+// Bin capacity kBinCap (LDS): ~2.3x the plan's expected fill; more (like a fine bucket over
+// kBucketCap) is the overflow the host falls back on.
 constexpr int kBinLog = 5;
 constexpr uint32_t kBinCap = 3072;
 constexpr int kBinTile = 4;          // entries per thread of sched_bin_file
@@ -1252,8 +1069,6 @@ constexpr int kBinFileThreads = RSV_BIN_FILE_THREADS;  // (dev builds vary it)
 constexpr int kBinSortThreads = 512;
 
 __host__ __device__ inline uint32_t bin_log(uint32_t lb, uint32_t fl = kBinLog) { return lb > fl ? lb - fl : 0u; }
-
-
 
 template <typename KeyT>
 __global__ __launch_bounds__(kBinFileThreads) void sched_bin_file(const SchedDev* __restrict__ sd, const int64_t* __restrict__ cand_h,
@@ -1974,60 +1789,36 @@ static hipError_t temp_bytes_for(int64_t cap, size_t* bytes) {
     return hipSuccess;
 }
 
-// Device buffers grow on demand (geometric, capped): a sampler with a huge k that sees few
-// elements (k may be up to Int.MaxValue - 2, Sampler.scala:71) allocates for what it holds.
-static hipError_t grow(void** p, size_t old_bytes, size_t new_bytes, bool keep, hipStream_t st) {
-    void* q = nullptr;
-    hipError_t e = pool_device_alloc(&q, new_bytes ? new_bytes : 16);
-    if (e != hipSuccess) return e;
-    if (keep && *p && old_bytes) e = hipMemcpyAsync(q, *p, old_bytes, hipMemcpyDeviceToDevice, st);
-    // queued work may still read the old block: wait before it goes back to the pool
-    if (e == hipSuccess && *p) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        pool_device_free(q);
-        return e;
-    }
-    pool_device_free(*p);
-    *p = q;
-    return hipSuccess;
-}
-
-static int64_t grown(int64_t cur, int64_t need, int64_t cap) {
-    int64_t c = std::max<int64_t>(cur, 1024);
-    while (c < need) c *= 2;
-    return std::min(c, cap);
-}
-
 static hipError_t ensure_caps(DistinctState* d, int64_t cand_need, int64_t merge_need, hipStream_t st) {
     const size_t kw = (size_t)d->kw;
     hipError_t e = hipSuccess;
     cand_need = std::min(cand_need, d->cand_limit);
     if (cand_need > d->cand_cap) {
-        const int64_t c = grown(d->cand_cap, cand_need, d->cand_limit);
-        if ((e = grow((void**)&d->cand_h, 0, (size_t)c * 8, false, st))) return e;
-        if ((e = grow(&d->cand_k, 0, (size_t)c * kw, false, st))) return e;
+        const int64_t c = grown_capacity(d->cand_cap, cand_need, d->cand_limit);
+        if ((e = pool_device_grow((void**)&d->cand_h, 0, (size_t)c * 8, false, st))) return e;
+        if ((e = pool_device_grow(&d->cand_k, 0, (size_t)c * kw, false, st))) return e;
         d->cand_cap = c;
     }
     const int64_t set_need = std::min<int64_t>(merge_need, d->k);
     if (set_need > d->set_cap) {
-        const int64_t c = grown(d->set_cap, set_need, d->k);
-        if ((e = grow((void**)&d->set_h, (size_t)d->m * 8, (size_t)c * 8, true, st))) return e;
-        if ((e = grow(&d->set_k, (size_t)d->m * kw, (size_t)c * kw, true, st))) return e;
+        const int64_t c = grown_capacity(d->set_cap, set_need, d->k);
+        if ((e = pool_device_grow((void**)&d->set_h, (size_t)d->m * 8, (size_t)c * 8, true, st))) return e;
+        if ((e = pool_device_grow(&d->set_k, (size_t)d->m * kw, (size_t)c * kw, true, st))) return e;
         d->set_cap = c;
     }
     if (merge_need > d->merge_cap) {
-        const int64_t c = grown(d->merge_cap, merge_need, (int64_t)d->k + d->cand_limit);
-        if ((e = grow((void**)&d->mh0, 0, (size_t)c * 8, false, st))) return e;
-        if ((e = grow((void**)&d->mh1, 0, (size_t)c * 8, false, st))) return e;
-        if ((e = grow(&d->mk0, 0, (size_t)c * kw, false, st))) return e;
-        if ((e = grow(&d->mk1, 0, (size_t)c * kw, false, st))) return e;
-        if ((e = grow((void**)&d->flags, 0, (size_t)c * 4, false, st))) return e;
-        if ((e = grow((void**)&d->pos, 0, (size_t)c * 4, false, st))) return e;
+        const int64_t c = grown_capacity(d->merge_cap, merge_need, (int64_t)d->k + d->cand_limit);
+        if ((e = pool_device_grow((void**)&d->mh0, 0, (size_t)c * 8, false, st))) return e;
+        if ((e = pool_device_grow((void**)&d->mh1, 0, (size_t)c * 8, false, st))) return e;
+        if ((e = pool_device_grow(&d->mk0, 0, (size_t)c * kw, false, st))) return e;
+        if ((e = pool_device_grow(&d->mk1, 0, (size_t)c * kw, false, st))) return e;
+        if ((e = pool_device_grow((void**)&d->flags, 0, (size_t)c * 4, false, st))) return e;
+        if ((e = pool_device_grow((void**)&d->pos, 0, (size_t)c * 4, false, st))) return e;
         size_t tb = 0;
         e = d->kw == 8 ? temp_bytes_for<int64_t>(c, &tb) : temp_bytes_for<int32_t>(c, &tb);
         if (e != hipSuccess) return e;
         if (tb > d->temp_bytes) {
-            if ((e = grow(&d->temp, 0, tb, false, st))) return e;
+            if ((e = pool_device_grow(&d->temp, 0, tb, false, st))) return e;
             d->temp_bytes = tb;
         }
         d->merge_cap = c;
@@ -2159,7 +1950,6 @@ void distinct_spec_target(DistinctState* d, void* dst_host_dev, uint32_t* flag_d
     d->spec_ok = false;
 }
 
-bool distinct_is_ordered(const DistinctState* d) { return d->ordered; }
 int64_t distinct_spec_min(const DistinctState* d) { return d->spec_min; }
 
 bool distinct_spec_take(DistinctState* d, uint32_t* gen) {
@@ -2543,17 +2333,17 @@ static hipError_t launch_filter_idx(DistinctState* d, const KeyT* keys, const in
 static hipError_t ensure_ordered(DistinctState* d, int64_t cap, hipStream_t st) {
     if (cap <= d->ord_cap) return hipSuccess;
     hipError_t e;
-    if ((e = grow((void**)&d->perm, 0, (size_t)cap * 4, false, st))) return e;
-    if ((e = grow((void**)&d->sorted_i, 0, (size_t)cap * 4, false, st))) return e;
-    if ((e = grow((void**)&d->ord_h, 0, (size_t)cap * 8, false, st))) return e;
-    if ((e = grow(&d->ord_k, 0, (size_t)cap * d->kw, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->perm, 0, (size_t)cap * 4, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->sorted_i, 0, (size_t)cap * 4, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->ord_h, 0, (size_t)cap * 8, false, st))) return e;
+    if ((e = pool_device_grow(&d->ord_k, 0, (size_t)cap * d->kw, false, st))) return e;
     pool_host_free(d->ph);
     pool_host_free(d->pk);
     d->ph = nullptr;
     d->pk = nullptr;
     if ((e = pool_host_alloc((void**)&d->ph, (size_t)cap * 8, hipHostMallocDefault))) return e;
     if ((e = pool_host_alloc(&d->pk, (size_t)cap * d->kw, hipHostMallocDefault))) return e;
-    if ((e = grow((void**)&d->fflag, 0, (size_t)cap, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->fflag, 0, (size_t)cap, false, st))) return e;
     pool_host_free(d->pflag);
     d->pflag = nullptr;
     if ((e = pool_host_alloc((void**)&d->pflag, (size_t)cap, hipHostMallocDefault))) return e;
@@ -2562,7 +2352,7 @@ static hipError_t ensure_ordered(DistinctState* d, int64_t cap, hipStream_t st) 
                                        rocprim::counting_iterator<uint32_t>(0), (uint32_t*)nullptr, (size_t)cap)))
         return e;
     if (tb > d->temp_bytes) {
-        if ((e = grow(&d->temp, 0, tb, false, st))) return e;
+        if ((e = pool_device_grow(&d->temp, 0, tb, false, st))) return e;
         d->temp_bytes = tb;
     }
     d->ord_cap = cap;
@@ -2575,11 +2365,11 @@ static hipError_t ensure_log(DistinctState* d, int64_t need, hipStream_t st) {
     if (need <= d->log_cap) return hipSuccess;
     const int64_t first = std::min<int64_t>(8 * d->cand_limit, (256ll << 20) / (12 + d->kw));
     const int64_t want = std::max(need, std::min(d->log_limit, d->log_cap ? need : first));
-    const int64_t c = grown(d->log_cap, want, std::max(want, d->log_limit));
+    const int64_t c = grown_capacity(d->log_cap, want, std::max(want, d->log_limit));
     hipError_t e;
-    if ((e = grow((void**)&d->log_h, (size_t)d->log_n * 8, (size_t)c * 8, true, st))) return e;
-    if ((e = grow(&d->log_k, (size_t)d->log_n * d->kw, (size_t)c * d->kw, true, st))) return e;
-    if ((e = grow((void**)&d->log_i, (size_t)d->log_n * 4, (size_t)c * 4, true, st))) return e;
+    if ((e = pool_device_grow((void**)&d->log_h, (size_t)d->log_n * 8, (size_t)c * 8, true, st))) return e;
+    if ((e = pool_device_grow(&d->log_k, (size_t)d->log_n * d->kw, (size_t)c * d->kw, true, st))) return e;
+    if ((e = pool_device_grow((void**)&d->log_i, (size_t)d->log_n * 4, (size_t)c * 4, true, st))) return e;
     d->log_cap = c;
     return hipSuccess;
 }
@@ -2628,15 +2418,15 @@ static hipError_t ensure_first(DistinctState* d, int64_t nm, int64_t total, hipS
         d->pmem_cap = c;
     }
     if (total <= d->fcap) return hipSuccess;
-    if ((e = grow(&d->fk_in, 0, (size_t)total * sizeof(KeyT), false, st))) return e;
-    if ((e = grow(&d->fk_out, 0, (size_t)total * sizeof(KeyT), false, st))) return e;
-    if ((e = grow((void**)&d->fv, 0, (size_t)total * 4, false, st))) return e;
+    if ((e = pool_device_grow(&d->fk_in, 0, (size_t)total * sizeof(KeyT), false, st))) return e;
+    if ((e = pool_device_grow(&d->fk_out, 0, (size_t)total * sizeof(KeyT), false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->fv, 0, (size_t)total * 4, false, st))) return e;
     size_t tb = 0;
     if ((e = rocprim::radix_sort_pairs(nullptr, tb, (KeyT*)nullptr, (KeyT*)nullptr,
                                        rocprim::counting_iterator<uint32_t>(0), (uint32_t*)nullptr, (size_t)total)))
         return e;
     if (tb > d->temp_bytes) {
-        if ((e = grow(&d->temp, 0, tb, false, st))) return e;
+        if ((e = pool_device_grow(&d->temp, 0, tb, false, st))) return e;
         d->temp_bytes = tb;
     }
     d->fcap = total;
@@ -3549,7 +3339,7 @@ static int merge_rows_impl(DistinctState* d, const int64_t* rows, int32_t parts,
     const uint32_t B = 1u << lb;
     const int64_t need = (int64_t)(parts + 1) * (B + 1);
     if (need > d->mstart_cap) {
-        RSV_HIP_TRY(grow((void**)&d->mstart, 0, (size_t)need * 4, false, st));
+        RSV_HIP_TRY(pool_device_grow((void**)&d->mstart, 0, (size_t)need * 4, false, st));
         d->mstart_cap = need;
     }
     const Runs<KeyT> R{rows, stride, k, d->set_h, (const KeyT*)d->set_k, d->m};
@@ -3573,7 +3363,7 @@ static int merge_rows_impl(DistinctState* d, const int64_t* rows, int32_t parts,
     // behind the merge kernels: parts x (2k + 6) words, ~8 MB at 8 x 65536)
     const int64_t rw = 2 * k + kRowMeta;
     if ((int64_t)parts * rw > d->rows_copy_cap) {
-        RSV_HIP_TRY(grow((void**)&d->rows_copy, 0, (size_t)parts * rw * 8, false, st));
+        RSV_HIP_TRY(pool_device_grow((void**)&d->rows_copy, 0, (size_t)parts * rw * 8, false, st));
         d->rows_copy_cap = (int64_t)parts * rw;
     }
     RSV_HIP_TRY(hipMemcpy2DAsync(d->rows_copy, (size_t)rw * 8, rows, (size_t)stride * 8, (size_t)rw * 8, (size_t)parts,

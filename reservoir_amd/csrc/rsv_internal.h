@@ -26,6 +26,11 @@ void set_error(const std::string& msg);
 // touch it (synchronize its stream first).
 hipError_t pool_device_alloc(void** p, size_t bytes);
 void pool_device_free(void* p);
+// Replace *p (old_bytes in use) by a block of new_bytes, its contents kept when `keep`; the stream is
+// synchronized before the old block goes back to the pool.
+hipError_t pool_device_grow(void** p, size_t old_bytes, size_t new_bytes, bool keep, hipStream_t st);
+// Capacity for `need` entries: `cur` (at least 1024) doubled until it holds them, at most `cap`.
+int64_t grown_capacity(int64_t cur, int64_t need, int64_t cap);
 hipError_t pool_host_alloc(void** p, size_t bytes, unsigned flags);
 void pool_host_free(void* p);
 void pool_trim();  // free every idle cached buffer
@@ -205,7 +210,6 @@ int distinct_publish(DistinctState* d, void* dst_host_dev, uint32_t* flag_dev, u
 // its ctl read; distinct_spec_take says whether the last one holds the batch's final set (its
 // generation in *gen) and clears the target.
 void distinct_spec_target(DistinctState* d, void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter);
-bool distinct_is_ordered(const DistinctState* d);
 int64_t distinct_spec_min(const DistinctState* d);  // smallest batch that publishes speculatively
 bool distinct_spec_take(DistinctState* d, uint32_t* gen);
 // copies the set (ascending hash) to device buffers; either may be null
@@ -241,7 +245,6 @@ void wide_destroy(WideDistinct* d);
 void wide_set_timer(WideDistinct* d, KernelTimer* t);
 int64_t wide_size(const WideDistinct* d);
 const void* wide_keys_dev(const WideDistinct* d);
-bool wide_is_ordered(const WideDistinct* d);
 int wide_sample_device(WideDistinct* d, const void* keys, const int64_t* hashes, int64_t n, hipStream_t st);
 int wide_finalize(WideDistinct* d, hipStream_t st);
 int wide_publish(WideDistinct* d, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st);

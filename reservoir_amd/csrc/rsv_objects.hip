@@ -42,6 +42,7 @@
 #include <string>
 
 #include "../../include/reservoir_hip.h"
+#include "rsv_cand.h"
 #include "rsv_device.h"
 #include "rsv_internal.h"
 
@@ -56,7 +57,6 @@ constexpr int kSortTile = 1024;     // elements one workgroup sorts in LDS
 constexpr int kCompactBlock = 1024;
 constexpr int64_t kGrow = 4;        // a chunk is ~kGrow seen lengths long
 constexpr int64_t kPinned = 1 << 18;  // hashes per pinned staging buffer (host batches)
-typedef long long o2i64 __attribute__((ext_vector_type(2)));
 
 // device control words
 enum : int {
@@ -71,71 +71,7 @@ enum : int {
     kCtlWords = 8
 };
 
-__device__ __forceinline__ unsigned long long lanemask_lt_o() {
-    const uint32_t lane = threadIdx.x & 63;
-    return lane ? (~0ull >> (64 - lane)) : 0ull;
-}
-
-// Candidate output of the filter: each wave stages (h, offset) in LDS and appends B at a time under
-// one reservation atomic; the workgroup's leftovers go out under one atomic at the end.  Places at
-// or past the room `cap` are counted, not written.
-struct ObjOut {
-    static constexpr uint32_t B = 128;
-    static constexpr uint32_t Q = B + 64;
-    int64_t* qh;
-    int64_t* qi;
-    uint32_t qn;
-    int64_t* cand_h;
-    int64_t* cand_i;
-    unsigned long long* counter;
-    int64_t cap;
-
-    __device__ __forceinline__ void write_at(unsigned long long base, uint32_t from, uint32_t cnt) {
-        const uint32_t lane = threadIdx.x & 63;
-        for (uint32_t j = lane; j < cnt; j += 64) {
-            const unsigned long long pos = base + j;
-            if (pos < (unsigned long long)cap) {
-                cand_h[pos] = qh[from + j];
-                cand_i[pos] = qi[from + j];
-            }
-        }
-    }
-    __device__ __forceinline__ void push(bool c, int64_t h, int64_t idx) {
-        const unsigned long long bal = __ballot(c);
-        if (bal == 0) return;
-        if (c) {
-            const uint32_t pos = qn + __popcll(bal & lanemask_lt_o());
-            qh[pos] = h;
-            qi[pos] = idx;
-        }
-        qn += (uint32_t)__popcll(bal);
-        if (qn >= B) {
-            qn -= B;
-            __builtin_amdgcn_wave_barrier();
-            unsigned long long base = 0;
-            if ((threadIdx.x & 63) == 0) base = atomicAdd(counter, (unsigned long long)B);
-            base = __shfl(base, 0);
-            write_at(base, qn, B);
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-    __device__ __forceinline__ void flush_block(uint32_t* s_q, unsigned long long* s_base) {
-        const uint32_t w = threadIdx.x >> 6;
-        __builtin_amdgcn_wave_barrier();
-        if ((threadIdx.x & 63) == 0) s_q[w] = qn;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t tot = 0;
-            for (int i = 0; i < kOBlock / 64; ++i) tot += s_q[i];
-            *s_base = tot ? atomicAdd(counter, (unsigned long long)tot) : 0ull;
-        }
-        __syncthreads();
-        uint32_t pre = 0;
-        for (uint32_t i = 0; i < w; ++i) pre += s_q[i];
-        if (qn) write_at(*s_base + pre, 0, qn);
-        qn = 0;
-    }
-};
+using ObjQueue = OffsetQueue<kOBlock / 64>;
 
 // The filter over n hashes (a chunk of the batch starting at batch offset `base`): 16-B non-temporal
 // loads (two hashes each), kOU in flight per lane; the <= 1 head element before the first 16-B
@@ -146,21 +82,21 @@ __global__ __launch_bounds__(kOBlock) void obj_filter(const int64_t* __restrict_
                                                       int64_t r0, int64_t r1, int64_t* __restrict__ ctl,
                                                       int64_t* __restrict__ cand_h, int64_t* __restrict__ cand_i,
                                                       int64_t cap) {
-    __shared__ int64_t sh_h[kOBlock / 64][ObjOut::Q];
-    __shared__ int64_t sh_i[kOBlock / 64][ObjOut::Q];
+    __shared__ int64_t sh_h[kOBlock / 64][ObjQueue::Q];
+    __shared__ int64_t sh_i[kOBlock / 64][ObjQueue::Q];
     __shared__ uint32_t s_q[kOBlock / 64];
     __shared__ unsigned long long s_base;
-    ObjOut out{sh_h[threadIdx.x >> 6], sh_i[threadIdx.x >> 6], 0u, cand_h, cand_i,
-               (unsigned long long*)(ctl + kCtlCount), cap};
+    ObjQueue out{sh_h[threadIdx.x >> 6], sh_i[threadIdx.x >> 6], 0u, cand_h, cand_i,
+                 (unsigned long long*)(ctl + kCtlCount), cap};
     const int64_t bound = ctl[kCtlBound];
     const bool open = ctl[kCtlOpen] != 0;
     const int64_t T = (int64_t)gridDim.x * blockDim.x;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t head = std::min<int64_t>(n, (int64_t)(((16u - ((uintptr_t)hashes & 15u)) & 15u) / 8u));
-    const o2i64* hv = reinterpret_cast<const o2i64*>(hashes + head);
+    const i64x2* hv = reinterpret_cast<const i64x2*>(hashes + head);
     const int64_t n_vec = (n - head) / 2;
     for (int64_t t0 = 0; t0 < n_vec; t0 += T * kOU) {
-        o2i64 x[kOU];
+        i64x2 x[kOU];
 #pragma unroll
         for (int u = 0; u < kOU; ++u) {
             const int64_t v = t0 + u * T + tid;

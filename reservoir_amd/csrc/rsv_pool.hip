@@ -8,10 +8,11 @@
 // the next sampler; blocks above kMaxPooled bytes go straight to the HIP allocator.
 //
 // Reuse safety: a block is only released once no queued work can touch it -- rsv_destroy
-// synchronizes the sampler's stream first, and in-place growth (rsv_distinct.hip) synchronizes
+// synchronizes the sampler's stream first, and in-place growth (pool_device_grow) synchronizes
 // before releasing the old block -- so handing it to a sampler on another stream cannot race.
 // Cached blocks live until process exit (no static destructor: the HIP runtime may already be
 // torn down by then).
+#include <algorithm>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -137,6 +138,31 @@ void release(void* p) {
 
 hipError_t pool_device_alloc(void** p, size_t bytes) { return alloc(kDevice, 0, bytes, p); }
 void pool_device_free(void* p) { release(p); }
+
+// Device buffers grow on demand (geometric, capped): a sampler with a huge k that sees few
+// elements (k may be up to Int.MaxValue - 2, Sampler.scala:71) allocates for what it holds.
+hipError_t pool_device_grow(void** p, size_t old_bytes, size_t new_bytes, bool keep, hipStream_t st) {
+    void* q = nullptr;
+    hipError_t e = pool_device_alloc(&q, new_bytes ? new_bytes : 16);
+    if (e != hipSuccess) return e;
+    if (keep && *p && old_bytes) e = hipMemcpyAsync(q, *p, old_bytes, hipMemcpyDeviceToDevice, st);
+    // queued work may still read the old block: wait before it goes back to the pool
+    if (e == hipSuccess && *p) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        pool_device_free(q);
+        return e;
+    }
+    pool_device_free(*p);
+    *p = q;
+    return hipSuccess;
+}
+
+int64_t grown_capacity(int64_t cur, int64_t need, int64_t cap) {
+    int64_t c = std::max<int64_t>(cur, 1024);
+    while (c < need) c *= 2;
+    return std::min(c, cap);
+}
+
 hipError_t pool_host_alloc(void** p, size_t bytes, unsigned flags) { return alloc(kHost, flags, bytes, p); }
 void pool_host_free(void* p) { release(p); }
 

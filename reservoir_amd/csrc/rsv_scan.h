@@ -15,11 +15,6 @@ namespace rsv {
 constexpr uint32_t kQueue = 128;  // per-wave LDS entries: < 64 waiting + one round of <= 64 pushes
 constexpr uint64_t kIndexMask = (1ull << 56) - 1;  // queue entry = (b_i << 56) | i
 
-__device__ __forceinline__ unsigned long long lanemask_lt64() {
-    const uint32_t lane = threadIdx.x & 63;
-    return lane ? (~0ull >> (64 - lane)) : 0ull;
-}
-
 __device__ __forceinline__ uint32_t clip_mask16(uint64_t i0, uint64_t lo, uint64_t hi) {
     uint32_t m = 0xFFFFu;
     if (i0 < lo) m = (lo - i0 >= 16) ? 0u : ((0xFFFFu << (uint32_t)(lo - i0)) & 0xFFFFu);

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/reservoir_hip.h"
+#include "rsv_cand.h"
 #include "rsv_device.h"
 #include "rsv_host_values.h"
 #include "rsv_internal.h"
@@ -44,7 +45,6 @@ constexpr int kWBlock = 256;
 constexpr int kRunMax = 64;         // longest run of equal h ordered by one thread
 constexpr int kWideU = 8;           // 16-B loads in flight per lane in the filter
 constexpr int64_t kWideGrid = 256 * 32;
-typedef long long w2i64 __attribute__((ext_vector_type(2)));
 
 inline unsigned wgrid(int64_t n, int64_t cap = 65535) {
     return (unsigned)std::min<int64_t>(std::max<int64_t>((n + kWBlock - 1) / kWBlock, 1), cap);
@@ -85,77 +85,13 @@ struct WRanges {
     }
 };
 
-__device__ __forceinline__ unsigned long long lanemask_lt_w() {
-    const uint32_t lane = threadIdx.x & 63;
-    return lane ? (~0ull >> (64 - lane)) : 0ull;
-}
-
 template <int SRC>
 __device__ __forceinline__ int64_t wide_hash(const int64_t* hashes, const uint64_t* rows, int64_t i) {
     if constexpr (SRC == kWideSrcHashes) return hashes[i];
     else return uuid_hash_code(rows[2 * i], rows[2 * i + 1]);
 }
 
-// Candidate output of the filter: each wave stages (h, offset) in LDS and appends B at a time under
-// one reservation atomic (the counter is a single contended word); the workgroup's leftovers go out
-// under one atomic at the end.
-struct WideOut {
-    static constexpr uint32_t B = 128;
-    static constexpr uint32_t Q = B + 64;
-    int64_t* qh;
-    int64_t* qi;
-    uint32_t qn;
-    int64_t* cand_h;
-    int64_t* cand_i;
-    unsigned long long* counter;
-    int64_t cap;
-
-    __device__ __forceinline__ void write_at(unsigned long long base, uint32_t from, uint32_t cnt) {
-        const uint32_t lane = threadIdx.x & 63;
-        for (uint32_t j = lane; j < cnt; j += 64) {
-            const unsigned long long pos = base + j;
-            if ((int64_t)pos < cap) {
-                cand_h[pos] = qh[from + j];
-                cand_i[pos] = qi[from + j];
-            }
-        }
-    }
-    __device__ __forceinline__ void push(bool c, int64_t h, int64_t idx) {
-        const unsigned long long bal = __ballot(c);
-        if (bal == 0) return;
-        if (c) {
-            const uint32_t pos = qn + __popcll(bal & lanemask_lt_w());
-            qh[pos] = h;
-            qi[pos] = idx;
-        }
-        qn += (uint32_t)__popcll(bal);
-        if (qn >= B) {
-            qn -= B;
-            __builtin_amdgcn_wave_barrier();
-            unsigned long long base = 0;
-            if ((threadIdx.x & 63) == 0) base = atomicAdd(counter, (unsigned long long)B);
-            base = __shfl(base, 0);
-            write_at(base, qn, B);
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-    __device__ __forceinline__ void flush_block(uint32_t* s_q, unsigned long long* s_base) {
-        const uint32_t w = threadIdx.x >> 6;
-        __builtin_amdgcn_wave_barrier();
-        if ((threadIdx.x & 63) == 0) s_q[w] = qn;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t tot = 0;
-            for (int i = 0; i < kWBlock / 64; ++i) tot += s_q[i];
-            *s_base = tot ? atomicAdd(counter, (unsigned long long)tot) : 0ull;
-        }
-        __syncthreads();
-        uint32_t pre = 0;
-        for (uint32_t i = 0; i < w; ++i) pre += s_q[i];
-        if (qn) write_at(*s_base + pre, 0, qn);
-        qn = 0;
-    }
-};
+using WideQueue = OffsetQueue<kWBlock / 64>;
 
 // The filter over precomputed hashes: 16-B non-temporal loads (two hashes each), kWideU in flight per
 // lane; the <= 1 head element before the first 16-B boundary and the odd tail go through the scalar
@@ -166,22 +102,22 @@ __global__ __launch_bounds__(kWBlock) void wide_filter_hashes(const int64_t* __r
                                                               int64_t* __restrict__ cand_i,
                                                               unsigned long long* __restrict__ counter, int64_t cap,
                                                               const int64_t* __restrict__ rtab, int32_t R) {
-    __shared__ int64_t sh_h[kWBlock / 64][WideOut::Q];
-    __shared__ int64_t sh_i[kWBlock / 64][WideOut::Q];
+    __shared__ int64_t sh_h[kWBlock / 64][WideQueue::Q];
+    __shared__ int64_t sh_i[kWBlock / 64][WideQueue::Q];
     __shared__ uint32_t s_q[kWBlock / 64];
     __shared__ unsigned long long s_base;
     __shared__ int64_t s_rs[kWMaxR + 1], s_rb[kWMaxR];
-    WideOut out{sh_h[threadIdx.x >> 6], sh_i[threadIdx.x >> 6], 0u, cand_h, cand_i, counter, cap};
+    WideQueue out{sh_h[threadIdx.x >> 6], sh_i[threadIdx.x >> 6], 0u, cand_h, cand_i, counter, cap};
     WRanges rg{s_rs, s_rb, R};
     if (R) rg.load(rtab);
     int32_t rl = 0, rh = 0;
     const int64_t T = (int64_t)gridDim.x * blockDim.x;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t head = std::min<int64_t>(n, (int64_t)(((16u - ((uintptr_t)hashes & 15u)) & 15u) / 8u));
-    const w2i64* hv = reinterpret_cast<const w2i64*>(hashes + head);
+    const i64x2* hv = reinterpret_cast<const i64x2*>(hashes + head);
     const int64_t n_vec = (n - head) / 2;
     for (int64_t t0 = 0; t0 < n_vec; t0 += T * kWideU) {
-        w2i64 x[kWideU];
+        i64x2 x[kWideU];
 #pragma unroll
         for (int u = 0; u < kWideU; ++u) {
             const int64_t v = t0 + u * T + tid;
@@ -229,12 +165,12 @@ __global__ __launch_bounds__(kWBlock) void wide_filter_uuid(const uint64_t* __re
                                                             int64_t* __restrict__ cand_i,
                                                             unsigned long long* __restrict__ counter, int64_t cap,
                                                             const int64_t* __restrict__ rtab, int32_t R) {
-    __shared__ int64_t sh_h[kWBlock / 64][WideOut::Q];
-    __shared__ int64_t sh_i[kWBlock / 64][WideOut::Q];
+    __shared__ int64_t sh_h[kWBlock / 64][WideQueue::Q];
+    __shared__ int64_t sh_i[kWBlock / 64][WideQueue::Q];
     __shared__ uint32_t s_q[kWBlock / 64];
     __shared__ unsigned long long s_base;
     __shared__ int64_t s_rs[kWMaxR + 1], s_rb[kWMaxR];
-    WideOut out{sh_h[threadIdx.x >> 6], sh_i[threadIdx.x >> 6], 0u, cand_h, cand_i, counter, cap};
+    WideQueue out{sh_h[threadIdx.x >> 6], sh_i[threadIdx.x >> 6], 0u, cand_h, cand_i, counter, cap};
     WRanges rg{s_rs, s_rb, R};
     if (R) rg.load(rtab);
     int32_t rl = 0, rh = 0;
@@ -748,7 +684,7 @@ __global__ __launch_bounds__(kWBlock) void wb_sort(int64_t m, uint32_t B, int64_
         if (i < n) first = i == 0 || su[i - 1] != su[i] || row_cmp(R(se[i - 1]), R(se[i]), R.words) != 0;
         const unsigned long long bal = __ballot(first);
         if (first) {
-            const uint32_t o = base + (uint32_t)__popcll(bal & lanemask_lt_w());
+            const uint32_t o = base + (uint32_t)__popcll(bal & lanemask_lt64());
             if (ba) {
                 const uint32_t e0 = se[i];
                 int64_t a = (int64_t)e0 < m ? -1 : cand_i[(int64_t)e0 - m];
@@ -956,66 +892,41 @@ struct WideDistinct {
 
 namespace {
 
-hipError_t walloc(void** p, size_t bytes) { return pool_device_alloc(p, bytes ? bytes : 16); }
-
-// replace a device buffer by a larger one (contents kept when `keep`); the stream is synchronized
-// before the old block goes back to the pool
-hipError_t wgrow(void** p, size_t old_bytes, size_t new_bytes, bool keep, hipStream_t st) {
-    void* q = nullptr;
-    hipError_t e = walloc(&q, new_bytes);
-    if (e != hipSuccess) return e;
-    if (keep && *p && old_bytes) e = hipMemcpyAsync(q, *p, old_bytes, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && *p) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        pool_device_free(q);
-        return e;
-    }
-    pool_device_free(*p);
-    *p = q;
-    return hipSuccess;
-}
-
-int64_t wgrown(int64_t cur, int64_t need) {
-    int64_t c = std::max<int64_t>(cur, 1024);
-    while (c < need) c *= 2;
-    return c;
-}
-
 hipError_t ensure_set(WideDistinct* d, int64_t need, hipStream_t st) {
     need = std::min<int64_t>(need, d->k);
     if (need <= d->set_cap) return hipSuccess;
-    const int64_t c = std::min<int64_t>(wgrown(d->set_cap, need), d->k);
+    const int64_t c = grown_capacity(d->set_cap, need, d->k);
     const size_t W = (size_t)d->words * 8;
     hipError_t e;
-    if ((e = wgrow((void**)&d->set_h, (size_t)d->m * 8, (size_t)c * 8, true, st))) return e;
-    if ((e = wgrow((void**)&d->set_k, (size_t)d->m * W, (size_t)c * W, true, st))) return e;
-    if ((e = wgrow((void**)&d->set_h2, 0, (size_t)c * 8, false, st))) return e;
-    if ((e = wgrow((void**)&d->set_k2, 0, (size_t)c * W, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->set_h, (size_t)d->m * 8, (size_t)c * 8, true, st))) return e;
+    if ((e = pool_device_grow((void**)&d->set_k, (size_t)d->m * W, (size_t)c * W, true, st))) return e;
+    if ((e = pool_device_grow((void**)&d->set_h2, 0, (size_t)c * 8, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->set_k2, 0, (size_t)c * W, false, st))) return e;
     d->set_cap = c;
     return hipSuccess;
 }
 
 hipError_t ensure_cand(WideDistinct* d, int64_t need, hipStream_t st) {
     if (need <= d->cand_cap) return hipSuccess;
-    const int64_t c = wgrown(d->cand_cap, need);
+    const int64_t c = grown_capacity(d->cand_cap, need, INT64_MAX);
     hipError_t e;
-    if ((e = wgrow((void**)&d->cand_h, 0, (size_t)c * 8, false, st))) return e;
-    if ((e = wgrow((void**)&d->cand_i, 0, (size_t)c * 8, false, st))) return e;
-    if ((e = wgrow((void**)&d->cand_k, 0, (size_t)c * d->words * 8, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->cand_h, 0, (size_t)c * 8, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->cand_i, 0, (size_t)c * 8, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->cand_k, 0, (size_t)c * d->words * 8, false, st))) return e;
     d->cand_cap = c;
     return hipSuccess;
 }
 
 hipError_t ensure_merge(WideDistinct* d, int64_t N, hipStream_t st) {
     if (N <= d->merge_cap) return hipSuccess;
-    const int64_t c = wgrown(d->merge_cap, N);
+    const int64_t c = grown_capacity(d->merge_cap, N, INT64_MAX);
     hipError_t e;
-    if ((e = wgrow((void**)&d->eh0, 0, (size_t)c * 8, false, st))) return e;
-    if ((e = wgrow((void**)&d->eh1, 0, (size_t)c * 8, false, st))) return e;
-    if ((e = wgrow((void**)&d->ev0, 0, (size_t)c * 4, false, st))) return e;
-    if ((e = wgrow((void**)&d->ev1, 0, (size_t)c * 4, false, st))) return e;
-    if ((e = wgrow((void**)&d->flags, 0, (size_t)c * 4, false, st))) return e;
-    if ((e = wgrow((void**)&d->pos, 0, (size_t)c * 4, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->eh0, 0, (size_t)c * 8, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->eh1, 0, (size_t)c * 8, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->ev0, 0, (size_t)c * 4, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->ev1, 0, (size_t)c * 4, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->flags, 0, (size_t)c * 4, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->pos, 0, (size_t)c * 4, false, st))) return e;
     size_t a = 0, b = 0, g = 0;
     if ((e = rocprim::radix_sort_pairs(nullptr, a, (int64_t*)nullptr, (int64_t*)nullptr, (uint32_t*)nullptr,
                                        (uint32_t*)nullptr, (size_t)c)))
@@ -1028,7 +939,7 @@ hipError_t ensure_merge(WideDistinct* d, int64_t N, hipStream_t st) {
         return e;
     const size_t tb = std::max(a, std::max(b, g));
     if (tb > d->temp_bytes) {
-        if ((e = wgrow(&d->temp, 0, tb, false, st))) return e;
+        if ((e = pool_device_grow(&d->temp, 0, tb, false, st))) return e;
         d->temp_bytes = tb;
     }
     d->merge_cap = c;
@@ -1037,7 +948,7 @@ hipError_t ensure_merge(WideDistinct* d, int64_t N, hipStream_t st) {
 
 hipError_t ensure_temp(WideDistinct* d, size_t bytes, hipStream_t st) {
     if (bytes <= d->temp_bytes) return hipSuccess;
-    hipError_t e = wgrow(&d->temp, 0, bytes, false, st);
+    hipError_t e = pool_device_grow(&d->temp, 0, bytes, false, st);
     if (e == hipSuccess) d->temp_bytes = bytes;
     return e;
 }
@@ -1053,12 +964,12 @@ hipError_t ensure_buckets(WideDistinct* d, uint32_t B, hipStream_t st) {
     if (B <= d->wb_cap) return hipSuccess;
     const size_t c = std::max<uint32_t>(B, 64);
     hipError_t e;
-    if ((e = wgrow((void**)&d->wb_h, 0, c * kWCap * 8, false, st))) return e;
-    if ((e = wgrow((void**)&d->wb_e, 0, c * kWCap * 4, false, st))) return e;
-    if ((e = wgrow((void**)&d->wb_a, 0, c * kWCap * 8, false, st))) return e;
-    if ((e = wgrow((void**)&d->wb_dist, 0, c * 4, false, st))) return e;
-    if ((e = wgrow((void**)&d->wb_gsum, 0, (c / 16 + 1) * 4, false, st))) return e;
-    if ((e = wgrow((void**)&d->wb_cnt, 0, c * kWStride * 4, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->wb_h, 0, c * kWCap * 8, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->wb_e, 0, c * kWCap * 4, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->wb_a, 0, c * kWCap * 8, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->wb_dist, 0, c * 4, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->wb_gsum, 0, (c / 16 + 1) * 4, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->wb_cnt, 0, c * kWStride * 4, false, st))) return e;
     d->wb_cnt_dirty = true;
     d->wb_cap = (uint32_t)c;
     return hipSuccess;
@@ -1385,14 +1296,14 @@ hipError_t replay_log(WideDistinct* d, hipStream_t st) {
 
 hipError_t ensure_log(WideDistinct* d, int64_t need, hipStream_t st) {
     if (need <= d->log_cap) return hipSuccess;
-    const int64_t c = wgrown(d->log_cap, need);
+    const int64_t c = grown_capacity(d->log_cap, need, INT64_MAX);
     const size_t W = (size_t)d->words * 8;
     void* nb[3] = {nullptr, nullptr, nullptr};
     const size_t bytes[3] = {(size_t)c * 8, (size_t)c * 8, (size_t)c * W};
     const size_t used[3] = {(size_t)d->log_n * 8, (size_t)d->log_n * 8, (size_t)d->log_n * W};
     void** old[3] = {(void**)&d->log_h, (void**)&d->log_g, (void**)&d->log_k};
     hipError_t e = hipSuccess;
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = walloc(&nb[i], bytes[i]);
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = pool_device_alloc(&nb[i], bytes[i]);
     for (int i = 0; i < 3 && e == hipSuccess; ++i)
         if (*old[i] && used[i]) e = hipMemcpyAsync(nb[i], *old[i], used[i], hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess && (d->log_h || d->log_g || d->log_k)) e = hipStreamSynchronize(st);  // one wait, three copies
@@ -1518,7 +1429,7 @@ hipError_t sample_sched(WideDistinct* d, const void* keys, const int64_t* hashes
     *ok = false;
     hipError_t e;
     if (!d->sched) {
-        if ((e = walloc((void**)&d->sched, kSchedWords * 8))) return e;
+        if ((e = pool_device_alloc((void**)&d->sched, kSchedWords * 8))) return e;
         if ((e = pool_host_alloc((void**)&d->hsched, kSchedWords * 8, hipHostMallocDefault))) return e;
     }
     // a bounded log is replayed first (as sample_chunk would), so the state saved below is the one
@@ -1701,7 +1612,7 @@ WideDistinct* wide_create(int32_t k, int key_width, int src, int64_t r0, int64_t
     if (const char* v = std::getenv("RSV_FIRST_MIN"))  // test hook: which replay form serves a log
         d->first_min = std::max<int64_t>(0, std::atoll(v));
     if (const char* v = std::getenv("RSV_WIDE_BUCKETED")) d->bucketed_on = std::atoi(v) != 0;  // A/B hook
-    hipError_t e = walloc((void**)&d->ctl, 8 * 8);
+    hipError_t e = pool_device_alloc((void**)&d->ctl, 8 * 8);
     if (e == hipSuccess) e = hipMemset(d->ctl, 0, 8 * 8);  // ctl[7]: the publication ticket
     if (e == hipSuccess) e = pool_host_alloc((void**)&d->hctl, 8 * 8, hipHostMallocDefault);
     if (e != hipSuccess) {
@@ -1732,7 +1643,6 @@ void wide_destroy(WideDistinct* d) {
 void wide_set_timer(WideDistinct* d, KernelTimer* t) { d->timer = t; }
 int64_t wide_size(const WideDistinct* d) { return d->m; }
 const void* wide_keys_dev(const WideDistinct* d) { return d->set_k; }
-bool wide_is_ordered(const WideDistinct* d) { return d->ordered; }
 
 int wide_sample_device(WideDistinct* d, const void* keys, const int64_t* hashes, int64_t n, hipStream_t st) {
     if (n <= 0) return RSV_OK;

@@ -491,6 +491,36 @@ def test_scheduled_pass_extreme_plan(cuda, oracle, k):
     assert info["sched_passes"] + info["sched_fallbacks"] == 1, info
 
 
+@pytest.mark.parametrize("c,passes", [(40, 1), (100, 1), (200, 1), (300, 0)])
+def test_scheduled_pass_tagged_sort_keeps_first_arrival(cuda, oracle, c, passes):
+    """The scheduled merge sorts each bucket by (h, key, arrival tag) and keeps an element's first arrival.
+    k = 64, a full heap, then 65 536 distinct random keys with c repeats of X, the member planted at
+    Long.MinValue, scattered among them: X never leaves the set and passes every range bound, so its merge bucket
+    holds the member (tag 0) and c entries equal in (h, key) that differ in their tag alone.  c = 40 fits
+    one register per lane, c = 100 needs R >= 2, c = 200 needs R = 4 (the pass verifies in all three);
+    c = 300 is more than kBucketCap: the overflow verdict, and the chunk loop runs with the set restored."""
+    k, seed, n = 64, 73, 65_536
+    assert n >= 9 * _cand_limit(k) and (c + 1 > BUCKET_CAP) == (passes == 0)
+    r0, r1 = r01(oracle, seed)
+    rng = np.random.default_rng(c)
+    h1 = _rand(rng, 5000)
+    h1[1234] = MIN  # X: nothing is ever below it
+    b1 = plant(r0, r1, h1)
+    b2 = _rand(rng, n)
+    _all_distinct(b1, b2)
+    x = b1[np.argmin(_scr(r0, r1, b1))]
+    b2[rng.choice(n, c, replace=False)] = x
+    batches = [b1, b2]
+    wants = _wants(oracle, k, seed, batches)
+    assert wants[0][0][0] == wants[1][0][0] == x == b1[1234] and wants[1][1][0] == MIN and len(wants[0][0]) == k
+    assert int((b2 == x).sum()) == c
+    d = _identity_run(cuda, k, seed, "ordered", batches, wants)
+    info = d.distinct_info()
+    print(f"c={c}:", info)
+    assert info["sched_passes"] + info["sched_fallbacks"] == 1, info
+    assert info["sched_passes"] == passes, info
+
+
 # ---- E. segmented distinct (K5) ---------------------------------------------------------------------
 K5_KS = [8, 100, 300, 1100]  # one k per form (k <= 64, <= 256, <= 1024, <= 4096)
 K5_S = 6

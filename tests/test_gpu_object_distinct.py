@@ -159,17 +159,18 @@ def _ids_as_rows(ids):
 
 def _run(cuda, k, seed, ids, hs, cuts, sh, device=True):
     """The candidate protocol over the batches [cuts[i], cuts[i+1]): checks the offsets and hashes of
-    every batch, replays the candidates; returns (global candidate positions, replica, per-batch counts)."""
+    every batch, replays the candidates; returns (global candidate positions, replica, per-batch counts).
+    device: True (hs copied to the GPU), False (host batches) or the CUDA tensor that holds hs."""
     import torch
 
     from reservoir_amd.values import RandomValues
 
-    hd = torch.from_numpy(hs).to(cuda) if device else None
+    hd = hs if device is False else torch.from_numpy(hs).to(cuda) if device is True else device
     H = Handle(k, seed)
     v = RandomValues(k)
     pos, counts = [], []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        offs, ch = H.candidates(hd[a:b] if device else hs[a:b])
+        offs, ch = H.candidates(hd[a:b])
         assert np.all(np.diff(offs) > 0), "offsets strictly ascending"
         assert offs.size == 0 or (offs[0] >= 0 and offs[-1] < b - a)
         assert np.array_equal(ch, sh[a + offs]), "scrambled hashes"
@@ -290,6 +291,39 @@ def test_tiny_and_tile_sized_batches(cuda, oracle, k):
             adm, _ = _admissions(k, ids[lo:lo + n], sh[lo:lo + n])
             assert np.all(np.isin(adm + lo, pos)), (n, lo)
             assert _ids_as_rows(v.result()) == _oracle_ids(oracle, k, 3, ids[lo:lo + n], hs[lo:lo + n]), (n, lo)
+
+
+@pytest.mark.parametrize("shift", [0, 1], ids=["aligned16", "plus8"])
+@pytest.mark.parametrize("bounded", [False, True], ids=["open", "bounded"])
+def test_filter_alignment_edges(cuda, oracle, bounded, shift):
+    """obj_filter at the edges of its 16-byte loads: batches of n = 1, 2, 3, 17 and 4099 hashes (4096 =
+    one workgroup's full tile, plus the head before the first 16-byte boundary and the odd tail) that
+    start on a 16-byte boundary or 8 bytes past one, into an empty handle (everything is a candidate) and
+    behind a committed batch of 2048 (+ 1) elements (k = 3: the filter runs with a bound).  The batch's
+    first and last element are fresh and hashed below everything before them, so the reference admits
+    both."""
+    import torch
+    from hash_targets import MIN, plant
+
+    k, seed, pre = 3, 3, 2048
+    r01 = _r01(oracle, seed)
+    for n in (1, 2, 3, 17, 4099):
+        a = pre + shift if bounded else shift
+        ids = np.random.default_rng(n).integers(0, (a + n) * 7 // 10 + 1, a + n)
+        hs = _hashes(ids, "random")
+        for e, i in enumerate(sorted({a, a + n - 1})):
+            ids[i] = a + n + e
+            hs[i] = plant(*r01, [MIN + 10 - e])[0]
+        sh = _scramble(*r01, hs)
+        hd = torch.from_numpy(hs).to(cuda)
+        assert hd.data_ptr() % 16 == 0 and hd[a:].data_ptr() % 16 == 8 * shift
+        lo = 0 if bounded else a
+        pos, v, counts = _run(cuda, k, seed, ids, hs, (lo, a, a + n) if bounded else (a, a + n), sh, device=hd)
+        adm, _ = _admissions(k, ids[lo:], sh[lo:])
+        assert a - lo in adm and a + n - 1 - lo in adm  # the planted head and tail
+        assert np.all(np.isin(adm + lo, pos)), (n, "an admission of the reference is no candidate")
+        assert _ids_as_rows(v.result()) == _oracle_ids(oracle, k, seed, ids[lo:], hs[lo:]), n
+        assert not bounded or n <= 3 or counts[1] < n, counts  # a bound was in force
 
 
 def test_empty_batch_is_valid(cuda):

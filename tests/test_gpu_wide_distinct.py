@@ -380,3 +380,45 @@ def test_wide_set_mode_degenerate_hash(cuda, k, nvals):
     d.sample_all(rd[: n // 4], hashes=hd[: n // 4])
     d.sample_all(rd[n // 4:], hashes=hd[n // 4:])
     assert _sorted_rows(d.result()) == [kv[0] for kv in want]
+
+
+@pytest.mark.parametrize("shift", [0, 1], ids=["aligned16", "plus8"])
+@pytest.mark.parametrize("order", ["set", "auto"])
+def test_wide_filter_alignment_edges(cuda, oracle, order, shift):
+    """wide_filter_hashes at the edges of its 16-byte loads: a full set (k = 5 after 2048 rows), then
+    batches of n = 1, 2, 3, 17 and 4099 hashes (one workgroup; 4096 = one full tile of 256 x 8 x 2, plus
+    the head before the first 16-byte boundary and the odd tail) that start on a 16-byte boundary or 8
+    bytes past one.  The first and the last element of every batch -- the ones the scalar head and tail
+    loops read -- are fresh rows planted below every hash seen, so the reference admits both; the set is
+    the oracle's after every batch."""
+    import torch
+    from hash_targets import MIN, plant, r01
+
+    from reservoir_amd import Sampler
+
+    k, seed, width, pre, ns = 5, 27, 16, 2048, (1, 2, 3, 17, 4099)
+    r0, r1 = r01(oracle, seed)
+    total = pre + sum(n + 1 for n in ns)
+    ids = _stream(total, 11)
+    hs = _hashes(ids, "random")
+    cuts, at = [(0, pre)], pre
+    for j, n in enumerate(ns):
+        at += (at - shift) % 2  # the batch starts at an even (odd) element of the tensor
+        for e, i in enumerate(sorted({at, at + n - 1})):
+            ids[i] = total + 2 * j + e
+            hs[i] = plant(r0, r1, [MIN + 1000 - 2 * j - e])[0]
+        cuts.append((at, at + n))
+        at += n
+    rows = _rows(ids, width)
+    rd, hd = torch.from_numpy(rows).to(cuda), torch.from_numpy(hs).to(cuda)
+    assert hd.data_ptr() % 16 == 0
+    ref = oracle.DistinctRows(k, seed, width, "precomputed")
+    d = Sampler.distinct(k, key_type=f"bytes{width}", seed=seed, order=order, reusable=True)(hash=lambda b: 0)
+    for j, (a, b) in enumerate(cuts):
+        ref.sample_all(rows[a:b], hs[a:b])
+        want = _sorted_rows(ref.result()[0])
+        if j:
+            assert hd[a:b].data_ptr() % 16 == 8 * shift
+            assert bytes(rows[a]) in want and bytes(rows[b - 1]) in want  # the planted head and tail
+        d.sample_all(rd[a:b], hashes=hd[a:b])
+        assert _sorted_rows(d.result()) == want, (j, b - a)
