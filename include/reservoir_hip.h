@@ -413,6 +413,31 @@ rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_de
                                   uint64_t stream_base, void* out_keys_dev, int64_t* out_hashes_dev,
                                   int64_t* counts_dev, void* hip_stream);
 
+/* Segmented distinct over fixed-width byte keys (java.util.UUID, case classes of primitives): what
+ * rsv_distinct_segmented is for 4- and 8-byte keys.  Stream s is rows [offsets[s], offsets[s+1]) of
+ * rows_dev -- offsets count rows, not bytes; a row is key_width bytes, a multiple of 8 in 16..256,
+ * read as key_width / 8 little-endian 64-bit words (a UUID: [mostSigBits | leastSigBits]).  Two
+ * elements are one element iff all their bytes are equal; equal rows must carry equal hashes (the
+ * caller's contract, as for a byte-key handle).  Seeding and h as rsv_distinct_segmented.
+ * hash_kind: PRECOMPUTED with hashes_dev, one int64 per row, indexed like the rows; or DEFAULT at
+ * key_width 16, java.util.UUID.hashCode computed on the device (hashes_dev unused).  The other kinds,
+ * and DEFAULT at another width, are RSV_E_UNSUPPORTED; key_width 4 or 8 is RSV_E_UNSUPPORTED (use
+ * rsv_distinct_segmented); 1 <= k <= 4096 (larger: RSV_E_UNSUPPORTED).
+ * The result is the engine's set order (RSV_DISTINCT_SET), as rsv_export_packed documents it for
+ * byte keys: the min(k, D_s) distinct rows with the smallest (h, words compared as unsigned 64-bit
+ * values, word 0 first), written ascending into out_rows_dev[(s*k + j) * key_width ..], their h
+ * into out_hashes_dev[s*k + j] when not NULL, counts_dev[s] = min(k, D_s); rows and hashes beyond
+ * the count are zero.  It does not depend on the arrival order, equals a single RSV_DISTINCT_SET
+ * handle per stream, and under an injective hash the reference's set.
+ * rows_dev and out_rows_dev must be 8-byte aligned (RSV_E_ILLEGAL_ARGUMENT); rows_dev may be NULL
+ * when every stream is empty.  Stateless and stream-ordered on hip_stream: no host wait, no
+ * allocation.  All pointers are device pointers.  The resumed update / merge take 4- and 8-byte keys
+ * only. */
+rsv_status rsv_distinct_segmented_rows(const void* rows_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
+                                       int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
+                                       uint64_t seed, uint64_t stream_base, void* out_rows_dev,
+                                       int64_t* out_hashes_dev, int64_t* counts_dev, void* hip_stream);
+
 /* Segmented distinct, resumed: long-lived distinct samplers advanced by one launch per batch.  The
  * state is the caller's device memory: state_keys_dev[num_states*k] (key_width values),
  * state_hashes_dev[num_states*k] and state_counts_dev[num_states] (int64).  Row r holds counts[r]

@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = (
     "rsv_sample_indexed", "rsv_fill_slots", "rsv_abort_indexed", "rsv_retain_log", "rsv_commit_indexed",
     "rsv_distinct_candidates", "rsv_candidates_read", "rsv_candidates_commit", "rsv_candidates_abort",
     "rsv_distinct_segmented", "rsv_distinct_segmented_update", "rsv_distinct_segmented_merge",
-    "rsv_sample_segmented_update", "rsv_sample_segmented_merge",
+    "rsv_sample_segmented_update", "rsv_sample_segmented_merge", "rsv_distinct_segmented_rows",
 )
 
 
@@ -134,6 +134,7 @@ def load():
     L.rsv_sample_segmented_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_sample_segmented_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
     L.rsv_distinct_segmented.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
+    L.rsv_distinct_segmented_rows.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_distinct_segmented_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_distinct_segmented_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
     L.rsv_replay_events.argtypes = [vp, i64, i32, i64, vp, vp, i64, i32, vp, vp]
@@ -167,7 +168,7 @@ def load():
                  "rsv_commit_indexed", "rsv_distinct_candidates", "rsv_candidates_read",
                  "rsv_candidates_commit", "rsv_candidates_abort", "rsv_distinct_segmented",
                  "rsv_distinct_segmented_update", "rsv_distinct_segmented_merge",
-                 "rsv_sample_segmented_update", "rsv_sample_segmented_merge"):
+                 "rsv_sample_segmented_update", "rsv_sample_segmented_merge", "rsv_distinct_segmented_rows"):
         getattr(L, name).restype = i32
     if L.rsv_abi_version() != 1:
         raise ImportError("libreservoir_hip.so ABI version mismatch")

@@ -5,6 +5,7 @@ libreservoir_hip.so.  Every function raises if the engine is unavailable.
 
     sample_segmented  -- K2: S independent samplers in one launch (one wave per stream)
     distinct_segmented -- K5: S independent Sampler.distinct streams in one launch (bottom-k per stream)
+    distinct_segmented_rows -- K5 over fixed-width byte keys (UUIDs): rows in, the winning rows out
     SegmentedDistinct -- K5 resumed: the same S streams as caller-held state, advanced by one launch
                          per micro-batch (update) and combined across launches, GPUs and ranks (merge)
     SegmentedSampler  -- K2 resumed: S Sampler.apply streams as caller-held state (keys, idx, next), fed in
@@ -129,6 +130,53 @@ def distinct_segmented(keys, offsets, k: int, seed: int, stream_base: int = 0, h
         C.c_void_p(offsets.data_ptr()), S, keys.element_size(), k, kind, seed & (2**64 - 1),
         stream_base & (2**64 - 1), C.c_void_p(out.data_ptr()), C.c_void_p(out_h.data_ptr()),
         C.c_void_p(counts.data_ptr()), _stream_ptr(torch, keys.device)))
+    return out, out_h, counts
+
+
+def distinct_segmented_rows(rows, offsets, k: int, seed: int, stream_base: int = 0, hash: str = "default", hashes=None):
+    """distinct_segmented over fixed-width byte keys (java.util.UUID, case classes of primitives).
+
+    rows: a contiguous 2-D device tensor whose rows hold W bytes, W a multiple of 8 in 16..256 -- uint8
+    (n, W) is the documented form, int64 (n, W / 8) is the same memory; offsets count rows.  Two rows
+    are one element iff all their bytes are equal.  hash="default": java.util.UUID.hashCode of 16-byte
+    rows [mostSigBits | leastSigBits]; hash="precomputed" (or just hashes=): one int64 per row, equal
+    rows carrying equal hashes.  Returns (out_rows uint8 [S, k, W], out_hashes int64 [S, k], counts
+    int64 [S]) device tensors: stream s holds the min(k, distinct) rows with the smallest (scrambled
+    hash, row as little-endian unsigned 64-bit words), ascending, rows and hashes beyond counts[s]
+    zero -- the set a single Sampler.distinct(k, key_type="bytesW", seed=seed + stream_base + s,
+    order="set") fed the same rows holds.  1 <= k <= 4096.
+    """
+    import torch
+
+    L = N.load()
+    if not (rows.is_cuda and offsets.is_cuda):
+        raise N.IllegalArgumentException("rows and offsets must be device tensors")
+    if rows.dim() != 2 or offsets.dtype != torch.int64:
+        raise N.IllegalArgumentException("rows must be 2-D (one key per row) and offsets int64")
+    if hashes is None and hash == "precomputed":
+        raise N.NullPointerException("hash='precomputed' needs hashes=")
+    if hashes is None and hash != "default":
+        raise N.IllegalArgumentException(f"unknown hash {hash!r}")
+    if hashes is not None:
+        if not hashes.is_cuda or hashes.dtype != torch.int64 or hashes.numel() != rows.shape[0]:
+            raise N.IllegalArgumentException("hashes must be an int64 device tensor, one per row")
+        # an empty tensor has no address; the engine wants one for precomputed hashes
+        hashes = hashes.contiguous() if hashes.numel() else torch.empty(1, dtype=torch.int64, device=rows.device)
+    rows, offsets = rows.contiguous(), offsets.contiguous()
+    W = rows.shape[1] * rows.element_size()
+    S = offsets.numel() - 1
+    # the kernel writes every row block (zeros beyond the count) and every count: no zero-fill
+    kk = max(int(k), 0)
+    out = torch.empty((max(S, 0), kk, W), dtype=torch.uint8, device=rows.device)
+    out_h = torch.empty((max(S, 0), kk), dtype=torch.int64, device=rows.device)
+    counts = torch.empty(max(S, 0), dtype=torch.int64, device=rows.device)
+    if S <= 0:
+        return out, out_h, counts
+    N.check(L.rsv_distinct_segmented_rows(
+        C.c_void_p(rows.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
+        C.c_void_p(offsets.data_ptr()), S, W, k, N.HASH_PRECOMPUTED if hashes is not None else N.HASH_DEFAULT,
+        seed & (2**64 - 1), stream_base & (2**64 - 1), C.c_void_p(out.data_ptr()), C.c_void_p(out_h.data_ptr()),
+        C.c_void_p(counts.data_ptr()), _stream_ptr(torch, rows.device)))
     return out, out_h, counts
 
 

@@ -161,6 +161,12 @@ constexpr uint32_t kSegDistinctMaxK = 4096;
 hipError_t launch_segdistinct(const void* keys, int key_width, const int64_t* hashes, const int64_t* offsets, int64_t S,
                               uint32_t k, int hash_kind, uint64_t seed0, void* out_keys, int64_t* out_hashes,
                               int64_t* counts, hipStream_t st);
+// K5 over byte keys (rsv_segdistinct.hip, the same element loop and forms): rows of key_width bytes (16..256, a
+// multiple of 8; rows and out_rows 8-byte aligned), the bottom-k by (scrambled hash, row words unsigned).
+// hashes: one per row, or null for UUID.hashCode of 16-byte rows.
+hipError_t launch_segdistinct_rows(const void* rows, int key_width, const int64_t* hashes, const int64_t* offsets,
+                                   int64_t S, uint32_t k, uint64_t seed0, void* out_rows, int64_t* out_hashes,
+                                   int64_t* counts, hipStream_t st);
 // K5 resumed (rsv_segdistinct.hip, the same element loop and forms): the teams started from the caller's state rows
 // (keys[num_states*k], hashes, counts; ascending by (h, key) as launch_segdistinct writes them) and
 // written back in place.  update: segment b into row stream_ids[b] (null: row b), seeded seed0 + row;

@@ -1680,6 +1680,39 @@ rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_de
     return RSV_OK;
 }
 
+rsv_status rsv_distinct_segmented_rows(const void* rows_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
+                                       int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
+                                       uint64_t seed, uint64_t stream_base, void* out_rows_dev,
+                                       int64_t* out_hashes_dev, int64_t* counts_dev, void* hip_stream) {
+    // the checks in rsv_distinct_segmented's order: k, key_width, hash_kind, num_streams, pointers
+    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
+    if (k > (int32_t)kSegDistinctMaxK)
+        return fail(RSV_E_UNSUPPORTED, "rsv_distinct_segmented_rows holds k <= " + std::to_string(kSegDistinctMaxK) +
+                                           " per stream; use separate handles beyond");
+    if (key_width == 4 || key_width == 8)
+        return fail(RSV_E_UNSUPPORTED, "rsv_distinct_segmented_rows takes byte keys; rsv_distinct_segmented takes 4- and 8-byte keys");
+    if (key_width < 16 || key_width > 256 || key_width % 8 != 0)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be a multiple of 8 in 16..256");
+    if (hash_kind < RSV_HASH_DEFAULT || hash_kind > RSV_HASH_PRECOMPUTED)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "unknown hash kind");
+    if (hash_kind != RSV_HASH_DEFAULT && hash_kind != RSV_HASH_PRECOMPUTED)
+        return fail(RSV_E_UNSUPPORTED, "byte keys take RSV_HASH_PRECOMPUTED, or RSV_HASH_DEFAULT (UUID.hashCode) at key_width 16");
+    if (hash_kind == RSV_HASH_DEFAULT && key_width != 16)
+        return fail(RSV_E_UNSUPPORTED, "RSV_HASH_DEFAULT is UUID.hashCode: key_width 16 only");
+    if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
+    if (num_streams == 0) return RSV_OK;
+    // rows_dev is not checked: a launch whose streams are all empty has no rows
+    if (!offsets_dev || !out_rows_dev || !counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (hash_kind == RSV_HASH_PRECOMPUTED && !hashes_dev)
+        return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
+    if (((uintptr_t)rows_dev | (uintptr_t)out_rows_dev) & 7)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "rows_dev and out_rows_dev must be 8-byte aligned");
+    RSV_HIP_TRY(launch_segdistinct_rows(rows_dev, key_width, hash_kind == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr,
+                                        offsets_dev, num_streams, (uint32_t)k, seed + stream_base, out_rows_dev,
+                                        out_hashes_dev, counts_dev, (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
 rsv_status rsv_distinct_segmented_update(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
                                          const int64_t* stream_ids_dev, int64_t num_segments, int64_t num_states,
                                          int32_t key_width, int32_t k, int32_t hash_kind, uint64_t seed,

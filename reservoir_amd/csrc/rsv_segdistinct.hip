@@ -48,6 +48,18 @@
 //              state moves no state bytes out).
 // Nothing read from the state or from the ids indexes memory unclamped: the count is clamped into
 // [0, k], an id outside [0, num_states) skips the segment.
+//
+// Byte keys (rsv_distinct_segmented_rows; rows of W = 16..256 bytes, W8 = W / 8 little-endian 64-bit
+// words): the same teams, forms, element loop, merge and grid over entries (h, i), i the row's index
+// into rows_dev, so the entry stays 16 bytes and every width keeps the LDS budget above.  What an
+// entry's second word means is the one thing the loop and the merge take as a parameter (Keys /
+// Rows below).  Order and equality go by h first; only two entries with equal h read their rows
+// from global memory, word by word as unsigned values, and equal rows are one element whatever their
+// indices.  The sort's pad is (INT64_MAX, -1): the index -1 is tested before any row is addressed,
+// is above every row and equal to itself.  T's row sits in LDS (s_trow, rewritten by the merge that
+// sets T), so admission reads a row only on the lanes with h == T.h.  Hashes are precomputed (8 bytes
+// per element; the rows are read on ties and for the output only) or UUID.hashCode of 16-byte rows
+// (one 16-byte load per element, two 8-byte loads when rows_dev sits at 8 mod 16).
 #include <algorithm>
 #include <type_traits>
 
@@ -84,14 +96,132 @@ struct alignas(16) Ent {
 __device__ __forceinline__ bool ent_less(const Ent& a, const Ent& b) { return a.h < b.h || (a.h == b.h && a.key < b.key); }
 __device__ __forceinline__ bool ent_eq(const Ent& a, const Ent& b) { return a.h == b.h && a.key == b.key; }
 
+// the team's registers across the pieces of one row (uniform over the team)
+struct Team {
+    uint32_t m;      // set size
+    uint32_t n_tot;  // set + waiting candidates (= s_cnt, read between two barriers)
+    int64_t Th, Tk;  // admission threshold: the k-th entry, or the pad below k entries
+    bool dirty;      // something was appended since the team started on the row
+};
+
+// What an entry's second word is, for the merge (pad, out_of_order, same) and for the element loop
+// (load, h_of, admits, set_T).  K5's own: the key itself, sign-extended.
+struct KeyOrd {
+    static __device__ __forceinline__ Ent pad() { return Ent{kMaxI64, kMaxI64}; }
+    __device__ __forceinline__ bool out_of_order(const Ent& a, const Ent& b, bool asc) const {
+        return ent_less(b, a) == asc && !ent_eq(a, b);
+    }
+    __device__ __forceinline__ bool same(const Ent& a, const Ent& b) const { return ent_eq(a, b); }
+};
+
+// SCRAMBLE: h = scramble(r0, r1, hash(key)); otherwise h = hashes[i] as stored.
+template <typename KeyT, bool SCRAMBLE>
+struct Keys : KeyOrd {
+    const KeyT* __restrict__ keys;
+    const int64_t* __restrict__ hashes;
+    int hash_kind;
+    int64_t r0, r1;
+    __device__ __forceinline__ void load(int64_t i, int64_t& key, int64_t& hv) const {
+        key = (int64_t)keys[i];
+        if (!SCRAMBLE || hash_kind == kHashPrecomputed) hv = hashes[i];
+    }
+    __device__ __forceinline__ int64_t h_of(int64_t key, int64_t hv) const {
+        if constexpr (SCRAMBLE) {
+            int64_t hashed;
+            if (hash_kind == kHashPrecomputed)
+                hashed = hv;
+            else if (hash_kind == kHashJavaLong)
+                hashed = hash_of<int64_t, kHashJavaLong>(key);
+            else if (hash_kind == kHashJavaInt)
+                hashed = hash_of<int64_t, kHashJavaInt>(key);
+            else
+                hashed = key;  // identity: the sign-extended key
+            return scramble(r0, r1, hashed);
+        } else {
+            return hv;
+        }
+    }
+    __device__ __forceinline__ bool admits(int64_t h, int64_t key, const Team& t) const {
+        return h < t.Th || (h == t.Th && key <= t.Tk);
+    }
+    __device__ __forceinline__ void set_T(const Ent* se, uint32_t k, Team& t) const {
+        t.Th = se[k - 1].h;
+        t.Tk = se[k - 1].key;
+    }
+};
+
+// Byte keys: the index of a row of W8 words in `rows`; -1 is the pad's.
+struct RowOrd {
+    const uint64_t* __restrict__ rows;
+    uint32_t W8;
+    static __device__ __forceinline__ Ent pad() { return Ent{kMaxI64, -1}; }
+    // <0, 0, >0.  The only place that turns an entry's index into an address of two rows: equal indices
+    // (two pads among them) and the pad are settled before it.
+    __device__ __forceinline__ int cmp(const Ent& a, const Ent& b) const {
+        if (a.h != b.h) return a.h < b.h ? -1 : 1;
+        if (a.key == b.key) return 0;
+        if (a.key < 0) return 1;
+        if (b.key < 0) return -1;
+        const uint64_t* const ra = rows + a.key * (int64_t)W8;
+        const uint64_t* const rb = rows + b.key * (int64_t)W8;
+        for (uint32_t w = 0; w < W8; ++w) {
+            const uint64_t x = ra[w], y = rb[w];
+            if (x != y) return x < y ? -1 : 1;
+        }
+        return 0;
+    }
+    __device__ __forceinline__ bool out_of_order(const Ent& a, const Ent& b, bool asc) const {
+        const int c = cmp(a, b);
+        return c != 0 && (c > 0) == asc;
+    }
+    __device__ __forceinline__ bool same(const Ent& a, const Ent& b) const { return cmp(a, b) == 0; }
+};
+
+struct Rows : RowOrd {
+    const int64_t* __restrict__ hashes;  // null: UUID.hashCode of the 16-byte row
+    bool vec16;                          // rows is 16-byte aligned: a UUID is one 16-byte load
+    int64_t r0, r1;
+    uint64_t* s_trow;  // LDS: T's row while t.Tk >= 0
+    __device__ __forceinline__ void load(int64_t i, int64_t& key, int64_t& hv) const {
+        key = i;
+        if (hashes) {
+            hv = hashes[i];
+        } else if (vec16) {
+            const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(rows + 2 * i);
+            hv = uuid_hash_code(v.x, v.y);
+        } else {
+            hv = uuid_hash_code(rows[2 * i], rows[2 * i + 1]);
+        }
+    }
+    __device__ __forceinline__ int64_t h_of(int64_t, int64_t hv) const { return scramble(r0, r1, hv); }
+    // (h, row i) <= T; below k entries T is the pad, above every row
+    __device__ __forceinline__ bool admits(int64_t h, int64_t i, const Team& t) const {
+        if (h != t.Th) return h < t.Th;
+        if (t.Tk < 0 || i == t.Tk) return true;
+        const uint64_t* const r = rows + i * (int64_t)W8;
+        for (uint32_t w = 0; w < W8; ++w) {
+            const uint64_t x = r[w], y = s_trow[w];
+            if (x != y) return x < y;
+        }
+        return true;
+    }
+    // between the merge and the two barriers that precede the next admission test
+    __device__ __forceinline__ void set_T(const Ent* se, uint32_t k, Team& t) const {
+        t.Th = se[k - 1].h;
+        t.Tk = se[k - 1].key;
+        if (threadIdx.x < W8) s_trow[threadIdx.x] = rows[t.Tk * (int64_t)W8 + threadIdx.x];
+    }
+};
+
 // Sort + dedup + trim of the team's first n entries; returns the new set size min(k, distinct).
-template <int NT>
-__device__ __forceinline__ uint32_t merge_set(Ent* __restrict__ se, uint32_t n, uint32_t k, uint32_t* __restrict__ s_scan) {
+template <int NT, typename Ord>
+__device__ __forceinline__ uint32_t merge_set(Ent* __restrict__ se, uint32_t n, uint32_t k, uint32_t* __restrict__ s_scan,
+                                              const Ord& ord) {
     const uint32_t tid = threadIdx.x;
     if (n == 0) return 0;
     uint32_t sz2 = 2;
     while (sz2 < n) sz2 <<= 1;
-    for (uint32_t i = n + tid; i < sz2; i += NT) se[i] = Ent{kMaxI64, kMaxI64};
+    for (uint32_t i = n + tid; i < sz2; i += NT) se[i] = Ord::pad();
     __syncthreads();
     for (uint32_t sz = 2; sz <= sz2; sz <<= 1) {
         for (uint32_t j = sz >> 1; j > 0; j >>= 1) {
@@ -99,7 +229,7 @@ __device__ __forceinline__ uint32_t merge_set(Ent* __restrict__ se, uint32_t n, 
                 const uint32_t l = ((t & ~(j - 1)) << 1) | (t & (j - 1));
                 const bool asc = (l & sz) == 0;
                 const Ent a = se[l], b = se[l + j];
-                if (ent_less(b, a) == asc && !ent_eq(a, b)) {
+                if (ord.out_of_order(a, b, asc)) {
                     se[l] = b;
                     se[l + j] = a;
                 }
@@ -118,7 +248,7 @@ __device__ __forceinline__ uint32_t merge_set(Ent* __restrict__ se, uint32_t n, 
         bool first = false;
         if (i < n) {
             e = se[i];
-            first = i == 0 || !ent_eq(e, se[i - 1]);
+            first = i == 0 || !ord.same(e, se[i - 1]);
         }
         const uint64_t mask = __ballot(first);
         uint32_t pre = (uint32_t)__popcll(mask & ((1ULL << (tid & 63)) - 1));
@@ -145,21 +275,10 @@ __device__ __forceinline__ uint32_t merge_set(Ent* __restrict__ se, uint32_t n, 
     return run < k ? run : k;
 }
 
-// the team's registers across the pieces of one row (uniform over the team)
-struct Team {
-    uint32_t m;      // set size
-    uint32_t n_tot;  // set + waiting candidates (= s_cnt, read between two barriers)
-    int64_t Th, Tk;  // admission threshold: the k-th entry, or (max, max) below k entries
-    bool dirty;      // something was appended since the team started on the row
-};
-
-// The element loop over one piece [lo, hi) of keys (and hashes).  SCRAMBLE: h = scramble(r0, r1,
-// hash(key)); otherwise h = hashes[i] as stored.
-template <typename KeyT, int NT, bool SCRAMBLE>
+// The element loop over one piece [lo, hi) of src's elements.
+template <typename Src, int NT>
 __device__ __forceinline__ void take_piece(Ent* __restrict__ se, uint32_t* __restrict__ s_cnt, uint32_t* __restrict__ s_scan,
-                                           const KeyT* __restrict__ keys, const int64_t* __restrict__ hashes, int64_t lo,
-                                           int64_t hi, uint32_t k, uint32_t P, int hash_kind, int64_t r0, int64_t r1,
-                                           Team& t) {
+                                           const Src& src, int64_t lo, int64_t hi, uint32_t k, uint32_t P, Team& t) {
     const uint32_t tid = threadIdx.x;
     constexpr int64_t kChunk = (int64_t)NT * kU;
     for (int64_t base = lo; base < hi; base += kChunk) {
@@ -170,42 +289,22 @@ __device__ __forceinline__ void take_piece(Ent* __restrict__ se, uint32_t* __res
             const int64_t i = base + (int64_t)u * NT + tid;
             key[u] = 0;
             hv[u] = 0;
-            if (i < hi) {
-                key[u] = (int64_t)keys[i];
-                if (!SCRAMBLE || hash_kind == kHashPrecomputed) hv[u] = hashes[i];
-            }
+            if (i < hi) src.load(i, key[u], hv[u]);
         }
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
             const int64_t i = base + (int64_t)u * NT + tid;
             if (base + (int64_t)u * NT >= hi) break;  // uniform: the tail chunk's empty steps
             if (t.n_tot + NT > P || (t.m < k && t.n_tot >= 4 * k)) {
-                t.m = merge_set<NT>(se, t.n_tot, k, s_scan);
-                if (t.m == k) {
-                    t.Th = se[k - 1].h;
-                    t.Tk = se[k - 1].key;
-                }
+                t.m = merge_set<NT>(se, t.n_tot, k, s_scan, src);
+                if (t.m == k) src.set_T(se, k, t);
                 __syncthreads();  // T is read before the appends below overwrite anything
                 if (tid == 0) *s_cnt = t.m;
                 t.n_tot = t.m;
                 __syncthreads();
             }
-            int64_t h;
-            if constexpr (SCRAMBLE) {
-                int64_t hashed;
-                if (hash_kind == kHashPrecomputed)
-                    hashed = hv[u];
-                else if (hash_kind == kHashJavaLong)
-                    hashed = hash_of<int64_t, kHashJavaLong>(key[u]);
-                else if (hash_kind == kHashJavaInt)
-                    hashed = hash_of<int64_t, kHashJavaInt>(key[u]);
-                else
-                    hashed = key[u];  // identity: the sign-extended key
-                h = scramble(r0, r1, hashed);
-            } else {
-                h = hv[u];
-            }
-            const bool pass = i < hi && (h < t.Th || (h == t.Th && key[u] <= t.Tk));
+            const int64_t h = src.h_of(key[u], hv[u]);
+            const bool pass = i < hi && src.admits(h, key[u], t);
             const uint64_t mask = __ballot(pass);
             if (mask) {
                 const uint32_t lead = (uint32_t)(__ffsll((long long)mask) - 1);  // the wave's first admitting lane
@@ -232,7 +331,7 @@ template <typename KeyT, int NT, bool HASHES_OPTIONAL>
 __device__ __forceinline__ void finish_row(Ent* se, uint32_t* s_scan, Team& t, uint32_t k, int64_t row, KeyT* keys,
                                            int64_t* hashes, int64_t* counts) {
     const uint32_t tid = threadIdx.x;
-    if (t.n_tot != t.m) t.m = merge_set<NT>(se, t.n_tot, k, s_scan);
+    if (t.n_tot != t.m) t.m = merge_set<NT>(se, t.n_tot, k, s_scan, KeyOrd{});
     __syncthreads();
     const int64_t ob = row * (int64_t)k;
     for (uint32_t i = tid; i < k; i += NT) {
@@ -262,8 +361,47 @@ __global__ __launch_bounds__(NT) void segdistinct_kernel(const KeyT* __restrict_
         if (threadIdx.x == 0) s_cnt = 0;
         __syncthreads();
         Team t{0, 0, kMaxI64, kMaxI64, false};
-        take_piece<KeyT, NT, true>(se, &s_cnt, s_scan, keys, hashes, offsets[s], offsets[s + 1], k, P, hash_kind, r0, r1, t);
+        const Keys<KeyT, true> src{{}, keys, hashes, hash_kind, r0, r1};
+        take_piece<Keys<KeyT, true>, NT>(se, &s_cnt, s_scan, src, offsets[s], offsets[s + 1], k, P, t);
         finish_row<KeyT, NT, true>(se, s_scan, t, k, s, out_keys, out_hashes, counts);
+    }
+}
+
+// Byte keys, stateless.  The epilogue gathers the m winning rows with lanes over (entry, word), so a
+// wave's stores are consecutive words of the row block, and zeroes the rest of it.
+template <int NT>
+__global__ __launch_bounds__(NT) void segrows_kernel(const uint64_t* __restrict__ rows, const int64_t* __restrict__ hashes,
+                                                     const int64_t* __restrict__ offsets, int64_t S, uint32_t W8,
+                                                     uint32_t k, uint32_t P, uint64_t seed0,
+                                                     uint64_t* __restrict__ out_rows, int64_t* __restrict__ out_hashes,
+                                                     int64_t* __restrict__ counts) {
+    extern __shared__ __align__(16) unsigned char seg_lds[];
+    Ent* const se = (Ent*)seg_lds;
+    __shared__ uint32_t s_cnt;
+    __shared__ uint32_t s_scan[NT / 64 > 1 ? NT / 64 : 1];
+    __shared__ uint64_t s_trow[32];  // kMaxRowWords
+    const uint32_t tid = threadIdx.x;
+    const bool vec16 = ((uintptr_t)rows & 15) == 0;
+
+    for (int64_t s = blockIdx.x; s < S; s += gridDim.x) {
+        int64_t r0, r1;
+        java_r0r1(seed0 + (uint64_t)s, r0, r1);
+        __syncthreads();  // the previous stream's output reads are done
+        if (tid == 0) s_cnt = 0;
+        __syncthreads();
+        Team t{0, 0, kMaxI64, -1, false};
+        const Rows src{{rows, W8}, hashes, vec16, r0, r1, s_trow};
+        take_piece<Rows, NT>(se, &s_cnt, s_scan, src, offsets[s], offsets[s + 1], k, P, t);
+        if (t.n_tot != t.m) t.m = merge_set<NT>(se, t.n_tot, k, s_scan, src);
+        __syncthreads();
+        const int64_t ob = s * (int64_t)k;
+        for (uint32_t x = tid; x < k * W8; x += NT) {  // k * W8 <= 4096 * 32
+            const uint32_t j = x / W8, w = x - j * W8;
+            out_rows[ob * W8 + x] = j < t.m ? rows[se[j].key * (int64_t)W8 + w] : 0;
+        }
+        if (out_hashes)
+            for (uint32_t i = tid; i < k; i += NT) out_hashes[ob + i] = i < t.m ? se[i].h : 0;
+        if (tid == 0) counts[s] = t.m;
     }
 }
 
@@ -312,12 +450,14 @@ __global__ __launch_bounds__(NT) void segstate_kernel(const KeyT* in_keys, const
                 const int64_t pc = part_counts[row];
                 const int64_t n = pc <= 0 ? 0 : (pc >= (int64_t)k ? (int64_t)k : pc);
                 const int64_t pb = row * (int64_t)k;
-                take_piece<KeyT, NT, false>(se, &s_cnt, s_scan, in_keys, in_hashes, pb, pb + n, k, P, hash_kind, 0, 0, t);
+                take_piece<Keys<KeyT, false>, NT>(se, &s_cnt, s_scan, Keys<KeyT, false>{{}, in_keys, in_hashes, hash_kind, 0, 0}, pb,
+                                                  pb + n, k, P, t);
             }
         } else {
             int64_t r0, r1;
             java_r0r1(seed0 + (uint64_t)r, r0, r1);
-            take_piece<KeyT, NT, true>(se, &s_cnt, s_scan, in_keys, in_hashes, lo, hi, k, P, hash_kind, r0, r1, t);
+            take_piece<Keys<KeyT, true>, NT>(se, &s_cnt, s_scan, Keys<KeyT, true>{{}, in_keys, in_hashes, hash_kind, r0, r1}, lo, hi,
+                                             k, P, t);
         }
         if (!t.dirty) continue;  // nothing admitted: the row stands as it is
         finish_row<KeyT, NT, false>(se, s_scan, t, k, r, state_keys, state_hashes, state_counts);
@@ -365,6 +505,18 @@ hipError_t launch_segdistinct(const void* keys, int key_width, const int64_t* ha
         return launch_teams(segdistinct_kernel<KeyT, NT>, NT, S, P, st, (const KeyT*)keys, hashes, offsets, S, k, P,
                             hash_kind, seed0, (KeyT*)out_keys, out_hashes, counts);
     });
+}
+
+hipError_t launch_segdistinct_rows(const void* rows, int key_width, const int64_t* hashes, const int64_t* offsets,
+                                   int64_t S, uint32_t k, uint64_t seed0, void* out_rows, int64_t* out_hashes,
+                                   int64_t* counts, hipStream_t st) {
+    if (S <= 0) return hipSuccess;
+    auto f = [&](int64_t, auto nt, uint32_t P) {
+        constexpr int NT = decltype(nt)::value;
+        return launch_teams(segrows_kernel<NT>, NT, S, P, st, (const uint64_t*)rows, hashes, offsets, S,
+                            (uint32_t)key_width / 8, k, P, seed0, (uint64_t*)out_rows, out_hashes, counts);
+    };
+    return with_form_of<int64_t>(k, f);
 }
 
 hipError_t launch_segdistinct_update(const void* keys, int key_width, const int64_t* hashes, const int64_t* offsets,
