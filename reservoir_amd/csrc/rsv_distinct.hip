@@ -1625,33 +1625,36 @@ inline unsigned grid_1d(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock
 
 }  // namespace
 
-struct DistinctState {
+// one logged chunk (or scheduled pass) of an ordered sampler
+struct LogSeg {
+    int64_t off, c, m;  // log offset, candidates, chunk length
+};
+
+// The Long (KeyT = int64_t) and Int (int32_t) engine behind DistinctEngine (rsv_internal.h).  Every
+// entry point settles a pending rows merge first (settle).
+template <typename KeyT>
+struct NarrowDistinct final : DistinctEngine {
+    static constexpr int kw = (int)sizeof(KeyT);
     int32_t k = 0;
-    int kw = 8;
     int hash_kind = kHashIdentity;
     int64_t r0 = 0, r1 = 0;
     int64_t m = 0;                // current set size
     int64_t max_h = INT64_MIN;    // valid when m == k
     int64_t set_top = INT64_MIN;  // the set's largest hash, valid when m > 0
     int64_t* set_h = nullptr;     // [set_cap <= k], ascending (h, key)
-    void* set_k = nullptr;
+    KeyT* set_k = nullptr;
     int64_t set_cap = 0;
-    // speculative set publication (set mode, batches >= kSpecMinBatch): target from the runtime
-    void* spec_dst = nullptr;     // coherent host buffer (device alias)
-    uint32_t* spec_flag = nullptr;
-    uint32_t* spec_gen_ctr = nullptr;  // the handle's publication generation counter
-    bool spec_arm = false;        // read_ctl enqueues publish_set_kernel behind ctl_publish
-    bool spec_ok = false;         // the last enqueued publication holds the batch's final set
-    uint32_t spec_gen = 0;
-    int64_t spec_min = 1ll << 27;  // smallest batch that publishes speculatively (~180 us of filter)
+    // speculative set publication (the base's `spec`; set mode, batches >= spec_min_batch): when armed,
+    // read_ctl enqueues publish_set_kernel behind ctl_publish
+    int64_t spec_min_batch = 1ll << 27;  // smallest batch that publishes speculatively (~180 us of filter)
     int64_t cand_limit = 0;       // 4k + 4096: the most candidates one filter pass may keep
     int64_t cand_cap = 0;         // allocated (grows on demand up to cand_limit)
     int64_t* cand_h = nullptr;
-    void* cand_k = nullptr;
+    KeyT* cand_k = nullptr;
     unsigned long long* counter = nullptr;
     int64_t merge_cap = 0;        // set + candidates of one merge (grows on demand)
     int64_t *mh0 = nullptr, *mh1 = nullptr;
-    void *mk0 = nullptr, *mk1 = nullptr;
+    KeyT *mk0 = nullptr, *mk1 = nullptr;
     uint32_t *flags = nullptr, *pos = nullptr;
     int64_t* d_count = nullptr;
     // bucketed merge (bucket_scatter/sort/emit); log_bmax < 0: radix-sort merge only
@@ -1661,7 +1664,7 @@ struct DistinctState {
     int64_t* hc_dev = nullptr;
     uint32_t hc_gen = 0;
     int64_t* bh = nullptr;        // [bmax * kBucketCap] bucket entries
-    void* bk = nullptr;
+    KeyT* bk = nullptr;
     void* temp = nullptr;
     size_t temp_bytes = 0;
     int64_t* samp = nullptr;      // [2 * kSample]
@@ -1672,19 +1675,14 @@ struct DistinctState {
     // RSV_DISTINCT_ORDERED (see ordered_sample_impl): the set arrays track the bottom-k by (h, key)
     // of what the reference could admit; the exact replica of RandomValues runs on the host over a
     // device log of the admitted candidates, only when the tie bucket makes it necessary
-    bool ordered = false;
     bool over = false;              // more admitted distinct elements have h <= max_h than k
     bool exact = true;              // the set arrays hold the reference's set
     HostValues rep;                 // the replica, current up to the first logged segment
-    int64_t seen = 0;               // elements sampled so far (chunk sizing)
     int64_t rate_c = 0, rate_m = 0; // the last full-heap chunk: candidates, length,
     double rate_span = 0;           // and its threshold's distance above Long.MinValue
-    struct Seg {
-        int64_t off, c, m;          // log offset, candidates, chunk length
-    };
-    std::vector<Seg> segs;
+    std::vector<LogSeg> segs;
     int64_t* log_h = nullptr;       // [log_cap] candidates of every chunk since the last replay
-    void* log_k = nullptr;
+    KeyT* log_k = nullptr;
     uint32_t* log_i = nullptr;      // chunk-relative arrival index
     int64_t log_n = 0, log_cap = 0, log_limit = 0;
     // the scheduled pass (sched_sample): range bounds, its own merge area, the set's backup
@@ -1692,11 +1690,11 @@ struct DistinctState {
     int64_t* sctl = nullptr;        // ctl words + bucket counts of the scheduled merge
     int32_t log_bmax_s = -1;
     int64_t* sbh = nullptr;
-    void* sbk = nullptr;
+    KeyT* sbk = nullptr;
     uint32_t* sbi = nullptr;
     int* vacc = nullptr;            // [kVerifyCopies][kMaxRanges + 1]
     int64_t* bak_h = nullptr;       // [k] the set before the pass
-    void* bak_k = nullptr;
+    KeyT* bak_k = nullptr;
     int64_t* shc = nullptr;         // coherent host: published words + flag at [12]
     int64_t* shc_dev = nullptr;
     uint32_t sgen = 0;
@@ -1706,45 +1704,42 @@ struct DistinctState {
     uint32_t* perm = nullptr;       // [ord_cap] one segment's candidates in arrival order
     uint32_t* sorted_i = nullptr;   // [ord_cap] radix-sort key output
     int64_t* ord_h = nullptr;       // [ord_cap] one segment's hashes and keys permuted into arrival order
-    void* ord_k = nullptr;
+    KeyT* ord_k = nullptr;
     int64_t ord_cap = 0;            // capacity of the two buffers above and of the pinned copies
     int64_t* ph = nullptr;          // pinned: hashes, keys (as KeyT) of one segment in arrival order
-    void* pk = nullptr;
+    KeyT* pk = nullptr;
     // first-occurrence flags (segment_to_host with `first`): members + segment keys, sorted copies,
     // their positions, the flags on the device and pinned, the members' pinned staging
-    void* fk_in = nullptr;
-    void* fk_out = nullptr;
+    KeyT* fk_in = nullptr;
+    KeyT* fk_out = nullptr;
     uint32_t* fv = nullptr;
     uint8_t* fflag = nullptr;
     uint8_t* pflag = nullptr;
-    void* pmem = nullptr;
+    KeyT* pmem = nullptr;
     int64_t fcap = 0;               // capacity (entries) of fk_in / fk_out / fv; fflag / pflag hold ord_cap
     int64_t pmem_cap = 0;
     int64_t first_min = 4096;       // segments at least this long replay through the flags (no host set)
     // the next segment staged while the host runs this one (replay_log): its pinned copies
     int64_t* ph2 = nullptr;
-    void* pk2 = nullptr;
+    KeyT* pk2 = nullptr;
     uint8_t* pflag2 = nullptr;
     int64_t ord2_cap = 0;
     bool overlap = true;            // RSV_REPLAY_OVERLAP=0 (test hook): stage no segment ahead
     hipEvent_t seg_ev = nullptr;    // a segment's own copies done (the next one's staging may still run)
     // Exact multi-rank merge of ordered samplers (rsv_export_log / rsv_merge_log): the candidates
     // the replica consumed (arrival order, host) + the segments still in the log, and the segments
-    // logged before the last merge -- together every candidate logged since creation (`arch_ok`).
-    // Sampling again after a merge drops them (the merged state has no single arrival order).
-    // Opt-in (rsv_retain_log, before the first sample): the archive holds 12-16 B per consumed
-    // candidate on the host, up to kArchMax of them.
-    bool retain = false;
-    std::vector<int64_t> arch_h, arch_k;  // keys: arch_k (8-byte keys) or arch_k4 (4-byte keys)
-    std::vector<int32_t> arch_k4;
-    bool arch_ok = true;
-    std::vector<Seg> pre_segs;
-    bool merged = false;
+    // logged before the last merge -- together every candidate logged since creation (the base's
+    // `arch_ok`).  Sampling again after a merge drops them (the merged state has no single arrival
+    // order).  Opt-in (rsv_retain_log, before the first sample): the archive holds 12-16 B per
+    // consumed candidate on the host, up to kArchMax of them.
+    std::vector<int64_t> arch_h;
+    std::vector<KeyT> arch_k;
+    std::vector<LogSeg> pre_segs;
     int64_t sched_passes = 0, sched_fallbacks = 0;  // rsv_distinct_info counters
     // the replica lags the set arrays (a merge replaced the set): rebuilt from them before the
     // next replay, which is the only reader (a merge without a later tie never pays for it)
     bool rep_stale = false;
-    // device combine of packed rows (distinct_merge_rows): enqueued without a host wait; the host
+    // device combine of packed rows (merge_rows): enqueued without a host wait; the host
     // fields (m, max_h, set_top, over) are settled from its published words at the next call
     bool pend = false;
     uint32_t pend_gen = 0;
@@ -1756,19 +1751,41 @@ struct DistinctState {
     int64_t pend_stride = 0;
     uint32_t* mstart = nullptr;  // [(parts + 1) x (B + 1)] bucket starts of every run
     int64_t mstart_cap = 0;
-    // key_width > 8 (fixed-width byte keys): the whole sampler is rsv_wide.hip's; every entry point
-    // below forwards to it
-    WideDistinct* wide = nullptr;
+
+    hipError_t init(int32_t k, int hash_kind, int64_t r0, int64_t r1, bool ordered);  // distinct_create's allocations
+    ~NarrowDistinct() override;
+    void set_timer(KernelTimer* t) override { timer = t; }
+    int sample_device(const void* keys, const int64_t* hashes, int64_t n, hipStream_t st) override;
+    int64_t size() const override { return m; }
+    int finalize(hipStream_t st) override;
+    const void* keys_dev() const override { return set_k; }
+    int publish(void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st) override;
+    void spec_target(void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter) override {
+        // the bucketed merge only: set mode behind ctl_publish, ordered mode behind the scheduled pass
+        if (log_bmax >= 0) spec.target(dst_host_dev, flag_dev, gen_counter);
+    }
+    int64_t spec_min() const override { return spec_min_batch; }
+    int export_set(void* keys_dev, int64_t* hash_dev, hipStream_t st) override;
+    int merge_parts(const void* keys_dev, const int64_t* hash_dev, const int64_t* part_n, int32_t parts,
+                    int64_t part_len, hipStream_t st) override;
+    void info(int32_t* ordered, int32_t* tied, int32_t* retained, int64_t* size, int64_t* max_hash,
+              int64_t* log_entries, int64_t* sched_passes, int64_t* sched_fallbacks) const override;
+    int log_export(int64_t bound, int64_t* out_h, void* out_k, int64_t cap, int64_t* out_n, hipStream_t st) override;
+    int log_merge(const int64_t* h, const void* keys, int64_t n, int64_t seen, hipStream_t st) override;
+    int export_row(int64_t* row, int64_t count, hipStream_t st) override;
+    int merge_rows(const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st) override;
+    int settle(hipStream_t st) override;
+
+    void drop_archive() override {  // (also when the archive outgrows kArchMax or a log merge replaces the history)
+        arch_ok = false;
+        std::vector<int64_t>().swap(arch_h);
+        std::vector<KeyT>().swap(arch_k);
+    }
 };
 
 // <= 2 GB of host archive (12-16 B per candidate): beyond it rsv_export_log reports the log as not
 // retained
 constexpr int64_t kArchMax = (int64_t)1 << 27;
-
-void distinct_set_timer(DistinctState* d, KernelTimer* t) {
-    d->timer = t;
-    if (d->wide) wide_set_timer(d->wide, t);
-}
 
 template <typename KeyT>
 static hipError_t temp_bytes_for(int64_t cap, size_t* bytes) {
@@ -1789,33 +1806,34 @@ static hipError_t temp_bytes_for(int64_t cap, size_t* bytes) {
     return hipSuccess;
 }
 
-static hipError_t ensure_caps(DistinctState* d, int64_t cand_need, int64_t merge_need, hipStream_t st) {
+template <typename KeyT>
+static hipError_t ensure_caps(NarrowDistinct<KeyT>* d, int64_t cand_need, int64_t merge_need, hipStream_t st) {
     const size_t kw = (size_t)d->kw;
     hipError_t e = hipSuccess;
     cand_need = std::min(cand_need, d->cand_limit);
     if (cand_need > d->cand_cap) {
         const int64_t c = grown_capacity(d->cand_cap, cand_need, d->cand_limit);
         if ((e = pool_device_grow((void**)&d->cand_h, 0, (size_t)c * 8, false, st))) return e;
-        if ((e = pool_device_grow(&d->cand_k, 0, (size_t)c * kw, false, st))) return e;
+        if ((e = pool_device_grow((void**)&d->cand_k, 0, (size_t)c * kw, false, st))) return e;
         d->cand_cap = c;
     }
     const int64_t set_need = std::min<int64_t>(merge_need, d->k);
     if (set_need > d->set_cap) {
         const int64_t c = grown_capacity(d->set_cap, set_need, d->k);
         if ((e = pool_device_grow((void**)&d->set_h, (size_t)d->m * 8, (size_t)c * 8, true, st))) return e;
-        if ((e = pool_device_grow(&d->set_k, (size_t)d->m * kw, (size_t)c * kw, true, st))) return e;
+        if ((e = pool_device_grow((void**)&d->set_k, (size_t)d->m * kw, (size_t)c * kw, true, st))) return e;
         d->set_cap = c;
     }
     if (merge_need > d->merge_cap) {
         const int64_t c = grown_capacity(d->merge_cap, merge_need, (int64_t)d->k + d->cand_limit);
         if ((e = pool_device_grow((void**)&d->mh0, 0, (size_t)c * 8, false, st))) return e;
         if ((e = pool_device_grow((void**)&d->mh1, 0, (size_t)c * 8, false, st))) return e;
-        if ((e = pool_device_grow(&d->mk0, 0, (size_t)c * kw, false, st))) return e;
-        if ((e = pool_device_grow(&d->mk1, 0, (size_t)c * kw, false, st))) return e;
+        if ((e = pool_device_grow((void**)&d->mk0, 0, (size_t)c * kw, false, st))) return e;
+        if ((e = pool_device_grow((void**)&d->mk1, 0, (size_t)c * kw, false, st))) return e;
         if ((e = pool_device_grow((void**)&d->flags, 0, (size_t)c * 4, false, st))) return e;
         if ((e = pool_device_grow((void**)&d->pos, 0, (size_t)c * 4, false, st))) return e;
         size_t tb = 0;
-        e = d->kw == 8 ? temp_bytes_for<int64_t>(c, &tb) : temp_bytes_for<int32_t>(c, &tb);
+        e = temp_bytes_for<KeyT>(c, &tb);
         if (e != hipSuccess) return e;
         if (tb > d->temp_bytes) {
             if ((e = pool_device_grow(&d->temp, 0, tb, false, st))) return e;
@@ -1826,26 +1844,13 @@ static hipError_t ensure_caps(DistinctState* d, int64_t cand_need, int64_t merge
     return hipSuccess;
 }
 
-DistinctState* distinct_create(int32_t k, int key_width, int hash_kind, int64_t r0, int64_t r1, bool ordered,
-                               int* status) {
-    DistinctState* d = new DistinctState();
+template <typename KeyT>
+hipError_t NarrowDistinct<KeyT>::init(int32_t k, int hash_kind, int64_t r0, int64_t r1, bool ordered) {
+    NarrowDistinct* const d = this;
+    const int key_width = kw;
     d->ordered = ordered;
-    if (key_width > 8) {  // fixed-width byte keys: rsv_wide.hip
-        d->k = k;
-        d->kw = key_width;
-        d->hash_kind = hash_kind;
-        // set mode's one-pass batches publish speculatively (rsv_wide.hip wide_spec_target)
-        d->wide = wide_create(k, key_width, hash_kind == kHashUuid ? kWideSrcUuid : kWideSrcHashes, r0, r1, ordered,
-                              status);
-        if (!d->wide) {
-            delete d;
-            return nullptr;
-        }
-        return d;
-    }
     if (ordered) d->rep.reset(k);
     d->k = k;
-    d->kw = key_width;
     d->hash_kind = hash_kind;
     d->r0 = r0;
     d->r1 = r1;
@@ -1859,7 +1864,7 @@ DistinctState* distinct_create(int32_t k, int key_width, int hash_kind, int64_t 
         d->first_min = std::max<int64_t>(1, std::atoll(v));
     if (const char* v = std::getenv("RSV_REPLAY_OVERLAP")) d->overlap = v[0] != '0';  // test hook
     if (const char* v = std::getenv("RSV_SPEC_MIN_BATCH"))  // test hook: speculative publication
-        d->spec_min = std::max<int64_t>(1, std::atoll(v));
+        d->spec_min_batch = std::max<int64_t>(1, std::atoll(v));
     hipError_t e = hipSuccess;
     auto A = [&](void** p, size_t bytes) {
         if (e == hipSuccess) e = pool_device_alloc(p, bytes ? bytes : 16);
@@ -1880,7 +1885,7 @@ DistinctState* distinct_create(int32_t k, int key_width, int hash_kind, int64_t 
     if (e == hipSuccess) ((uint32_t*)(d->hc + 8))[0] = 0;
     if (bucketed) {
         A((void**)&d->bh, ((size_t)1 << log_bmax) * kBucketCap * 8);
-        A(&d->bk, ((size_t)1 << log_bmax) * kBucketCap * key_width);
+        A((void**)&d->bk, ((size_t)1 << log_bmax) * kBucketCap * key_width);
         if (e == hipSuccess) d->log_bmax = log_bmax;
     }
     A((void**)&d->d_count, 32);
@@ -1898,23 +1903,33 @@ DistinctState* distinct_create(int32_t k, int key_width, int hash_kind, int64_t 
     const int64_t full_merge = (int64_t)k + d->cand_limit;
     const double eager_bytes = (double)full_merge * (2 * 8 + 2 * key_width + 8) + (double)d->cand_limit * (8 + key_width);
     if (e == hipSuccess && eager_bytes < 512.0 * 1024 * 1024) e = ensure_caps(d, d->cand_limit, full_merge, 0);
-    if (e != hipSuccess) {
-        set_error(std::string("distinct_create: ") + hipGetErrorString(e));
-        *status = e == hipErrorOutOfMemory ? RSV_E_OUT_OF_MEMORY : RSV_E_DEVICE;
-        distinct_destroy(d);
+    return e;
+}
+
+template <typename KeyT>
+static DistinctEngine* narrow_create(int32_t k, int hash_kind, int64_t r0, int64_t r1, bool ordered, int* status) {
+    NarrowDistinct<KeyT>* d = new NarrowDistinct<KeyT>();
+    if (hipError_t e = d->init(k, hash_kind, r0, r1, ordered)) {
+        *status = hip_status(e, "distinct_create");
+        delete d;
         return nullptr;
     }
     *status = RSV_OK;
     return d;
 }
 
-void distinct_destroy(DistinctState* d) {
-    if (!d) return;
-    if (d->wide) {
-        wide_destroy(d->wide);
-        delete d;
-        return;
-    }
+DistinctEngine* distinct_create(int32_t k, int key_width, int hash_kind, int64_t r0, int64_t r1, bool ordered,
+                                int* status) {
+    if (key_width > 8)  // fixed-width byte keys: rsv_wide.hip
+        return new_wide_distinct(k, key_width, hash_kind == kHashUuid ? kWideSrcUuid : kWideSrcHashes, r0, r1, ordered,
+                                 status);
+    return key_width == 8 ? narrow_create<int64_t>(k, hash_kind, r0, r1, ordered, status)
+                          : narrow_create<int32_t>(k, hash_kind, r0, r1, ordered, status);
+}
+
+template <typename KeyT>
+NarrowDistinct<KeyT>::~NarrowDistinct() {
+    NarrowDistinct* const d = this;
     void* ps[] = {d->set_h, d->set_k, d->cand_h, d->cand_k, d->ctl, d->bh, d->bk, d->mh0, d->mh1, d->mk0,
                   d->mk1, d->flags, d->pos, d->d_count, d->samp, d->temp, d->log_h, d->log_k, d->log_i,
                   d->perm, d->sorted_i, d->ord_h, d->ord_k, d->sdev, d->sctl, d->sbh, d->sbk, d->sbi, d->vacc,
@@ -1931,46 +1946,18 @@ void distinct_destroy(DistinctState* d) {
     if (d->seg_ev) (void)hipEventDestroy(d->seg_ev);
     pool_host_free(d->pmem);
     pool_host_free(d->shc);
-    delete d;
 }
 
-int64_t distinct_size(const DistinctState* d) { return d->wide ? wide_size(d->wide) : d->m; }
-const void* distinct_keys_dev(const DistinctState* d) { return d->wide ? wide_keys_dev(d->wide) : d->set_k; }
-
-void distinct_spec_target(DistinctState* d, void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter) {
-    // the bucketed merge only: set mode behind ctl_publish, ordered mode behind the scheduled pass
-    if (d->wide) {
-        wide_spec_target(d->wide, dst_host_dev, flag_dev, gen_counter);
-        return;
-    }
-    if (d->log_bmax < 0) return;
-    d->spec_dst = dst_host_dev;
-    d->spec_flag = flag_dev;
-    d->spec_gen_ctr = gen_counter;
-    d->spec_ok = false;
-}
-
-int64_t distinct_spec_min(const DistinctState* d) { return d->spec_min; }
-
-bool distinct_spec_take(DistinctState* d, uint32_t* gen) {
-    if (d->wide) return wide_spec_take(d->wide, gen);
-    const bool ok = d->spec_ok && d->spec_dst;
-    if (ok) *gen = d->spec_gen;
-    d->spec_dst = nullptr;
-    d->spec_arm = d->spec_ok = false;
-    return ok;
-}
-
-int distinct_publish(DistinctState* d, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st) {
-    if (d->wide) return wide_publish(d->wide, dst_host_dev, flag_dev, gen, st);
-    RSV_HIP_TRY(launch_publish_multi(d->set_k, d->m * d->kw, dst_host_dev, flag_dev, gen, (uint32_t*)(d->ctl + 4), st));
+template <typename KeyT>
+int NarrowDistinct<KeyT>::publish(void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st) {
+    RSV_HIP_TRY(launch_publish_multi(set_k, m * kw, dst_host_dev, flag_dev, gen, (uint32_t*)(ctl + 4), st));
     return RSV_OK;
 }
 
 template <typename KeyT>
-static hipError_t launch_filter(DistinctState* d, const KeyT* keys, const int64_t* hashes, int64_t n,
+static hipError_t launch_filter(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t* hashes, int64_t n,
                                 int64_t tinc, hipStream_t st) {
-    KeyT* ck = (KeyT*)d->cand_k;
+    KeyT* ck = d->cand_k;
     if (tinc == INT64_MAX && n <= d->cand_cap) {  // no bound: every element a candidate, in place
         const unsigned g = (unsigned)std::min<int64_t>(std::max<int64_t>(grid_1d(n), 1), 4096);
 #define RSV_HASH_ALL(H)                                                                                       \
@@ -2008,7 +1995,7 @@ static hipError_t launch_filter(DistinctState* d, const KeyT* keys, const int64_
 }
 
 template <typename KeyT>
-static hipError_t launch_sample(DistinctState* d, const KeyT* keys, const int64_t* hashes, int64_t n,
+static hipError_t launch_sample(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t* hashes, int64_t n,
                                 int64_t ns, hipStream_t st) {
     const unsigned grid = grid_1d(ns);
     switch (d->hash_kind) {
@@ -2043,23 +2030,24 @@ static unsigned span_bits(int64_t top) {
 
 // ctl[0..5] to the host: published by one wave into coherent memory and spun on (a stream
 // synchronize costs ~15-20 us more); falls back to a blocking synchronize after ~2 ms
-static hipError_t read_ctl(DistinctState* d, int64_t* out, hipStream_t st) {
+template <typename KeyT>
+static hipError_t read_ctl(NarrowDistinct<KeyT>* d, int64_t* out, hipStream_t st) {
     const uint32_t gen = ++d->hc_gen;
     uint32_t* flag = (uint32_t*)(d->hc + 8);
     hipLaunchKernelGGL(ctl_publish, dim3(1), dim3(64), 0, st, d->ctl, d->hc_dev,
                        (uint32_t*)(d->hc_dev + 8), gen);
     if (hipError_t e = hipGetLastError()) return e;
-    if (d->spec_arm) {  // behind ctl_publish (which re-arms ctl[0..1]; the kernel reads ctl[2])
-        d->spec_arm = false;
-        const uint32_t g = ++*d->spec_gen_ctr;
+    if (d->spec.arm) {  // behind ctl_publish (which re-arms ctl[0..1]; the kernel reads ctl[2])
+        d->spec.arm = false;
+        const uint32_t g = ++*d->spec.gen_ctr;
         const int64_t per = 32 * 1024;  // bytes per workgroup, as launch_publish_multi
         const unsigned grid =
             (unsigned)std::min<int64_t>(32, std::max<int64_t>(1, ((int64_t)d->k * d->kw + per - 1) / per));
         hipLaunchKernelGGL(publish_set_kernel, dim3(grid), dim3(1024), 0, st, (const uint32_t*)d->set_k,
-                           (uint32_t*)d->spec_dst, (const int64_t*)d->ctl, (int64_t)d->k, d->kw / 4, d->spec_flag,
+                           (uint32_t*)d->spec.dst, (const int64_t*)d->ctl, (int64_t)d->k, d->kw / 4, d->spec.flag,
                            g, (uint32_t*)(d->ctl + 4));
         if (hipError_t e = hipGetLastError()) return e;
-        d->spec_gen = g;
+        d->spec.gen = g;
     }
     const auto t0 = std::chrono::steady_clock::now();
     bool seen = false;
@@ -2082,11 +2070,11 @@ static hipError_t read_ctl(DistinctState* d, int64_t* out, hipStream_t st) {
 // the filter's candidates (count read on the device) + the current set -> new set, on the
 // bucketed path; results land in ctl[1..3] (overflow, distinct count, largest kept h)
 template <typename KeyT>
-static hipError_t launch_bucket_merge(DistinctState* d, int64_t tinc, hipStream_t st, const int64_t* cand_h = nullptr,
+static hipError_t launch_bucket_merge(NarrowDistinct<KeyT>* d, int64_t tinc, hipStream_t st, const int64_t* cand_h = nullptr,
                                       const KeyT* cand_k = nullptr, int64_t cand_cap = 0) {
     if (!cand_h) {  // the set-mode filter's buffer
         cand_h = d->cand_h;
-        cand_k = (const KeyT*)d->cand_k;
+        cand_k = d->cand_k;
         cand_cap = d->cand_cap;
     }
     const int64_t top = d->m ? std::max(tinc, d->set_top) : tinc;
@@ -2095,7 +2083,7 @@ static hipError_t launch_bucket_merge(DistinctState* d, int64_t tinc, hipStream_
     const unsigned waves = 1u << d->log_bmax;  // one per bucket
     const unsigned wgrid = (waves + kBlock / 64 - 1) / (kBlock / 64);
     const unsigned sgrid = (unsigned)std::min<int64_t>(std::max<int64_t>(grid_1d(d->m + cand_cap), 1), 1024);
-    KeyT* bk = (KeyT*)d->bk;
+    KeyT* bk = d->bk;
     hipLaunchKernelGGL(bucket_scatter<KeyT>, dim3(sgrid), dim3(kBlock), 0, st, d->set_h, (const KeyT*)d->set_k, d->m,
                        cand_h, cand_k, cand_cap, d->ctl, q, d->log_bmax, d->bh, bk);
     hipLaunchKernelGGL(bucket_sort<KeyT>, dim3(wgrid), dim3(kBlock), 0, st, d->m, cand_cap, d->ctl, d->log_bmax,
@@ -2109,7 +2097,7 @@ static hipError_t launch_bucket_merge(DistinctState* d, int64_t tinc, hipStream_
 // Merge `c` entries at (src_h, src_k) with the current set; new set = first k distinct by
 // (h, key).  Returns the distinct count of the union in *n_distinct.
 template <typename KeyT>
-static hipError_t merge_into_set(DistinctState* d, const int64_t* src_h, const KeyT* src_k, int64_t c,
+static hipError_t merge_into_set(NarrowDistinct<KeyT>* d, const int64_t* src_h, const KeyT* src_k, int64_t c,
                                  int64_t* n_distinct, hipStream_t st, int64_t h_max = INT64_MAX) {
     // every hash in the merge is <= h_max (the filter threshold; the set lies below it too): the
     // keys share their top bits, so the radix passes stop at the highest bit that varies
@@ -2125,8 +2113,8 @@ static hipError_t merge_into_set(DistinctState* d, const int64_t* src_h, const K
         return hipSuccess;
     }
     if (hipError_t e0 = ensure_caps(d, 0, total, st)) return e0;
-    KeyT* mk0 = (KeyT*)d->mk0;
-    KeyT* mk1 = (KeyT*)d->mk1;
+    KeyT* mk0 = d->mk0;
+    KeyT* mk1 = d->mk1;
     hipError_t e;
     if (d->m) {
         if ((e = hipMemcpyAsync(d->mh0, d->set_h, d->m * 8, hipMemcpyDeviceToDevice, st))) return e;
@@ -2143,8 +2131,8 @@ static hipError_t merge_into_set(DistinctState* d, const int64_t* src_h, const K
             return e;
         std::swap(d->mh0, d->mh1);
         std::swap(d->mk0, d->mk1);
-        mk0 = (KeyT*)d->mk0;
-        mk1 = (KeyT*)d->mk1;
+        mk0 = d->mk0;
+        mk1 = d->mk1;
     } else {
         // stable LSD order: by key, then by h  ->  sorted by (h, key)
         if ((e = rocprim::radix_sort_pairs(d->temp, tb, mk0, mk1, d->mh0, d->mh1, (size_t)total, 0,
@@ -2176,17 +2164,13 @@ static hipError_t merge_into_set(DistinctState* d, const int64_t* src_h, const K
 }
 
 template <typename KeyT>
-static int sample_impl(DistinctState* d, const KeyT* keys, const int64_t* hashes, int64_t n,
+static int sample_impl(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t* hashes, int64_t n,
                        hipStream_t st) {
-#define DTRY(x)                                                                      \
-    do {                                                                             \
-        hipError_t _e = (x);                                                         \
-        if (_e != hipSuccess) {                                                      \
-            set_error(std::string("distinct: " #x ": ") + hipGetErrorString(_e));    \
-            return _e == hipErrorOutOfMemory ? RSV_E_OUT_OF_MEMORY : RSV_E_DEVICE;   \
-        }                                                                            \
+#define DTRY(x)                                                          \
+    do {                                                                 \
+        if (hipError_t _e = (x)) return hip_status(_e, "distinct: " #x); \
     } while (0)
-    d->spec_ok = false;
+    d->spec.ok = false;
     if (n <= 0) return RSV_OK;
     const bool full = d->m == d->k;
     // Set mode keeps the bottom-k by (h, key): an element tied with the current maximum hash can
@@ -2241,8 +2225,8 @@ static int sample_impl(DistinctState* d, const KeyT* keys, const int64_t* hashes
         // large batches: publish the merged set speculatively (used if this pass is the last) --
         // armed only on a pass expected to be final: the analytic first pass, or one whose
         // threshold admits everything; a retry that tightens or widens publishes at result()
-        const bool spec = bucketed && d->spec_dst && n >= d->spec_min && (attempt == 0 || tinc >= t_allowed);
-        d->spec_arm = spec;
+        const bool spec = bucketed && d->spec.dst && n >= d->spec_min_batch && (attempt == 0 || tinc >= t_allowed);
+        d->spec.arm = spec;
         DTRY(read_ctl(d, d->h_pinned + 4, st));
         const int64_t c = d->h_pinned[4];
         if (c > d->cand_cap) {  // threshold too loose for the candidate buffer: tighten
@@ -2267,11 +2251,11 @@ static int sample_impl(DistinctState* d, const KeyT* keys, const int64_t* hashes
         } else {
             if (bucketed)  // bucket overflow: the scatter's counts were not consumed
                 DTRY(hipMemsetAsync(d->ctl + kCtlWords, 0, (size_t)kCountStride * 4 << d->log_bmax, st));
-            DTRY(merge_into_set<KeyT>(d, d->cand_h, (const KeyT*)d->cand_k, c, &nd, st, tinc));
+            DTRY(merge_into_set<KeyT>(d, d->cand_h, d->cand_k, c, &nd, st, tinc));
         }
         // exact once every batch element below the new k-th hash was a candidate
         if (tinc >= t_allowed || (d->m == d->k && d->max_h <= tinc)) {
-            d->spec_ok = spec && d->h_pinned[5] == 0;  // merged on the device: the publication holds it
+            d->spec.ok = spec && d->h_pinned[5] == 0;  // merged on the device: the publication holds it
             return RSV_OK;
         }
         // too tight: widen (the partial merge is harmless: bottom-k(bottom-k(S u C1) u C2) equals
@@ -2294,7 +2278,7 @@ static int sample_impl(DistinctState* d, const KeyT* keys, const int64_t* hashes
 }
 
 template <typename KeyT>
-static hipError_t launch_filter_idx(DistinctState* d, const KeyT* keys, const int64_t* hashes, int64_t n,
+static hipError_t launch_filter_idx(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t* hashes, int64_t n,
                                     int64_t tinc, int64_t* out_h, KeyT* out_k, uint32_t* out_i, int64_t cap,
                                     hipStream_t st) {
     if (tinc == INT64_MAX && n <= cap) {  // no bound (the heap filling): every element in place
@@ -2330,19 +2314,20 @@ static hipError_t launch_filter_idx(DistinctState* d, const KeyT* keys, const in
 
 // ordered-mode replay buffers: device permutation / sort output and pinned host copies of one
 // logged segment
-static hipError_t ensure_ordered(DistinctState* d, int64_t cap, hipStream_t st) {
+template <typename KeyT>
+static hipError_t ensure_ordered(NarrowDistinct<KeyT>* d, int64_t cap, hipStream_t st) {
     if (cap <= d->ord_cap) return hipSuccess;
     hipError_t e;
     if ((e = pool_device_grow((void**)&d->perm, 0, (size_t)cap * 4, false, st))) return e;
     if ((e = pool_device_grow((void**)&d->sorted_i, 0, (size_t)cap * 4, false, st))) return e;
     if ((e = pool_device_grow((void**)&d->ord_h, 0, (size_t)cap * 8, false, st))) return e;
-    if ((e = pool_device_grow(&d->ord_k, 0, (size_t)cap * d->kw, false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->ord_k, 0, (size_t)cap * d->kw, false, st))) return e;
     pool_host_free(d->ph);
     pool_host_free(d->pk);
     d->ph = nullptr;
     d->pk = nullptr;
     if ((e = pool_host_alloc((void**)&d->ph, (size_t)cap * 8, hipHostMallocDefault))) return e;
-    if ((e = pool_host_alloc(&d->pk, (size_t)cap * d->kw, hipHostMallocDefault))) return e;
+    if ((e = pool_host_alloc((void**)&d->pk, (size_t)cap * d->kw, hipHostMallocDefault))) return e;
     if ((e = pool_device_grow((void**)&d->fflag, 0, (size_t)cap, false, st))) return e;
     pool_host_free(d->pflag);
     d->pflag = nullptr;
@@ -2361,14 +2346,15 @@ static hipError_t ensure_ordered(DistinctState* d, int64_t cap, hipStream_t st) 
 
 // room for `need` log entries (kept contents).  The first allocation takes ~8 full chunks (at most
 // 256 MB): a growth copies the log and waits for the stream (~100 us each, measured).
-static hipError_t ensure_log(DistinctState* d, int64_t need, hipStream_t st) {
+template <typename KeyT>
+static hipError_t ensure_log(NarrowDistinct<KeyT>* d, int64_t need, hipStream_t st) {
     if (need <= d->log_cap) return hipSuccess;
     const int64_t first = std::min<int64_t>(8 * d->cand_limit, (256ll << 20) / (12 + d->kw));
     const int64_t want = std::max(need, std::min(d->log_limit, d->log_cap ? need : first));
     const int64_t c = grown_capacity(d->log_cap, want, std::max(want, d->log_limit));
     hipError_t e;
     if ((e = pool_device_grow((void**)&d->log_h, (size_t)d->log_n * 8, (size_t)c * 8, true, st))) return e;
-    if ((e = pool_device_grow(&d->log_k, (size_t)d->log_n * d->kw, (size_t)c * d->kw, true, st))) return e;
+    if ((e = pool_device_grow((void**)&d->log_k, (size_t)d->log_n * d->kw, (size_t)c * d->kw, true, st))) return e;
     if ((e = pool_device_grow((void**)&d->log_i, (size_t)d->log_n * 4, (size_t)c * 4, true, st))) return e;
     d->log_cap = c;
     return hipSuccess;
@@ -2377,7 +2363,7 @@ static hipError_t ensure_log(DistinctState* d, int64_t need, hipStream_t st) {
 // The replica's set -> the device set arrays (ascending (h, key), as the SET mode keeps them), so
 // result / export / merge read the same place in both modes.
 template <typename KeyT>
-static hipError_t upload_replica(DistinctState* d, hipStream_t st) {
+static hipError_t upload_replica(NarrowDistinct<KeyT>* d, hipStream_t st) {
     // the heap's entries go up in heap order and are put in ascending (h, key) order on the device by
     // two stable radix sorts, key then h (a host std::sort of k = 65536 entries took ~3 ms)
     const int64_t m = d->rep.size();
@@ -2391,11 +2377,11 @@ static hipError_t upload_replica(DistinctState* d, hipStream_t st) {
     if ((e = hipMemcpyAsync(d->mh0, d->rep.hh.data() + 1, (size_t)m * 8, hipMemcpyHostToDevice, st))) return e;
     if ((e = hipMemcpyAsync(d->mk0, kk.data(), (size_t)m * sizeof(KeyT), hipMemcpyHostToDevice, st))) return e;
     size_t tb = d->temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(d->temp, tb, (KeyT*)d->mk0, (KeyT*)d->mk1, d->mh0, d->mh1, (size_t)m, 0,
+    if ((e = rocprim::radix_sort_pairs(d->temp, tb, d->mk0, d->mk1, d->mh0, d->mh1, (size_t)m, 0,
                                        8 * (unsigned)sizeof(KeyT), st)))
         return e;
     tb = d->temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(d->temp, tb, d->mh1, d->set_h, (KeyT*)d->mk1, (KeyT*)d->set_k, (size_t)m, 0,
+    if ((e = rocprim::radix_sort_pairs(d->temp, tb, d->mh1, d->set_h, d->mk1, d->set_k, (size_t)m, 0,
                                        64, st)))
         return e;
     if ((e = hipStreamSynchronize(st))) return e;  // kk goes out of scope
@@ -2407,19 +2393,19 @@ static hipError_t upload_replica(DistinctState* d, hipStream_t st) {
 
 // the first-occurrence sort's buffers for `total` entries (members + one segment)
 template <typename KeyT>
-static hipError_t ensure_first(DistinctState* d, int64_t nm, int64_t total, hipStream_t st) {
+static hipError_t ensure_first(NarrowDistinct<KeyT>* d, int64_t nm, int64_t total, hipStream_t st) {
     hipError_t e;
     if (nm > d->pmem_cap) {
         const int64_t c = std::min<int64_t>(d->k, std::max<int64_t>(nm, 2 * d->pmem_cap));
         pool_host_free(d->pmem);
         d->pmem = nullptr;
         d->pmem_cap = 0;
-        if ((e = pool_host_alloc(&d->pmem, (size_t)c * sizeof(KeyT), hipHostMallocDefault))) return e;
+        if ((e = pool_host_alloc((void**)&d->pmem, (size_t)c * sizeof(KeyT), hipHostMallocDefault))) return e;
         d->pmem_cap = c;
     }
     if (total <= d->fcap) return hipSuccess;
-    if ((e = pool_device_grow(&d->fk_in, 0, (size_t)total * sizeof(KeyT), false, st))) return e;
-    if ((e = pool_device_grow(&d->fk_out, 0, (size_t)total * sizeof(KeyT), false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->fk_in, 0, (size_t)total * sizeof(KeyT), false, st))) return e;
+    if ((e = pool_device_grow((void**)&d->fk_out, 0, (size_t)total * sizeof(KeyT), false, st))) return e;
     if ((e = pool_device_grow((void**)&d->fv, 0, (size_t)total * 4, false, st))) return e;
     size_t tb = 0;
     if ((e = rocprim::radix_sort_pairs(nullptr, tb, (KeyT*)nullptr, (KeyT*)nullptr,
@@ -2438,7 +2424,7 @@ static hipError_t ensure_first(DistinctState* d, int64_t nm, int64_t total, hipS
 // the host reads the segment sequentially (two random reads per element from a ~20 MB log cost
 // more than the replica's heap).  With `first`, also its first-occurrence flags into d->pflag.
 template <typename KeyT>
-static hipError_t segment_to_host(DistinctState* d, const DistinctState::Seg& g, hipStream_t st, bool first,
+static hipError_t segment_to_host(NarrowDistinct<KeyT>* d, const LogSeg& g, hipStream_t st, bool first,
                                   bool sync = true) {
     hipError_t e;
     if ((e = ensure_ordered(d, g.c, st))) return e;
@@ -2455,13 +2441,13 @@ static hipError_t segment_to_host(DistinctState* d, const DistinctState::Seg& g,
     if (first) {
         const int64_t nm = d->rep.size(), total = nm + g.c;
         if ((e = ensure_first<KeyT>(d, nm, total, st))) return e;
-        KeyT* pm = (KeyT*)d->pmem;
+        KeyT* pm = d->pmem;
         for (int64_t i = 0; i < nm; ++i) pm[i] = (KeyT)d->rep.he[(size_t)i + 1];
         if (nm && (e = hipMemcpyAsync(d->fk_in, pm, (size_t)nm * sizeof(KeyT), hipMemcpyHostToDevice, st))) return e;
-        if ((e = hipMemcpyAsync((KeyT*)d->fk_in + nm, d->ord_k, (size_t)g.c * sizeof(KeyT), hipMemcpyDeviceToDevice, st)))
+        if ((e = hipMemcpyAsync(d->fk_in + nm, d->ord_k, (size_t)g.c * sizeof(KeyT), hipMemcpyDeviceToDevice, st)))
             return e;
         size_t fb = d->temp_bytes;
-        if ((e = rocprim::radix_sort_pairs(d->temp, fb, (KeyT*)d->fk_in, (KeyT*)d->fk_out,
+        if ((e = rocprim::radix_sort_pairs(d->temp, fb, d->fk_in, d->fk_out,
                                            rocprim::counting_iterator<uint32_t>(0), d->fv, (size_t)total, 0,
                                            8 * (unsigned)sizeof(KeyT), st)))
             return e;
@@ -2479,17 +2465,10 @@ static hipError_t segment_to_host(DistinctState* d, const DistinctState::Seg& g,
     return hipEventRecord(d->seg_ev, st);
 }
 
-static void archive_drop(DistinctState* d) {
-    d->arch_ok = false;
-    std::vector<int64_t>().swap(d->arch_h);
-    std::vector<int64_t>().swap(d->arch_k);
-    std::vector<int32_t>().swap(d->arch_k4);
-}
-
 // The replica from the set arrays, in (h, key) order, after a merge replaced the set (a merged set
 // has no single arrival order; rsv_merge_log is the exact form).
 template <typename KeyT>
-static hipError_t rebuild_replica(DistinctState* d, hipStream_t st) {
+static hipError_t rebuild_replica(NarrowDistinct<KeyT>* d, hipStream_t st) {
     std::vector<int64_t> hh((size_t)d->m);
     std::vector<KeyT> kk((size_t)d->m);
     hipError_t e = hipSuccess;
@@ -2514,15 +2493,15 @@ static hipError_t rebuild_replica(DistinctState* d, hipStream_t st) {
 // would be.  gs's keys are still in ord_k (put there in arrival order for gs's own copies).  Enqueued
 // only: the caller synchronizes the stream before it reads the copies.
 template <typename KeyT>
-static hipError_t segment_stage_next(DistinctState* d, const DistinctState::Seg& gs, const DistinctState::Seg& gn,
-                                     int64_t* dph, void* dpk, uint8_t* dpflag, hipStream_t st) {
+static hipError_t segment_stage_next(NarrowDistinct<KeyT>* d, const LogSeg& gs, const LogSeg& gn,
+                                     int64_t* dph, KeyT* dpk, uint8_t* dpflag, hipStream_t st) {
     hipError_t e;
     const int64_t nm = d->rep.size();  // the members at gs's start (gs has not been replayed yet)
     const int64_t total = nm + gs.c + gn.c;
-    KeyT* pm = (KeyT*)d->pmem;  // free: the stream was synchronized since its last upload
+    KeyT* pm = d->pmem;  // free: the stream was synchronized since its last upload
     for (int64_t i = 0; i < nm; ++i) pm[i] = (KeyT)d->rep.he[(size_t)i + 1];
     if (nm && (e = hipMemcpyAsync(d->fk_in, pm, (size_t)nm * sizeof(KeyT), hipMemcpyHostToDevice, st))) return e;
-    if ((e = hipMemcpyAsync((KeyT*)d->fk_in + nm, d->ord_k, (size_t)gs.c * sizeof(KeyT), hipMemcpyDeviceToDevice, st)))
+    if ((e = hipMemcpyAsync(d->fk_in + nm, d->ord_k, (size_t)gs.c * sizeof(KeyT), hipMemcpyDeviceToDevice, st)))
         return e;
     unsigned bits = 1;
     while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)gn.m) ++bits;
@@ -2534,11 +2513,11 @@ static hipError_t segment_stage_next(DistinctState* d, const DistinctState::Seg&
                        dim3(kBlock), 0, st, d->perm, d->log_h + gn.off, (const KeyT*)d->log_k + gn.off, gn.c, d->ord_h,
                        (KeyT*)d->ord_k);
     if ((e = hipGetLastError())) return e;
-    if ((e = hipMemcpyAsync((KeyT*)d->fk_in + nm + gs.c, d->ord_k, (size_t)gn.c * sizeof(KeyT), hipMemcpyDeviceToDevice,
+    if ((e = hipMemcpyAsync(d->fk_in + nm + gs.c, d->ord_k, (size_t)gn.c * sizeof(KeyT), hipMemcpyDeviceToDevice,
                             st)))
         return e;
     size_t fb = d->temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(d->temp, fb, (KeyT*)d->fk_in, (KeyT*)d->fk_out,
+    if ((e = rocprim::radix_sort_pairs(d->temp, fb, d->fk_in, d->fk_out,
                                        rocprim::counting_iterator<uint32_t>(0), d->fv, (size_t)total, 0,
                                        8 * (unsigned)sizeof(KeyT), st)))
         return e;
@@ -2552,7 +2531,8 @@ static hipError_t segment_stage_next(DistinctState* d, const DistinctState::Seg&
 }
 
 // the alternate pinned copies for segments of up to `cap` candidates
-static hipError_t ensure_ordered2(DistinctState* d, int64_t cap) {
+template <typename KeyT>
+static hipError_t ensure_ordered2(NarrowDistinct<KeyT>* d, int64_t cap) {
     if (cap <= d->ord2_cap) return hipSuccess;
     hipError_t e;
     pool_host_free(d->ph2);
@@ -2564,7 +2544,7 @@ static hipError_t ensure_ordered2(DistinctState* d, int64_t cap) {
     d->pflag2 = nullptr;
     d->ord2_cap = 0;
     if ((e = pool_host_alloc((void**)&d->ph2, (size_t)cap * 8, hipHostMallocDefault))) return e;
-    if ((e = pool_host_alloc(&d->pk2, (size_t)cap * d->kw, hipHostMallocDefault))) return e;
+    if ((e = pool_host_alloc((void**)&d->pk2, (size_t)cap * d->kw, hipHostMallocDefault))) return e;
     if ((e = pool_host_alloc((void**)&d->pflag2, (size_t)cap, hipHostMallocDefault))) return e;
     d->ord2_cap = cap;
     return hipSuccess;
@@ -2577,7 +2557,7 @@ static hipError_t ensure_ordered2(DistinctState* d, int64_t cap) {
 // the host replays the current one (segment_stage_next; C4's hash-twin share: the second segment's
 // 0.76 ms to the host hidden under the first one's 2.4 ms heap run).
 template <typename KeyT>
-static hipError_t replay_log(DistinctState* d, hipStream_t st) {
+static hipError_t replay_log(NarrowDistinct<KeyT>* d, hipStream_t st) {
     hipError_t e;
     if (d->rep_stale && (e = rebuild_replica<KeyT>(d, st))) return e;
     // (the flags' sort holds the members too: ~20 B per entry on the device, so a huge replica
@@ -2604,7 +2584,7 @@ static hipError_t replay_log(DistinctState* d, hipStream_t st) {
     bool staged = false;  // segment s's copies (and flags) were staged behind the previous run
     int cur = 0;          // the set segment s's copies are in
     for (size_t s = 0; s < ns; ++s) {
-        const DistinctState::Seg& g = d->segs[s];
+        const LogSeg& g = d->segs[s];
         if (g.c == 0) {
             staged = false;
             continue;
@@ -2617,7 +2597,7 @@ static hipError_t replay_log(DistinctState* d, hipStream_t st) {
             cur ^= 1;
         }
         // the next segment is staged behind this one when both replay through the flags
-        const DistinctState::Seg* gn = s + 1 < ns ? &d->segs[s + 1] : nullptr;
+        const LogSeg* gn = s + 1 < ns ? &d->segs[s + 1] : nullptr;
         const int64_t nm = d->rep.size();
         const bool stage_next = d->overlap && d->ph2 && gn && gn->c > 0 && first_ok(gn->c, g.c) &&
                                 nm + g.c + gn->c <= d->fcap && gn->c <= d->ord2_cap && gn->c <= d->ord_cap &&
@@ -2636,16 +2616,15 @@ static hipError_t replay_log(DistinctState* d, hipStream_t st) {
             if (!was_staged && (e = hipEventSynchronize(d->seg_ev))) return e;
         }
         const auto t1 = std::chrono::steady_clock::now();
-        const KeyT* pk = (const KeyT*)set_k(cur);
+        const KeyT* pk = set_k(cur);
         const int64_t* ph = set_h(cur);
         const uint8_t* pflag = set_f(cur);
         if (d->retain && d->arch_ok) {
             if ((int64_t)d->arch_h.size() + g.c > kArchMax) {
-                archive_drop(d);
+                d->drop_archive();
             } else {
                 d->arch_h.insert(d->arch_h.end(), ph, ph + g.c);
-                if constexpr (sizeof(KeyT) == 8) d->arch_k.insert(d->arch_k.end(), pk, pk + g.c);
-                else d->arch_k4.insert(d->arch_k4.end(), pk, pk + g.c);
+                d->arch_k.insert(d->arch_k.end(), pk, pk + g.c);
             }
         }
         if (first)
@@ -2672,7 +2651,7 @@ static hipError_t replay_log(DistinctState* d, hipStream_t st) {
 
 // the scheduled pass's buffers for merges of up to `entries` (set + candidates); allocated on first use
 template <typename KeyT>
-static hipError_t sched_ensure(DistinctState* d, int32_t lb, hipStream_t st, bool defer_zero = false) {
+static hipError_t sched_ensure(NarrowDistinct<KeyT>* d, int32_t lb, hipStream_t st, bool defer_zero = false) {
     hipError_t e = hipSuccess;
     if (!d->sdev) {
         if ((e = pool_device_alloc((void**)&d->sdev, sizeof(SchedDev)))) return e;
@@ -2682,12 +2661,12 @@ static hipError_t sched_ensure(DistinctState* d, int32_t lb, hipStream_t st, boo
         if ((e = pool_device_alloc((void**)&d->vacc, (size_t)kVerifyCopies * (kMaxRanges + 1) * 4))) return e;
         d->sdirty = true;  // re-armed by sched_publish after every pass
         if ((e = pool_device_alloc((void**)&d->bak_h, (size_t)d->k * 8))) return e;
-        if ((e = pool_device_alloc(&d->bak_k, (size_t)d->k * d->kw))) return e;
+        if ((e = pool_device_alloc((void**)&d->bak_k, (size_t)d->k * d->kw))) return e;
     }
     if (lb > d->log_bmax_s) {
         // the old area may still be read by queued work: wait before it goes back to the pool
         if (d->sctl && (e = hipStreamSynchronize(st))) return e;
-        for (void* p : {(void*)d->sctl, (void*)d->sbh, d->sbk, (void*)d->sbi}) pool_device_free(p);
+        for (void* p : {(void*)d->sctl, (void*)d->sbh, (void*)d->sbk, (void*)d->sbi}) pool_device_free(p);
         d->sctl = nullptr;
         d->sbh = nullptr;
         d->sbk = nullptr;
@@ -2699,7 +2678,7 @@ static hipError_t sched_ensure(DistinctState* d, int32_t lb, hipStream_t st, boo
         if ((e = pool_device_alloc((void**)&d->sctl, ctl_bytes))) return e;
         d->sdirty = true;  // counts, counter: re-armed after each pass
         if ((e = pool_device_alloc((void**)&d->sbh, B * kBucketCap * 8))) return e;
-        if ((e = pool_device_alloc(&d->sbk, B * kBucketCap * sizeof(KeyT)))) return e;
+        if ((e = pool_device_alloc((void**)&d->sbk, B * kBucketCap * sizeof(KeyT)))) return e;
         if ((e = pool_device_alloc((void**)&d->sbi, B * kBucketCap * 4))) return e;
         d->log_bmax_s = lb;
     }
@@ -2727,7 +2706,8 @@ static bool sched_sizes(int64_t k, double c_pred, int64_t* cap, int32_t* lb) {
 
 // a pass over n keys at the heap's first fill: its expected candidates (sched_plan_ranges' c_pred
 // with D0 = k and distinct elements arriving at >= 3/4 of the positions)
-static double sched_estimate(const DistinctState* d, int64_t n) {
+template <typename KeyT>
+static double sched_estimate(const NarrowDistinct<KeyT>* d, int64_t n) {
     const double k = (double)d->k;
     return d->sched_beta * k / 0.75 * std::log1p(0.75 * (double)n / k);
 }
@@ -2736,36 +2716,32 @@ static double sched_estimate(const DistinctState* d, int64_t n) {
 // first chunk so that the pass itself starts without a host round trip for them; a pass that needs
 // more reallocates in sched_ensure.
 template <typename KeyT>
-static hipError_t sched_prepare(DistinctState* d, int64_t n, hipStream_t st, bool defer_zero) {
+static hipError_t sched_prepare(NarrowDistinct<KeyT>* d, int64_t n, hipStream_t st, bool defer_zero) {
     int64_t cap;
     int32_t lb;
     if (!sched_sizes(d->k, sched_estimate(d, n), &cap, &lb)) return hipSuccess;
     return sched_ensure<KeyT>(d, lb, st, defer_zero);
 }
 
-#define STRY(x)                                                                                        \
-    do {                                                                                               \
-        hipError_t _e = (x);                                                                           \
-        if (_e != hipSuccess) {                                                                        \
-            set_error(std::string("distinct (scheduled pass): " #x ": ") + hipGetErrorString(_e));    \
-            return _e == hipErrorOutOfMemory ? RSV_E_OUT_OF_MEMORY : RSV_E_DEVICE;                     \
-        }                                                                                              \
+#define STRY(x)                                                                           \
+    do {                                                                                  \
+        if (hipError_t _e = (x)) return hip_status(_e, "distinct (scheduled pass): " #x); \
     } while (0)
 
 // The pass's kernels over keys[0, n), the plan already in d->sdev (or being written there by a
 // kernel ahead of them): candidates into the log from lbase (+ the plan's `off`), the set's
 // backup, the bucket merge, the verdict to d->shc; then the speculative publication of the set.
 template <typename KeyT>
-static int sched_launch(DistinctState* d, const KeyT* keys, const int64_t* hashes, int64_t n, int64_t lbase,
+static int sched_launch(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t* hashes, int64_t n, int64_t lbase,
                         int64_t cap, uint32_t B, int32_t lb, hipStream_t st, uint32_t* gen, bool* spec,
                         bool zero = false) {
     const int64_t k = d->k;
     const size_t kw = sizeof(KeyT);
-    KeyT* bk = (KeyT*)d->sbk;
+    KeyT* bk = d->sbk;
     if (d->timer) d->timer->mark(st);
     {
         const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(grid_1d(n / 32 + 1), 1), kK3Grid);
-        KeyT* lk = (KeyT*)d->log_k + lbase;
+        KeyT* lk = d->log_k + lbase;
 #define RSV_SCHED_FILTER(H)                                                                                        \
     hipLaunchKernelGGL((sched_filter<KeyT, H>), dim3(grid), dim3(kBlock), 0, st, keys, hashes, n, d->r0, d->r1,      \
                        (const SchedDev*)d->sdev, d->log_h + lbase, lk, d->log_i + lbase, d->sctl, cap, d->log_bmax_s,     \
@@ -2797,22 +2773,23 @@ static int sched_launch(DistinctState* d, const KeyT* keys, const int64_t* hashe
     *gen = ++d->sgen;
     // the merged set published speculatively with the verdict (size from sctl[2] on the device):
     // result() takes it if the pass verified and left no tie for the replica to settle
-    *spec = d->spec_dst && n >= d->spec_min;
+    *spec = d->spec.dst && n >= d->spec_min_batch;
     const int64_t per = 32 * 1024;  // bytes per workgroup, as launch_publish_multi
     const unsigned pgrid =
         *spec ? (unsigned)std::min<int64_t>(32, std::max<int64_t>(1, (k * (int64_t)kw + per - 1) / per)) : 1u;
-    const uint32_t g = *spec ? ++*d->spec_gen_ctr : 0u;
+    const uint32_t g = *spec ? ++*d->spec.gen_ctr : 0u;
     hipLaunchKernelGGL(sched_publish, dim3(pgrid), dim3(1024), 0, st, d->sctl, d->vacc, (const SchedDev*)d->sdev, k,
                        d->shc_dev, (uint32_t*)(d->shc_dev + 12), *gen, (const uint32_t*)d->set_k,
-                       *spec ? (uint32_t*)d->spec_dst : nullptr, (int32_t)(kw / 4), d->spec_flag, g,
+                       *spec ? (uint32_t*)d->spec.dst : nullptr, (int32_t)(kw / 4), d->spec.flag, g,
                        (uint32_t*)(d->ctl + 4));
     STRY(hipGetLastError());
-    if (*spec) d->spec_gen = g;
+    if (*spec) d->spec.gen = g;
     return RSV_OK;
 }
 
 // the host side of a pass's verdict: spin on the flag (a stream synchronize after 50 ms)
-static int sched_wait(DistinctState* d, uint32_t gen, hipStream_t st, int64_t* hv) {
+template <typename KeyT>
+static int sched_wait(NarrowDistinct<KeyT>* d, uint32_t gen, hipStream_t st, int64_t* hv) {
     uint32_t* flag = (uint32_t*)(d->shc + 12);
     const auto t0w = std::chrono::steady_clock::now();
     bool seen = false;
@@ -2835,7 +2812,7 @@ static int sched_wait(DistinctState* d, uint32_t gen, hipStream_t st, int64_t* h
 // The verdict of a pass over n elements from bound t0 whose log starts at log_n: the host fields,
 // or (false *done) the batch left to the chunk loop with the set restored
 template <typename KeyT>
-static int sched_finish(DistinctState* d, const int64_t* hv, int64_t n, int64_t t0, int64_t cap, uint32_t B,
+static int sched_finish(NarrowDistinct<KeyT>* d, const int64_t* hv, int64_t n, int64_t t0, int64_t cap, uint32_t B,
                         bool spec, hipStream_t st, bool* done) {
     *done = false;
     const int64_t k = d->k;
@@ -2866,10 +2843,10 @@ static int sched_finish(DistinctState* d, const int64_t* hv, int64_t n, int64_t 
     d->rate_c = c;
     d->rate_m = n;
     d->rate_span = (double)((uint64_t)t0 - (uint64_t)INT64_MIN) + 1.0;
-    d->segs.push_back(DistinctState::Seg{d->log_n, c, n});
+    d->segs.push_back(LogSeg{d->log_n, c, n});
     d->log_n += c;
     d->seen += n;
-    d->spec_ok = spec && d->m == k && !d->over;  // verified, and no replay will change the set
+    d->spec.ok = spec && d->m == k && !d->over;  // verified, and no replay will change the set
     *done = true;
     return RSV_OK;
 }
@@ -2881,7 +2858,7 @@ static int sched_finish(DistinctState* d, const int64_t* hv, int64_t n, int64_t 
 // (beta = 1.6: a stream whose new-distinct rate falls to ~60% of its history's still verifies).
 // Ranges grow geometrically (<= kMaxRanges).  *done = false: nothing changed, run the chunk loop.
 template <typename KeyT>
-static int sched_sample(DistinctState* d, const KeyT* keys, const int64_t* hashes, int64_t n, hipStream_t st,
+static int sched_sample(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t* hashes, int64_t n, hipStream_t st,
                         bool* done) {
     *done = false;
     const int64_t k = d->k;
@@ -2918,11 +2895,11 @@ static int sched_sample(DistinctState* d, const KeyT* keys, const int64_t* hashe
 // (its log right behind the chunk's candidates); waits once, for the pass's verdict; leaves the
 // chunk's control words in hp.  *pass: the plan was valid (the pass ran; its verdict in hv).
 template <typename KeyT>
-static int fused_fill_and_pass(DistinctState* d, const KeyT* keys, const int64_t* hashes, int64_t m, int64_t n,
+static int fused_fill_and_pass(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t* hashes, int64_t m, int64_t n,
                                int64_t ccap, int64_t cap, int32_t lb, hipStream_t st, int64_t* hp, int64_t* hv,
                                bool* pass, bool* spec) {
     int64_t* lh = d->log_h + d->log_n;
-    KeyT* lk = (KeyT*)d->log_k + d->log_n;
+    KeyT* lk = d->log_k + d->log_n;
     if (d->timer) d->timer->mark(st);
     STRY(launch_filter_idx<KeyT>(d, keys, hashes, m, INT64_MAX, lh, lk, d->log_i + d->log_n, ccap, st));
     if (d->timer) d->timer->mark(st);
@@ -2959,18 +2936,14 @@ static int fused_fill_and_pass(DistinctState* d, const KeyT* keys, const int64_t
 // the bucketed merge reports whether rank k ties rank k - 1 on h.  Only when more than k admitted
 // elements have hash <= M (`over`, sticky while M stays) does the set depend on the heap's history;
 // then the logged candidates of every chunk since the last replay go through the host replica in
-// arrival order and the replica's set replaces the device set (`distinct_finalize`, at result /
+// arrival order and the replica's set replaces the device set (`finalize`, at result /
 // export / merge).  The log is replayed eagerly when it would outgrow log_limit.
 template <typename KeyT>
-static int ordered_sample_impl(DistinctState* d, const KeyT* keys, const int64_t* hashes, int64_t n,
+static int ordered_sample_impl(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t* hashes, int64_t n,
                                hipStream_t st) {
-#define OTRY(x)                                                                               \
-    do {                                                                                      \
-        hipError_t _e = (x);                                                                  \
-        if (_e != hipSuccess) {                                                               \
-            set_error(std::string("distinct (ordered): " #x ": ") + hipGetErrorString(_e));   \
-            return _e == hipErrorOutOfMemory ? RSV_E_OUT_OF_MEMORY : RSV_E_DEVICE;            \
-        }                                                                                     \
+#define OTRY(x)                                                                    \
+    do {                                                                           \
+        if (hipError_t _e = (x)) return hip_status(_e, "distinct (ordered): " #x); \
     } while (0)
     if (n <= 0) return RSV_OK;
     const int64_t k = d->k;
@@ -3024,7 +2997,7 @@ static int ordered_sample_impl(DistinctState* d, const KeyT* keys, const int64_t
         if (d->log_n + ccap > d->log_limit && !d->segs.empty()) OTRY(replay_log<KeyT>(d, st));
         OTRY(ensure_log(d, d->log_n + ccap, st));
         int64_t* lh = d->log_h + d->log_n;
-        KeyT* lk = (KeyT*)d->log_k + d->log_n;
+        KeyT* lk = d->log_k + d->log_n;
         const bool bucketed = d->log_bmax >= 0 && d->set_cap >= k;
         int64_t* hp = d->h_pinned + 4;
         // the chunk that may fill the heap, with the pass over the rest planned on the device behind
@@ -3076,7 +3049,7 @@ static int ordered_sample_impl(DistinctState* d, const KeyT* keys, const int64_t
             d->rate_m = m;
             d->rate_span = (double)((uint64_t)tinc - (uint64_t)INT64_MIN) + 1.0;
         }
-        d->segs.push_back(DistinctState::Seg{d->log_n, c, m});
+        d->segs.push_back(LogSeg{d->log_n, c, m});
         d->log_n += c;
         pos += m;
         d->seen += m;
@@ -3095,76 +3068,67 @@ static int ordered_sample_impl(DistinctState* d, const KeyT* keys, const int64_t
 #undef OTRY
 }
 
-int distinct_sample_device(DistinctState* d, const void* keys, const int64_t* hashes, int64_t n,
-                           hipStream_t st) {
-    if (d->wide) return wide_sample_device(d->wide, keys, hashes, n, st);
-    if (int rc = distinct_settle(d, st)) return rc;
-    if (d->merged && n > 0) {  // sampling on after a merge: the pre-merge candidates are history
-        d->merged = false;
-        d->pre_segs.clear();
-        if (d->segs.empty()) d->log_n = 0;
-        archive_drop(d);
+template <typename KeyT>
+int NarrowDistinct<KeyT>::sample_device(const void* keys, const int64_t* hashes, int64_t n, hipStream_t st) {
+    if (int rc = settle(st)) return rc;
+    if (merged && n > 0) {  // sampling on after a merge: the pre-merge candidates are history
+        merged = false;
+        pre_segs.clear();
+        if (segs.empty()) log_n = 0;
+        drop_archive();
     }
-    if (d->ordered)
-        return d->kw == 8 ? ordered_sample_impl<int64_t>(d, (const int64_t*)keys, hashes, n, st)
-                          : ordered_sample_impl<int32_t>(d, (const int32_t*)keys, hashes, n, st);
-    return d->kw == 8 ? sample_impl<int64_t>(d, (const int64_t*)keys, hashes, n, st)
-                      : sample_impl<int32_t>(d, (const int32_t*)keys, hashes, n, st);
+    return ordered ? ordered_sample_impl<KeyT>(this, (const KeyT*)keys, hashes, n, st)
+                   : sample_impl<KeyT>(this, (const KeyT*)keys, hashes, n, st);
 }
 
-int distinct_finalize(DistinctState* d, hipStream_t st) {
-    if (d->wide) return wide_finalize(d->wide, st);
-    if (int rc = distinct_settle(d, st)) return rc;
-    if (!d->ordered || d->exact) return RSV_OK;
+template <typename KeyT>
+int NarrowDistinct<KeyT>::finalize(hipStream_t st) {
+    if (int rc = settle(st)) return rc;
+    if (!ordered || exact) return RSV_OK;
     const auto t0 = std::chrono::steady_clock::now();
-    hipError_t e = d->kw == 8 ? replay_log<int64_t>(d, st) : replay_log<int32_t>(d, st);
+    hipError_t e = replay_log<KeyT>(this, st);
     const auto t1 = std::chrono::steady_clock::now();
-    if (e == hipSuccess) e = d->kw == 8 ? upload_replica<int64_t>(d, st) : upload_replica<int32_t>(d, st);
+    if (e == hipSuccess) e = upload_replica<KeyT>(this, st);
     static const bool debug = std::getenv("RSV_REPLAY_DEBUG") != nullptr;
     if (debug)
         std::fprintf(stderr, "[rsv replay] finalize: replay_us=%.1f upload_us=%.1f\n",
                      std::chrono::duration<double, std::micro>(t1 - t0).count(),
                      std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count());
-    if (e != hipSuccess) {
-        set_error(std::string("distinct (ordered) replay: ") + hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? RSV_E_OUT_OF_MEMORY : RSV_E_DEVICE;
-    }
-    d->exact = true;
+    if (e != hipSuccess) return hip_status(e, "distinct (ordered) replay");
+    exact = true;
     return RSV_OK;
 }
 
-int distinct_export(DistinctState* d, void* keys_dev, int64_t* hash_dev, hipStream_t st) {
-    if (d->wide) return wide_export(d->wide, keys_dev, hash_dev, st);
-    if (d->m == 0) return RSV_OK;
-    if (keys_dev) RSV_HIP_TRY(hipMemcpyAsync(keys_dev, d->set_k, d->m * d->kw, hipMemcpyDeviceToDevice, st));
-    if (hash_dev) RSV_HIP_TRY(hipMemcpyAsync(hash_dev, d->set_h, d->m * 8, hipMemcpyDeviceToDevice, st));
+template <typename KeyT>
+int NarrowDistinct<KeyT>::export_set(void* keys_dev, int64_t* hash_dev, hipStream_t st) {
+    if (m == 0) return RSV_OK;
+    if (keys_dev) RSV_HIP_TRY(hipMemcpyAsync(keys_dev, set_k, m * kw, hipMemcpyDeviceToDevice, st));
+    if (hash_dev) RSV_HIP_TRY(hipMemcpyAsync(hash_dev, set_h, m * 8, hipMemcpyDeviceToDevice, st));
     return RSV_OK;
 }
 
-void distinct_info(const DistinctState* d, int32_t* ordered, int32_t* tied, int32_t* retained, int64_t* size,
-                   int64_t* max_hash, int64_t* log_entries, int64_t* sched_passes, int64_t* sched_fallbacks) {
-    if (d->wide) {
-        *sched_passes = *sched_fallbacks = 0;
-        wide_info(d->wide, ordered, tied, retained, size, max_hash, log_entries);
-        return;
-    }
-    *sched_passes = d->sched_passes;
-    *sched_fallbacks = d->sched_fallbacks;
-    *ordered = d->ordered;
-    *tied = d->m == d->k && d->over;
-    *retained = d->ordered && d->retain && d->arch_ok;
-    *size = d->m;
-    *max_hash = d->m ? d->set_top : INT64_MIN;
-    int64_t c = (int64_t)d->arch_h.size();
-    for (const DistinctState::Seg& g : d->pre_segs) c += g.c;
-    for (const DistinctState::Seg& g : d->segs) c += g.c;
-    *log_entries = d->ordered ? c : 0;
+template <typename KeyT>
+void NarrowDistinct<KeyT>::info(int32_t* o_ordered, int32_t* o_tied, int32_t* o_retained, int64_t* o_size,
+                                int64_t* o_max_hash, int64_t* o_log_entries, int64_t* o_sched_passes,
+                                int64_t* o_sched_fallbacks) const {
+    *o_sched_passes = sched_passes;
+    *o_sched_fallbacks = sched_fallbacks;
+    *o_ordered = ordered;
+    *o_tied = m == k && over;
+    *o_retained = retained();
+    *o_size = m;
+    *o_max_hash = m ? set_top : INT64_MIN;
+    int64_t c = (int64_t)arch_h.size();
+    for (const LogSeg& g : pre_segs) c += g.c;
+    for (const LogSeg& g : segs) c += g.c;
+    *o_log_entries = ordered ? c : 0;
 }
 
 // After a merge replaced the set: an ordered sampler's replica starts over from the union (rebuilt
 // lazily, rep_stale); the logged segments stay readable for rsv_export_log until the next sample.
-static void merged_bookkeeping(DistinctState* d) {
-    d->spec_ok = false;
+template <typename KeyT>
+static void merged_bookkeeping(NarrowDistinct<KeyT>* d) {
+    d->spec.ok = false;
     if (!d->ordered) return;
     d->rep_stale = true;
     d->pre_segs.insert(d->pre_segs.end(), d->segs.begin(), d->segs.end());
@@ -3179,29 +3143,29 @@ static void merged_bookkeeping(DistinctState* d) {
 // merges while the maximum stays).  An ordered sampler rebuilds its replica from the union in
 // (h, key) order (a merged set has no single arrival order; rsv_merge_log is the exact form) and
 // keeps its logged candidates for rsv_export_log until it samples again.
-int distinct_merge_parts(DistinctState* d, const void* keys_dev, const int64_t* hash_dev, const int64_t* part_n,
-                         int32_t parts, int64_t part_len, hipStream_t st) {
-    if (d->wide) return wide_merge_parts(d->wide, keys_dev, hash_dev, part_n, parts, part_len, st);
+template <typename KeyT>
+int NarrowDistinct<KeyT>::merge_parts(const void* keys_dev, const int64_t* hash_dev, const int64_t* part_n,
+                                      int32_t parts, int64_t part_len, hipStream_t st) {
+    NarrowDistinct* const d = this;
     int64_t total = 0;
     for (int32_t p = 0; p < parts; ++p) total += std::max<int64_t>(0, std::min(part_n[p], part_len));
-    if (int rc = distinct_settle(d, st)) return rc;
+    if (int rc = settle(st)) return rc;
     if (total == 0) return RSV_OK;
-    if (int rc = distinct_finalize(d, st)) return rc;
+    if (int rc = finalize(st)) return rc;
     bool tie = d->m == d->k && d->over;
     for (int32_t p = 0; p < parts; ++p) {
         const int64_t n = std::max<int64_t>(0, std::min(part_n[p], part_len));
-        const uint8_t* kp = (const uint8_t*)keys_dev + (size_t)p * part_len * d->kw;
+        const KeyT* kp = (const KeyT*)keys_dev + (size_t)p * part_len;
         const int64_t* hp = hash_dev + (size_t)p * part_len;
         for (int64_t off = 0; off < n;) {  // chunks that fit the merge buffer
             const int64_t c = std::min<int64_t>(n - off, d->cand_limit);
             const int64_t old_max = d->max_h;
             const bool was_full = d->m == d->k;
             int64_t nd = 0;
-            hipError_t e = d->kw == 8
-                               ? merge_into_set<int64_t>(d, hp + off, (const int64_t*)kp + off, c, &nd, st)
-                               : merge_into_set<int32_t>(d, hp + off, (const int32_t*)kp + off, c, &nd, st);
-            if (e != hipSuccess) {
-                set_error(std::string("distinct_merge: ") + hipGetErrorString(e));
+            if (hipError_t e = merge_into_set<KeyT>(d, hp + off, kp + off, c, &nd, st)) {
+                // (RSV_E_DEVICE here even for hipErrorOutOfMemory, unlike every other entry point:
+                // hip_status supplies the message only)
+                hip_status(e, "distinct_merge");
                 return RSV_E_DEVICE;
             }
             tie = d->m == d->k && (d->last_tie || (tie && was_full && d->max_h == old_max));
@@ -3215,20 +3179,17 @@ int distinct_merge_parts(DistinctState* d, const void* keys_dev, const int64_t* 
 
 // ---- packed rows (rsv_export_packed / rsv_merge_packed) ----------------------------------------
 
-int distinct_export_row(DistinctState* d, int64_t* row, int64_t count, hipStream_t st) {
-    if (d->wide) return wide_export_row(d->wide, row, count, st);
-    if (int rc = distinct_settle(d, st)) return rc;
-    if (int rc = distinct_finalize(d, st)) return rc;
+template <typename KeyT>
+int NarrowDistinct<KeyT>::export_row(int64_t* row, int64_t count, hipStream_t st) {
+    NarrowDistinct* const d = this;
+    if (int rc = settle(st)) return rc;
+    if (int rc = finalize(st)) return rc;
     const int64_t k = d->k;
     const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(grid_1d(k), 1), 2048);
     const int64_t tied = d->m == k && d->over, mx = d->m ? d->set_top : INT64_MIN;
-    const int64_t ret = d->ordered && d->retain && d->arch_ok;
-    if (d->kw == 8)
-        hipLaunchKernelGGL(export_row_kernel<int64_t>, dim3(grid), dim3(kBlock), 0, st, (const int64_t*)d->set_h,
-                           (const int64_t*)d->set_k, d->m, k, row, count, tied, mx, ret, (int64_t)d->ordered);
-    else
-        hipLaunchKernelGGL(export_row_kernel<int32_t>, dim3(grid), dim3(kBlock), 0, st, (const int64_t*)d->set_h,
-                           (const int32_t*)d->set_k, d->m, k, row, count, tied, mx, ret, (int64_t)d->ordered);
+    const int64_t ret = retained();
+    hipLaunchKernelGGL(export_row_kernel<KeyT>, dim3(grid), dim3(kBlock), 0, st, (const int64_t*)d->set_h,
+                       (const KeyT*)d->set_k, d->m, k, row, count, tied, mx, ret, (int64_t)d->ordered);
     RSV_HIP_TRY(hipGetLastError());
     return RSV_OK;
 }
@@ -3236,7 +3197,7 @@ int distinct_export_row(DistinctState* d, int64_t* row, int64_t count, hipStream
 // The radix-sort form of a rows merge (host waits): rows whose merge overflows a bucket (a
 // degenerate hash), more than 64 rows, or buckets beyond 1 GiB.  `over` as the device form sets it.
 template <typename KeyT>
-static int merge_rows_radix(DistinctState* d, const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st) {
+static int merge_rows_radix(NarrowDistinct<KeyT>* d, const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st) {
     const int64_t k = d->k;
     std::vector<int64_t> meta((size_t)parts * kRowMeta);
     for (int32_t p = 0; p < parts; ++p)
@@ -3264,7 +3225,7 @@ static int merge_rows_radix(DistinctState* d, const int64_t* rows, int32_t parts
         const KeyT* keys = (const KeyT*)rk;
         if constexpr (sizeof(KeyT) == 4) {  // row keys are int64-widened
             RSV_HIP_TRY(ensure_caps(d, std::min<int64_t>(n, d->cand_limit), 0, st));
-            keys = (const KeyT*)d->cand_k;
+            keys = d->cand_k;
         }
         for (int64_t off = 0; off < n;) {  // chunks that fit the merge buffer
             const int64_t c = std::min<int64_t>(n - off, d->cand_limit);
@@ -3288,7 +3249,9 @@ static int merge_rows_radix(DistinctState* d, const int64_t* rows, int32_t parts
 // Settle a pending device merge: wait for its published words (normally long since there) and take
 // the new set's size, maximum and tie state; a bucket overflow redoes the merge on the radix path.
 template <typename KeyT>
-static int settle_impl(DistinctState* d, hipStream_t st) {
+int NarrowDistinct<KeyT>::settle(hipStream_t st) {
+    NarrowDistinct* const d = this;
+    if (!d->pend) return RSV_OK;
     d->pend = false;
     uint32_t* flag = (uint32_t*)(d->shc + 12);
     const auto t0 = std::chrono::steady_clock::now();
@@ -3317,13 +3280,12 @@ static int settle_impl(DistinctState* d, hipStream_t st) {
     return RSV_OK;
 }
 
-int distinct_settle(DistinctState* d, hipStream_t st) {
-    if (!d->pend) return RSV_OK;  // (wide-key merges complete before they return: never pending)
-    return d->kw == 8 ? settle_impl<int64_t>(d, st) : settle_impl<int32_t>(d, st);
-}
-
 template <typename KeyT>
-static int merge_rows_impl(DistinctState* d, const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st) {
+int NarrowDistinct<KeyT>::merge_rows(const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st) {
+    NarrowDistinct* const d = this;
+    if (int rc = settle(st)) return rc;
+    if (parts <= 0) return RSV_OK;  // (settled all the same, unlike a byte-key engine's empty merge)
+    if (int rc = finalize(st)) return rc;  // an ordered set must be exact before it merges
     const int64_t k = d->k;
     const int64_t total = d->m + (int64_t)parts * k;
     int32_t lb = 1;  // <= 64 entries per bucket on average: most sort in one 64-lane pass
@@ -3342,14 +3304,14 @@ static int merge_rows_impl(DistinctState* d, const int64_t* rows, int32_t parts,
         RSV_HIP_TRY(pool_device_grow((void**)&d->mstart, 0, (size_t)need * 4, false, st));
         d->mstart_cap = need;
     }
-    const Runs<KeyT> R{rows, stride, k, d->set_h, (const KeyT*)d->set_k, d->m};
+    const Runs<KeyT> R{rows, stride, k, d->set_h, d->set_k, d->m};
     RSV_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d->mstart, 0xFFFFFFFFu, (size_t)need, st));
     const int64_t longest = std::max<int64_t>(d->m, k) + 1;
     const dim3 bgrid((unsigned)std::min<int64_t>((longest + kBlock - 1) / kBlock, 1024), (unsigned)(parts + 1));
     hipLaunchKernelGGL(rows_bounds<KeyT>, bgrid, dim3(kBlock), 0, st, R, parts, d->m ? d->set_top : INT64_MIN,
                        (int32_t)(d->m == k && d->over), (uint32_t)lb, d->sctl, d->log_bmax_s, d->mstart);
     hipLaunchKernelGGL(rows_fill, dim3((unsigned)(parts + 1)), dim3(1024), 0, st, (uint32_t)lb, d->mstart);
-    KeyT* bk = (KeyT*)d->sbk;
+    KeyT* bk = d->sbk;
     hipLaunchKernelGGL(rows_sort<KeyT>, dim3((B + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, st, R, parts,
                        (uint32_t)lb, (const uint32_t*)d->mstart, d->sctl, d->log_bmax_s, d->sbh, bk);
     hipLaunchKernelGGL(bucket_emit<KeyT>, dim3((B + kEmitBuckets - 1) / kEmitBuckets), dim3(kBlock), 0, st, d->m,
@@ -3378,104 +3340,53 @@ static int merge_rows_impl(DistinctState* d, const int64_t* rows, int32_t parts,
     return RSV_OK;
 }
 
-int distinct_merge_rows(DistinctState* d, const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st) {
-    if (d->wide) return parts > 0 ? wide_merge_rows(d->wide, rows, parts, stride, st) : RSV_OK;
-    if (int rc = distinct_settle(d, st)) return rc;
-    if (parts <= 0) return RSV_OK;
-    if (int rc = distinct_finalize(d, st)) return rc;  // an ordered set must be exact before it merges
-    return d->kw == 8 ? merge_rows_impl<int64_t>(d, rows, parts, stride, st)
-                      : merge_rows_impl<int32_t>(d, rows, parts, stride, st);
-}
-
-void distinct_retain_log(DistinctState* d, bool on) {
-    if (d->wide) return wide_retain_log(d->wide, on);
-    if (on && !d->retain && d->seen > 0) d->arch_ok = false;  // earlier candidates are gone
-    d->retain = on;
-    if (!on) archive_drop(d);
-}
-
 template <typename KeyT>
-static int log_export_impl(DistinctState* d, int64_t bound, int64_t* out_h, KeyT* out_k, int64_t cap, int64_t* out_n,
-                           hipStream_t st) {
-    const bool all = bound == INT64_MAX;
-    int64_t cnt = 0;
-    auto emit = [&](int64_t h, int64_t key) {
-        if (all || h < bound) {
-            if (cnt < cap) {
-                out_h[cnt] = h;
-                out_k[cnt] = (KeyT)key;
-            }
-            ++cnt;
-        }
+int NarrowDistinct<KeyT>::log_export(int64_t bound, int64_t* out_h, void* out_k, int64_t cap, int64_t* out_n,
+                                     hipStream_t st) {
+    if (int rc = settle(st)) return rc;
+    if (int rc = log_export_check()) return rc;
+    KeyT* ok = (KeyT*)out_k;
+    LogEmit emit{bound, cap};
+    auto one = [&](int64_t h, KeyT key) {
+        emit(h, [&](int64_t i) {
+            out_h[i] = h;
+            ok[i] = key;
+        });
     };
-    for (size_t i = 0; i < d->arch_h.size(); ++i)
-        emit(d->arch_h[i], sizeof(KeyT) == 8 ? d->arch_k[i] : (int64_t)d->arch_k4[i]);
-    for (const std::vector<DistinctState::Seg>* v : {&d->pre_segs, &d->segs})
-        for (const DistinctState::Seg& g : *v) {
+    for (size_t i = 0; i < arch_h.size(); ++i) one(arch_h[i], arch_k[i]);
+    for (const std::vector<LogSeg>* v : {&pre_segs, &segs})
+        for (const LogSeg& g : *v) {
             if (g.c == 0) continue;
-            if (hipError_t e = segment_to_host<KeyT>(d, g, st, false)) {
-                set_error(std::string("rsv_export_log: ") + hipGetErrorString(e));
-                return e == hipErrorOutOfMemory ? RSV_E_OUT_OF_MEMORY : RSV_E_DEVICE;
-            }
-            const KeyT* pk = (const KeyT*)d->pk;
-            for (int64_t t = 0; t < g.c; ++t) emit(d->ph[t], (int64_t)pk[t]);
+            if (hipError_t e = segment_to_host<KeyT>(this, g, st, false)) return hip_status(e, "rsv_export_log");
+            for (int64_t t = 0; t < g.c; ++t) one(ph[t], pk[t]);
         }
-    *out_n = cnt;
-    if (cnt > cap && cap > 0) {  // (cap 0: a count-only query)
-        set_error("rsv_export_log: cap is smaller than the number of candidates (*out_n)");
-        return RSV_E_ILLEGAL_ARGUMENT;
-    }
-    return RSV_OK;
-}
-
-int distinct_log_export(DistinctState* d, int64_t bound, int64_t* out_h, void* out_k, int64_t cap, int64_t* out_n,
-                        hipStream_t st) {
-    if (d->wide) return wide_log_export(d->wide, bound, out_h, out_k, cap, out_n, st);
-    if (int rc = distinct_settle(d, st)) return rc;
-    if (!d->ordered || !d->retain || !d->arch_ok) {
-        set_error(!d->ordered  ? "rsv_export_log needs an RSV_DISTINCT_ORDERED sampler"
-                  : !d->retain ? "rsv_export_log: the candidate log was not retained (rsv_retain_log before sampling)"
-                               : "rsv_export_log: the candidate log was not retained (archive limit, or sampled "
-                                 "after a merge)");
-        return RSV_E_UNSUPPORTED;
-    }
-    return d->kw == 8 ? log_export_impl<int64_t>(d, bound, out_h, (int64_t*)out_k, cap, out_n, st)
-                      : log_export_impl<int32_t>(d, bound, out_h, (int32_t*)out_k, cap, out_n, st);
+    return emit.finish(out_n);
 }
 
 // The exact multi-rank merge: a fresh replica runs RandomValues.sample over the concatenated
 // candidate run (every rank's rsv_export_log output, in rank = global arrival order) and becomes
 // the sampler's state, as if it had seen the whole stream.
-int distinct_log_merge(DistinctState* d, const int64_t* h, const void* keys, int64_t n, int64_t seen,
-                       hipStream_t st) {
-    if (d->wide) return wide_log_merge(d->wide, h, keys, n, seen, st);
+template <typename KeyT>
+int NarrowDistinct<KeyT>::log_merge(const int64_t* h, const void* keys, int64_t n, int64_t seen, hipStream_t st) {
+    NarrowDistinct* const d = this;
     if (!d->ordered) {
         set_error("rsv_merge_log needs an RSV_DISTINCT_ORDERED sampler");
         return RSV_E_UNSUPPORTED;
     }
-    if (int rc = distinct_settle(d, st)) return rc;
+    if (int rc = settle(st)) return rc;
     d->rep.reset(d->k);
     d->rep_stale = false;
-    if (d->kw == 8) {
-        const int64_t* kk = (const int64_t*)keys;
-        d->rep.sample_run(n, [&](int64_t t) { return kk[t]; }, [&](int64_t t) { return h[t]; });
-    } else {
-        const int32_t* kk = (const int32_t*)keys;
-        d->rep.sample_run(n, [&](int64_t t) { return (int64_t)kk[t]; }, [&](int64_t t) { return h[t]; });
-    }
+    const KeyT* kk = (const KeyT*)keys;
+    d->rep.sample_run(n, [&](int64_t t) { return (int64_t)kk[t]; }, [&](int64_t t) { return h[t]; });
     d->segs.clear();
     d->pre_segs.clear();
     d->log_n = 0;
-    archive_drop(d);
-    hipError_t e = d->kw == 8 ? upload_replica<int64_t>(d, st) : upload_replica<int32_t>(d, st);
-    if (e != hipSuccess) {
-        set_error(std::string("rsv_merge_log: ") + hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? RSV_E_OUT_OF_MEMORY : RSV_E_DEVICE;
-    }
+    drop_archive();
+    if (hipError_t e = upload_replica<KeyT>(d, st)) return hip_status(e, "rsv_merge_log");
     d->over = false;
     d->exact = true;
     d->merged = true;
-    d->spec_ok = false;
+    d->spec.ok = false;
     d->seen = std::max(d->seen, seen);
     return RSV_OK;
 }

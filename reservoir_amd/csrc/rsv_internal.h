@@ -11,6 +11,9 @@ namespace rsv {
 
 // thread-local last error (rsv_last_error)
 void set_error(const std::string& msg);
+// a failed HIP call as the last error, "<what>: <the HIP error string>"; returns its status
+// (RSV_E_OUT_OF_MEMORY for hipErrorOutOfMemory, else RSV_E_DEVICE)
+int hip_status(hipError_t e, const char* what);
 
 #define RSV_HIP_TRY(expr)                                                                     \
     do {                                                                                      \
@@ -195,80 +198,121 @@ hipError_t launch_merge_packed_publish(const int64_t* rows, int32_t parts, int64
                                        uint32_t* flag_dev, uint32_t gen, hipStream_t st);
 
 // ---- distinct (bottom-k over the scrambled hash) --------------------------------------------
-struct DistinctState;  // defined in rsv_distinct.hip
-// ordered: RSV_DISTINCT_ORDERED semantics (exact sequential replay; see rsv_distinct.hip)
-DistinctState* distinct_create(int32_t k, int key_width, int hash_kind, int64_t r0, int64_t r1, bool ordered,
-                               int* status);
-void distinct_set_timer(DistinctState* d, KernelTimer* t);
-void distinct_destroy(DistinctState* d);
-// keys/hashes are device pointers
-int distinct_sample_device(DistinctState* d, const void* keys, const int64_t* hashes, int64_t n,
-                           hipStream_t st);
-int64_t distinct_size(const DistinctState* d);
-// RSV_DISTINCT_ORDERED: bring the set arrays to the reference's set (host replay of the logged
-// candidates when the tie bucket requires it); a no-op otherwise.  Before size / export / publish.
-int distinct_finalize(DistinctState* d, hipStream_t st);
-const void* distinct_keys_dev(const DistinctState* d);  // the current set's keys (m of them)
-// the set's m keys into coherent host memory (device-mapped pointer) + flag = gen
-int distinct_publish(DistinctState* d, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st);
-// Speculative publication (set mode, large batches): the next distinct_sample_device enqueues the
-// merged set's publication into dst_host_dev + flag_dev (generation ++*gen_counter) right behind
-// its ctl read; distinct_spec_take says whether the last one holds the batch's final set (its
-// generation in *gen) and clears the target.
-void distinct_spec_target(DistinctState* d, void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter);
-int64_t distinct_spec_min(const DistinctState* d);  // smallest batch that publishes speculatively
-bool distinct_spec_take(DistinctState* d, uint32_t* gen);
-// copies the set (ascending hash) to device buffers; either may be null
-int distinct_export(DistinctState* d, void* keys_dev, int64_t* hash_dev, hipStream_t st);
-// merge `parts` external (key, hash) runs (device; run p at p * part_len) into the set
-int distinct_merge_parts(DistinctState* d, const void* keys_dev, const int64_t* hash_dev, const int64_t* part_n,
-                         int32_t parts, int64_t part_len, hipStream_t st);
-void distinct_info(const DistinctState* d, int32_t* ordered, int32_t* tied, int32_t* retained, int64_t* size,
-                   int64_t* max_hash, int64_t* log_entries, int64_t* sched_passes, int64_t* sched_fallbacks);
-// ordered samplers: every logged candidate with h < bound (all of them for bound = INT64_MAX) in
-// arrival order into host buffers; the exact replay of a concatenated candidate run
-int distinct_log_export(DistinctState* d, int64_t bound, int64_t* out_h, void* out_k, int64_t cap, int64_t* out_n,
-                        hipStream_t st);
-int distinct_log_merge(DistinctState* d, const int64_t* h, const void* keys, int64_t n, int64_t seen,
-                       hipStream_t st);
-// packed rows [keys as int64 (k) | hashes (k) | n, count, tied, max_hash, log_retained, ordered]:
-// export of the set (count = the handle's element count), and the device merge of `parts` rows into
-// the set -- enqueued without a host wait; `rows` must stay valid until the next call on the state,
-// which settles the merge (distinct_settle; every other distinct_* call settles first)
-int distinct_export_row(DistinctState* d, int64_t* row, int64_t count, hipStream_t st);
-int distinct_merge_rows(DistinctState* d, const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st);
-int distinct_settle(DistinctState* d, hipStream_t st);
-// ordered samplers: keep every replayed candidate on the host for rsv_export_log (opt-in)
-void distinct_retain_log(DistinctState* d, bool on);
+// The target of a speculative publication: the engine enqueues the merged set's publication into
+// dst + flag (generation ++*gen_ctr) right behind a merge it expects to be the batch's last.
+struct SpecPublish {
+    void* dst = nullptr;          // coherent host buffer (device alias)
+    uint32_t* flag = nullptr;
+    uint32_t* gen_ctr = nullptr;  // the handle's publication generation counter
+    bool arm = false;             // the next merge enqueues the publication behind it
+    bool ok = false;              // the last enqueued publication holds the batch's final set
+    uint32_t gen = 0;
+    void target(void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter) {
+        dst = dst_host_dev;
+        flag = flag_dev;
+        gen_ctr = gen_counter;
+        ok = false;
+    }
+    // whether the last publication holds the batch's final set (its generation in *g); clears the target
+    bool take(uint32_t* g) {
+        const bool held = ok && dst;
+        if (held) *g = gen;
+        dst = nullptr;
+        arm = ok = false;
+        return held;
+    }
+};
 
-// ---- distinct over fixed-width byte keys (rsv_wide.hip; key_width 16..256, a multiple of 8) ------
-// The same contract as the distinct_* functions above (which forward here for key_width > 8); keys
-// are rows of key_width / 8 int64 words, hashes precomputed (src kWideSrcHashes) or UUID.hashCode of
-// 16-byte rows (kWideSrcUuid).  Every call completes its device work before it returns.
-struct WideDistinct;
-WideDistinct* wide_create(int32_t k, int key_width, int src, int64_t r0, int64_t r1, bool ordered, int* status);
-void wide_destroy(WideDistinct* d);
-void wide_set_timer(WideDistinct* d, KernelTimer* t);
-int64_t wide_size(const WideDistinct* d);
-const void* wide_keys_dev(const WideDistinct* d);
-int wide_sample_device(WideDistinct* d, const void* keys, const int64_t* hashes, int64_t n, hipStream_t st);
-int wide_finalize(WideDistinct* d, hipStream_t st);
-int wide_publish(WideDistinct* d, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st);
-int wide_export(WideDistinct* d, void* keys_dev, int64_t* hash_dev, hipStream_t st);
-void wide_info(const WideDistinct* d, int32_t* ordered, int32_t* tied, int32_t* retained, int64_t* size,
-               int64_t* max_hash, int64_t* log_entries);
-int wide_merge_parts(WideDistinct* d, const void* keys_dev, const int64_t* hash_dev, const int64_t* part_n,
-                     int32_t parts, int64_t part_len, hipStream_t st);
-int wide_export_row(WideDistinct* d, int64_t* row, int64_t count, hipStream_t st);
-int wide_merge_rows(WideDistinct* d, const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st);
-void wide_retain_log(WideDistinct* d, bool on);
-// set mode's one-pass batches: the merged set published into dst_host_dev + flag_dev (generation
-// ++*gen_counter) right behind the merge; wide_spec_take says whether it holds the batch's final set
-void wide_spec_target(WideDistinct* d, void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter);
-bool wide_spec_take(WideDistinct* d, uint32_t* gen);
-int wide_log_export(WideDistinct* d, int64_t bound, int64_t* out_h, void* out_k, int64_t cap, int64_t* out_n,
-                    hipStream_t st);
-int wide_log_merge(WideDistinct* d, const int64_t* h, const void* keys, int64_t n, int64_t seen, hipStream_t st);
+// rsv_export_log's output rule: the candidates under `bound` (all of them for INT64_MAX) are stored
+// while they fit `cap` and counted past it
+struct LogEmit {
+    int64_t bound, cap, cnt = 0;
+    template <typename Store>  // store(i): the candidate into entry i of the caller's buffers
+    void operator()(int64_t h, Store&& store) {
+        if (bound == INT64_MAX || h < bound) {
+            if (cnt < cap) store(cnt);
+            ++cnt;
+        }
+    }
+    int finish(int64_t* out_n) const;  // *out_n = the count; RSV_E_ILLEGAL_ARGUMENT past a cap > 0
+};
+
+// One distinct sampler behind the C ABI: NarrowDistinct<int64_t> / <int32_t> (Long / Int keys,
+// rsv_distinct.hip) or WideDistinct (fixed-width byte keys, rsv_wide.hip).  keys / hashes are device
+// pointers of the engine's key type (rows of key_width / 8 int64 words for byte keys).  A byte-key
+// engine completes its device work before every call returns; a Long / Int engine may leave a rows
+// merge pending (merge_rows) and settles it at the top of every other call.
+struct DistinctEngine {
+    // ordered: RSV_DISTINCT_ORDERED semantics (exact sequential replay; see rsv_distinct.hip)
+    bool ordered = false;
+    int64_t seen = 0;  // elements sampled so far (chunk sizing)
+    SpecPublish spec;
+    // Log retention (rsv_retain_log / rsv_export_log): `retain` is the caller's opt-in, `arch_ok` says
+    // the host archive still holds every candidate consumed since creation, `merged` that the log
+    // describes the history before a merge (sampling again drops it).
+    bool retain = false;
+    bool arch_ok = true;
+    bool merged = false;
+
+    virtual ~DistinctEngine() = default;
+    virtual void set_timer(KernelTimer* t) = 0;
+    virtual int sample_device(const void* keys, const int64_t* hashes, int64_t n, hipStream_t st) = 0;
+    virtual int64_t size() const = 0;
+    // RSV_DISTINCT_ORDERED: bring the set arrays to the reference's set (host replay of the logged
+    // candidates when the tie bucket requires it); a no-op otherwise.  Before size / export / publish.
+    virtual int finalize(hipStream_t st) = 0;
+    virtual const void* keys_dev() const = 0;  // the current set's keys (size() of them)
+    // the set's keys into coherent host memory (device-mapped pointer) + flag = gen
+    virtual int publish(void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st) = 0;
+    // Speculative publication (large batches): the next sample_device enqueues the merged set's
+    // publication into dst_host_dev + flag_dev (generation ++*gen_counter) right behind its merge;
+    // spec_take says whether the last one holds the batch's final set (its generation in *gen) and
+    // clears the target.
+    virtual void spec_target(void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter) = 0;
+    virtual int64_t spec_min() const = 0;  // smallest batch that publishes speculatively
+    bool spec_take(uint32_t* gen) { return spec.take(gen); }
+    // copies the set (ascending hash) to device buffers; either may be null
+    virtual int export_set(void* keys_dev, int64_t* hash_dev, hipStream_t st) = 0;
+    // merge `parts` external (key, hash) runs (device; run p at p * part_len) into the set
+    virtual int merge_parts(const void* keys_dev, const int64_t* hash_dev, const int64_t* part_n, int32_t parts,
+                            int64_t part_len, hipStream_t st) = 0;
+    virtual void info(int32_t* ordered, int32_t* tied, int32_t* retained, int64_t* size, int64_t* max_hash,
+                      int64_t* log_entries, int64_t* sched_passes, int64_t* sched_fallbacks) const = 0;
+    // ordered samplers: every logged candidate with h < bound (all of them for bound = INT64_MAX) in
+    // arrival order into host buffers; the exact replay of a concatenated candidate run
+    virtual int log_export(int64_t bound, int64_t* out_h, void* out_k, int64_t cap, int64_t* out_n,
+                           hipStream_t st) = 0;
+    virtual int log_merge(const int64_t* h, const void* keys, int64_t n, int64_t seen, hipStream_t st) = 0;
+    // packed rows [keys as int64 words (k) | hashes (k) | n, count, tied, max_hash, log_retained, ordered]:
+    // export of the set (count = the handle's element count), and the device merge of `parts` rows into
+    // the set -- a Long / Int engine enqueues it without a host wait; `rows` must stay valid until the
+    // next call on the engine, which settles the merge (settle; every other call settles first)
+    virtual int export_row(int64_t* row, int64_t count, hipStream_t st) = 0;
+    virtual int merge_rows(const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st) = 0;
+    virtual int settle(hipStream_t st) = 0;
+    // ordered samplers: keep every replayed candidate on the host for rsv_export_log (opt-in);
+    // switched on after sampling, the log is not retained; switched off, the archive goes
+    void retain_log(bool on) {
+        if (on && !retain && seen > 0) arch_ok = false;  // earlier candidates are gone
+        retain = on;
+        if (!on) drop_archive();
+    }
+
+    bool retained() const { return ordered && retain && arch_ok; }  // rsv_export_log can serve the log
+    // rsv_export_log's precondition: RSV_OK, or RSV_E_UNSUPPORTED with the reason as the last error
+    int log_export_check() const;
+
+    virtual void drop_archive() = 0;  // release the host archive (retain_log(false))
+};
+
+// The engine for a key width: Long (8), Int (4) or byte keys (16..256, a multiple of 8; hashes
+// precomputed, or UUID.hashCode of 16-byte rows for kHashUuid).  Null with *status set on failure.
+DistinctEngine* distinct_create(int32_t k, int key_width, int hash_kind, int64_t r0, int64_t r1, bool ordered,
+                                int* status);
+// distinct_create's byte-key case: WideDistinct is defined in rsv_wide.hip, so its construction is too
+// (src: kWideSrcHashes or kWideSrcUuid)
+DistinctEngine* new_wide_distinct(int32_t k, int key_width, int src, int64_t r0, int64_t r1, bool ordered,
+                                  int* status);
 
 // ---- distinct for any B: the hash-only candidate pass (rsv_objects.hip) ---------------------------
 // The engine sees scrambled-hash inputs only; the caller keeps the elements and replays RandomValues

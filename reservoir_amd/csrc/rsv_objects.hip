@@ -280,15 +280,10 @@ __global__ __launch_bounds__(kCompactBlock) void obj_compact(int64_t* __restrict
     }
 }
 
-int fail_obj(hipError_t e, const char* what) {
-    set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return e == hipErrorOutOfMemory ? RSV_E_OUT_OF_MEMORY : RSV_E_DEVICE;
-}
-
 #define OBJ_TRY(expr)                                      \
     do {                                                   \
         hipError_t _e = (expr);                            \
-        if (_e != hipSuccess) return fail_obj(_e, #expr);  \
+        if (_e != hipSuccess) return hip_status(_e, #expr);  \
     } while (0)
 
 int64_t pow2_ceil(int64_t v) {
@@ -435,7 +430,7 @@ ObjDistinct* obj_create(int32_t k, int64_t r0, int64_t r1, int* status) {
     if (e == hipSuccess) e = pool_host_alloc((void**)&d->ctl_h, kCtlWords * 8, hipHostMallocDefault);
     for (int b = 0; b < 2 && e == hipSuccess; ++b) e = pool_device_alloc((void**)&d->sh[b], (size_t)k * 8);
     if (e != hipSuccess) {
-        *status = fail_obj(e, "allocating the hash shadow");
+        *status = hip_status(e, "allocating the hash shadow");
         obj_destroy(d);
         return nullptr;
     }

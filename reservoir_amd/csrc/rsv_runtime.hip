@@ -23,6 +23,29 @@ namespace rsv {
 static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
 
+int hip_status(hipError_t e, const char* what) {
+    set_error(std::string(what) + ": " + hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? RSV_E_OUT_OF_MEMORY : RSV_E_DEVICE;
+}
+
+// ---- the log-retention rules every distinct engine shares (rsv_internal.h DistinctEngine) -----
+int DistinctEngine::log_export_check() const {
+    if (retained()) return RSV_OK;
+    set_error(!ordered  ? "rsv_export_log needs an RSV_DISTINCT_ORDERED sampler"
+              : !retain ? "rsv_export_log: the candidate log was not retained (rsv_retain_log before sampling)"
+                        : "rsv_export_log: the candidate log was not retained (archive limit, or sampled "
+                          "after a merge)");
+    return RSV_E_UNSUPPORTED;
+}
+
+int LogEmit::finish(int64_t* out_n) const {
+    *out_n = cnt;
+    if (cnt > cap && cap > 0) {  // (cap 0: a count-only query)
+        set_error("rsv_export_log: cap is smaller than the number of candidates (*out_n)");
+        return RSV_E_ILLEGAL_ARGUMENT;
+    }
+    return RSV_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // java.util.Random + Algorithm L event generator for RSV_ENGINE_JAVA_L (product implementation;
@@ -147,7 +170,7 @@ struct rsv_sampler {
     uint8_t* gath_h = nullptr;
     void* gath_dev = nullptr;
     // DISTINCT
-    DistinctState* distinct = nullptr;
+    DistinctEngine* distinct = nullptr;
     int hash_kind = kHashIdentity;
     // distinct for any B (rsv_distinct_candidates): the hash-only candidate pass; the caller keeps the
     // elements (keys_external) and owes a commit or abort while cand_pending
@@ -441,17 +464,17 @@ rsv_status process_device_batch(rsv_sampler* s, const void* keys, const int64_t*
         s->win_zero = false;  // until this batch's resolve is enqueued
     }
     if (s->cfg.kind == RSV_KIND_DISTINCT) {
-        // large batches publish the merged set speculatively (distinct_spec_target: set mode behind
+        // large batches publish the merged set speculatively (DistinctEngine::spec_target: set mode behind
         // its last merge, ordered mode behind the scheduled pass) -- only where a publication can
         // happen at all (a coherent result buffer of k keys); other samplers (huge k, device-only
         // consumers) keep the result buffer lazy
-        if ((int64_t)s->k * s->kw <= kPublishMaxBytes && n >= distinct_spec_min(s->distinct)) {
+        if ((int64_t)s->k * s->kw <= kPublishMaxBytes && n >= s->distinct->spec_min()) {
             if (rsv_status st = ensure_result_buffer(s)) return st;
-            if (s->result_publish) distinct_spec_target(s->distinct, s->result_dev, s->result_flag_dev, &s->result_gen);
+            if (s->result_publish) s->distinct->spec_target(s->result_dev, s->result_flag_dev, &s->result_gen);
         }
-        int rc = distinct_sample_device(s->distinct, keys, hashes, n, s->stream);
+        int rc = s->distinct->sample_device(keys, hashes, n, s->stream);
         uint32_t gen = 0;
-        const bool published = distinct_spec_take(s->distinct, &gen);
+        const bool published = s->distinct->spec_take(&gen);
         if (rc != RSV_OK) return (rsv_status)rc;
         s->pub_valid = published;  // result() waits for it instead of publishing
         if (published) {
@@ -798,7 +821,7 @@ void free_all(rsv_sampler* s) {
     if (s->handover) pool_release_event(s->device, s->handover, hipEventDisableTiming);
     if (s->side_fork) pool_release_event(s->device, s->side_fork, hipEventDisableTiming);
     if (s->side_join) pool_release_event(s->device, s->side_join, hipEventDisableTiming);
-    if (s->distinct) distinct_destroy(s->distinct);
+    delete s->distinct;
     if (s->obj) obj_destroy(s->obj);
     if (s->stream && s->own_stream) pool_release_stream(s->device, s->stream);
 }
@@ -929,7 +952,7 @@ rsv_status rsv_create(const rsv_config* cfg, rsv_sampler** out) {
             std::string msg = g_last_error;
             return bail((rsv_status)st, msg);
         }
-        distinct_set_timer(s->distinct, &s->timer);
+        s->distinct->set_timer(&s->timer);
     }
     *out = s;
     return RSV_OK;
@@ -1174,22 +1197,22 @@ static rsv_status result_impl(rsv_sampler* s, void* out, int64_t cap, int64_t* o
     int64_t m;
     const void* src;
     if (s->cfg.kind == RSV_KIND_DISTINCT) {
-        if (int rc = distinct_finalize(s->distinct, s->stream)) return (rsv_status)rc;
-        m = distinct_size(s->distinct);
+        if (int rc = s->distinct->finalize(s->stream)) return (rsv_status)rc;
+        m = s->distinct->size();
         if (m > cap) return fail(RSV_E_ILLEGAL_ARGUMENT, "result buffer too small");
         if (m && !out && !take) return fail(RSV_E_NULL_POINTER, "out is NULL");
         if (m) {
             if (device_out) {
-                if (int rc = distinct_export(s->distinct, out, nullptr, s->stream)) return (rsv_status)rc;
+                if (int rc = s->distinct->export_set(out, nullptr, s->stream)) return (rsv_status)rc;
             } else {
                 if (rsv_status st = ensure_result_buffer(s)) return st;
-                const void* set_k = distinct_keys_dev(s->distinct);
+                const void* set_k = s->distinct->keys_dev();
                 if (s->result_publish) {  // the set straight into coherent host memory + flag spin
                     uint32_t gen = s->pub_gen;
                     if (!(s->pub_valid && s->pub_ops == s->ops)) {  // no speculative publication of it
                         touch(s);
                         gen = ++s->result_gen;
-                        if (int rc = distinct_publish(s->distinct, s->result_dev, s->result_flag_dev, gen, s->stream))
+                        if (int rc = s->distinct->publish(s->result_dev, s->result_flag_dev, gen, s->stream))
                             return (rsv_status)rc;
                     }
                     s->pub_valid = false;
@@ -1414,9 +1437,9 @@ rsv_status rsv_export_state(rsv_sampler* s, int64_t* idx_dev, void* keys_dev, in
     touch(s);
     if (rsv_status st = flush_stage(s)) return st;
     if (s->cfg.kind == RSV_KIND_DISTINCT) {
-        if (int rc = distinct_finalize(s->distinct, s->stream)) return (rsv_status)rc;
-        if (int rc = distinct_export(s->distinct, keys_dev, hash_dev, s->stream)) return (rsv_status)rc;
-        *out_n = distinct_size(s->distinct);
+        if (int rc = s->distinct->finalize(s->stream)) return (rsv_status)rc;
+        if (int rc = s->distinct->export_set(keys_dev, hash_dev, s->stream)) return (rsv_status)rc;
+        *out_n = s->distinct->size();
     } else {
         if (rsv_status st = ensure_slots(s)) return st;
         if (idx_dev) RSV_HIP_TRY(hipMemcpyAsync(idx_dev, s->slot_idx, s->k * 8ull, hipMemcpyDeviceToDevice, s->stream));
@@ -1441,7 +1464,7 @@ rsv_status rsv_merge_state(rsv_sampler* s, const int64_t* idx_dev, const void* k
     if (s->cfg.kind == RSV_KIND_DISTINCT) {
         if (parts > 0 && (!hash_dev || !part_n_host)) return fail(RSV_E_NULL_POINTER, "hash_dev/part_n is NULL");
         if (parts > 0)
-            if (int rc = distinct_merge_parts(s->distinct, keys_dev, hash_dev, part_n_host, parts, part_len, s->stream))
+            if (int rc = s->distinct->merge_parts(keys_dev, hash_dev, part_n_host, parts, part_len, s->stream))
                 return (rsv_status)rc;
     } else {
         if (part_len < (int64_t)s->k) return fail(RSV_E_ILLEGAL_ARGUMENT, "part_len < k");
@@ -1471,8 +1494,8 @@ rsv_status rsv_get_distinct_info(rsv_sampler* s, rsv_distinct_info* out) {
     DeviceGuard g(s->device);
     touch(s);
     if (rsv_status st = flush_stage(s)) return st;
-    if (int rc = distinct_settle(s->distinct, s->stream)) return (rsv_status)rc;
-    distinct_info(s->distinct, &out->ordered, &out->tied, &out->log_retained, &out->size, &out->max_hash,
+    if (int rc = s->distinct->settle(s->stream)) return (rsv_status)rc;
+    s->distinct->info(&out->ordered, &out->tied, &out->log_retained, &out->size, &out->max_hash,
                   &out->log_entries, &out->sched_passes, &out->sched_fallbacks);
     return RSV_OK;
 }
@@ -1487,7 +1510,7 @@ rsv_status rsv_export_log(rsv_sampler* s, int64_t bound, int64_t* hashes_host, v
     DeviceGuard g(s->device);
     touch(s);
     if (rsv_status st = flush_stage(s)) return st;
-    return (rsv_status)distinct_log_export(s->distinct, bound, hashes_host, keys_host, cap, out_n, s->stream);
+    return (rsv_status)s->distinct->log_export(bound, hashes_host, keys_host, cap, out_n, s->stream);
 }
 
 rsv_status rsv_merge_log(rsv_sampler* s, const int64_t* hashes_host, const void* keys_host, int64_t n,
@@ -1498,7 +1521,7 @@ rsv_status rsv_merge_log(rsv_sampler* s, const int64_t* hashes_host, const void*
     DeviceGuard g(s->device);
     touch(s);
     if (rsv_status st = flush_stage(s)) return st;
-    if (int rc = distinct_log_merge(s->distinct, hashes_host, keys_host, n, total_count, s->stream))
+    if (int rc = s->distinct->log_merge(hashes_host, keys_host, n, total_count, s->stream))
         return (rsv_status)rc;
     if (total_count > s->count) s->count = total_count;
     s->pub_valid = false;
@@ -1508,7 +1531,7 @@ rsv_status rsv_merge_log(rsv_sampler* s, const int64_t* hashes_host, const void*
 
 rsv_status rsv_retain_log(rsv_sampler* s, int32_t on) {
     if (rsv_status st = check_distinct(s, "rsv_retain_log")) return st;
-    distinct_retain_log(s->distinct, on != 0);
+    s->distinct->retain_log(on != 0);
     return RSV_OK;
 }
 
@@ -1519,7 +1542,7 @@ rsv_status rsv_export_packed(rsv_sampler* s, int64_t* row_dev) {
     touch(s);
     if (rsv_status st = flush_stage(s)) return st;
     if (s->cfg.kind == RSV_KIND_DISTINCT) {
-        if (int rc = distinct_export_row(s->distinct, row_dev, s->count, s->stream)) return (rsv_status)rc;
+        if (int rc = s->distinct->export_row(row_dev, s->count, s->stream)) return (rsv_status)rc;
         if (s->own_stream) RSV_HIP_TRY(sync_stream(s));
         return RSV_OK;
     }
@@ -1541,12 +1564,12 @@ rsv_status rsv_merge_packed(rsv_sampler* s, const int64_t* rows_dev, int32_t par
         DeviceGuard g(s->device);
         touch(s);
         if (rsv_status st = flush_stage(s)) return st;
-        if (int rc = distinct_merge_rows(s->distinct, rows_dev, parts, row_stride, s->stream)) return (rsv_status)rc;
+        if (int rc = s->distinct->merge_rows(rows_dev, parts, row_stride, s->stream)) return (rsv_status)rc;
         if (total_count > s->count) s->count = total_count;
         s->pub_valid = false;
         if (s->own_stream) {  // the call returns with its work done: settle now, while the rows are the caller's
             RSV_HIP_TRY(sync_stream(s));
-            if (int rc = distinct_settle(s->distinct, s->stream)) return (rsv_status)rc;
+            if (int rc = s->distinct->settle(s->stream)) return (rsv_status)rc;
         }
         return RSV_OK;
     }

@@ -19,6 +19,11 @@
 // candidate (h, global index, row) on the device; when the set's boundary hash bucket holds more
 // distinct elements than the set keeps, the log is replayed in arrival order through the host replica
 // HostValuesWide (scala PriorityQueue tie order) -- the same scheme as rsv_distinct.hip's ordered mode.
+//
+// WideDistinct is one of the three DistinctEngine implementations (rsv_internal.h; the factory
+// distinct_create in rsv_distinct.hip picks it for key_width > 8): the runtime calls its methods
+// through the interface, and the speculative-publication target, the log-retention rules and
+// rsv_export_log's messages are the base's, shared with the Long / Int engine.
 #include <rocprim/device/device_merge_sort.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -50,7 +55,7 @@ inline unsigned wgrid(int64_t n, int64_t cap = 65535) {
     return (unsigned)std::min<int64_t>(std::max<int64_t>((n + kWBlock - 1) / kWBlock, 1), cap);
 }
 
-// The ordered mode's scheduled pass (see wide_sample_device): ranges [s_r, s_r+1) of the rest with
+// The ordered mode's scheduled pass (see WideDistinct::sample_device): ranges [s_r, s_r+1) of the rest with
 // falling bounds B_r; device table = starts [R + 1] then bounds [R].
 constexpr int kWMaxR = 64;
 
@@ -811,17 +816,15 @@ __global__ __launch_bounds__(kWBlock) void wb_verify(uint32_t B, const int64_t* 
 
 }  // namespace
 
-struct WideDistinct {
+struct WideDistinct final : DistinctEngine {
     int32_t k = 0;
     int32_t words = 0;  // key_width / 8
     int src = kWideSrcHashes;
     int64_t r0 = 0, r1 = 0;
-    bool ordered = false;
     int64_t m = 0;                // set size
     int64_t top = INT64_MIN;      // the set's largest h (valid when m > 0)
     bool tied = false;            // full, and the boundary hash bucket holds more distinct elements
     bool exact = true;            // ordered: the set arrays hold the reference's set
-    int64_t seen = 0;             // elements sampled (chunk sizing)
     KernelTimer* timer = nullptr;
     // device
     int64_t* set_h = nullptr;     // [set_cap] ascending (h, key words)
@@ -847,10 +850,7 @@ struct WideDistinct {
     int64_t log_n = 0, log_cap = 0, log_limit = 0;
     HostValuesWide rep;           // the exact RandomValues state before the log's first entry
     bool rep_stale = false;       // a merge replaced the set: rebuild the replica from it first
-    bool merged = false;          // the log still describes the pre-merge history (rsv_export_log)
-    bool retain = false;          // keep the consumed log on the host (rsv_retain_log)
-    bool arch_ok = true;
-    std::vector<int64_t> arch_h;  // consumed candidates in arrival order
+    std::vector<int64_t> arch_h;  // consumed candidates in arrival order (the base's `retain`)
     std::vector<uint64_t> arch_k;
     // ordered mode's scheduled pass: range table + verification counts (device [0, 2 kWMaxR + 1) the
     // table, [kSchedCounts, + kWMaxR + 1) the counts; pinned staging alike)
@@ -870,13 +870,8 @@ struct WideDistinct {
     uint32_t last_B = 0;
     WSegTable hwb_seg;            // the bucket map's segment table (passed by value to wb_scatter)
     int64_t merges = 0;           // merges applied (a set swap each)
-    // speculative publication (set mode's one-pass batches, wide_spec_target): armed around the pass,
+    // speculative publication (set mode's one-pass batches, the base's `spec`): armed around the pass,
     // enqueued behind its merge; valid when the pass proved its bound and no other merge followed
-    void* spec_dst = nullptr;
-    uint32_t* spec_flag = nullptr;
-    uint32_t* spec_gen_ctr = nullptr;
-    bool spec_arm = false, spec_ok = false;
-    uint32_t spec_gen = 0;
     int64_t spec_merges = -1;
     double sched_beta = 1.6;      // bound margin over the predicted k-th smallest hash
     int64_t first_min = 4096;     // logs at least this long replay through first-occurrence flags
@@ -888,6 +883,33 @@ struct WideDistinct {
     uint64_t* p_ok = nullptr;
     uint32_t* p_fl = nullptr;
     int64_t p_cap = 0;
+
+    ~WideDistinct() override;
+    void set_timer(KernelTimer* t) override { timer = t; }
+    int sample_device(const void* keys, const int64_t* hashes, int64_t n, hipStream_t st) override;
+    int64_t size() const override { return m; }
+    int finalize(hipStream_t st) override;
+    const void* keys_dev() const override { return set_k; }
+    int publish(void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st) override;
+    void spec_target(void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter) override;
+    // the one-pass batches decide by their own shape, whatever RSV_SPEC_MIN_BATCH says
+    int64_t spec_min() const override { return (int64_t)1 << 27; }
+    int export_set(void* keys_dev, int64_t* hash_dev, hipStream_t st) override;
+    int merge_parts(const void* keys_dev, const int64_t* hash_dev, const int64_t* part_n, int32_t parts,
+                    int64_t part_len, hipStream_t st) override;
+    void info(int32_t* ordered, int32_t* tied, int32_t* retained, int64_t* size, int64_t* max_hash,
+              int64_t* log_entries, int64_t* sched_passes, int64_t* sched_fallbacks) const override;
+    int log_export(int64_t bound, int64_t* out_h, void* out_k, int64_t cap, int64_t* out_n, hipStream_t st) override;
+    int log_merge(const int64_t* h, const void* keys, int64_t n, int64_t seen, hipStream_t st) override;
+    int export_row(int64_t* row, int64_t count, hipStream_t st) override;
+    int merge_rows(const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st) override;
+    // every merge completes before its call returns: nothing is ever pending
+    int settle(hipStream_t) override { return RSV_OK; }
+
+    void drop_archive() override {  // (arch_ok stays: an archive switched off and on again before sampling is whole)
+        arch_h.clear();
+        arch_k.clear();
+    }
 };
 
 namespace {
@@ -1039,12 +1061,12 @@ hipError_t merge_bucketed(WideDistinct* d, int64_t c, int64_t span_hi, bool arri
                        (uint32_t)B, d->wb_h, d->wb_e, d->wb_dist, d->wb_gsum, (int64_t)d->k, R, d->set_h2, d->set_k2,
                        d->ctl);
     if ((e = hipGetLastError())) return e;
-    if (d->spec_arm && d->spec_dst) {  // the merged set straight to the host, before the host reads ctl
-        const uint32_t gen = ++*d->spec_gen_ctr;
-        if ((e = launch_publish_multi(d->set_k2, (int64_t)d->k * d->words * 8, d->spec_dst, d->spec_flag, gen,
+    if (d->spec.arm && d->spec.dst) {  // the merged set straight to the host, before the host reads ctl
+        const uint32_t gen = ++*d->spec.gen_ctr;
+        if ((e = launch_publish_multi(d->set_k2, (int64_t)d->k * d->words * 8, d->spec.dst, d->spec.flag, gen,
                                       (uint32_t*)(d->ctl + 7), st)))
             return e;
-        d->spec_gen = gen;
+        d->spec.gen = gen;
         d->spec_merges = d->merges + 1;
     }
     if ((e = read_ctl(d, st))) return e;
@@ -1539,11 +1561,6 @@ hipError_t sample_sched(WideDistinct* d, const void* keys, const int64_t* hashes
     return hipStreamSynchronize(st);
 }
 
-int fail_hip(hipError_t e, const char* what) {
-    set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return e == hipErrorOutOfMemory ? RSV_E_OUT_OF_MEMORY : RSV_E_DEVICE;
-}
-
 // a merge of external entries (rows of other ranks, exported states): bottom-k of the union; the
 // replica restarts from the union when next needed (a merged set has no single arrival order --
 // rsv_merge_log is the exact form), the log stays readable for rsv_export_log until the next sample
@@ -1568,15 +1585,15 @@ int merge_external(WideDistinct* d, const std::vector<std::pair<const int64_t*, 
         for (int64_t off = 0; off < n;) {
             const int64_t c = std::min<int64_t>(n - off, 8 * (int64_t)d->k + 4096);
             hipError_t e;
-            if ((e = ensure_cand(d, c, st))) return fail_hip(e, "distinct merge");
+            if ((e = ensure_cand(d, c, st))) return hip_status(e, "distinct merge");
             if ((e = hipMemcpyAsync(d->cand_h, src[p].first + off, (size_t)c * 8, hipMemcpyDeviceToDevice, st)))
-                return fail_hip(e, "distinct merge");
+                return hip_status(e, "distinct merge");
             if ((e = hipMemcpyAsync(d->cand_k, src[p].second + (size_t)off * d->words, (size_t)c * d->words * 8,
                                     hipMemcpyDeviceToDevice, st)))
-                return fail_hip(e, "distinct merge");
+                return hip_status(e, "distinct merge");
             const int64_t old_top = d->top;
             const bool was_full = d->m == d->k;
-            if ((e = merge_cands(d, c, st))) return fail_hip(e, "distinct merge");
+            if ((e = merge_cands(d, c, st))) return hip_status(e, "distinct merge");
             tie = d->m == d->k && (d->tied || (tie && was_full && d->top == old_top));
             off += c;
         }
@@ -1592,9 +1609,10 @@ int merge_external(WideDistinct* d, const std::vector<std::pair<const int64_t*, 
 
 }  // namespace
 
-// ---- entry points (rsv_internal.h) -------------------------------------------------------------
+// ---- the engine interface (rsv_internal.h DistinctEngine) ----------------------------------------
 
-WideDistinct* wide_create(int32_t k, int key_width, int src, int64_t r0, int64_t r1, bool ordered, int* status) {
+DistinctEngine* new_wide_distinct(int32_t k, int key_width, int src, int64_t r0, int64_t r1, bool ordered,
+                                  int* status) {
     WideDistinct* d = new WideDistinct();
     d->k = k;
     d->words = key_width / 8;
@@ -1616,16 +1634,16 @@ WideDistinct* wide_create(int32_t k, int key_width, int src, int64_t r0, int64_t
     if (e == hipSuccess) e = hipMemset(d->ctl, 0, 8 * 8);  // ctl[7]: the publication ticket
     if (e == hipSuccess) e = pool_host_alloc((void**)&d->hctl, 8 * 8, hipHostMallocDefault);
     if (e != hipSuccess) {
-        *status = fail_hip(e, "distinct_create (wide keys)");
-        wide_destroy(d);
+        *status = hip_status(e, "distinct_create (wide keys)");
+        delete d;
         return nullptr;
     }
     *status = RSV_OK;
     return d;
 }
 
-void wide_destroy(WideDistinct* d) {
-    if (!d) return;
+WideDistinct::~WideDistinct() {
+    WideDistinct* const d = this;
     void* ps[] = {d->set_h, d->set_k, d->set_h2, d->set_k2, d->cand_h, d->cand_i, d->cand_k, d->eh0, d->eh1,
                   d->ev0, d->ev1, d->flags, d->pos, d->temp, d->ctl, d->log_h, d->log_g, d->log_k};
     for (void* p : ps) pool_device_free(p);  // the owner's stream is idle (rsv_destroy)
@@ -1637,14 +1655,10 @@ void wide_destroy(WideDistinct* d) {
     pool_host_free(d->p_oh);
     pool_host_free(d->p_ok);
     pool_host_free(d->p_fl);
-    delete d;
 }
 
-void wide_set_timer(WideDistinct* d, KernelTimer* t) { d->timer = t; }
-int64_t wide_size(const WideDistinct* d) { return d->m; }
-const void* wide_keys_dev(const WideDistinct* d) { return d->set_k; }
-
-int wide_sample_device(WideDistinct* d, const void* keys, const int64_t* hashes, int64_t n, hipStream_t st) {
+int WideDistinct::sample_device(const void* keys, const int64_t* hashes, int64_t n, hipStream_t st) {
+    WideDistinct* const d = this;
     if (n <= 0) return RSV_OK;
     if (d->merged) {  // sampling on after a merge: the pre-merge candidates are history
         d->merged = false;
@@ -1661,7 +1675,7 @@ int wide_sample_device(WideDistinct* d, const void* keys, const int64_t* hashes,
             predicted = true;
             bool ok = false;
             if (hipError_t e = sample_sched(d, keys, hashes, off, rest, seen0, st, &ok))
-                return fail_hip(e, "distinct sample");
+                return hip_status(e, "distinct sample");
             if (ok) {
                 d->seen += rest;
                 break;
@@ -1677,12 +1691,12 @@ int wide_sample_device(WideDistinct* d, const void* keys, const int64_t* hashes,
             predicted = true;
             const double frac = 2.5 * (double)d->k / (double)rest;
             const int64_t B = (int64_t)((uint64_t)INT64_MIN + (uint64_t)(18446744073709551616.0 * frac));
-            d->spec_arm = true;
+            d->spec.arm = true;
             hipError_t e = sample_chunk(d, keys, hashes, off, rest, seen0, st, &B);
-            d->spec_arm = false;
-            if (e) return fail_hip(e, "distinct sample");
+            d->spec.arm = false;
+            if (e) return hip_status(e, "distinct sample");
             if (d->m == d->k && d->top <= B) {
-                d->spec_ok = d->spec_dst && d->merges == d->spec_merges;  // the published set is the final one
+                d->spec.ok = d->spec.dst && d->merges == d->spec_merges;  // the published set is the final one
                 d->seen += rest;
                 break;
             }
@@ -1700,7 +1714,7 @@ int wide_sample_device(WideDistinct* d, const void* keys, const int64_t* hashes,
             const uint64_t span = (uint64_t)d->top - (uint64_t)INT64_MIN;
             const int64_t B = frac >= 1.0 ? d->top : (int64_t)((uint64_t)INT64_MIN + (uint64_t)((double)span * frac));
             if (hipError_t e = sample_chunk(d, keys, hashes, off, rest, seen0, st, &B))
-                return fail_hip(e, "distinct sample");
+                return hip_status(e, "distinct sample");
             if (d->m == d->k && d->top <= B) {
                 d->seen += rest;
                 break;
@@ -1710,51 +1724,52 @@ int wide_sample_device(WideDistinct* d, const void* keys, const int64_t* hashes,
         // filling: enough for the set plus slack; full: ~4 seen lengths (~4k candidates a chunk)
         const int64_t L = d->m < d->k ? std::min<int64_t>(rest, 4 * ((int64_t)d->k - d->m) + 4096)
                                       : std::min<int64_t>(rest, std::max<int64_t>(4 * d->seen, 1 << 16));
-        if (hipError_t e = sample_chunk(d, keys, hashes, off, L, seen0, st)) return fail_hip(e, "distinct sample");
+        if (hipError_t e = sample_chunk(d, keys, hashes, off, L, seen0, st)) return hip_status(e, "distinct sample");
         off += L;
         d->seen += L;
     }
     return RSV_OK;
 }
 
-int wide_finalize(WideDistinct* d, hipStream_t st) {
-    if (!d->ordered || d->exact) return RSV_OK;
-    if (hipError_t e = replay_log(d, st)) return fail_hip(e, "distinct (ordered) replay");
+int WideDistinct::finalize(hipStream_t st) {
+    if (!ordered || exact) return RSV_OK;
+    if (hipError_t e = replay_log(this, st)) return hip_status(e, "distinct (ordered) replay");
     return RSV_OK;
 }
 
-int wide_publish(WideDistinct* d, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st) {
-    const int64_t bytes = d->m * d->words * 8;
+int WideDistinct::publish(void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st) {
+    const int64_t bytes = m * words * 8;
     // one workgroup's posted PCIe writes run at ~20 GB/s (a 1 MB UUID set: 45 us): large sets from
     // several workgroups (ctl[7] is the ticket: zero at creation, re-armed by every publication)
     if (bytes >= (64 << 10))
-        RSV_HIP_TRY(launch_publish_multi(d->set_k, bytes, dst_host_dev, flag_dev, gen, (uint32_t*)(d->ctl + 7), st));
+        RSV_HIP_TRY(launch_publish_multi(set_k, bytes, dst_host_dev, flag_dev, gen, (uint32_t*)(ctl + 7), st));
     else
-        RSV_HIP_TRY(launch_publish(d->set_k, bytes, dst_host_dev, flag_dev, gen, st));
+        RSV_HIP_TRY(launch_publish(set_k, bytes, dst_host_dev, flag_dev, gen, st));
     return RSV_OK;
 }
 
-int wide_export(WideDistinct* d, void* keys_dev, int64_t* hash_dev, hipStream_t st) {
-    if (d->m == 0) return RSV_OK;
-    if (keys_dev)
-        RSV_HIP_TRY(hipMemcpyAsync(keys_dev, d->set_k, (size_t)d->m * d->words * 8, hipMemcpyDeviceToDevice, st));
-    if (hash_dev) RSV_HIP_TRY(hipMemcpyAsync(hash_dev, d->set_h, (size_t)d->m * 8, hipMemcpyDeviceToDevice, st));
+int WideDistinct::export_set(void* keys_dev, int64_t* hash_dev, hipStream_t st) {
+    if (m == 0) return RSV_OK;
+    if (keys_dev) RSV_HIP_TRY(hipMemcpyAsync(keys_dev, set_k, (size_t)m * words * 8, hipMemcpyDeviceToDevice, st));
+    if (hash_dev) RSV_HIP_TRY(hipMemcpyAsync(hash_dev, set_h, (size_t)m * 8, hipMemcpyDeviceToDevice, st));
     return RSV_OK;
 }
 
-void wide_info(const WideDistinct* d, int32_t* ordered, int32_t* tied, int32_t* retained, int64_t* size,
-               int64_t* max_hash, int64_t* log_entries) {
-    *ordered = d->ordered;
-    *tied = d->m == d->k && d->tied;
-    *retained = d->ordered && d->retain && d->arch_ok;
-    *size = d->m;
-    *max_hash = d->m ? d->top : INT64_MIN;
-    *log_entries = d->ordered ? (int64_t)d->arch_h.size() + d->log_n : 0;
+void WideDistinct::info(int32_t* o_ordered, int32_t* o_tied, int32_t* o_retained, int64_t* o_size, int64_t* o_max_hash,
+                        int64_t* o_log_entries, int64_t* o_sched_passes, int64_t* o_sched_fallbacks) const {
+    *o_sched_passes = *o_sched_fallbacks = 0;  // the scheduled pass of byte keys is not counted
+    *o_ordered = ordered;
+    *o_tied = m == k && tied;
+    *o_retained = retained();
+    *o_size = m;
+    *o_max_hash = m ? top : INT64_MIN;
+    *o_log_entries = ordered ? (int64_t)arch_h.size() + log_n : 0;
 }
 
-int wide_merge_parts(WideDistinct* d, const void* keys_dev, const int64_t* hash_dev, const int64_t* part_n,
-                     int32_t parts, int64_t part_len, hipStream_t st) {
-    if (int rc = wide_finalize(d, st)) return rc;
+int WideDistinct::merge_parts(const void* keys_dev, const int64_t* hash_dev, const int64_t* part_n, int32_t parts,
+                              int64_t part_len, hipStream_t st) {
+    WideDistinct* const d = this;
+    if (int rc = finalize(st)) return rc;
     std::vector<std::pair<const int64_t*, const uint64_t*>> src;
     std::vector<int64_t> counts, tops;
     std::vector<int32_t> ties;
@@ -1768,19 +1783,22 @@ int wide_merge_parts(WideDistinct* d, const void* keys_dev, const int64_t* hash_
     return merge_external(d, src, counts, tops, ties, st);
 }
 
-int wide_export_row(WideDistinct* d, int64_t* row, int64_t count, hipStream_t st) {
-    if (int rc = wide_finalize(d, st)) return rc;
+int WideDistinct::export_row(int64_t* row, int64_t count, hipStream_t st) {
+    WideDistinct* const d = this;
+    if (int rc = finalize(st)) return rc;
     const int64_t k = d->k;
     const int64_t tied = d->m == k && d->tied, mx = d->m ? d->top : INT64_MIN;
-    const int64_t ret = d->ordered && d->retain && d->arch_ok;
+    const int64_t ret = retained();
     hipLaunchKernelGGL(wide_export_row, dim3(wgrid(k * (d->words + 1), 4096)), dim3(kWBlock), 0, st, d->set_h,
                        d->set_k, d->m, k, d->words, row, count, tied, mx, ret, (int64_t)d->ordered);
     RSV_HIP_TRY(hipGetLastError());
     return RSV_OK;
 }
 
-int wide_merge_rows(WideDistinct* d, const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st) {
-    if (int rc = wide_finalize(d, st)) return rc;
+int WideDistinct::merge_rows(const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st) {
+    WideDistinct* const d = this;
+    if (parts <= 0) return RSV_OK;  // (no finalize either: an empty merge leaves the engine as it was)
+    if (int rc = finalize(st)) return rc;
     const int64_t k = d->k, kw = k * d->words;
     std::vector<int64_t> meta((size_t)parts * 6);
     for (int32_t p = 0; p < parts; ++p)
@@ -1801,67 +1819,33 @@ int wide_merge_rows(WideDistinct* d, const int64_t* rows, int32_t parts, int64_t
     return merge_external(d, src, counts, tops, ties, st);
 }
 
-void wide_spec_target(WideDistinct* d, void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter) {
-    if (d->ordered) return;  // (ordered mode: the scheduled pass's result waits for its proof)
-    d->spec_dst = dst_host_dev;
-    d->spec_flag = flag_dev;
-    d->spec_gen_ctr = gen_counter;
-    d->spec_ok = false;
+void WideDistinct::spec_target(void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter) {
+    if (ordered) return;  // (ordered mode: the scheduled pass's result waits for its proof)
+    spec.target(dst_host_dev, flag_dev, gen_counter);
 }
 
-bool wide_spec_take(WideDistinct* d, uint32_t* gen) {
-    const bool ok = d->spec_ok && d->spec_dst;
-    if (ok) *gen = d->spec_gen;
-    d->spec_dst = nullptr;
-    d->spec_arm = d->spec_ok = false;
-    return ok;
-}
-
-void wide_retain_log(WideDistinct* d, bool on) {
-    if (on && !d->retain && d->seen > 0) d->arch_ok = false;  // earlier candidates are gone
-    d->retain = on;
-    if (!on) {
-        d->arch_h.clear();
-        d->arch_k.clear();
-    }
-}
-
-int wide_log_export(WideDistinct* d, int64_t bound, int64_t* out_h, void* out_k, int64_t cap, int64_t* out_n,
-                    hipStream_t st) {
-    if (!d->ordered || !d->retain || !d->arch_ok) {
-        set_error(!d->ordered  ? "rsv_export_log needs an RSV_DISTINCT_ORDERED sampler"
-                  : !d->retain ? "rsv_export_log: the candidate log was not retained (rsv_retain_log before sampling)"
-                               : "rsv_export_log: the candidate log was not retained (archive limit, or sampled "
-                                 "after a merge)");
-        return RSV_E_UNSUPPORTED;
-    }
+int WideDistinct::log_export(int64_t bound, int64_t* out_h, void* out_k, int64_t cap, int64_t* out_n, hipStream_t st) {
+    WideDistinct* const d = this;
+    if (int rc = log_export_check()) return rc;
     std::vector<int64_t> lh;
     std::vector<uint64_t> lk;
-    if (hipError_t e = log_to_host(d, lh, lk, st)) return fail_hip(e, "rsv_export_log");
-    const bool all = bound == INT64_MAX;
+    if (hipError_t e = log_to_host(d, lh, lk, st)) return hip_status(e, "rsv_export_log");
     const int64_t W = d->words;
     uint64_t* ok = (uint64_t*)out_k;
-    int64_t cnt = 0;
-    auto emit = [&](int64_t h, const uint64_t* r) {
-        if (all || h < bound) {
-            if (cnt < cap) {
-                out_h[cnt] = h;
-                std::memcpy(ok + cnt * W, r, (size_t)W * 8);
-            }
-            ++cnt;
-        }
+    LogEmit emit{bound, cap};
+    auto one = [&](int64_t h, const uint64_t* r) {
+        emit(h, [&](int64_t i) {
+            out_h[i] = h;
+            std::memcpy(ok + i * W, r, (size_t)W * 8);
+        });
     };
-    for (size_t i = 0; i < d->arch_h.size(); ++i) emit(d->arch_h[i], d->arch_k.data() + i * W);
-    for (size_t i = 0; i < lh.size(); ++i) emit(lh[i], lk.data() + i * W);
-    *out_n = cnt;
-    if (cnt > cap && cap > 0) {
-        set_error("rsv_export_log: cap is smaller than the number of candidates (*out_n)");
-        return RSV_E_ILLEGAL_ARGUMENT;
-    }
-    return RSV_OK;
+    for (size_t i = 0; i < d->arch_h.size(); ++i) one(d->arch_h[i], d->arch_k.data() + i * W);
+    for (size_t i = 0; i < lh.size(); ++i) one(lh[i], lk.data() + i * W);
+    return emit.finish(out_n);
 }
 
-int wide_log_merge(WideDistinct* d, const int64_t* h, const void* keys, int64_t n, int64_t seen, hipStream_t st) {
+int WideDistinct::log_merge(const int64_t* h, const void* keys, int64_t n, int64_t seen, hipStream_t st) {
+    WideDistinct* const d = this;
     if (!d->ordered) {
         set_error("rsv_merge_log needs an RSV_DISTINCT_ORDERED sampler");
         return RSV_E_UNSUPPORTED;
@@ -1873,7 +1857,7 @@ int wide_log_merge(WideDistinct* d, const int64_t* h, const void* keys, int64_t 
     d->log_n = 0;
     d->arch_h.clear();
     d->arch_k.clear();
-    if (hipError_t e = upload_replica(d, st)) return fail_hip(e, "rsv_merge_log");
+    if (hipError_t e = upload_replica(d, st)) return hip_status(e, "rsv_merge_log");
     d->tied = false;
     d->exact = true;
     d->merged = true;
