@@ -431,8 +431,8 @@ rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_de
  * handle per stream, and under an injective hash the reference's set.
  * rows_dev and out_rows_dev must be 8-byte aligned (RSV_E_ILLEGAL_ARGUMENT); rows_dev may be NULL
  * when every stream is empty.  Stateless and stream-ordered on hip_stream: no host wait, no
- * allocation.  All pointers are device pointers.  The resumed update / merge take 4- and 8-byte keys
- * only. */
+ * allocation.  All pointers are device pointers.  Resumed and combined:
+ * rsv_distinct_segmented_rows_update / rsv_distinct_segmented_rows_merge below. */
 rsv_status rsv_distinct_segmented_rows(const void* rows_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
                                        int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
                                        uint64_t seed, uint64_t stream_base, void* out_rows_dev,
@@ -476,6 +476,56 @@ rsv_status rsv_distinct_segmented_merge(const void* part_keys_dev, const int64_t
                                         const int64_t* part_counts_dev, int32_t parts, int64_t num_states,
                                         int32_t key_width, int32_t k, void* state_keys_dev, int64_t* state_hashes_dev,
                                         int64_t* state_counts_dev, void* hip_stream);
+
+/* Segmented distinct over byte keys, resumed: what rsv_distinct_segmented_update is for 4- and 8-byte
+ * keys.  The state is the caller's device memory in exactly the layout rsv_distinct_segmented_rows
+ * writes, so a stateless result is a valid state: state_rows_dev[num_states*k] rows of key_width bytes
+ * (8-byte aligned), state_hashes_dev[num_states*k] and state_counts_dev[num_states] (int64).  Row r
+ * holds counts[r] entries ascending by (h, words as unsigned 64-bit values, word 0 first), no row
+ * twice; a row with counts[r] == 0 is the empty sampler, whatever its slots hold.  A row fed a stream
+ * in pieces, in any number of launches, ends bit-identical to one rsv_distinct_segmented_rows launch
+ * over the concatenated stream (one element loop, one table of thread counts and buffer sizes per k,
+ * one set of k, key_width and hash_kind checks).
+ * Segment b = rows [offsets[b], offsets[b+1]) of rows_dev goes into row r = stream_ids_dev[b], or
+ * r = b when stream_ids_dev is NULL (then num_segments <= num_states).  Row r is seeded as
+ * java.util.Random(seed + stream_base + r); key widths, hash kinds (PRECOMPUTED with hashes_dev, or
+ * DEFAULT = UUID.hashCode at key_width 16) and k as rsv_distinct_segmented_rows; key_width 4 or 8 is
+ * RSV_E_UNSUPPORTED (use rsv_distinct_segmented_update).  Afterwards row r holds the bottom-k of (its
+ * previous rows u the segment's distinct rows), ascending.  The row block is rewritten in place, and
+ * only where it changes: a row that admitted nothing is not written at all, an entry that keeps its
+ * slot is not moved.  Rows and hashes beyond the new count are zero whenever the row was empty before
+ * or its count had to be clamped; a row that held entries keeps what it had there, which is zero in
+ * every state these entry points or rsv_distinct_segmented_rows wrote.
+ * The ids of one launch must be distinct (two segments on one row race: the caller's contract); a
+ * segment whose id lies outside [0, num_states) is skipped.  Rows that no segment names, and rows
+ * whose segment is empty, are not touched.  rows_dev and hashes_dev must not overlap the state (the
+ * caller's contract); rows_dev may be NULL when every segment is empty.  A row's count is clamped into
+ * [0, k] before use and nothing else read from the state addresses memory: rows that are not
+ * ascending, or that hold a row twice, give an unspecified set, never an out-of-range access.
+ * rows_dev and state_rows_dev must be 8-byte aligned (RSV_E_ILLEGAL_ARGUMENT); a NULL state pointer
+ * is RSV_E_NULL_POINTER; zero segments or states return RSV_OK with nothing launched.
+ * Stateless and stream-ordered on hip_stream: no host wait, no allocation.  All pointers are device
+ * pointers. */
+rsv_status rsv_distinct_segmented_rows_update(const void* rows_dev, const int64_t* hashes_dev,
+                                              const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                              int64_t num_segments, int64_t num_states, int32_t key_width, int32_t k,
+                                              int32_t hash_kind, uint64_t seed, uint64_t stream_base,
+                                              void* state_rows_dev, int64_t* state_hashes_dev,
+                                              int64_t* state_counts_dev, void* hip_stream);
+
+/* Combine of segmented distinct states over byte keys: part_* are `parts` states laid back to back
+ * ([parts][num_states][k] rows of key_width bytes and hashes, [parts][num_states] counts: what an
+ * all-gather of every rank's state tensors gives).  Row r becomes the bottom-k of (row r u the first
+ * clamp(part_counts[p][r], 0, k) entries of row r of every part p); equal rows are one element.  The
+ * parts' hashes are final (already scrambled): nothing is hashed again, so all parts and the state
+ * must come from the same seed, stream_base and hash (the caller's contract), and the parts must not
+ * overlap the state.  A row whose parts are all empty, or add nothing, is not touched.  part_rows_dev
+ * and state_rows_dev must be 8-byte aligned.  Checks (without a hash kind), in-place writes and
+ * stream order as the update. */
+rsv_status rsv_distinct_segmented_rows_merge(const void* part_rows_dev, const int64_t* part_hashes_dev,
+                                             const int64_t* part_counts_dev, int32_t parts, int64_t num_states,
+                                             int32_t key_width, int32_t k, void* state_rows_dev,
+                                             int64_t* state_hashes_dev, int64_t* state_counts_dev, void* hip_stream);
 
 /* Event replay (K1'): apply eviction events (1-based position, slot) -- the
  * `samples(rand.nextInt(k)) = map(element)` writes of S:243-246 -- for elements at global indices

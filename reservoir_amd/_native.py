@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "rsv_distinct_candidates", "rsv_candidates_read", "rsv_candidates_commit", "rsv_candidates_abort",
     "rsv_distinct_segmented", "rsv_distinct_segmented_update", "rsv_distinct_segmented_merge",
     "rsv_sample_segmented_update", "rsv_sample_segmented_merge", "rsv_distinct_segmented_rows",
+    "rsv_distinct_segmented_rows_update", "rsv_distinct_segmented_rows_merge",
 )
 
 
@@ -137,6 +138,8 @@ def load():
     L.rsv_distinct_segmented_rows.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_distinct_segmented_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_distinct_segmented_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
+    L.rsv_distinct_segmented_rows_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
+    L.rsv_distinct_segmented_rows_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
     L.rsv_replay_events.argtypes = [vp, i64, i32, i64, vp, vp, i64, i32, vp, vp]
     L.rsv_export_draws.argtypes = [u64, u64, u64, i64, vp, vp]
     L.rsv_profile_enable.argtypes = [vp, i32]
@@ -168,7 +171,8 @@ def load():
                  "rsv_commit_indexed", "rsv_distinct_candidates", "rsv_candidates_read",
                  "rsv_candidates_commit", "rsv_candidates_abort", "rsv_distinct_segmented",
                  "rsv_distinct_segmented_update", "rsv_distinct_segmented_merge",
-                 "rsv_sample_segmented_update", "rsv_sample_segmented_merge", "rsv_distinct_segmented_rows"):
+                 "rsv_sample_segmented_update", "rsv_sample_segmented_merge", "rsv_distinct_segmented_rows",
+                 "rsv_distinct_segmented_rows_update", "rsv_distinct_segmented_rows_merge"):
         getattr(L, name).restype = i32
     if L.rsv_abi_version() != 1:
         raise ImportError("libreservoir_hip.so ABI version mismatch")

@@ -8,6 +8,7 @@ libreservoir_hip.so.  Every function raises if the engine is unavailable.
     distinct_segmented_rows -- K5 over fixed-width byte keys (UUIDs): rows in, the winning rows out
     SegmentedDistinct -- K5 resumed: the same S streams as caller-held state, advanced by one launch
                          per micro-batch (update) and combined across launches, GPUs and ranks (merge)
+    SegmentedDistinctRows -- K5 resumed over byte keys: the rows move inside the caller-held state (update, merge)
     SegmentedSampler  -- K2 resumed: S Sampler.apply streams as caller-held state (keys, idx, next), fed in
                          pieces from any start index (update) and combined per slot by largest index (merge)
     replay_events     -- K1': apply the reference's Algorithm-L eviction events on the GPU
@@ -133,6 +134,24 @@ def distinct_segmented(keys, offsets, k: int, seed: int, stream_base: int = 0, h
     return out, out_h, counts
 
 
+def _segd_rows_inputs(torch, rows, offsets, hash, hashes):
+    """rows / offsets / hashes of a K5 call over byte keys, checked and contiguous."""
+    if not (rows.is_cuda and offsets.is_cuda):
+        raise N.IllegalArgumentException("rows and offsets must be device tensors")
+    if rows.dim() != 2 or offsets.dtype != torch.int64:
+        raise N.IllegalArgumentException("rows must be 2-D (one key per row) and offsets int64")
+    if hashes is None and hash == "precomputed":
+        raise N.NullPointerException("hash='precomputed' needs hashes=")
+    if hashes is None and hash != "default":
+        raise N.IllegalArgumentException(f"unknown hash {hash!r}")
+    if hashes is not None:
+        if not hashes.is_cuda or hashes.dtype != torch.int64 or hashes.numel() != rows.shape[0]:
+            raise N.IllegalArgumentException("hashes must be an int64 device tensor, one per row")
+        # an empty tensor has no address; the engine wants one for precomputed hashes
+        hashes = hashes.contiguous() if hashes.numel() else torch.empty(1, dtype=torch.int64, device=rows.device)
+    return rows.contiguous(), offsets.contiguous(), hashes
+
+
 def distinct_segmented_rows(rows, offsets, k: int, seed: int, stream_base: int = 0, hash: str = "default", hashes=None):
     """distinct_segmented over fixed-width byte keys (java.util.UUID, case classes of primitives).
 
@@ -149,20 +168,7 @@ def distinct_segmented_rows(rows, offsets, k: int, seed: int, stream_base: int =
     import torch
 
     L = N.load()
-    if not (rows.is_cuda and offsets.is_cuda):
-        raise N.IllegalArgumentException("rows and offsets must be device tensors")
-    if rows.dim() != 2 or offsets.dtype != torch.int64:
-        raise N.IllegalArgumentException("rows must be 2-D (one key per row) and offsets int64")
-    if hashes is None and hash == "precomputed":
-        raise N.NullPointerException("hash='precomputed' needs hashes=")
-    if hashes is None and hash != "default":
-        raise N.IllegalArgumentException(f"unknown hash {hash!r}")
-    if hashes is not None:
-        if not hashes.is_cuda or hashes.dtype != torch.int64 or hashes.numel() != rows.shape[0]:
-            raise N.IllegalArgumentException("hashes must be an int64 device tensor, one per row")
-        # an empty tensor has no address; the engine wants one for precomputed hashes
-        hashes = hashes.contiguous() if hashes.numel() else torch.empty(1, dtype=torch.int64, device=rows.device)
-    rows, offsets = rows.contiguous(), offsets.contiguous()
+    rows, offsets, hashes = _segd_rows_inputs(torch, rows, offsets, hash, hashes)
     W = rows.shape[1] * rows.element_size()
     S = offsets.numel() - 1
     # the kernel writes every row block (zeros beyond the count) and every count: no zero-fill
@@ -293,6 +299,133 @@ class SegmentedDistinct:
         N.check(L.rsv_distinct_segmented_merge(
             C.c_void_p(part_keys.data_ptr()), C.c_void_p(part_hashes.data_ptr()), C.c_void_p(part_counts.data_ptr()),
             P, S, part_keys.element_size(), k, C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.hashes.data_ptr()),
+            C.c_void_p(self.counts.data_ptr()), _stream_ptr(torch, dev)))
+        return self
+
+
+class SegmentedDistinctRows:
+    """SegmentedDistinct over fixed-width byte keys (java.util.UUID, case classes of primitives).
+
+    The state is three device tensors in distinct_segmented_rows' layout: rows uint8 (S, k, width),
+    hashes int64 (S, k), counts int64 (S,); row s holds counts[s] entries ascending by (scrambled
+    hash, row as little-endian unsigned 64-bit words) and is seeded like a single
+    Sampler.distinct(k, key_type="bytesW", seed=seed + stream_base + s, order="set").  Fed a stream in
+    any number of update() calls, a row ends bit-identical to distinct_segmented_rows over the whole
+    stream.  Only the counts are zero-filled: a row with count 0 is empty whatever its slots hold, and
+    the update that first writes a row zeroes it beyond its count.  width: a multiple of 8 in 16..256.
+    hash="default" is UUID.hashCode (width 16 only); hash="precomputed": update(hashes=...).
+    Everything runs on torch's current stream.
+    """
+
+    def __init__(self, num_streams: int, k: int, width: int, seed: int, stream_base: int = 0, hash: str = "default",
+                 device=None):
+        import torch
+
+        N.load()
+        if hash not in ("default", "precomputed"):
+            raise N.IllegalArgumentException(f"unknown hash {hash!r}")
+        if num_streams < 0:
+            raise N.IllegalArgumentException("negative stream count")
+        if k <= 0:
+            raise N.IllegalArgumentException("k out of range")
+        if k > _SEG_DISTINCT_MAX_K:
+            raise N.ReservoirError(
+                f"SegmentedDistinctRows holds k <= {_SEG_DISTINCT_MAX_K} per stream; use separate handles beyond")
+        if width in (4, 8):
+            raise N.ReservoirError("SegmentedDistinctRows takes byte keys; SegmentedDistinct takes 4- and 8-byte keys")
+        if width < 16 or width > 256 or width % 8:
+            raise N.IllegalArgumentException("width must be a multiple of 8 in 16..256")
+        if hash == "default" and width != 16:
+            raise N.ReservoirError("hash='default' is UUID.hashCode: width 16 only")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise N.IllegalArgumentException("the state lives on the device")
+        self.num_streams, self.k, self.width = int(num_streams), int(k), int(width)
+        self.seed, self.stream_base = seed & (2**64 - 1), stream_base & (2**64 - 1)
+        self._hash = hash
+        self.rows = torch.empty((self.num_streams, self.k, self.width), dtype=torch.uint8, device=dev)
+        self.hashes = torch.empty((self.num_streams, self.k), dtype=torch.int64, device=dev)
+        self.counts = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
+
+    def update(self, rows, offsets, stream_ids=None, hashes=None, check_ids: bool = True):
+        """Segment b = rows[offsets[b]:offsets[b+1]] into row stream_ids[b] (None: row b).
+
+        rows: uint8 (n, width) or int64 (n, width / 8), as distinct_segmented_rows takes them; they must
+        not overlap the state.  stream_ids and check_ids as SegmentedDistinct.update.  Rows that no
+        segment names, or whose segment is empty, are not touched.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        if hashes is not None and self._hash != "precomputed":
+            raise N.IllegalArgumentException("hashes= needs hash='precomputed'")
+        rows, offsets, hashes = _segd_rows_inputs(torch, rows, offsets, self._hash, hashes)
+        if rows.shape[1] * rows.element_size() != self.width:
+            raise N.IllegalArgumentException(f"rows must hold {self.width} bytes each")
+        if rows.device != self.rows.device or offsets.device != self.rows.device:
+            raise N.IllegalArgumentException("rows and offsets must live on the state's device")
+        B = offsets.numel() - 1
+        if B <= 0:
+            return self
+        if stream_ids is not None:
+            if not stream_ids.is_cuda or stream_ids.dtype != torch.int64 or stream_ids.numel() != B:
+                raise N.IllegalArgumentException("stream_ids must be an int64 device tensor, one per segment")
+            stream_ids = stream_ids.contiguous()
+            if check_ids:
+                _check_stream_ids(torch, stream_ids, self.num_streams)
+        N.check(L.rsv_distinct_segmented_rows_update(
+            C.c_void_p(rows.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
+            C.c_void_p(offsets.data_ptr()), C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
+            B, self.num_streams, self.width, self.k, N.HASH_PRECOMPUTED if hashes is not None else N.HASH_DEFAULT,
+            self.seed, self.stream_base, C.c_void_p(self.rows.data_ptr()), C.c_void_p(self.hashes.data_ptr()),
+            C.c_void_p(self.counts.data_ptr()), _stream_ptr(torch, self.rows.device)))
+        return self
+
+    def merge(self, part_rows, part_hashes=None, part_counts=None):
+        """Row s becomes the bottom-k of (row s u row s of every part).
+
+        merge(part_rows, part_hashes, part_counts): tensors (P, S, k, width), (P, S, k), (P, S) -- or
+        (S, k, width), (S, k), (S,) for one part -- e.g. an all-gather of every rank's state tensors;
+        or merge(other, ...) with SegmentedDistinctRows objects.  All parts must come from this
+        state's seed, stream_base and hash: their hashes are taken as stored.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        if isinstance(part_rows, SegmentedDistinctRows):
+            others = [part_rows] + [o for o in (part_hashes, part_counts) if o is not None]
+            mine = (self.num_streams, self.k, self.width, self.seed, self.stream_base, self._hash)
+            for o in others:
+                if not isinstance(o, SegmentedDistinctRows) or (
+                        o.num_streams, o.k, o.width, o.seed, o.stream_base, o._hash) != mine:
+                    raise N.IllegalArgumentException(
+                        "merge needs states of the same shape, width, seed, stream_base and hash")
+            if len(others) == 1:
+                part_rows, part_hashes, part_counts = others[0].rows, others[0].hashes, others[0].counts
+            else:
+                part_rows = torch.stack([o.rows for o in others])
+                part_hashes = torch.stack([o.hashes for o in others])
+                part_counts = torch.stack([o.counts for o in others])
+        if part_hashes is None or part_counts is None:
+            raise N.NullPointerException("merge needs part_rows, part_hashes and part_counts")
+        S, k, W = self.num_streams, self.k, self.width
+        if part_rows.dim() == 3:
+            part_rows, part_hashes, part_counts = part_rows[None], part_hashes[None], part_counts[None]
+        P = part_rows.shape[0]
+        if part_rows.dtype != torch.uint8 or part_hashes.dtype != torch.int64 or part_counts.dtype != torch.int64:
+            raise N.IllegalArgumentException("part rows must be uint8, hashes and counts int64")
+        if (tuple(part_rows.shape) != (P, S, k, W) or tuple(part_hashes.shape) != (P, S, k)
+                or tuple(part_counts.shape) != (P, S)):
+            raise N.IllegalArgumentException(f"parts must be shaped (P, {S}, {k}, {W}), (P, {S}, {k}), (P, {S})")
+        dev = self.rows.device
+        if part_rows.device != dev or part_hashes.device != dev or part_counts.device != dev:
+            raise N.IllegalArgumentException("parts must live on the state's device")
+        if P == 0 or S == 0:
+            return self
+        part_rows, part_hashes, part_counts = part_rows.contiguous(), part_hashes.contiguous(), part_counts.contiguous()
+        N.check(L.rsv_distinct_segmented_rows_merge(
+            C.c_void_p(part_rows.data_ptr()), C.c_void_p(part_hashes.data_ptr()), C.c_void_p(part_counts.data_ptr()),
+            P, S, W, k, C.c_void_p(self.rows.data_ptr()), C.c_void_p(self.hashes.data_ptr()),
             C.c_void_p(self.counts.data_ptr()), _stream_ptr(torch, dev)))
         return self
 

@@ -181,6 +181,17 @@ hipError_t launch_segdistinct_update(const void* keys, int key_width, const int6
 hipError_t launch_segdistinct_merge(const void* part_keys, int key_width, const int64_t* part_hashes,
                                     const int64_t* part_counts, int32_t parts, int64_t num_states, uint32_t k,
                                     void* state_keys, int64_t* state_hashes, int64_t* state_counts, hipStream_t st);
+// K5 resumed over byte keys (rsv_segdistinct.hip): the state is rows[num_states*k] of key_width bytes, hashes,
+// counts, as launch_segdistinct_rows writes them, moved in place.  rows / part_rows ([parts][num_states][k] rows)
+// and state_rows 8-byte aligned, and no input may alias the state.  hashes as for launch_segdistinct_rows.
+hipError_t launch_segdistinct_rows_update(const void* rows, int key_width, const int64_t* hashes, const int64_t* offsets,
+                                          const int64_t* stream_ids, int64_t num_segments, int64_t num_states,
+                                          uint32_t k, uint64_t seed0, void* state_rows, int64_t* state_hashes,
+                                          int64_t* state_counts, hipStream_t st);
+hipError_t launch_segdistinct_rows_merge(const void* part_rows, int key_width, const int64_t* part_hashes,
+                                         const int64_t* part_counts, int32_t parts, int64_t num_states, uint32_t k,
+                                         void* state_rows, int64_t* state_hashes, int64_t* state_counts,
+                                         hipStream_t st);
 // merge of exported element states: per slot max index among parts (and current state)
 hipError_t launch_merge_slots(const int64_t* idx_parts, const void* key_parts, int key_width,
                               int32_t parts, int64_t part_len, uint32_t k, int64_t* slot_idx,

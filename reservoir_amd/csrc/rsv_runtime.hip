@@ -1703,25 +1703,38 @@ rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_de
     return RSV_OK;
 }
 
-rsv_status rsv_distinct_segmented_rows(const void* rows_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
-                                       int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
-                                       uint64_t seed, uint64_t stream_base, void* out_rows_dev,
-                                       int64_t* out_hashes_dev, int64_t* counts_dev, void* hip_stream) {
-    // the checks in rsv_distinct_segmented's order: k, key_width, hash_kind, num_streams, pointers
+// k and key_width of the three K5 entry points over byte keys (fn: the entry point's name, long_fn: its
+// counterpart for 4- and 8-byte keys, for the messages)
+static rsv_status check_segrows_shape(const char* fn, const char* long_fn, int32_t k, int32_t key_width) {
     if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
     if (k > (int32_t)kSegDistinctMaxK)
-        return fail(RSV_E_UNSUPPORTED, "rsv_distinct_segmented_rows holds k <= " + std::to_string(kSegDistinctMaxK) +
+        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " holds k <= " + std::to_string(kSegDistinctMaxK) +
                                            " per stream; use separate handles beyond");
     if (key_width == 4 || key_width == 8)
-        return fail(RSV_E_UNSUPPORTED, "rsv_distinct_segmented_rows takes byte keys; rsv_distinct_segmented takes 4- and 8-byte keys");
+        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " takes byte keys; " + long_fn + " takes 4- and 8-byte keys");
     if (key_width < 16 || key_width > 256 || key_width % 8 != 0)
         return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be a multiple of 8 in 16..256");
+    return RSV_OK;
+}
+
+// the hash kind of the two that hash: PRECOMPUTED, or DEFAULT (UUID.hashCode) at key_width 16
+static rsv_status check_segrows_hash(int32_t hash_kind, int32_t key_width) {
     if (hash_kind < RSV_HASH_DEFAULT || hash_kind > RSV_HASH_PRECOMPUTED)
         return fail(RSV_E_ILLEGAL_ARGUMENT, "unknown hash kind");
     if (hash_kind != RSV_HASH_DEFAULT && hash_kind != RSV_HASH_PRECOMPUTED)
         return fail(RSV_E_UNSUPPORTED, "byte keys take RSV_HASH_PRECOMPUTED, or RSV_HASH_DEFAULT (UUID.hashCode) at key_width 16");
     if (hash_kind == RSV_HASH_DEFAULT && key_width != 16)
         return fail(RSV_E_UNSUPPORTED, "RSV_HASH_DEFAULT is UUID.hashCode: key_width 16 only");
+    return RSV_OK;
+}
+
+rsv_status rsv_distinct_segmented_rows(const void* rows_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
+                                       int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
+                                       uint64_t seed, uint64_t stream_base, void* out_rows_dev,
+                                       int64_t* out_hashes_dev, int64_t* counts_dev, void* hip_stream) {
+    // the checks in rsv_distinct_segmented's order: k, key_width, hash_kind, num_streams, pointers
+    if (rsv_status st = check_segrows_shape("rsv_distinct_segmented_rows", "rsv_distinct_segmented", k, key_width)) return st;
+    if (rsv_status st = check_segrows_hash(hash_kind, key_width)) return st;
     if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
     if (num_streams == 0) return RSV_OK;
     // rows_dev is not checked: a launch whose streams are all empty has no rows
@@ -1772,6 +1785,53 @@ rsv_status rsv_distinct_segmented_merge(const void* part_keys_dev, const int64_t
     RSV_HIP_TRY(launch_segdistinct_merge(part_keys_dev, key_width, part_hashes_dev, part_counts_dev, parts, num_states,
                                          (uint32_t)k, state_keys_dev, state_hashes_dev, state_counts_dev,
                                          (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
+rsv_status rsv_distinct_segmented_rows_update(const void* rows_dev, const int64_t* hashes_dev,
+                                              const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                              int64_t num_segments, int64_t num_states, int32_t key_width, int32_t k,
+                                              int32_t hash_kind, uint64_t seed, uint64_t stream_base,
+                                              void* state_rows_dev, int64_t* state_hashes_dev,
+                                              int64_t* state_counts_dev, void* hip_stream) {
+    if (rsv_status st = check_segrows_shape("rsv_distinct_segmented_rows_update", "rsv_distinct_segmented_update", k, key_width))
+        return st;
+    if (rsv_status st = check_segrows_hash(hash_kind, key_width)) return st;
+    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
+    if (!stream_ids_dev && num_segments > num_states)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
+    if (num_segments == 0 || num_states == 0) return RSV_OK;
+    // rows_dev is not checked: a launch whose segments are all empty has no rows
+    if (!offsets_dev || !state_rows_dev || !state_hashes_dev || !state_counts_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (hash_kind == RSV_HASH_PRECOMPUTED && !hashes_dev)
+        return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
+    if (((uintptr_t)rows_dev | (uintptr_t)state_rows_dev) & 7)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "rows_dev and state_rows_dev must be 8-byte aligned");
+    RSV_HIP_TRY(launch_segdistinct_rows_update(rows_dev, key_width,
+                                               hash_kind == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr, offsets_dev,
+                                               stream_ids_dev, num_segments, num_states, (uint32_t)k,
+                                               seed + stream_base, state_rows_dev, state_hashes_dev, state_counts_dev,
+                                               (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
+rsv_status rsv_distinct_segmented_rows_merge(const void* part_rows_dev, const int64_t* part_hashes_dev,
+                                             const int64_t* part_counts_dev, int32_t parts, int64_t num_states,
+                                             int32_t key_width, int32_t k, void* state_rows_dev,
+                                             int64_t* state_hashes_dev, int64_t* state_counts_dev, void* hip_stream) {
+    if (rsv_status st = check_segrows_shape("rsv_distinct_segmented_rows_merge", "rsv_distinct_segmented_merge", k, key_width))
+        return st;
+    if (parts < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative part or state count");
+    if (parts == 0 || num_states == 0) return RSV_OK;
+    if (!part_rows_dev || !part_hashes_dev || !part_counts_dev || !state_rows_dev || !state_hashes_dev ||
+        !state_counts_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (((uintptr_t)part_rows_dev | (uintptr_t)state_rows_dev) & 7)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "part_rows_dev and state_rows_dev must be 8-byte aligned");
+    RSV_HIP_TRY(launch_segdistinct_rows_merge(part_rows_dev, key_width, part_hashes_dev, part_counts_dev, parts,
+                                              num_states, (uint32_t)k, state_rows_dev, state_hashes_dev,
+                                              state_counts_dev, (hipStream_t)hip_stream));
     return RSV_OK;
 }
 

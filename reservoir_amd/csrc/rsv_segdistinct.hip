@@ -60,6 +60,12 @@
 // sets T), so admission reads a row only on the lanes with h == T.h.  Hashes are precomputed (8 bytes
 // per element; the rows are read on ties and for the output only) or UUID.hashCode of 16-byte rows
 // (one 16-byte load per element, two 8-byte loads when rows_dev sits at 8 mod 16).
+//
+// Byte keys resumed (rsv_distinct_segmented_rows_update / _merge; segrowstate_kernel): the state is
+// rows[num_states][k][W8], hashes and counts as the stateless launch writes them.  An entry's second
+// word is then a ref to one of two row sources, the launch's input or a slot of the row's own state
+// block (RowSrc<true>), the prologue also loads T's row from the block, and the epilogue moves the rows
+// in place from the top down (the comment at the kernel).
 #include <algorithm>
 #include <type_traits>
 
@@ -150,21 +156,51 @@ struct Keys : KeyOrd {
     }
 };
 
-// Byte keys: the index of a row of W8 words in `rows`; -1 is the pad's.
-struct RowOrd {
+// Byte keys: where an entry's second word (its ref) finds its row of W8 words.  One source, the stateless
+// launch: the ref is the row's index into `rows`.  Two sources, the resumed launches: a ref below 2^62 is
+// an index into the launch's input (rows_dev, or the parts), a ref with kStateRef set is slot
+// ref & (kStateRef - 1) of the block `srow` of the state row the team works on, clamped below k before it
+// addresses anything.  Both kinds are >= 0, so the pad's -1 stays what it is.  at() is the only place
+// that turns a ref into an address.
+constexpr int64_t kStateRef = 1LL << 62;
+
+template <bool TWO>
+struct RowSrc;
+template <>
+struct RowSrc<false> {
     const uint64_t* __restrict__ rows;
     uint32_t W8;
+    __device__ __forceinline__ const uint64_t* at(int64_t ref) const { return rows + ref * (int64_t)W8; }
+};
+template <>
+struct RowSrc<true> {
+    const uint64_t* rows;  // not __restrict__: the state is read and written through other pointers
+    uint32_t W8;
+    const uint64_t* srow;
+    uint32_t k;
+    __device__ __forceinline__ const uint64_t* at(int64_t ref) const {
+        if (ref & kStateRef) {
+            const uint64_t j = (uint64_t)(ref & (kStateRef - 1));
+            return srow + (j < k ? (uint32_t)j : k - 1) * W8;
+        }
+        return rows + ref * (int64_t)W8;
+    }
+};
+
+// -1 is the pad's ref.
+template <bool TWO>
+struct RowOrd : RowSrc<TWO> {
     static __device__ __forceinline__ Ent pad() { return Ent{kMaxI64, -1}; }
-    // <0, 0, >0.  The only place that turns an entry's index into an address of two rows: equal indices
-    // (two pads among them) and the pad are settled before it.
+    // <0, 0, >0.  Equal refs (two pads among them) and the pad are settled before a row is addressed.
+    // Two refs to equal rows, whichever their sources, compare equal: they are one element.
     __device__ __forceinline__ int cmp(const Ent& a, const Ent& b) const {
         if (a.h != b.h) return a.h < b.h ? -1 : 1;
         if (a.key == b.key) return 0;
         if (a.key < 0) return 1;
         if (b.key < 0) return -1;
-        const uint64_t* const ra = rows + a.key * (int64_t)W8;
-        const uint64_t* const rb = rows + b.key * (int64_t)W8;
-        for (uint32_t w = 0; w < W8; ++w) {
+        const uint64_t* const ra = this->at(a.key);
+        const uint64_t* const rb = this->at(b.key);
+        for (uint32_t w = 0; w < this->W8; ++w) {
             const uint64_t x = ra[w], y = rb[w];
             if (x != y) return x < y ? -1 : 1;
         }
@@ -177,7 +213,10 @@ struct RowOrd {
     __device__ __forceinline__ bool same(const Ent& a, const Ent& b) const { return cmp(a, b) == 0; }
 };
 
-struct Rows : RowOrd {
+// The element loop's side: element i is row i of the input (`rows`), whichever sources the refs have.
+// SCRAMBLE as for Keys: otherwise h = hashes[i] as stored (the parts of a merge).
+template <bool TWO, bool SCRAMBLE>
+struct Rows : RowOrd<TWO> {
     const int64_t* __restrict__ hashes;  // null: UUID.hashCode of the 16-byte row
     bool vec16;                          // rows is 16-byte aligned: a UUID is one 16-byte load
     int64_t r0, r1;
@@ -187,19 +226,24 @@ struct Rows : RowOrd {
         if (hashes) {
             hv = hashes[i];
         } else if (vec16) {
-            const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(rows + 2 * i);
+            const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(this->rows + 2 * i);
             hv = uuid_hash_code(v.x, v.y);
         } else {
-            hv = uuid_hash_code(rows[2 * i], rows[2 * i + 1]);
+            hv = uuid_hash_code(this->rows[2 * i], this->rows[2 * i + 1]);
         }
     }
-    __device__ __forceinline__ int64_t h_of(int64_t, int64_t hv) const { return scramble(r0, r1, hv); }
+    __device__ __forceinline__ int64_t h_of(int64_t, int64_t hv) const {
+        if constexpr (SCRAMBLE)
+            return scramble(r0, r1, hv);
+        else
+            return hv;
+    }
     // (h, row i) <= T; below k entries T is the pad, above every row
     __device__ __forceinline__ bool admits(int64_t h, int64_t i, const Team& t) const {
         if (h != t.Th) return h < t.Th;
         if (t.Tk < 0 || i == t.Tk) return true;
-        const uint64_t* const r = rows + i * (int64_t)W8;
-        for (uint32_t w = 0; w < W8; ++w) {
+        const uint64_t* const r = this->at(i);
+        for (uint32_t w = 0; w < this->W8; ++w) {
             const uint64_t x = r[w], y = s_trow[w];
             if (x != y) return x < y;
         }
@@ -209,7 +253,7 @@ struct Rows : RowOrd {
     __device__ __forceinline__ void set_T(const Ent* se, uint32_t k, Team& t) const {
         t.Th = se[k - 1].h;
         t.Tk = se[k - 1].key;
-        if (threadIdx.x < W8) s_trow[threadIdx.x] = rows[t.Tk * (int64_t)W8 + threadIdx.x];
+        if (threadIdx.x < this->W8) s_trow[threadIdx.x] = this->at(t.Tk)[threadIdx.x];
     }
 };
 
@@ -390,8 +434,8 @@ __global__ __launch_bounds__(NT) void segrows_kernel(const uint64_t* __restrict_
         if (tid == 0) s_cnt = 0;
         __syncthreads();
         Team t{0, 0, kMaxI64, -1, false};
-        const Rows src{{rows, W8}, hashes, vec16, r0, r1, s_trow};
-        take_piece<Rows, NT>(se, &s_cnt, s_scan, src, offsets[s], offsets[s + 1], k, P, t);
+        const Rows<false, true> src{{{rows, W8}}, hashes, vec16, r0, r1, s_trow};
+        take_piece<Rows<false, true>, NT>(se, &s_cnt, s_scan, src, offsets[s], offsets[s + 1], k, P, t);
         if (t.n_tot != t.m) t.m = merge_set<NT>(se, t.n_tot, k, s_scan, src);
         __syncthreads();
         const int64_t ob = s * (int64_t)k;
@@ -461,6 +505,121 @@ __global__ __launch_bounds__(NT) void segstate_kernel(const KeyT* in_keys, const
         }
         if (!t.dirty) continue;  // nothing admitted: the row stands as it is
         finish_row<KeyT, NT, false>(se, s_scan, t, k, r, state_keys, state_hashes, state_counts);
+    }
+}
+
+// Byte keys, resumed: segstate_kernel for rows, MERGE as there (in = rows_dev / hashes / offsets, or the
+// parts' rows [parts][num_states][k][W8] and hashes).  A state entry enters LDS as (h, kStateRef | slot),
+// so nothing of the row block is read but what a tie on h or T asks for.
+// The epilogue moves rows inside the block they are read from.  In a valid state the surviving state
+// entries keep their order and inputs are only inserted between them, so the entry of slot j ends at a
+// position p >= j and the word it moves goes from j * W8 + w up to p * W8 + w: a destination word x is
+// read from a word <= x of the block, or from the input.  The words are therefore walked in chunks from
+// the top down; per chunk every lane loads its kMoveWords sources, the team meets at a barrier, then it
+// stores.  A chunk [lo, hi) reads below hi only and every earlier chunk wrote at or above hi, so
+// nothing is read after it was overwritten.  An entry that stays at its slot moves no word and no hash,
+// and a state that is not ascending or repeats a row breaks p >= j only: its set is unspecified, its
+// addresses are the same.  Rows and hashes in [m, k) are zeroed where they are not the kernel's own
+// zeros already: the row was empty (its slots are the caller's), its count was clamped, or the set
+// shrank (an invalid state).
+constexpr uint32_t kMoveWords = 4;
+
+template <int NT, bool MERGE>
+__global__ __launch_bounds__(NT) void segrowstate_kernel(const uint64_t* in_rows, const int64_t* in_hashes,
+                                                         const int64_t* __restrict__ offsets,
+                                                         const int64_t* __restrict__ ids, const int64_t* part_counts,
+                                                         int64_t teams, int64_t num_states, int32_t parts, uint32_t W8,
+                                                         uint32_t k, uint32_t P, uint64_t seed0, uint64_t* state_rows,
+                                                         int64_t* state_hashes, int64_t* state_counts) {
+    extern __shared__ __align__(16) unsigned char seg_lds[];
+    Ent* const se = (Ent*)seg_lds;
+    __shared__ uint32_t s_cnt;
+    __shared__ uint32_t s_scan[NT / 64 > 1 ? NT / 64 : 1];
+    __shared__ uint64_t s_trow[32];  // kMaxRowWords
+    const uint32_t tid = threadIdx.x;
+    const bool vec16 = ((uintptr_t)in_rows & 15) == 0;
+
+    for (int64_t b = blockIdx.x; b < teams; b += gridDim.x) {
+        // everything that decides the control flow below is uniform over the team
+        int64_t r = b, lo = 0, hi = 0;
+        if constexpr (!MERGE) {
+            if (ids) r = ids[b];
+            if (r < 0 || r >= num_states) continue;  // an id outside the state: no row is addressed
+            lo = offsets[b];
+            hi = offsets[b + 1];
+            if (hi <= lo) continue;  // an empty segment leaves its row as it is
+        }
+        const int64_t ob = r * (int64_t)k;
+        uint64_t* const srow = state_rows + ob * (int64_t)W8;
+        const int64_t c0 = state_counts[r];
+        const uint32_t m0 = c0 <= 0 ? 0u : (c0 >= (int64_t)k ? k : (uint32_t)c0);
+        __syncthreads();  // the previous row's output reads are done
+        for (uint32_t i = tid; i < m0; i += NT) se[i] = Ent{state_hashes[ob + i], kStateRef | (int64_t)i};
+        // a full row's T and T's row, before the first admission test
+        if (m0 == k && tid < W8) s_trow[tid] = srow[(k - 1) * W8 + tid];
+        if (tid == 0) s_cnt = m0;
+        __syncthreads();
+        Team t{m0, m0, kMaxI64, -1, false};
+        if (m0 == k) {
+            t.Th = se[k - 1].h;
+            t.Tk = kStateRef | (int64_t)(k - 1);
+        }
+        int64_t r0 = 0, r1 = 0;
+        if constexpr (!MERGE) java_r0r1(seed0 + (uint64_t)r, r0, r1);
+        const Rows<true, !MERGE> src{{{in_rows, W8, srow, k}}, in_hashes, vec16, r0, r1, s_trow};
+        if constexpr (MERGE) {
+            for (int32_t p = 0; p < parts; ++p) {
+                const int64_t row = (int64_t)p * num_states + r;
+                const int64_t pc = part_counts[row];
+                const int64_t n = pc <= 0 ? 0 : (pc >= (int64_t)k ? (int64_t)k : pc);
+                const int64_t pb = row * (int64_t)k;
+                take_piece<Rows<true, false>, NT>(se, &s_cnt, s_scan, src, pb, pb + n, k, P, t);
+            }
+        } else {
+            take_piece<Rows<true, true>, NT>(se, &s_cnt, s_scan, src, lo, hi, k, P, t);
+        }
+        if (!t.dirty) continue;  // nothing admitted: the row stands as it is
+        if (t.n_tot != t.m) t.m = merge_set<NT>(se, t.n_tot, k, s_scan, src);
+        __syncthreads();
+        const uint32_t m = t.m;
+        // an empty row holds no state ref: its chunks have nothing to wait for
+        const bool staged = m0 != 0;
+        for (uint32_t top = m * W8; top > 0;) {  // m * W8 <= 4096 * 32
+            const uint32_t bot = top > NT * kMoveWords ? top - NT * kMoveWords : 0;
+            uint64_t v[kMoveWords];
+            bool mv[kMoveWords];
+#pragma unroll
+            for (uint32_t u = 0; u < kMoveWords; ++u) {
+                const uint32_t x = bot + u * NT + tid;
+                mv[u] = false;
+                v[u] = 0;
+                if (x < top) {
+                    const uint32_t j = x / W8, w = x - j * W8;
+                    const int64_t ref = se[j].key;
+                    mv[u] = ref != (kStateRef | (int64_t)j);
+                    if (mv[u]) v[u] = src.at(ref)[w];
+                }
+            }
+            if (staged) {
+                // the loads have returned before any lane of the team stores
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < kMoveWords; ++u)
+                if (mv[u]) srow[bot + u * NT + tid] = v[u];
+            top = bot;
+        }
+        for (uint32_t i = tid; i < m; i += NT) {
+            const Ent e = se[i];
+            if (e.key != (kStateRef | (int64_t)i)) state_hashes[ob + i] = e.h;
+        }
+        if (m0 == 0 || c0 != (int64_t)m0 || m < m0) {
+            __syncthreads();  // an invalid state may have read above m
+            for (uint32_t x = m * W8 + tid; x < k * W8; x += NT) srow[x] = 0;
+            for (uint32_t i = m + tid; i < k; i += NT) state_hashes[ob + i] = 0;
+        }
+        if (tid == 0) state_counts[r] = m;
     }
 }
 
@@ -545,6 +704,35 @@ hipError_t launch_segdistinct_merge(const void* part_keys, int key_width, const 
                             num_states, parts, k, P, (int)kHashPrecomputed, (uint64_t)0, (KeyT*)state_keys, state_hashes,
                             state_counts);
     });
+}
+
+hipError_t launch_segdistinct_rows_update(const void* rows, int key_width, const int64_t* hashes, const int64_t* offsets,
+                                          const int64_t* stream_ids, int64_t num_segments, int64_t num_states,
+                                          uint32_t k, uint64_t seed0, void* state_rows, int64_t* state_hashes,
+                                          int64_t* state_counts, hipStream_t st) {
+    if (num_segments <= 0 || num_states <= 0) return hipSuccess;
+    auto f = [&](int64_t, auto nt, uint32_t P) {
+        constexpr int NT = decltype(nt)::value;
+        return launch_teams(segrowstate_kernel<NT, false>, NT, num_segments, P, st, (const uint64_t*)rows, hashes,
+                            offsets, stream_ids, (const int64_t*)nullptr, num_segments, num_states, (int32_t)0,
+                            (uint32_t)key_width / 8, k, P, seed0, (uint64_t*)state_rows, state_hashes, state_counts);
+    };
+    return with_form_of<int64_t>(k, f);
+}
+
+hipError_t launch_segdistinct_rows_merge(const void* part_rows, int key_width, const int64_t* part_hashes,
+                                         const int64_t* part_counts, int32_t parts, int64_t num_states, uint32_t k,
+                                         void* state_rows, int64_t* state_hashes, int64_t* state_counts,
+                                         hipStream_t st) {
+    if (parts <= 0 || num_states <= 0) return hipSuccess;
+    auto f = [&](int64_t, auto nt, uint32_t P) {
+        constexpr int NT = decltype(nt)::value;
+        return launch_teams(segrowstate_kernel<NT, true>, NT, num_states, P, st, (const uint64_t*)part_rows,
+                            part_hashes, (const int64_t*)nullptr, (const int64_t*)nullptr, part_counts, num_states,
+                            num_states, parts, (uint32_t)key_width / 8, k, P, (uint64_t)0, (uint64_t*)state_rows,
+                            state_hashes, state_counts);
+    };
+    return with_form_of<int64_t>(k, f);
 }
 
 }  // namespace rsv
