@@ -392,6 +392,46 @@ rsv_status rsv_sample_segmented_merge(const void* part_keys_dev, const int64_t* 
                                       int32_t key_width, int32_t k, void* state_keys_dev, int64_t* state_idx_dev,
                                       int64_t* state_next_dev, void* hip_stream);
 
+/* Segmented sampling over fixed-width byte keys (java.util.UUID, case classes of primitives): as
+ * rsv_sample_segmented, the elements being rows of key_width bytes -- a multiple of 8 in 16..256;
+ * offsets_dev counts rows, and rows_dev and out_rows_dev are 8-byte aligned.  Stream s samples the rows
+ * [offsets[s], offsets[s+1]) with Philox stream id stream_base + s and writes the k rows at
+ * out_rows_dev[(s*k + j) * key_width ..) (slot order: slot j holds the row at its last writer, row j of
+ * the stream where no replacement hit it, zeros for j >= counts[s]) and counts_dev[s] = min(len, k):
+ * stream s is bit-identical to a single ELEMENTS handle of that key_width on RSV_ENGINE_PHILOX_R fed the
+ * same rows.  Every slot and every count is written.  key_width 4 or 8: RSV_E_UNSUPPORTED (use
+ * rsv_sample_segmented).  No row is read before its stream's winners are known; the gather moves
+ * 16-byte granules where key_width % 16 == 0 and both buffers are 16-byte aligned, else 8-byte ones.
+ * All pointers are device pointers. */
+rsv_status rsv_sample_segmented_rows(const void* rows_dev, const int64_t* offsets_dev, int64_t num_streams,
+                                     int32_t key_width, int32_t k, uint64_t seed, uint64_t stream_base,
+                                     void* out_rows_dev, int64_t* counts_dev, void* hip_stream);
+
+/* rsv_sample_segmented_update over byte keys: the state is state_rows_dev[num_states*k] rows of key_width
+ * bytes, state_idx_dev and state_next_dev as there (a fresh state is idx = -1, next = 0, rows anything).
+ * Segments, stream_ids_dev, bases_dev and the skipped segments as rsv_sample_segmented_update; a slot's
+ * row is rewritten only where the segment's last writer or fill index is later than its idx, so any
+ * sequence of updates and merges whose pieces cover [0, n) leaves rows and idx as one
+ * rsv_sample_segmented_rows launch over the whole stream does.  rows_dev must not overlap the state; both
+ * are 8-byte aligned.  key_width a multiple of 8 in 16..256 (4 or 8: RSV_E_UNSUPPORTED, use
+ * rsv_sample_segmented_update); 1 <= k <= 15104 (larger: RSV_E_UNSUPPORTED).  Stateless and
+ * stream-ordered on hip_stream: no host wait, no allocation. */
+rsv_status rsv_sample_segmented_rows_update(const void* rows_dev, const int64_t* offsets_dev,
+                                            const int64_t* stream_ids_dev, const int64_t* bases_dev,
+                                            int64_t num_segments, int64_t num_states, int32_t key_width, int32_t k,
+                                            uint64_t seed, uint64_t stream_base, void* state_rows_dev,
+                                            int64_t* state_idx_dev, int64_t* state_next_dev, void* hip_stream);
+
+/* rsv_sample_segmented_merge over byte keys: part_rows_dev is [parts][num_states][k] rows of key_width
+ * bytes, part_idx_dev and part_next_dev as there.  Per slot the part with the largest idx wins if it
+ * beats the state's, and its key_width bytes are copied (a slot that no part beats is not written); next
+ * becomes the max over the row and the parts.  A state may be merged into itself.  Widths and k as
+ * rsv_sample_segmented_rows_update. */
+rsv_status rsv_sample_segmented_rows_merge(const void* part_rows_dev, const int64_t* part_idx_dev,
+                                           const int64_t* part_next_dev, int32_t parts, int64_t num_states,
+                                           int32_t key_width, int32_t k, void* state_rows_dev,
+                                           int64_t* state_idx_dev, int64_t* state_next_dev, void* hip_stream);
+
 /* Segmented distinct: S independent Sampler.distinct samplers (no reference counterpart; = S separate
  * RandomValues instances, S:383-412).  Stream s covers keys_dev[offsets[s] .. offsets[s+1]) and is
  * seeded like a single DISTINCT handle with java.util.Random(seed + stream_base + s) (wrapping to a

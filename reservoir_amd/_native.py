@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "rsv_distinct_segmented", "rsv_distinct_segmented_update", "rsv_distinct_segmented_merge",
     "rsv_sample_segmented_update", "rsv_sample_segmented_merge", "rsv_distinct_segmented_rows",
     "rsv_distinct_segmented_rows_update", "rsv_distinct_segmented_rows_merge",
+    "rsv_sample_segmented_rows", "rsv_sample_segmented_rows_update", "rsv_sample_segmented_rows_merge",
 )
 
 
@@ -134,6 +135,9 @@ def load():
     L.rsv_sample_segmented.argtypes = [vp, vp, i64, i32, i32, u64, u64, vp, vp, vp]
     L.rsv_sample_segmented_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_sample_segmented_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
+    L.rsv_sample_segmented_rows.argtypes = [vp, vp, i64, i32, i32, u64, u64, vp, vp, vp]
+    L.rsv_sample_segmented_rows_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, u64, u64, vp, vp, vp, vp]
+    L.rsv_sample_segmented_rows_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
     L.rsv_distinct_segmented.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_distinct_segmented_rows.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_distinct_segmented_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
@@ -172,7 +176,9 @@ def load():
                  "rsv_candidates_commit", "rsv_candidates_abort", "rsv_distinct_segmented",
                  "rsv_distinct_segmented_update", "rsv_distinct_segmented_merge",
                  "rsv_sample_segmented_update", "rsv_sample_segmented_merge", "rsv_distinct_segmented_rows",
-                 "rsv_distinct_segmented_rows_update", "rsv_distinct_segmented_rows_merge"):
+                 "rsv_distinct_segmented_rows_update", "rsv_distinct_segmented_rows_merge",
+                 "rsv_sample_segmented_rows", "rsv_sample_segmented_rows_update",
+                 "rsv_sample_segmented_rows_merge"):
         getattr(L, name).restype = i32
     if L.rsv_abi_version() != 1:
         raise ImportError("libreservoir_hip.so ABI version mismatch")

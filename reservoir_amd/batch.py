@@ -11,6 +11,8 @@ libreservoir_hip.so.  Every function raises if the engine is unavailable.
     SegmentedDistinctRows -- K5 resumed over byte keys: the rows move inside the caller-held state (update, merge)
     SegmentedSampler  -- K2 resumed: S Sampler.apply streams as caller-held state (keys, idx, next), fed in
                          pieces from any start index (update) and combined per slot by largest index (merge)
+    sample_segmented_rows -- K2 over fixed-width byte keys (UUIDs): rows in, each slot's winning row out
+    SegmentedSamplerRows -- K2 resumed over byte keys: state (rows, idx, next), update and merge as SegmentedSampler
     replay_events     -- K1': apply the reference's Algorithm-L eviction events on the GPU
     export_draws      -- the per-element draw sequence j_i of draw format R2
 """
@@ -557,6 +559,173 @@ class SegmentedSampler:
         N.check(L.rsv_sample_segmented_merge(
             C.c_void_p(part_keys.data_ptr()), C.c_void_p(part_idx.data_ptr()), C.c_void_p(part_next.data_ptr()),
             P, S, part_keys.element_size(), k, C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.idx.data_ptr()),
+            C.c_void_p(self.next.data_ptr()), _stream_ptr(torch, dev)))
+        return self
+
+
+def _seg_rows_inputs(torch, rows, offsets):
+    """rows / offsets of a K2 call over byte keys, checked and contiguous; returns (rows, offsets, width)."""
+    if not (rows.is_cuda and offsets.is_cuda):
+        raise N.IllegalArgumentException("rows and offsets must be device tensors")
+    if rows.dim() != 2 or rows.dtype not in (torch.uint8, torch.int64) or offsets.dtype != torch.int64:
+        raise N.IllegalArgumentException("rows must be 2-D uint8 or int64 (one key per row) and offsets int64")
+    return rows.contiguous(), offsets.contiguous(), rows.shape[1] * rows.element_size()
+
+
+def _check_rows_width(what: str, long_what: str, width: int) -> None:
+    if width in (4, 8):
+        raise N.ReservoirError(f"{what} takes byte keys; {long_what} takes 4- and 8-byte keys")
+    if width < 16 or width > 256 or width % 8:
+        raise N.IllegalArgumentException("width must be a multiple of 8 in 16..256")
+
+
+def sample_segmented_rows(rows, offsets, k: int, seed: int, stream_base: int = 0):
+    """sample_segmented over fixed-width byte keys (java.util.UUID, case classes of primitives).
+
+    rows: a contiguous 2-D device tensor whose rows hold W bytes, W a multiple of 8 in 16..256 -- uint8
+    (n, W) is the documented form, int64 (n, W / 8) is the same memory; offsets count rows.  Returns
+    (out uint8 [S, k, W], counts int64 [S]) device tensors: slot j of stream s holds the row at the
+    slot's last writer (row j of the stream where no replacement hit it, zeros for j >= counts[s]) --
+    bit-identical to a single Sampler(k, key_type="bytesW", engine="philox_r", stream_id=stream_base + s)
+    fed the same rows.  No row is read before its stream's winners are known.
+    """
+    import torch
+
+    L = N.load()
+    rows, offsets, W = _seg_rows_inputs(torch, rows, offsets)
+    S = offsets.numel() - 1
+    # the kernel writes every slot (empty ones as zeros) and every count: no zero-fill
+    kk = max(int(k), 0)
+    out = torch.empty((max(S, 0), kk, W), dtype=torch.uint8, device=rows.device)
+    counts = torch.empty(max(S, 0), dtype=torch.int64, device=rows.device)
+    if S <= 0:
+        return out, counts
+    N.check(L.rsv_sample_segmented_rows(
+        C.c_void_p(rows.data_ptr()), C.c_void_p(offsets.data_ptr()), S, W, k, seed & (2**64 - 1),
+        stream_base & (2**64 - 1), C.c_void_p(out.data_ptr()), C.c_void_p(counts.data_ptr()),
+        _stream_ptr(torch, rows.device)))
+    return out, counts
+
+
+class SegmentedSamplerRows:
+    """SegmentedSampler over fixed-width byte keys (java.util.UUID, case classes of primitives).
+
+    The state is three device tensors: rows uint8 (S, k, width); idx (S, k), the global index of each
+    slot's last writer, -1 for an empty slot; next (S,).  Row s draws like a single "philox_r"
+    Sampler(k, key_type="bytesW") with stream_id = stream_base + s, and per slot the largest index wins:
+    fed its stream in any number of update() calls -- in order, or out of order with bases= -- or
+    assembled by merge(), a row ends with the rows sample_segmented_rows gives over the whole stream.
+    Only idx and next are filled: a slot with idx -1 is empty whatever its row holds.  width: a multiple
+    of 8 in 16..256.  Everything runs on torch's current stream.
+    """
+
+    def __init__(self, num_streams: int, k: int, width: int, seed: int, stream_base: int = 0, device=None):
+        import torch
+
+        N.load()
+        if num_streams < 0:
+            raise N.IllegalArgumentException("negative stream count")
+        if k <= 0:
+            raise N.IllegalArgumentException("k out of range")
+        if k > _SEG_SAMPLE_STATE_MAX_K:
+            raise N.ReservoirError(
+                f"SegmentedSamplerRows holds k <= {_SEG_SAMPLE_STATE_MAX_K} per stream; use separate handles beyond")
+        _check_rows_width("SegmentedSamplerRows", "SegmentedSampler", width)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise N.IllegalArgumentException("the state lives on the device")
+        self.num_streams, self.k, self.width = int(num_streams), int(k), int(width)
+        self.seed, self.stream_base = seed & (2**64 - 1), stream_base & (2**64 - 1)
+        self.rows = torch.empty((self.num_streams, self.k, self.width), dtype=torch.uint8, device=dev)
+        self.idx = torch.full((self.num_streams, self.k), -1, dtype=torch.int64, device=dev)
+        self.next = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
+
+    @property
+    def counts(self):
+        """Filled slots per row: min(k, elements seen) once a row's pieces cover a prefix of its stream."""
+        return (self.idx >= 0).sum(1)
+
+    def update(self, rows, offsets, stream_ids=None, bases=None, check_ids: bool = True):
+        """Segment b = rows[offsets[b]:offsets[b+1]] into row stream_ids[b] (None: row b).
+
+        rows: uint8 (n, width) or int64 (n, width / 8), as sample_segmented_rows takes them; they must
+        not overlap the state.  stream_ids, bases and check_ids as SegmentedSampler.update.  Rows that
+        no segment names are not touched.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        rows, offsets, W = _seg_rows_inputs(torch, rows, offsets)
+        if W != self.width:
+            raise N.IllegalArgumentException(f"rows must hold {self.width} bytes each")
+        dev = self.rows.device
+        if rows.device != dev or offsets.device != dev:
+            raise N.IllegalArgumentException("rows and offsets must live on the state's device")
+        B = offsets.numel() - 1
+        if B <= 0:
+            return self
+        for name, t in (("stream_ids", stream_ids), ("bases", bases)):
+            if t is not None and (not t.is_cuda or t.dtype != torch.int64 or t.numel() != B or t.device != dev):
+                raise N.IllegalArgumentException(f"{name} must be an int64 device tensor, one per segment")
+        if stream_ids is not None:
+            stream_ids = stream_ids.contiguous()
+            if check_ids:
+                _check_stream_ids(torch, stream_ids, self.num_streams)
+        if bases is not None:
+            bases = bases.contiguous()
+        N.check(L.rsv_sample_segmented_rows_update(
+            C.c_void_p(rows.data_ptr()), C.c_void_p(offsets.data_ptr()),
+            C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
+            C.c_void_p(bases.data_ptr()) if bases is not None else None,
+            B, self.num_streams, W, self.k, self.seed, self.stream_base,
+            C.c_void_p(self.rows.data_ptr()), C.c_void_p(self.idx.data_ptr()), C.c_void_p(self.next.data_ptr()),
+            _stream_ptr(torch, dev)))
+        return self
+
+    def merge(self, part_rows, part_idx=None, part_next=None):
+        """Per slot the largest idx among row s and row s of every part wins; next takes the max.
+
+        merge(part_rows, part_idx, part_next): tensors (P, S, k, width), (P, S, k), (P, S) -- or
+        (S, k, width), (S, k), (S,) for one part -- e.g. an all-gather of every rank's state tensors; or
+        merge(other, ...) with SegmentedSamplerRows objects.  All parts must come from this state's
+        seed and stream_base.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        if isinstance(part_rows, SegmentedSamplerRows):
+            others = [part_rows] + [o for o in (part_idx, part_next) if o is not None]
+            mine = (self.num_streams, self.k, self.width, self.seed, self.stream_base)
+            for o in others:
+                if not isinstance(o, SegmentedSamplerRows) or (
+                        o.num_streams, o.k, o.width, o.seed, o.stream_base) != mine:
+                    raise N.IllegalArgumentException("merge needs states of the same shape, width, seed and stream_base")
+            if len(others) == 1:
+                part_rows, part_idx, part_next = others[0].rows, others[0].idx, others[0].next
+            else:
+                part_rows = torch.stack([o.rows for o in others])
+                part_idx = torch.stack([o.idx for o in others])
+                part_next = torch.stack([o.next for o in others])
+        if part_idx is None or part_next is None:
+            raise N.NullPointerException("merge needs part_rows, part_idx and part_next")
+        S, k, W = self.num_streams, self.k, self.width
+        if part_rows.dim() == 3:
+            part_rows, part_idx, part_next = part_rows[None], part_idx[None], part_next[None]
+        P = part_rows.shape[0]
+        if part_rows.dtype != torch.uint8 or part_idx.dtype != torch.int64 or part_next.dtype != torch.int64:
+            raise N.IllegalArgumentException("part rows must be uint8, idx and next int64")
+        if (tuple(part_rows.shape) != (P, S, k, W) or tuple(part_idx.shape) != (P, S, k)
+                or tuple(part_next.shape) != (P, S)):
+            raise N.IllegalArgumentException(f"parts must be shaped (P, {S}, {k}, {W}), (P, {S}, {k}), (P, {S})")
+        dev = self.rows.device
+        if part_rows.device != dev or part_idx.device != dev or part_next.device != dev:
+            raise N.IllegalArgumentException("parts must live on the state's device")
+        if P == 0 or S == 0:
+            return self
+        part_rows, part_idx, part_next = part_rows.contiguous(), part_idx.contiguous(), part_next.contiguous()
+        N.check(L.rsv_sample_segmented_rows_merge(
+            C.c_void_p(part_rows.data_ptr()), C.c_void_p(part_idx.data_ptr()), C.c_void_p(part_next.data_ptr()),
+            P, S, W, k, C.c_void_p(self.rows.data_ptr()), C.c_void_p(self.idx.data_ptr()),
             C.c_void_p(self.next.data_ptr()), _stream_ptr(torch, dev)))
         return self
 

@@ -156,6 +156,20 @@ hipError_t launch_segmented_update(const void* keys, int key_width, const int64_
 hipError_t launch_segmented_merge(const void* part_keys, int key_width, const int64_t* part_idx,
                                   const int64_t* part_next, int32_t parts, int64_t num_states, uint32_t k,
                                   void* state_keys, int64_t* state_idx, int64_t* state_next, hipStream_t st);
+// K2 over byte keys (rsv_segmented.hip, the same element loops and forms): rows of key_width bytes (16..256, a
+// multiple of 8; every rows buffer 8-byte aligned), offsets and indices count rows.  out_rows[S*k] rows, zero
+// beyond counts[s]; the resumed state is rows[num_states*k], idx, next as above (k <= kSegSampleStateMaxK);
+// part_rows is [parts][num_states][k] rows.  The gather moves 16-byte granules where key_width % 16 == 0 and
+// both buffers are 16-byte aligned, else 8-byte ones.
+hipError_t launch_segmented_rows(const void* rows, int key_width, const int64_t* offsets, int64_t S, uint32_t k,
+                                 const DrawParams& dp, void* out_rows, int64_t* counts, hipStream_t st);
+hipError_t launch_segmented_rows_update(const void* rows, int key_width, const int64_t* offsets,
+                                        const int64_t* stream_ids, const int64_t* bases, int64_t num_segments,
+                                        int64_t num_states, uint32_t k, const DrawParams& dp, void* state_rows,
+                                        int64_t* state_idx, int64_t* state_next, hipStream_t st);
+hipError_t launch_segmented_rows_merge(const void* part_rows, int key_width, const int64_t* part_idx,
+                                       const int64_t* part_next, int32_t parts, int64_t num_states, uint32_t k,
+                                       void* state_rows, int64_t* state_idx, int64_t* state_next, hipStream_t st);
 // K5: segmented distinct (rsv_segdistinct.hip): per stream the bottom-k by (scrambled hash, key),
 // (r0, r1) from java.util.Random(seed0 + s); hashes only for kHashPrecomputed, out_hashes may be null.
 // k <= kSegDistinctMaxK; one wave per stream up to kSegDistinctWaveMaxK, one workgroup above.

@@ -755,5 +755,323 @@ __global__ __launch_bounds__(256) void k2_segmented_merge(const KeyT* part_keys,
     }
 }
 
+// ---- byte keys: the streams' elements are rows of W bytes (java.util.UUID: W = 16) ----------------
+// rsv_sample_segmented_rows / _update / _merge.  The winners are found by the element loops above in
+// their RES mode (only the last-writer table is built; n0 = 0 is a whole stream), so nothing here reads
+// a row before its stream's at most k winners are known.  What is new is the gather: a row is C
+// granules of sizeof(G) bytes -- uint4 where W % 16 == 0 and every base is 16-byte aligned (the host
+// checks), else uint64_t: rows are only 8-byte aligned, W = 24 puts every other row off a 16-byte
+// boundary -- and a team of NT threads walks the (slot, granule) pairs t = j C + c in steps of NT, so
+// consecutive lanes move consecutive granules of a row.  Four pairs per lane are loaded before the
+// first is stored.  Every byte offset is 64-bit, whatever the width of the index arithmetic in the
+// element loops: a stream 2^28 rows into a 16-byte-row tensor starts past 4 GiB.
+
+// the pair a thread starts at and its step, t = j C + c advanced by NT without a division per pair
+struct PairStep {
+    uint32_t j, c, dj, dc;
+};
+__device__ __forceinline__ PairStep pair_step(uint32_t tid, uint32_t nt, uint32_t C) {
+    const uint32_t j = tid / C, dj = nt / C;
+    return PairStep{j, tid - j * C, dj, nt - dj * C};
+}
+__device__ __forceinline__ void pair_next(PairStep& p, uint32_t C) {
+    p.j += p.dj;
+    p.c += p.dc;
+    if (p.c >= C) {
+        p.c -= C;
+        ++p.j;
+    }
+}
+
+// dst row j (of k) takes the row src_of(j) names: a row index into rows (64-bit), or -1 for a zero row
+// (zero_empty) or a row that stays as it is
+template <typename G, bool ZERO_EMPTY, typename SrcOf>
+__device__ __forceinline__ void gather_rows(const unsigned char* rows, unsigned char* dst, uint32_t k, uint32_t C,
+                                            PairStep p, SrcOf src_of) {
+    constexpr int U = 4;
+    const uint64_t Wb = (uint64_t)C * sizeof(G);
+    while (p.j < k) {
+        G v[U];
+        G* d[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            d[u] = nullptr;
+            v[u] = G{};
+            if (p.j < k) {
+                const int64_t at = src_of(p.j);
+                if (ZERO_EMPTY || at >= 0) d[u] = (G*)(dst + (uint64_t)p.j * Wb) + p.c;
+                if (at >= 0) v[u] = ((const G*)(rows + (uint64_t)at * Wb))[p.c];
+            }
+            pair_next(p, C);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (d[u]) *d[u] = v[u];
+    }
+}
+
+// stateless, one wave per stream (k < kWGMinK).  DEFER (k C <= 64: one pair per lane, a compile-time
+// count): the lane's granule is loaded at its stream's end and stored after the NEXT stream's draws, so
+// the random gather's latency overlaps them.  The load is plain C++ and the wait is the compiler's: it
+// waits for everything in flight (vmcnt(0)) before the store, which is why a second register set does
+// not put two streams' gathers in flight -- that takes hand-counted waits, as in k2_segmented.
+template <typename G, bool DEFER>
+__global__ __launch_bounds__(64 * kWaves) void k2_segmented_rows(const unsigned char* __restrict__ rows,
+                                                                 const int64_t* __restrict__ offsets, int64_t S,
+                                                                 uint32_t k, uint32_t C, uint32_t k0, uint32_t k1,
+                                                                 uint64_t stream_base, unsigned char* __restrict__ out,
+                                                                 int64_t* __restrict__ counts, uint32_t fifo_cap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    uint16_t* lut = (uint16_t*)lds;
+    const uint64_t dense_lim = 256ull * k;
+    build_lut(lut, dense_lim);
+    __syncthreads();
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes + (size_t)k * 8);
+    void* tab = base + kStashBytes + kQueueBytes;
+    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), tab, lut, lane, k,
+                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    const uint64_t Wb = (uint64_t)C * sizeof(G);
+    const PairStep p0 = pair_step(lane, 64, C);
+    const int64_t wave_stride = (int64_t)gridDim.x * kWaves;
+    G pv = G{};       // DEFER: the previous stream's granule, in flight
+    G* po = nullptr;  // and where it goes
+    for (int64_t s = (int64_t)blockIdx.x * kWaves + wave; s < S; s += wave_stride) {
+        const int64_t off = uniform64(offsets[s]);
+        const int64_t len = std::max<int64_t>(uniform64(offsets[s + 1]) - off, 0);
+        const uint64_t stream = stream_base + (uint64_t)s;
+        const bool small = len < kSmallLen;
+        if (small) k2_stream<int64_t, true, false, true>(W, nullptr, off, len, stream, nullptr, 0);
+        else k2_stream<int64_t, false, false, true>(W, nullptr, off, len, stream, nullptr, 0);
+        // slot j's row: its last writer, else row j of the stream, else none
+        auto src_of = [&](uint32_t j) -> int64_t {
+            const uint64_t wi = small ? (uint64_t)((const uint32_t*)tab)[j] : ((const uint64_t*)tab)[j];
+            return wi ? off + (int64_t)wi : ((int64_t)j < len ? off + (int64_t)j : -1);
+        };
+        unsigned char* o = out + (uint64_t)s * k * Wb;
+        if constexpr (DEFER) {
+            if (po) *po = pv;
+            po = nullptr;
+            if (p0.j < k) {
+                const int64_t at = src_of(p0.j);
+                po = (G*)(o + (uint64_t)p0.j * Wb) + p0.c;
+                pv = G{};
+                if (at >= 0) pv = ((const G*)(rows + (uint64_t)at * Wb))[p0.c];
+            }
+        } else {
+            gather_rows<G, true>(rows, o, k, C, p0, src_of);
+        }
+        if (lane == 0) counts[s] = len < (int64_t)k ? len : (int64_t)k;
+        __builtin_amdgcn_wave_barrier();  // the table is read before the next stream zeroes it
+    }
+    if constexpr (DEFER)
+        if (po) *po = pv;
+}
+
+// stateless, one workgroup per stream (k >= kWGMinK), as k2_segmented_wg.  GTAB: several threads read a
+// slot's entry, so the gather loads the global table and a second pass puts the zeros back.
+template <typename G, typename TabT, bool GTAB>
+__global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_rows_wg(
+    const unsigned char* __restrict__ rows, const int64_t* __restrict__ offsets, int64_t S, uint32_t k, uint32_t C,
+    uint32_t k0, uint32_t k1, uint64_t stream_base, unsigned char* __restrict__ out, int64_t* __restrict__ counts,
+    uint32_t fifo_cap, TabT* __restrict__ gtab) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    uint16_t* lut = (uint16_t*)lds;
+    const uint64_t dense_lim = 256ull * k;
+    build_lut(lut, dense_lim);
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes);
+    TabT* tab = GTAB ? gtab + (size_t)blockIdx.x * k
+                     : (TabT*)(lds + kLutBytes + (size_t)kWavesWG * (kStashBytes + kQueueBytes));
+    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), nullptr, lut, lane, k,
+                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    const uint32_t nthr = 64u * kWavesWG;
+    const uint64_t Wb = (uint64_t)C * sizeof(G);
+    const PairStep p0 = pair_step(threadIdx.x, nthr, C);
+    for (int64_t s = blockIdx.x; s < S; s += gridDim.x) {
+        const int64_t off = uniform64(offsets[s]);
+        const int64_t len = std::max<int64_t>(uniform64(offsets[s + 1]) - off, 0);
+        if constexpr (!GTAB)
+            for (uint32_t j = threadIdx.x; j < k; j += nthr) tab[j] = 0;
+        __syncthreads();  // the table is zero (GTAB: the previous stream's second pass left it so)
+        const uint64_t stream = stream_base + (uint64_t)s;
+        if (len < kSmallLen) k2_part<TabT, true, GTAB, true>(W, tab, len, stream, wave, 0);
+        else k2_part<TabT, false, GTAB, true>(W, tab, len, stream, wave, 0);
+        if constexpr (GTAB) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // this wave's table atomics
+        __syncthreads();
+        if constexpr (GTAB) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // every wave's, before the gather
+        auto src_of = [&](uint32_t j) -> int64_t {
+            TabT wi;
+            if constexpr (GTAB) wi = __hip_atomic_load(&tab[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else wi = tab[j];
+            return wi ? off + (int64_t)wi : ((int64_t)j < len ? off + (int64_t)j : -1);
+        };
+        gather_rows<G, true>(rows, out + (uint64_t)s * k * Wb, k, C, p0, src_of);
+        if (threadIdx.x == 0) counts[s] = len < (int64_t)k ? len : (int64_t)k;
+        __syncthreads();  // the gather has read the table before anyone zeroes it
+        if constexpr (GTAB) {
+            for (uint32_t j = threadIdx.x; j < k; j += nthr)
+                __hip_atomic_store(&tab[j], (TabT)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // the zeros, before the next stream's atomics
+        }
+    }
+}
+
+// resumed write-back, first pass (one thread per slot): the table entry becomes 1 + the segment-local
+// row that slot j takes -- its winner w (0: none) or its fill index, where that is later than the row's
+// idx -- else 0, and idx[j] is moved.  Only this thread reads or writes idx[j]; the second pass copies
+// the rows the entries name.
+template <typename TabT>
+__device__ __forceinline__ void update_slot_rows(TabT* tab, int64_t n0, int64_t nend, uint32_t j,
+                                                 int64_t* __restrict__ si) {
+    const uint64_t w = tab[j];
+    int64_t at = (int64_t)w;
+    if (!w) at = ((int64_t)j >= n0 && (int64_t)j < nend) ? (int64_t)j : -1;  // a fill index of this segment
+    TabT e = 0;
+    if (at >= 0 && si[j] < at) {
+        si[j] = at;
+        e = (TabT)(at - n0 + 1);
+    }
+    tab[j] = e;
+}
+
+template <typename G>
+__global__ __launch_bounds__(64 * kWaves) void k2_segmented_rows_update(
+    const unsigned char* __restrict__ rows, const int64_t* __restrict__ offsets, const int64_t* __restrict__ ids,
+    const int64_t* __restrict__ bases, int64_t B, int64_t S, uint32_t k, uint32_t C, uint32_t k0, uint32_t k1,
+    uint64_t stream_base, unsigned char* __restrict__ state_rows, int64_t* __restrict__ state_idx,
+    int64_t* __restrict__ state_next, uint32_t fifo_cap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    uint16_t* lut = (uint16_t*)lds;
+    const uint64_t dense_lim = 256ull * k;
+    build_lut(lut, dense_lim);
+    __syncthreads();
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes + (size_t)k * 8);
+    void* tab = base + kStashBytes + kQueueBytes;
+    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), tab, lut, lane, k,
+                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    const uint64_t Wb = (uint64_t)C * sizeof(G);
+    const PairStep p0 = pair_step(lane, 64, C);
+    const int64_t wave_stride = (int64_t)gridDim.x * kWaves;
+    for (int64_t b = (int64_t)blockIdx.x * kWaves + wave; b < B; b += wave_stride) {
+        const int64_t off = uniform64(offsets[b]), len = uniform64(offsets[b + 1]) - off;
+        const int64_t r = ids ? uniform64(ids[b]) : b;
+        if (len <= 0 || r < 0 || r >= S) continue;
+        const int64_t n0 = uniform64(bases ? bases[b] : state_next[r]);
+        if (n0 < 0) continue;
+        const int64_t nend = n0 + len;
+        const uint64_t stream = stream_base + (uint64_t)r;
+        int64_t* si = state_idx + r * (int64_t)k;
+        const bool small = nend < kSmallLen;
+        if (small) {
+            k2_stream<int64_t, true, false, true>(W, nullptr, off, len, stream, nullptr, n0);
+            for (uint32_t j = lane; j < k; j += 64) update_slot_rows((uint32_t*)tab, n0, nend, j, si);
+        } else {
+            k2_stream<int64_t, false, false, true>(W, nullptr, off, len, stream, nullptr, n0);
+            for (uint32_t j = lane; j < k; j += 64) update_slot_rows((uint64_t*)tab, n0, nend, j, si);
+        }
+        __builtin_amdgcn_wave_barrier();
+        auto src_of = [&](uint32_t j) -> int64_t {
+            const uint64_t e = small ? (uint64_t)((const uint32_t*)tab)[j] : ((const uint64_t*)tab)[j];
+            return e ? off + (int64_t)e - 1 : -1;
+        };
+        gather_rows<G, false>(rows, state_rows + (uint64_t)r * k * Wb, k, C, p0, src_of);
+        if (lane == 0 && state_next[r] < nend) state_next[r] = nend;
+        __builtin_amdgcn_wave_barrier();  // the table is read before the next segment zeroes it
+    }
+}
+
+// the workgroup form of k2_segmented_rows_update (k >= kWGMinK), as k2_segmented_update_wg
+template <typename G>
+__global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_rows_update_wg(
+    const unsigned char* __restrict__ rows, const int64_t* __restrict__ offsets, const int64_t* __restrict__ ids,
+    const int64_t* __restrict__ bases, int64_t B, int64_t S, uint32_t k, uint32_t C, uint32_t k0, uint32_t k1,
+    uint64_t stream_base, unsigned char* __restrict__ state_rows, int64_t* __restrict__ state_idx,
+    int64_t* __restrict__ state_next, uint32_t fifo_cap) {
+    using TabT = unsigned long long;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    uint16_t* lut = (uint16_t*)lds;
+    const uint64_t dense_lim = 256ull * k;
+    build_lut(lut, dense_lim);
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes);
+    TabT* tab = (TabT*)(lds + kLutBytes + (size_t)kWavesWG * (kStashBytes + kQueueBytes));
+    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), nullptr, lut, lane, k,
+                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    const uint32_t nthr = 64u * kWavesWG;
+    const uint64_t Wb = (uint64_t)C * sizeof(G);
+    const PairStep p0 = pair_step(threadIdx.x, nthr, C);
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        // workgroup-uniform: every thread reads the same words (state_next[r] before anyone writes it)
+        const int64_t off = uniform64(offsets[b]), len = uniform64(offsets[b + 1]) - off;
+        const int64_t r = ids ? uniform64(ids[b]) : b;
+        if (len <= 0 || r < 0 || r >= S) continue;
+        const int64_t n0 = uniform64(bases ? bases[b] : state_next[r]);
+        if (n0 < 0) continue;
+        const int64_t nend = n0 + len;
+        for (uint32_t j = threadIdx.x; j < k; j += nthr) tab[j] = 0;
+        __syncthreads();  // the table is zero, the lut built, and n0 read by every wave
+        const uint64_t stream = stream_base + (uint64_t)r;
+        if (nend < kSmallLen) k2_part<TabT, true, false, true>(W, tab, len, stream, wave, n0);
+        else k2_part<TabT, false, false, true>(W, tab, len, stream, wave, n0);
+        __syncthreads();
+        int64_t* si = state_idx + r * (int64_t)k;
+        for (uint32_t j = threadIdx.x; j < k; j += nthr) update_slot_rows(tab, n0, nend, j, si);
+        __syncthreads();  // every slot's entry names its row (or none)
+        auto src_of = [&](uint32_t j) -> int64_t {
+            const uint64_t e = tab[j];
+            return e ? off + (int64_t)e - 1 : -1;
+        };
+        gather_rows<G, false>(rows, state_rows + (uint64_t)r * k * Wb, k, C, p0, src_of);
+        if (threadIdx.x == 0 && state_next[r] < nend) state_next[r] = nend;
+        __syncthreads();  // the write-back has read the table before the next segment zeroes it
+    }
+}
+
+// rsv_sample_segmented_rows_merge: a workgroup takes 256 (row, slot) entries.  First pass, one thread per
+// entry: the part with the largest idx, if it beats the state's (only this thread reads or writes the
+// entry's idx), into LDS; second pass: the winning parts' rows by (entry, granule) pairs.
+template <typename G>
+__global__ __launch_bounds__(256) void k2_segmented_rows_merge(const unsigned char* part_rows, const int64_t* part_idx,
+                                                               const int64_t* part_next, int32_t P, int64_t S,
+                                                               uint32_t k, uint32_t C, unsigned char* state_rows,
+                                                               int64_t* state_idx, int64_t* state_next) {
+    // (no __restrict__: a state merged into itself names the same memory twice)
+    __shared__ int32_t win[256];
+    const int64_t total = S * (int64_t)k;
+    const int64_t t0 = (int64_t)blockIdx.x * 256, t = t0 + threadIdx.x;
+    int32_t bp = -1;
+    if (t < total) {
+        const int64_t cur = state_idx[t];
+        int64_t best = cur;
+        for (int32_t p = 0; p < P; ++p) {
+            const int64_t pi = part_idx[(int64_t)p * total + t];
+            if (pi > best) {
+                best = pi;
+                bp = p;
+            }
+        }
+        if (bp >= 0) state_idx[t] = best;
+        if (t % k == 0) {  // the row's first slot also takes its next
+            const int64_t r = t / k;
+            const int64_t cn = state_next[r];
+            int64_t n = cn;
+            for (int32_t p = 0; p < P; ++p) n = std::max<int64_t>(n, part_next[(int64_t)p * S + r]);
+            if (n > cn) state_next[r] = n;
+        }
+    }
+    win[threadIdx.x] = bp;
+    __syncthreads();
+    const uint32_t here = (uint32_t)std::min<int64_t>(256, total - t0);
+    // source row of entry t0 + j: entry t0 + j of part win[j]
+    auto src_of = [&](uint32_t j) -> int64_t {
+        const int32_t p = win[j];
+        return p >= 0 ? (int64_t)p * total + t0 + (int64_t)j : -1;
+    };
+    gather_rows<G, false>(part_rows, state_rows + (uint64_t)t0 * C * sizeof(G), here, C, pair_step(threadIdx.x, 256, C),
+                          src_of);
+}
+
 }  // namespace k2
 }  // namespace rsv

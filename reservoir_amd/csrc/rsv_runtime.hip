@@ -1665,6 +1665,81 @@ rsv_status rsv_sample_segmented_merge(const void* part_keys_dev, const int64_t* 
     return RSV_OK;
 }
 
+// k and key_width of the three K2 entry points over byte keys (fn: the entry point's name, long_fn: its
+// counterpart for 4- and 8-byte keys, for the messages; state: the two resumed ones, whose k is bounded)
+static rsv_status check_segsample_rows_shape(const char* fn, const char* long_fn, int32_t k, int32_t key_width,
+                                             bool state) {
+    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
+    if (state && k > (int32_t)kSegSampleStateMaxK)
+        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " holds k <= " + std::to_string(kSegSampleStateMaxK) +
+                                           " per stream; use separate handles beyond");
+    if (key_width == 4 || key_width == 8)
+        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " takes byte keys; " + long_fn + " takes 4- and 8-byte keys");
+    if (key_width < 16 || key_width > 256 || key_width % 8 != 0)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be a multiple of 8 in 16..256");
+    return RSV_OK;
+}
+
+rsv_status rsv_sample_segmented_rows(const void* rows_dev, const int64_t* offsets_dev, int64_t num_streams,
+                                     int32_t key_width, int32_t k, uint64_t seed, uint64_t stream_base,
+                                     void* out_rows_dev, int64_t* counts_dev, void* hip_stream) {
+    if (rsv_status st = check_segsample_rows_shape("rsv_sample_segmented_rows", "rsv_sample_segmented", k, key_width, false))
+        return st;
+    if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
+    if (num_streams == 0) return RSV_OK;
+    // rows_dev is not checked: a launch whose streams are all empty has no rows
+    if (!offsets_dev || !out_rows_dev || !counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (((uintptr_t)rows_dev | (uintptr_t)out_rows_dev) & 7)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "rows_dev and out_rows_dev must be 8-byte aligned");
+    const DrawParams dp{seed, stream_base};
+    RSV_HIP_TRY(launch_segmented_rows(rows_dev, key_width, offsets_dev, num_streams, (uint32_t)k, dp, out_rows_dev,
+                                      counts_dev, (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
+rsv_status rsv_sample_segmented_rows_update(const void* rows_dev, const int64_t* offsets_dev,
+                                            const int64_t* stream_ids_dev, const int64_t* bases_dev,
+                                            int64_t num_segments, int64_t num_states, int32_t key_width, int32_t k,
+                                            uint64_t seed, uint64_t stream_base, void* state_rows_dev,
+                                            int64_t* state_idx_dev, int64_t* state_next_dev, void* hip_stream) {
+    if (rsv_status st = check_segsample_rows_shape("rsv_sample_segmented_rows_update", "rsv_sample_segmented_update", k,
+                                                   key_width, true))
+        return st;
+    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
+    if (!stream_ids_dev && num_segments > num_states)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
+    if (num_segments == 0 || num_states == 0) return RSV_OK;
+    // rows_dev is not checked: a launch whose segments are all empty has no rows
+    if (!offsets_dev || !state_rows_dev || !state_idx_dev || !state_next_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (((uintptr_t)rows_dev | (uintptr_t)state_rows_dev) & 7)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "rows_dev and state_rows_dev must be 8-byte aligned");
+    const DrawParams dp{seed, stream_base};
+    RSV_HIP_TRY(launch_segmented_rows_update(rows_dev, key_width, offsets_dev, stream_ids_dev, bases_dev, num_segments,
+                                             num_states, (uint32_t)k, dp, state_rows_dev, state_idx_dev,
+                                             state_next_dev, (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
+rsv_status rsv_sample_segmented_rows_merge(const void* part_rows_dev, const int64_t* part_idx_dev,
+                                           const int64_t* part_next_dev, int32_t parts, int64_t num_states,
+                                           int32_t key_width, int32_t k, void* state_rows_dev, int64_t* state_idx_dev,
+                                           int64_t* state_next_dev, void* hip_stream) {
+    if (rsv_status st = check_segsample_rows_shape("rsv_sample_segmented_rows_merge", "rsv_sample_segmented_merge", k,
+                                                   key_width, true))
+        return st;
+    if (parts < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative part or state count");
+    if (parts == 0 || num_states == 0) return RSV_OK;
+    if (!part_rows_dev || !part_idx_dev || !part_next_dev || !state_rows_dev || !state_idx_dev || !state_next_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (((uintptr_t)part_rows_dev | (uintptr_t)state_rows_dev) & 7)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "part_rows_dev and state_rows_dev must be 8-byte aligned");
+    RSV_HIP_TRY(launch_segmented_rows_merge(part_rows_dev, key_width, part_idx_dev, part_next_dev, parts, num_states,
+                                            (uint32_t)k, state_rows_dev, state_idx_dev, state_next_dev,
+                                            (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
 // k and key_width of the three K5 entry points (fn: the entry point's name, for the messages)
 static rsv_status check_segdistinct_shape(const char* fn, int32_t k, int32_t key_width) {
     if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");

@@ -29,6 +29,11 @@
 // of its stream from any start index, and the largest index per slot wins.  The same two forms
 // (k2_segmented_update, k2_segmented_update_wg) over the same element loops; the workgroup form keeps
 // 64-bit table entries in LDS, so k <= kSegSampleStateMaxK.
+//
+// Byte keys (rsv_sample_segmented_rows / _rows_update / _rows_merge): the elements are
+// rows of 16..256 bytes.  The same element loops find the winners without reading a row; separate
+// kernels (k2_segmented_rows*, rsv_k2.h) then gather whole rows, lanes side by side on a row's 16- or
+// 8-byte granules, with 64-bit byte offsets.  The key-typed kernels above are not instantiated for rows.
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -228,6 +233,139 @@ hipError_t launch_segmented_merge(const void* part_keys, int key_width, const in
         hipLaunchKernelGGL(k2_segmented_merge<int32_t>, dim3((unsigned)blocks), dim3(256), 0, st,
                            (const int32_t*)part_keys, part_idx, part_next, parts, num_states, k, (int32_t*)state_keys,
                            state_idx, state_next);
+    return hipGetLastError();
+}
+
+// ---- byte keys (rows) ----------------------------------------------------------------------------
+namespace {
+// 16-byte granules where every row of every buffer sits on a 16-byte boundary, else 8-byte ones
+bool rows_vec16(int key_width, const void* a, const void* b) {
+    return key_width % 16 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0;
+}
+
+template <typename G, typename TabT>
+hipError_t launch_rows_wg(const unsigned char* rows, uint32_t C, const int64_t* offsets, int64_t S, uint32_t k,
+                          const DrawParams& dp, unsigned char* out, int64_t* counts, hipStream_t st,
+                          uint32_t fifo_cap) {
+    const uint32_t k0 = (uint32_t)dp.seed, k1 = (uint32_t)(dp.seed >> 32);
+    const size_t lds = k2::lds_bytes_wg(k, sizeof(TabT), false);
+    if (lds <= k2::kLdsMax) {  // grids as launch_wg
+        const uint64_t per_cu = std::max<uint64_t>(1, k2::kLdsMax / lds);
+        const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)S, 256ull * per_cu * 2);
+        hipLaunchKernelGGL((k2_segmented_rows_wg<G, TabT, false>), dim3(grid), dim3(64 * kWavesWG), lds, st, rows,
+                           offsets, S, k, C, k0, k1, dp.stream, out, counts, fifo_cap, (TabT*)nullptr);
+        return hipGetLastError();
+    }
+    int dev = 0;
+    RSV_HIP_RET(hipGetDevice(&dev));
+    const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)S, 512);
+    const size_t bytes = (size_t)grid * k * sizeof(TabT);
+    std::lock_guard<std::mutex> lk(g_gt_mu);
+    void* gt = nullptr;
+    bool priv = false;
+    RSV_HIP_RET(gt_acquire(dev, bytes, st, &gt, &priv));
+    hipLaunchKernelGGL((k2_segmented_rows_wg<G, TabT, true>), dim3(grid), dim3(64 * kWavesWG),
+                       k2::lds_bytes_wg(k, sizeof(TabT), true), st, rows, offsets, S, k, C, k0, k1, dp.stream, out,
+                       counts, fifo_cap, (TabT*)gt);
+    const hipError_t e = hipGetLastError();
+    gt_release(dev, st, priv, gt);
+    return e;
+}
+
+template <typename G>
+hipError_t launch_rows(const unsigned char* rows, int key_width, const int64_t* offsets, int64_t S, uint32_t k,
+                       const DrawParams& dp, unsigned char* out, int64_t* counts, hipStream_t st) {
+    const uint32_t C = (uint32_t)key_width / (uint32_t)sizeof(G);
+    const uint32_t fifo_cap = env_fifo_cap();
+    if (k >= k2::kWGMinK) {  // one workgroup per stream; u32 tables by the rule of launch_segmented
+        int64_t ends[2] = {0, 0};
+        RSV_HIP_RET(hipMemcpyAsync(&ends[0], offsets, 8, hipMemcpyDeviceToHost, st));
+        RSV_HIP_RET(hipMemcpyAsync(&ends[1], offsets + S, 8, hipMemcpyDeviceToHost, st));
+        RSV_HIP_RET(hipStreamSynchronize(st));
+        if (ends[1] - ends[0] < ((int64_t)1 << 32))
+            return launch_rows_wg<G, uint32_t>(rows, C, offsets, S, k, dp, out, counts, st, fifo_cap);
+        return launch_rows_wg<G, unsigned long long>(rows, C, offsets, S, k, dp, out, counts, st, fifo_cap);
+    }
+    const uint32_t k0 = (uint32_t)dp.seed, k1 = (uint32_t)(dp.seed >> 32);
+    const uint64_t blocks = ((uint64_t)S + kWaves - 1) / kWaves;  // grids as launch_segmented
+    const unsigned grid = (unsigned)std::min<uint64_t>(blocks, 256ull * 128);
+    // one (slot, granule) pair per lane: the gather is deferred past the next stream's draws (C3 with UUID
+    // rows: 1.79 ms against 1.85 ms plain, profiles/segmented_rows/bench.json).  RSV_K2_ROWS_DEFER=0 (read
+    // once per process) keeps the plain gather, for that A/B in tools/bench_segmented_rows.py.
+    static const bool defer = [] {
+        const char* e = std::getenv("RSV_K2_ROWS_DEFER");
+        return !e || std::atoi(e) != 0;
+    }();
+    if (defer && (uint64_t)k * C <= 64)
+        hipLaunchKernelGGL((k2_segmented_rows<G, true>), dim3(grid), dim3(64 * kWaves), k2::lds_bytes(k), st, rows,
+                           offsets, S, k, C, k0, k1, dp.stream, out, counts, fifo_cap);
+    else
+        hipLaunchKernelGGL((k2_segmented_rows<G, false>), dim3(grid), dim3(64 * kWaves), k2::lds_bytes(k), st, rows,
+                           offsets, S, k, C, k0, k1, dp.stream, out, counts, fifo_cap);
+    return hipGetLastError();
+}
+
+template <typename G>
+hipError_t launch_rows_update(const unsigned char* rows, int key_width, const int64_t* offsets, const int64_t* ids,
+                              const int64_t* bases, int64_t B, int64_t S, uint32_t k, const DrawParams& dp,
+                              unsigned char* state_rows, int64_t* state_idx, int64_t* state_next, hipStream_t st) {
+    const uint32_t C = (uint32_t)key_width / (uint32_t)sizeof(G);
+    const uint32_t k0 = (uint32_t)dp.seed, k1 = (uint32_t)(dp.seed >> 32);
+    const uint32_t fifo_cap = env_fifo_cap();
+    if (k >= k2::kWGMinK) {  // grids as launch_update
+        const size_t lds = k2::lds_bytes_wg(k, 8, false);
+        const uint64_t per_cu = std::max<uint64_t>(1, k2::kLdsMax / lds);
+        const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)B, 256ull * per_cu * 2);
+        hipLaunchKernelGGL(k2_segmented_rows_update_wg<G>, dim3(grid), dim3(64 * kWavesWG), lds, st, rows, offsets,
+                           ids, bases, B, S, k, C, k0, k1, dp.stream, state_rows, state_idx, state_next, fifo_cap);
+        return hipGetLastError();
+    }
+    const uint64_t blocks = ((uint64_t)B + kWaves - 1) / kWaves;
+    const unsigned grid = (unsigned)std::min<uint64_t>(blocks, 256ull * 128);
+    hipLaunchKernelGGL(k2_segmented_rows_update<G>, dim3(grid), dim3(64 * kWaves), k2::lds_bytes(k), st, rows, offsets,
+                       ids, bases, B, S, k, C, k0, k1, dp.stream, state_rows, state_idx, state_next, fifo_cap);
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_segmented_rows(const void* rows, int key_width, const int64_t* offsets, int64_t S, uint32_t k,
+                                 const DrawParams& dp, void* out_rows, int64_t* counts, hipStream_t st) {
+    if (S <= 0) return hipSuccess;
+    if (rows_vec16(key_width, rows, out_rows))
+        return launch_rows<uint4>((const unsigned char*)rows, key_width, offsets, S, k, dp, (unsigned char*)out_rows,
+                                  counts, st);
+    return launch_rows<uint64_t>((const unsigned char*)rows, key_width, offsets, S, k, dp, (unsigned char*)out_rows,
+                                 counts, st);
+}
+
+hipError_t launch_segmented_rows_update(const void* rows, int key_width, const int64_t* offsets,
+                                        const int64_t* stream_ids, const int64_t* bases, int64_t num_segments,
+                                        int64_t num_states, uint32_t k, const DrawParams& dp, void* state_rows,
+                                        int64_t* state_idx, int64_t* state_next, hipStream_t st) {
+    if (num_segments <= 0 || num_states <= 0) return hipSuccess;
+    if (k > kSegSampleStateMaxK) return hipErrorInvalidValue;
+    if (rows_vec16(key_width, rows, state_rows))
+        return launch_rows_update<uint4>((const unsigned char*)rows, key_width, offsets, stream_ids, bases,
+                                         num_segments, num_states, k, dp, (unsigned char*)state_rows, state_idx,
+                                         state_next, st);
+    return launch_rows_update<uint64_t>((const unsigned char*)rows, key_width, offsets, stream_ids, bases, num_segments,
+                                        num_states, k, dp, (unsigned char*)state_rows, state_idx, state_next, st);
+}
+
+hipError_t launch_segmented_rows_merge(const void* part_rows, int key_width, const int64_t* part_idx,
+                                       const int64_t* part_next, int32_t parts, int64_t num_states, uint32_t k,
+                                       void* state_rows, int64_t* state_idx, int64_t* state_next, hipStream_t st) {
+    if (parts <= 0 || num_states <= 0) return hipSuccess;
+    const uint64_t blocks = ((uint64_t)num_states * k + 255) / 256;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (rows_vec16(key_width, part_rows, state_rows))
+        hipLaunchKernelGGL(k2_segmented_rows_merge<uint4>, dim3((unsigned)blocks), dim3(256), 0, st,
+                           (const unsigned char*)part_rows, part_idx, part_next, parts, num_states, k,
+                           (uint32_t)key_width / 16u, (unsigned char*)state_rows, state_idx, state_next);
+    else
+        hipLaunchKernelGGL(k2_segmented_rows_merge<uint64_t>, dim3((unsigned)blocks), dim3(256), 0, st,
+                           (const unsigned char*)part_rows, part_idx, part_next, parts, num_states, k,
+                           (uint32_t)key_width / 8u, (unsigned char*)state_rows, state_idx, state_next);
     return hipGetLastError();
 }
 
