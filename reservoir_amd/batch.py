@@ -136,12 +136,20 @@ def distinct_segmented(keys, offsets, k: int, seed: int, stream_base: int = 0, h
     return out, out_h, counts
 
 
-def _segd_rows_inputs(torch, rows, offsets, hash, hashes):
-    """rows / offsets / hashes of a K5 call over byte keys, checked and contiguous."""
+def _rows_inputs(torch, rows, offsets, dtypes=None):
+    """rows / offsets of a call over byte keys (dtypes: the row dtypes it takes, None: any), checked and
+    contiguous; returns (rows, offsets, width)."""
     if not (rows.is_cuda and offsets.is_cuda):
         raise N.IllegalArgumentException("rows and offsets must be device tensors")
-    if rows.dim() != 2 or offsets.dtype != torch.int64:
-        raise N.IllegalArgumentException("rows must be 2-D (one key per row) and offsets int64")
+    if rows.dim() != 2 or (dtypes and rows.dtype not in dtypes) or offsets.dtype != torch.int64:
+        what = "uint8 or int64 " if dtypes else ""
+        raise N.IllegalArgumentException(f"rows must be 2-D {what}(one key per row) and offsets int64")
+    return rows.contiguous(), offsets.contiguous(), rows.shape[1] * rows.element_size()
+
+
+def _segd_rows_inputs(torch, rows, offsets, hash, hashes):
+    """rows / offsets / hashes of a K5 call over byte keys, checked and contiguous."""
+    rows, offsets, _ = _rows_inputs(torch, rows, offsets)
     if hashes is None and hash == "precomputed":
         raise N.NullPointerException("hash='precomputed' needs hashes=")
     if hashes is None and hash != "default":
@@ -151,7 +159,7 @@ def _segd_rows_inputs(torch, rows, offsets, hash, hashes):
             raise N.IllegalArgumentException("hashes must be an int64 device tensor, one per row")
         # an empty tensor has no address; the engine wants one for precomputed hashes
         hashes = hashes.contiguous() if hashes.numel() else torch.empty(1, dtype=torch.int64, device=rows.device)
-    return rows.contiguous(), offsets.contiguous(), hashes
+    return rows, offsets, hashes
 
 
 def distinct_segmented_rows(rows, offsets, k: int, seed: int, stream_base: int = 0, hash: str = "default", hashes=None):
@@ -188,7 +196,124 @@ def distinct_segmented_rows(rows, offsets, k: int, seed: int, stream_base: int =
     return out, out_h, counts
 
 
-class SegmentedDistinct:
+def _check_rows_width(what: str, long_what: str, width: int) -> None:
+    if width in (4, 8):
+        raise N.ReservoirError(f"{what} takes byte keys; {long_what} takes 4- and 8-byte keys")
+    if width < 16 or width > 256 or width % 8:
+        raise N.IllegalArgumentException("width must be a multiple of 8 in 16..256")
+
+
+class _SegmentedState:
+    """What the four caller-held states share: the constructor's checks, the segment side of update() and
+    the argument handling of merge().  A subclass names its three tensors (_TENSORS: the payload keys (S, k) or
+    rows (S, k, width), the per-slot and the per-row tensor), itself and its cap on k for the messages (_NAME,
+    _MAX_K; _LONG: a rows class's counterpart for 4- and 8-byte keys), what merge(other) compares (_identity(),
+    _SAME in the message), and makes its own native calls."""
+
+    _NAME = _LONG = _SAME = ""
+    _TENSORS: tuple = ()
+    _MAX_K = 0
+
+    def _check_width(self, width) -> None:
+        if width is not None:  # a rows class
+            _check_rows_width(self._NAME, self._LONG, width)
+            self.width = int(width)
+
+    def _init_state(self, torch, num_streams, k, seed, stream_base, device, width=None):
+        """The checks every constructor ends with; returns the state's device."""
+        if num_streams < 0:
+            raise N.IllegalArgumentException("negative stream count")
+        if k <= 0:
+            raise N.IllegalArgumentException("k out of range")
+        if k > self._MAX_K:
+            raise N.ReservoirError(
+                f"{self._NAME} holds k <= {self._MAX_K} per stream; use separate handles beyond")
+        self._check_width(width)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise N.IllegalArgumentException("the state lives on the device")
+        self.num_streams, self.k = int(num_streams), int(k)
+        self.seed, self.stream_base = seed & (2**64 - 1), stream_base & (2**64 - 1)
+        return dev
+
+    def _state(self):
+        return [getattr(self, name) for name in self._TENSORS]
+
+    def _key_width(self) -> int:
+        return self.width if self._TENSORS[0] == "rows" else self.keys.element_size()
+
+    def _check_same_device(self, data, offsets) -> None:
+        """The payload of an update against the state: its row width (the rows classes) and its device."""
+        if data.dim() == 2 and self._TENSORS[0] == "rows" and data.shape[1] * data.element_size() != self.width:
+            raise N.IllegalArgumentException(f"rows must hold {self.width} bytes each")
+        dev = self._state()[0].device
+        if data.device != dev or offsets.device != dev:
+            raise N.IllegalArgumentException(f"{self._TENSORS[0]} and offsets must live on the state's device")
+
+    def _segments(self, torch, offsets, check_ids, stream_ids, **per_segment):
+        """The segment side of an update: None if there is no segment, else [B, stream_ids, ...] with
+        stream_ids and the optional per-segment tensor (bases=) checked, contiguous, and the ids verified."""
+        B = offsets.numel() - 1
+        if B <= 0:
+            return None
+        dev = self._state()[0].device
+        out = [B]
+        for name, t in dict(stream_ids=stream_ids, **per_segment).items():
+            if t is not None:
+                if not t.is_cuda or t.dtype != torch.int64 or t.numel() != B or t.device != dev:
+                    raise N.IllegalArgumentException(f"{name} must be an int64 device tensor, one per segment")
+                t = t.contiguous()
+            out.append(t)
+        if stream_ids is not None and check_ids:
+            _check_stream_ids(torch, out[1], self.num_streams)
+        return out
+
+    def _merge(self, torch, fn, cls, parts):
+        """merge() of every class: parts = (payload, per-slot, per-row) tensors, stacked (P, ...) or one part
+        without the leading axis, or up to three states of class cls; fn is the native merge."""
+        names = self._TENSORS
+        if isinstance(parts[0], cls):
+            others = [o for o in parts if o is not None]
+            for o in others:
+                if not isinstance(o, cls) or o._identity() != self._identity():
+                    raise N.IllegalArgumentException(f"merge needs states of the same shape, {self._SAME}")
+            if len(others) == 1:
+                parts = others[0]._state()
+            else:
+                parts = [torch.stack([getattr(o, name) for o in others]) for name in names]
+        if parts[1] is None or parts[2] is None:
+            raise N.NullPointerException(f"merge needs part_{names[0]}, part_{names[1]} and part_{names[2]}")
+        mine = self._state()
+        if parts[0].dim() == mine[0].dim():
+            parts = [p[None] for p in parts]
+        P = parts[0].shape[0]
+        rows = names[0] == "rows"
+
+        def check_shapes():
+            if any(tuple(p.shape) != (P,) + tuple(m.shape) for p, m in zip(parts, mine)):
+                want = ", ".join("(P, " + ", ".join(str(n) for n in m.shape) + ")" for m in mine)
+                raise N.IllegalArgumentException(f"parts must be shaped {want}")
+
+        if not rows:  # (the rows classes look at the dtypes first)
+            check_shapes()
+        if parts[0].dtype != mine[0].dtype or parts[1].dtype != torch.int64 or parts[2].dtype != torch.int64:
+            raise N.IllegalArgumentException(
+                f"part rows must be uint8, {names[1]} and {names[2]} int64" if rows else
+                f"part keys must have the state's dtype, {names[1]} and {names[2]} must be int64")
+        if rows:
+            check_shapes()
+        dev = mine[0].device
+        if any(p.device != dev for p in parts):
+            raise N.IllegalArgumentException("parts must live on the state's device")
+        if P == 0 or self.num_streams == 0:
+            return self
+        parts = [p.contiguous() for p in parts]
+        N.check(fn(*(C.c_void_p(p.data_ptr()) for p in parts), P, self.num_streams, self._key_width(), self.k,
+                   *(C.c_void_p(m.data_ptr()) for m in mine), _stream_ptr(torch, dev)))
+        return self
+
+
+class SegmentedDistinct(_SegmentedState):
     """S long-lived Sampler.distinct streams advanced by one launch per batch (K5 resumed).
 
     The state is three device tensors in distinct_segmented's layout: keys (S, k), hashes (S, k),
@@ -199,6 +324,12 @@ class SegmentedDistinct:
     row an update writes has zeros beyond its count.  hash="precomputed": update(hashes=...).
     Everything runs on torch's current stream.
     """
+
+    _NAME, _TENSORS, _MAX_K = "SegmentedDistinct", ("keys", "hashes", "counts"), _SEG_DISTINCT_MAX_K
+    _SAME = "seed, stream_base and hash"
+
+    def _identity(self):
+        return self.num_streams, self.k, self.seed, self.stream_base, self._kind
 
     def __init__(self, num_streams: int, k: int, seed: int, stream_base: int = 0, hash: str = "default",
                  dtype=None, device=None):
@@ -214,18 +345,7 @@ class SegmentedDistinct:
             self._kind = _SEG_HASH[hash]
         else:
             raise N.IllegalArgumentException(f"unknown hash {hash!r}")
-        if num_streams < 0:
-            raise N.IllegalArgumentException("negative stream count")
-        if k <= 0:
-            raise N.IllegalArgumentException("k out of range")
-        if k > _SEG_DISTINCT_MAX_K:
-            raise N.ReservoirError(
-                f"SegmentedDistinct holds k <= {_SEG_DISTINCT_MAX_K} per stream; use separate handles beyond")
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if dev.type != "cuda":
-            raise N.IllegalArgumentException("the state lives on the device")
-        self.num_streams, self.k = int(num_streams), int(k)
-        self.seed, self.stream_base = seed & (2**64 - 1), stream_base & (2**64 - 1)
+        dev = self._init_state(torch, num_streams, k, seed, stream_base, device)
         self.keys = torch.empty((self.num_streams, self.k), dtype=dtype, device=dev)
         self.hashes = torch.empty((self.num_streams, self.k), dtype=torch.int64, device=dev)
         self.counts = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
@@ -242,15 +362,10 @@ class SegmentedDistinct:
 
         L = N.load()
         keys, offsets, hashes = _segd_inputs(torch, keys, offsets, hashes, state=self)
-        B = offsets.numel() - 1
-        if B <= 0:
+        seg = self._segments(torch, offsets, check_ids, stream_ids)
+        if seg is None:
             return self
-        if stream_ids is not None:
-            if not stream_ids.is_cuda or stream_ids.dtype != torch.int64 or stream_ids.numel() != B:
-                raise N.IllegalArgumentException("stream_ids must be an int64 device tensor, one per segment")
-            stream_ids = stream_ids.contiguous()
-            if check_ids:
-                _check_stream_ids(torch, stream_ids, self.num_streams)
+        B, stream_ids = seg
         N.check(L.rsv_distinct_segmented_update(
             C.c_void_p(keys.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
             C.c_void_p(offsets.data_ptr()), C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
@@ -270,42 +385,10 @@ class SegmentedDistinct:
         import torch
 
         L = N.load()
-        if isinstance(part_keys, SegmentedDistinct):
-            others = [part_keys] + [o for o in (part_hashes, part_counts) if o is not None]
-            for o in others:
-                if not isinstance(o, SegmentedDistinct) or (o.num_streams, o.k, o.seed, o.stream_base, o._kind) != (
-                        self.num_streams, self.k, self.seed, self.stream_base, self._kind):
-                    raise N.IllegalArgumentException("merge needs states of the same shape, seed, stream_base and hash")
-            if len(others) == 1:
-                part_keys, part_hashes, part_counts = others[0].keys, others[0].hashes, others[0].counts
-            else:
-                part_keys = torch.stack([o.keys for o in others])
-                part_hashes = torch.stack([o.hashes for o in others])
-                part_counts = torch.stack([o.counts for o in others])
-        if part_hashes is None or part_counts is None:
-            raise N.NullPointerException("merge needs part_keys, part_hashes and part_counts")
-        S, k = self.num_streams, self.k
-        if part_keys.dim() == 2:
-            part_keys, part_hashes, part_counts = part_keys[None], part_hashes[None], part_counts[None]
-        P = part_keys.shape[0]
-        if tuple(part_keys.shape) != (P, S, k) or tuple(part_hashes.shape) != (P, S, k) or tuple(part_counts.shape) != (P, S):
-            raise N.IllegalArgumentException(f"parts must be shaped (P, {S}, {k}), (P, {S}, {k}), (P, {S})")
-        if part_keys.dtype != self.keys.dtype or part_hashes.dtype != torch.int64 or part_counts.dtype != torch.int64:
-            raise N.IllegalArgumentException("part keys must have the state's dtype, hashes and counts must be int64")
-        dev = self.keys.device
-        if part_keys.device != dev or part_hashes.device != dev or part_counts.device != dev:
-            raise N.IllegalArgumentException("parts must live on the state's device")
-        if P == 0 or S == 0:
-            return self
-        part_keys, part_hashes, part_counts = part_keys.contiguous(), part_hashes.contiguous(), part_counts.contiguous()
-        N.check(L.rsv_distinct_segmented_merge(
-            C.c_void_p(part_keys.data_ptr()), C.c_void_p(part_hashes.data_ptr()), C.c_void_p(part_counts.data_ptr()),
-            P, S, part_keys.element_size(), k, C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.hashes.data_ptr()),
-            C.c_void_p(self.counts.data_ptr()), _stream_ptr(torch, dev)))
-        return self
+        return self._merge(torch, L.rsv_distinct_segmented_merge, SegmentedDistinct, (part_keys, part_hashes, part_counts))
 
 
-class SegmentedDistinctRows:
+class SegmentedDistinctRows(_SegmentedState):
     """SegmentedDistinct over fixed-width byte keys (java.util.UUID, case classes of primitives).
 
     The state is three device tensors in distinct_segmented_rows' layout: rows uint8 (S, k, width),
@@ -319,6 +402,17 @@ class SegmentedDistinctRows:
     Everything runs on torch's current stream.
     """
 
+    _NAME, _LONG, _MAX_K = "SegmentedDistinctRows", "SegmentedDistinct", _SEG_DISTINCT_MAX_K
+    _TENSORS, _SAME = ("rows", "hashes", "counts"), "width, seed, stream_base and hash"
+
+    def _identity(self):
+        return self.num_streams, self.k, self.width, self.seed, self.stream_base, self._hash
+
+    def _check_width(self, width) -> None:
+        super()._check_width(width)
+        if self._hash == "default" and width != 16:
+            raise N.ReservoirError("hash='default' is UUID.hashCode: width 16 only")
+
     def __init__(self, num_streams: int, k: int, width: int, seed: int, stream_base: int = 0, hash: str = "default",
                  device=None):
         import torch
@@ -326,25 +420,8 @@ class SegmentedDistinctRows:
         N.load()
         if hash not in ("default", "precomputed"):
             raise N.IllegalArgumentException(f"unknown hash {hash!r}")
-        if num_streams < 0:
-            raise N.IllegalArgumentException("negative stream count")
-        if k <= 0:
-            raise N.IllegalArgumentException("k out of range")
-        if k > _SEG_DISTINCT_MAX_K:
-            raise N.ReservoirError(
-                f"SegmentedDistinctRows holds k <= {_SEG_DISTINCT_MAX_K} per stream; use separate handles beyond")
-        if width in (4, 8):
-            raise N.ReservoirError("SegmentedDistinctRows takes byte keys; SegmentedDistinct takes 4- and 8-byte keys")
-        if width < 16 or width > 256 or width % 8:
-            raise N.IllegalArgumentException("width must be a multiple of 8 in 16..256")
-        if hash == "default" and width != 16:
-            raise N.ReservoirError("hash='default' is UUID.hashCode: width 16 only")
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if dev.type != "cuda":
-            raise N.IllegalArgumentException("the state lives on the device")
-        self.num_streams, self.k, self.width = int(num_streams), int(k), int(width)
-        self.seed, self.stream_base = seed & (2**64 - 1), stream_base & (2**64 - 1)
         self._hash = hash
+        dev = self._init_state(torch, num_streams, k, seed, stream_base, device, width)
         self.rows = torch.empty((self.num_streams, self.k, self.width), dtype=torch.uint8, device=dev)
         self.hashes = torch.empty((self.num_streams, self.k), dtype=torch.int64, device=dev)
         self.counts = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
@@ -362,19 +439,11 @@ class SegmentedDistinctRows:
         if hashes is not None and self._hash != "precomputed":
             raise N.IllegalArgumentException("hashes= needs hash='precomputed'")
         rows, offsets, hashes = _segd_rows_inputs(torch, rows, offsets, self._hash, hashes)
-        if rows.shape[1] * rows.element_size() != self.width:
-            raise N.IllegalArgumentException(f"rows must hold {self.width} bytes each")
-        if rows.device != self.rows.device or offsets.device != self.rows.device:
-            raise N.IllegalArgumentException("rows and offsets must live on the state's device")
-        B = offsets.numel() - 1
-        if B <= 0:
+        self._check_same_device(rows, offsets)
+        seg = self._segments(torch, offsets, check_ids, stream_ids)
+        if seg is None:
             return self
-        if stream_ids is not None:
-            if not stream_ids.is_cuda or stream_ids.dtype != torch.int64 or stream_ids.numel() != B:
-                raise N.IllegalArgumentException("stream_ids must be an int64 device tensor, one per segment")
-            stream_ids = stream_ids.contiguous()
-            if check_ids:
-                _check_stream_ids(torch, stream_ids, self.num_streams)
+        B, stream_ids = seg
         N.check(L.rsv_distinct_segmented_rows_update(
             C.c_void_p(rows.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
             C.c_void_p(offsets.data_ptr()), C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
@@ -394,48 +463,14 @@ class SegmentedDistinctRows:
         import torch
 
         L = N.load()
-        if isinstance(part_rows, SegmentedDistinctRows):
-            others = [part_rows] + [o for o in (part_hashes, part_counts) if o is not None]
-            mine = (self.num_streams, self.k, self.width, self.seed, self.stream_base, self._hash)
-            for o in others:
-                if not isinstance(o, SegmentedDistinctRows) or (
-                        o.num_streams, o.k, o.width, o.seed, o.stream_base, o._hash) != mine:
-                    raise N.IllegalArgumentException(
-                        "merge needs states of the same shape, width, seed, stream_base and hash")
-            if len(others) == 1:
-                part_rows, part_hashes, part_counts = others[0].rows, others[0].hashes, others[0].counts
-            else:
-                part_rows = torch.stack([o.rows for o in others])
-                part_hashes = torch.stack([o.hashes for o in others])
-                part_counts = torch.stack([o.counts for o in others])
-        if part_hashes is None or part_counts is None:
-            raise N.NullPointerException("merge needs part_rows, part_hashes and part_counts")
-        S, k, W = self.num_streams, self.k, self.width
-        if part_rows.dim() == 3:
-            part_rows, part_hashes, part_counts = part_rows[None], part_hashes[None], part_counts[None]
-        P = part_rows.shape[0]
-        if part_rows.dtype != torch.uint8 or part_hashes.dtype != torch.int64 or part_counts.dtype != torch.int64:
-            raise N.IllegalArgumentException("part rows must be uint8, hashes and counts int64")
-        if (tuple(part_rows.shape) != (P, S, k, W) or tuple(part_hashes.shape) != (P, S, k)
-                or tuple(part_counts.shape) != (P, S)):
-            raise N.IllegalArgumentException(f"parts must be shaped (P, {S}, {k}, {W}), (P, {S}, {k}), (P, {S})")
-        dev = self.rows.device
-        if part_rows.device != dev or part_hashes.device != dev or part_counts.device != dev:
-            raise N.IllegalArgumentException("parts must live on the state's device")
-        if P == 0 or S == 0:
-            return self
-        part_rows, part_hashes, part_counts = part_rows.contiguous(), part_hashes.contiguous(), part_counts.contiguous()
-        N.check(L.rsv_distinct_segmented_rows_merge(
-            C.c_void_p(part_rows.data_ptr()), C.c_void_p(part_hashes.data_ptr()), C.c_void_p(part_counts.data_ptr()),
-            P, S, W, k, C.c_void_p(self.rows.data_ptr()), C.c_void_p(self.hashes.data_ptr()),
-            C.c_void_p(self.counts.data_ptr()), _stream_ptr(torch, dev)))
-        return self
+        return self._merge(torch, L.rsv_distinct_segmented_rows_merge, SegmentedDistinctRows,
+                           (part_rows, part_hashes, part_counts))
 
 
 _SEG_SAMPLE_STATE_MAX_K = 15104  # rsv_internal.h kSegSampleStateMaxK
 
 
-class SegmentedSampler:
+class SegmentedSampler(_SegmentedState):
     """S long-lived Sampler.apply streams advanced by one launch per batch (K2 resumed).
 
     The state is three device tensors: keys (S, k); idx (S, k), the global index of each slot's
@@ -447,6 +482,12 @@ class SegmentedSampler:
     a slot with idx -1 is empty whatever its key holds.  Everything runs on torch's current stream.
     """
 
+    _NAME, _TENSORS, _MAX_K = "SegmentedSampler", ("keys", "idx", "next"), _SEG_SAMPLE_STATE_MAX_K
+    _SAME = "seed and stream_base"
+
+    def _identity(self):
+        return self.num_streams, self.k, self.seed, self.stream_base
+
     def __init__(self, num_streams: int, k: int, seed: int, stream_base: int = 0, dtype=None, device=None):
         import torch
 
@@ -454,18 +495,7 @@ class SegmentedSampler:
         dtype = torch.int64 if dtype is None else dtype
         if dtype not in (torch.int64, torch.int32):
             raise N.IllegalArgumentException("keys must be int64/int32")
-        if num_streams < 0:
-            raise N.IllegalArgumentException("negative stream count")
-        if k <= 0:
-            raise N.IllegalArgumentException("k out of range")
-        if k > _SEG_SAMPLE_STATE_MAX_K:
-            raise N.ReservoirError(
-                f"SegmentedSampler holds k <= {_SEG_SAMPLE_STATE_MAX_K} per stream; use separate handles beyond")
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if dev.type != "cuda":
-            raise N.IllegalArgumentException("the state lives on the device")
-        self.num_streams, self.k = int(num_streams), int(k)
-        self.seed, self.stream_base = seed & (2**64 - 1), stream_base & (2**64 - 1)
+        dev = self._init_state(torch, num_streams, k, seed, stream_base, device)
         self.keys = torch.empty((self.num_streams, self.k), dtype=dtype, device=dev)
         self.idx = torch.full((self.num_streams, self.k), -1, dtype=torch.int64, device=dev)
         self.next = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
@@ -492,29 +522,19 @@ class SegmentedSampler:
             raise N.IllegalArgumentException("keys and offsets must be device tensors")
         if keys.dtype != self.keys.dtype or offsets.dtype != torch.int64:
             raise N.IllegalArgumentException("keys must have the state's dtype and offsets must be int64")
-        dev = self.keys.device
-        if keys.device != dev or offsets.device != dev:
-            raise N.IllegalArgumentException("keys and offsets must live on the state's device")
+        self._check_same_device(keys, offsets)
         keys, offsets = keys.contiguous(), offsets.contiguous()
-        B = offsets.numel() - 1
-        if B <= 0:
+        seg = self._segments(torch, offsets, check_ids, stream_ids, bases=bases)
+        if seg is None:
             return self
-        for name, t in (("stream_ids", stream_ids), ("bases", bases)):
-            if t is not None and (not t.is_cuda or t.dtype != torch.int64 or t.numel() != B or t.device != dev):
-                raise N.IllegalArgumentException(f"{name} must be an int64 device tensor, one per segment")
-        if stream_ids is not None:
-            stream_ids = stream_ids.contiguous()
-            if check_ids:
-                _check_stream_ids(torch, stream_ids, self.num_streams)
-        if bases is not None:
-            bases = bases.contiguous()
+        B, stream_ids, bases = seg
         N.check(L.rsv_sample_segmented_update(
             C.c_void_p(keys.data_ptr()), C.c_void_p(offsets.data_ptr()),
             C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
             C.c_void_p(bases.data_ptr()) if bases is not None else None,
             B, self.num_streams, keys.element_size(), self.k, self.seed, self.stream_base,
             C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.idx.data_ptr()), C.c_void_p(self.next.data_ptr()),
-            _stream_ptr(torch, dev)))
+            _stream_ptr(torch, self.keys.device)))
         return self
 
     def merge(self, part_keys, part_idx=None, part_next=None):
@@ -528,55 +548,12 @@ class SegmentedSampler:
         import torch
 
         L = N.load()
-        if isinstance(part_keys, SegmentedSampler):
-            others = [part_keys] + [o for o in (part_idx, part_next) if o is not None]
-            for o in others:
-                if not isinstance(o, SegmentedSampler) or (o.num_streams, o.k, o.seed, o.stream_base) != (
-                        self.num_streams, self.k, self.seed, self.stream_base):
-                    raise N.IllegalArgumentException("merge needs states of the same shape, seed and stream_base")
-            if len(others) == 1:
-                part_keys, part_idx, part_next = others[0].keys, others[0].idx, others[0].next
-            else:
-                part_keys = torch.stack([o.keys for o in others])
-                part_idx = torch.stack([o.idx for o in others])
-                part_next = torch.stack([o.next for o in others])
-        if part_idx is None or part_next is None:
-            raise N.NullPointerException("merge needs part_keys, part_idx and part_next")
-        S, k = self.num_streams, self.k
-        if part_keys.dim() == 2:
-            part_keys, part_idx, part_next = part_keys[None], part_idx[None], part_next[None]
-        P = part_keys.shape[0]
-        if tuple(part_keys.shape) != (P, S, k) or tuple(part_idx.shape) != (P, S, k) or tuple(part_next.shape) != (P, S):
-            raise N.IllegalArgumentException(f"parts must be shaped (P, {S}, {k}), (P, {S}, {k}), (P, {S})")
-        if part_keys.dtype != self.keys.dtype or part_idx.dtype != torch.int64 or part_next.dtype != torch.int64:
-            raise N.IllegalArgumentException("part keys must have the state's dtype, idx and next must be int64")
-        dev = self.keys.device
-        if part_keys.device != dev or part_idx.device != dev or part_next.device != dev:
-            raise N.IllegalArgumentException("parts must live on the state's device")
-        if P == 0 or S == 0:
-            return self
-        part_keys, part_idx, part_next = part_keys.contiguous(), part_idx.contiguous(), part_next.contiguous()
-        N.check(L.rsv_sample_segmented_merge(
-            C.c_void_p(part_keys.data_ptr()), C.c_void_p(part_idx.data_ptr()), C.c_void_p(part_next.data_ptr()),
-            P, S, part_keys.element_size(), k, C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.idx.data_ptr()),
-            C.c_void_p(self.next.data_ptr()), _stream_ptr(torch, dev)))
-        return self
+        return self._merge(torch, L.rsv_sample_segmented_merge, SegmentedSampler, (part_keys, part_idx, part_next))
 
 
 def _seg_rows_inputs(torch, rows, offsets):
     """rows / offsets of a K2 call over byte keys, checked and contiguous; returns (rows, offsets, width)."""
-    if not (rows.is_cuda and offsets.is_cuda):
-        raise N.IllegalArgumentException("rows and offsets must be device tensors")
-    if rows.dim() != 2 or rows.dtype not in (torch.uint8, torch.int64) or offsets.dtype != torch.int64:
-        raise N.IllegalArgumentException("rows must be 2-D uint8 or int64 (one key per row) and offsets int64")
-    return rows.contiguous(), offsets.contiguous(), rows.shape[1] * rows.element_size()
-
-
-def _check_rows_width(what: str, long_what: str, width: int) -> None:
-    if width in (4, 8):
-        raise N.ReservoirError(f"{what} takes byte keys; {long_what} takes 4- and 8-byte keys")
-    if width < 16 or width > 256 or width % 8:
-        raise N.IllegalArgumentException("width must be a multiple of 8 in 16..256")
+    return _rows_inputs(torch, rows, offsets, (torch.uint8, torch.int64))
 
 
 def sample_segmented_rows(rows, offsets, k: int, seed: int, stream_base: int = 0):
@@ -607,7 +584,7 @@ def sample_segmented_rows(rows, offsets, k: int, seed: int, stream_base: int = 0
     return out, counts
 
 
-class SegmentedSamplerRows:
+class SegmentedSamplerRows(_SegmentedState):
     """SegmentedSampler over fixed-width byte keys (java.util.UUID, case classes of primitives).
 
     The state is three device tensors: rows uint8 (S, k, width); idx (S, k), the global index of each
@@ -619,23 +596,17 @@ class SegmentedSamplerRows:
     of 8 in 16..256.  Everything runs on torch's current stream.
     """
 
+    _NAME, _LONG, _MAX_K = "SegmentedSamplerRows", "SegmentedSampler", _SEG_SAMPLE_STATE_MAX_K
+    _TENSORS, _SAME = ("rows", "idx", "next"), "width, seed and stream_base"
+
+    def _identity(self):
+        return self.num_streams, self.k, self.width, self.seed, self.stream_base
+
     def __init__(self, num_streams: int, k: int, width: int, seed: int, stream_base: int = 0, device=None):
         import torch
 
         N.load()
-        if num_streams < 0:
-            raise N.IllegalArgumentException("negative stream count")
-        if k <= 0:
-            raise N.IllegalArgumentException("k out of range")
-        if k > _SEG_SAMPLE_STATE_MAX_K:
-            raise N.ReservoirError(
-                f"SegmentedSamplerRows holds k <= {_SEG_SAMPLE_STATE_MAX_K} per stream; use separate handles beyond")
-        _check_rows_width("SegmentedSamplerRows", "SegmentedSampler", width)
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if dev.type != "cuda":
-            raise N.IllegalArgumentException("the state lives on the device")
-        self.num_streams, self.k, self.width = int(num_streams), int(k), int(width)
-        self.seed, self.stream_base = seed & (2**64 - 1), stream_base & (2**64 - 1)
+        dev = self._init_state(torch, num_streams, k, seed, stream_base, device, width)
         self.rows = torch.empty((self.num_streams, self.k, self.width), dtype=torch.uint8, device=dev)
         self.idx = torch.full((self.num_streams, self.k), -1, dtype=torch.int64, device=dev)
         self.next = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
@@ -656,30 +627,18 @@ class SegmentedSamplerRows:
 
         L = N.load()
         rows, offsets, W = _seg_rows_inputs(torch, rows, offsets)
-        if W != self.width:
-            raise N.IllegalArgumentException(f"rows must hold {self.width} bytes each")
-        dev = self.rows.device
-        if rows.device != dev or offsets.device != dev:
-            raise N.IllegalArgumentException("rows and offsets must live on the state's device")
-        B = offsets.numel() - 1
-        if B <= 0:
+        self._check_same_device(rows, offsets)
+        seg = self._segments(torch, offsets, check_ids, stream_ids, bases=bases)
+        if seg is None:
             return self
-        for name, t in (("stream_ids", stream_ids), ("bases", bases)):
-            if t is not None and (not t.is_cuda or t.dtype != torch.int64 or t.numel() != B or t.device != dev):
-                raise N.IllegalArgumentException(f"{name} must be an int64 device tensor, one per segment")
-        if stream_ids is not None:
-            stream_ids = stream_ids.contiguous()
-            if check_ids:
-                _check_stream_ids(torch, stream_ids, self.num_streams)
-        if bases is not None:
-            bases = bases.contiguous()
+        B, stream_ids, bases = seg
         N.check(L.rsv_sample_segmented_rows_update(
             C.c_void_p(rows.data_ptr()), C.c_void_p(offsets.data_ptr()),
             C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
             C.c_void_p(bases.data_ptr()) if bases is not None else None,
             B, self.num_streams, W, self.k, self.seed, self.stream_base,
             C.c_void_p(self.rows.data_ptr()), C.c_void_p(self.idx.data_ptr()), C.c_void_p(self.next.data_ptr()),
-            _stream_ptr(torch, dev)))
+            _stream_ptr(torch, self.rows.device)))
         return self
 
     def merge(self, part_rows, part_idx=None, part_next=None):
@@ -693,41 +652,8 @@ class SegmentedSamplerRows:
         import torch
 
         L = N.load()
-        if isinstance(part_rows, SegmentedSamplerRows):
-            others = [part_rows] + [o for o in (part_idx, part_next) if o is not None]
-            mine = (self.num_streams, self.k, self.width, self.seed, self.stream_base)
-            for o in others:
-                if not isinstance(o, SegmentedSamplerRows) or (
-                        o.num_streams, o.k, o.width, o.seed, o.stream_base) != mine:
-                    raise N.IllegalArgumentException("merge needs states of the same shape, width, seed and stream_base")
-            if len(others) == 1:
-                part_rows, part_idx, part_next = others[0].rows, others[0].idx, others[0].next
-            else:
-                part_rows = torch.stack([o.rows for o in others])
-                part_idx = torch.stack([o.idx for o in others])
-                part_next = torch.stack([o.next for o in others])
-        if part_idx is None or part_next is None:
-            raise N.NullPointerException("merge needs part_rows, part_idx and part_next")
-        S, k, W = self.num_streams, self.k, self.width
-        if part_rows.dim() == 3:
-            part_rows, part_idx, part_next = part_rows[None], part_idx[None], part_next[None]
-        P = part_rows.shape[0]
-        if part_rows.dtype != torch.uint8 or part_idx.dtype != torch.int64 or part_next.dtype != torch.int64:
-            raise N.IllegalArgumentException("part rows must be uint8, idx and next int64")
-        if (tuple(part_rows.shape) != (P, S, k, W) or tuple(part_idx.shape) != (P, S, k)
-                or tuple(part_next.shape) != (P, S)):
-            raise N.IllegalArgumentException(f"parts must be shaped (P, {S}, {k}, {W}), (P, {S}, {k}), (P, {S})")
-        dev = self.rows.device
-        if part_rows.device != dev or part_idx.device != dev or part_next.device != dev:
-            raise N.IllegalArgumentException("parts must live on the state's device")
-        if P == 0 or S == 0:
-            return self
-        part_rows, part_idx, part_next = part_rows.contiguous(), part_idx.contiguous(), part_next.contiguous()
-        N.check(L.rsv_sample_segmented_rows_merge(
-            C.c_void_p(part_rows.data_ptr()), C.c_void_p(part_idx.data_ptr()), C.c_void_p(part_next.data_ptr()),
-            P, S, W, k, C.c_void_p(self.rows.data_ptr()), C.c_void_p(self.idx.data_ptr()),
-            C.c_void_p(self.next.data_ptr()), _stream_ptr(torch, dev)))
-        return self
+        return self._merge(torch, L.rsv_sample_segmented_rows_merge, SegmentedSamplerRows,
+                           (part_rows, part_idx, part_next))
 
 
 def replay_events(keys, base_index: int, ev_pos, ev_slot, k: int, reservoir=None):

@@ -106,8 +106,21 @@ __device__ __forceinline__ uint64_t draw_j(uint32_t b, uint32_t Lh, uint32_t Ll,
     return __umul64hi(((uint64_t)Uh << 32) | Ul, i1);
 }
 
-// the workgroup's table of T for the first kLut blocks, as k2_segmented and k2_segmented_wg build theirs
-// (the resumed kernels call this; the stateless ones keep their loops so that their code stays as measured)
+// wave-uniform 64-bit value in scalar registers
+__device__ __forceinline__ int64_t uniform64(int64_t v) {
+    return ((int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v)) |
+           ((int64_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32);
+}
+
+// The stateless slot rule: slot j of the stream at [off, off + len) takes the element at its last writer wi
+// (0: no draw hit it), else the stream's own element j, else none (-1: the slot is zero).
+__device__ __forceinline__ int64_t slot_source(uint64_t wi, uint32_t j, int64_t off, int64_t len) {
+    return wi ? off + (int64_t)wi : ((int64_t)j < len ? off + (int64_t)j : -1);
+}
+
+// the workgroup's table of T for the first kLut blocks, at the start of its LDS (k2_segmented spells it out)
+// (32-bit division while the dividend fits: the table is rebuilt by every workgroup, and the
+// 64-bit form was ~2.5 % of a C3 launch at 32768 workgroups)
 __device__ __forceinline__ void build_lut(uint16_t* lut, uint64_t dense_lim) {
     for (uint32_t g = threadIdx.x; g < kLut; g += blockDim.x) {
         const uint64_t i0 = (uint64_t)g << 4;
@@ -127,7 +140,26 @@ struct Wave {
     uint32_t lane, k, k0, k1;
     uint64_t dense_lim;
     uint32_t fifo_cap;  // bulk appends while pending + new <= fifo_cap (<= the FIFO size; tests lower it)
+    uint32_t wave;      // the wave's index in its workgroup, in a scalar register
 };
+
+// The frame every kernel opens with, over the workgroup's dynamic LDS (its first kLutBytes hold build_lut's
+// table): this wave's stash [kRing][64] x 16 B and FIFO kQCap x u16 at base, and the winner table at tab.
+__device__ __forceinline__ Wave make_wave(unsigned char* lds, unsigned char* base, void* tab, uint32_t wave,
+                                          uint32_t lane, uint32_t k, uint32_t k0, uint32_t k1, uint32_t fifo_cap) {
+    return Wave{(u32x4*)base, (uint16_t*)(base + kStashBytes), tab, (const uint16_t*)lds, lane, k, k0, k1,
+                256ull * k, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap), wave};
+}
+
+// the wave form (one wave per stream): per wave stash | FIFO | last-writer table k x (u32 | u64).
+// The wave index is a scalar, so stream numbers and the offsets[] loads that follow from it are wave-uniform
+// (scalar loads, counted by lgkmcnt -- never waited for together with a deferred key gather).
+__device__ __forceinline__ Wave wave_frame(unsigned char* lds, uint32_t k, uint32_t k0, uint32_t k1,
+                                           uint32_t fifo_cap) {
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes + (size_t)k * 8);
+    return make_wave(lds, base, base + kStashBytes + kQueueBytes, wave, lane, k, k0, k1, fifo_cap);
+}
 
 // One stream on one wave.  SMALL: n < 2^27 -- 32-bit indices, u32 winner table, and Philox counters
 // whose high words are wave-uniform (level 0: g < 2^32; level 1: i/2 < 2^32).
@@ -302,6 +334,8 @@ __device__ __forceinline__ int64_t k2_stream(const Wave& W, const KeyT* __restri
         return at;
     }
     for (uint32_t j = lane; j < k; j += 64) {
+        // slot_source, spelled out: through the helper k2_segmented (this loop's only caller) compiles to
+        // another register allocation, and its stateless launch measured 0.2-0.7 % slower
         const IdxT wi = tab[j];
         o[j] = wi ? keys[off + (int64_t)wi] : ((int64_t)j < len ? keys[off + j] : (KeyT)0);
     }
@@ -316,10 +350,11 @@ __global__ __launch_bounds__(64 * kWaves) void k2_segmented(const KeyT* __restri
                                                             KeyT* __restrict__ out, int64_t* __restrict__ counts,
                                                             uint32_t fifo_cap = kQCap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    // build_lut, written out: the call moves this kernel's kernel-argument loads and renumbers its scalar
+    // registers, and with that its stateless launch measured 0.2-0.7 % slower; with the loop
+    // here the kernel is the measured one instruction for instruction
     uint16_t* lut = (uint16_t*)lds;
     const uint64_t dense_lim = 256ull * k;
-    // (32-bit division while the dividend fits: the table is rebuilt by every workgroup, and the
-    // 64-bit form was ~2.5 % of a C3 launch at 32768 workgroups)
     for (uint32_t g = threadIdx.x; g < kLut; g += blockDim.x) {
         const uint64_t i0 = (uint64_t)g << 4;
         uint32_t T;
@@ -329,18 +364,10 @@ __global__ __launch_bounds__(64 * kWaves) void k2_segmented(const KeyT* __restri
         lut[g] = (uint16_t)T;
     }
     __syncthreads();
-    // wave index in a scalar register: stream numbers and offsets[] loads below are wave-uniform
-    // (scalar loads, counted by lgkmcnt -- never waited for together with the deferred key gather)
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    // per wave: stash [kRing][64] x 16 B | FIFO kQCap x u16 | last-writer table k x (u32 | u64)
-    constexpr size_t qbytes = kQueueBytes, sbytes = kStashBytes;
-    const size_t tbytes = (size_t)k * 8;
-    unsigned char* base = lds + kLutBytes + (size_t)wave * (sbytes + qbytes + tbytes);
-    void* tab = base + sbytes + qbytes;
-    const Wave W{(u32x4*)base, (uint16_t*)(base + sbytes), tab, lut, lane, k,
-                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    const Wave W = wave_frame(lds, k, k0, k1, fifo_cap);
+    const uint32_t lane = W.lane;
     const int64_t wave_stride = (int64_t)gridDim.x * kWaves;
-    int64_t s = (int64_t)blockIdx.x * kWaves + wave;
+    int64_t s = (int64_t)blockIdx.x * kWaves + W.wave;
     int64_t off = 0, end = 0;
     if (s < S) {
         off = offsets[s];
@@ -358,10 +385,8 @@ __global__ __launch_bounds__(64 * kWaves) void k2_segmented(const KeyT* __restri
         const __attribute__((address_space(4))) int64_t* co =
             (const __attribute__((address_space(4))) int64_t*)offsets;
         auto one = [&](int u) {
-            off = ((int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)off)) |
-                  ((int64_t)__builtin_amdgcn_readfirstlane((int)(off >> 32)) << 32);
-            end = ((int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)end)) |
-                  ((int64_t)__builtin_amdgcn_readfirstlane((int)(end >> 32)) << 32);
+            off = uniform64(off);
+            end = uniform64(end);
             const int64_t len = end - off;
             const int64_t s_pf = std::min<int64_t>(s + wave_stride, S - 1);
             // scalar loads (constant address space: offsets[] is read-only here), so that no
@@ -403,10 +428,8 @@ __global__ __launch_bounds__(64 * kWaves) void k2_segmented(const KeyT* __restri
     }
     for (; s < S; s += wave_stride) {
         // wave-uniform stream bounds (scalar registers: uniform control flow below)
-        off = ((int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)off)) |
-              ((int64_t)__builtin_amdgcn_readfirstlane((int)(off >> 32)) << 32);
-        end = ((int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)end)) |
-              ((int64_t)__builtin_amdgcn_readfirstlane((int)(end >> 32)) << 32);
+        off = uniform64(off);
+        end = uniform64(end);
         const int64_t len = end - off;
         const int64_t s_next = s + wave_stride;
         // prefetch, in flight during this stream's work; unconditional (clamped index), so the
@@ -434,10 +457,25 @@ __global__ __launch_bounds__(64 * kWaves) void k2_segmented(const KeyT* __restri
 // the row's idx -- the largest index per slot wins, whatever order the segments arrive in.  Segments
 // with an id outside [0, S), a negative base or no elements are skipped.
 
-// wave-uniform 64-bit value in scalar registers
-__device__ __forceinline__ int64_t uniform64(int64_t v) {
-    return ((int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v)) |
-           ((int64_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32);
+
+// segment b of an update: keys[off, off + len) are the indices [n0, nend) of state row r
+struct Segment {
+    int64_t off, len, r, n0, nend;
+};
+
+// Reads segment b's header; false: the segment is skipped (empty, an id outside [0, S), a negative base).
+// Every thread of the wave -- in the workgroup form, of the workgroup -- reads the same words, and reads
+// state_next[r] before anyone writes it.
+__device__ __forceinline__ bool read_segment(Segment& g, const int64_t* offsets, const int64_t* ids,
+                                             const int64_t* bases, const int64_t* state_next, int64_t b, int64_t S) {
+    g.off = uniform64(offsets[b]);
+    g.len = uniform64(offsets[b + 1]) - g.off;
+    g.r = ids ? uniform64(ids[b]) : b;
+    if (g.len <= 0 || g.r < 0 || g.r >= S) return false;
+    g.n0 = uniform64(bases ? bases[b] : state_next[g.r]);
+    if (g.n0 < 0) return false;
+    g.nend = g.n0 + g.len;
+    return true;
 }
 
 // slot j of a row: winner w (0: none) of the segment [n0, nend) at keys[off ...]
@@ -460,34 +498,27 @@ __global__ __launch_bounds__(64 * kWaves) void k2_segmented_update(
     uint64_t stream_base, KeyT* __restrict__ state_keys, int64_t* __restrict__ state_idx,
     int64_t* __restrict__ state_next, uint32_t fifo_cap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    uint16_t* lut = (uint16_t*)lds;
-    const uint64_t dense_lim = 256ull * k;
-    build_lut(lut, dense_lim);
+    build_lut((uint16_t*)lds, 256ull * k);
     __syncthreads();
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes + (size_t)k * 8);
-    void* tab = base + kStashBytes + kQueueBytes;
-    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), tab, lut, lane, k,
-                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    const Wave W = wave_frame(lds, k, k0, k1, fifo_cap);
+    const uint32_t lane = W.lane;
     const int64_t wave_stride = (int64_t)gridDim.x * kWaves;
-    for (int64_t b = (int64_t)blockIdx.x * kWaves + wave; b < B; b += wave_stride) {
-        const int64_t off = uniform64(offsets[b]), len = uniform64(offsets[b + 1]) - off;
-        const int64_t r = ids ? uniform64(ids[b]) : b;
-        if (len <= 0 || r < 0 || r >= S) continue;
-        const int64_t n0 = uniform64(bases ? bases[b] : state_next[r]);
-        if (n0 < 0) continue;
-        const int64_t nend = n0 + len;
-        const uint64_t stream = stream_base + (uint64_t)r;
-        KeyT* sk = state_keys + r * (int64_t)k;
-        int64_t* si = state_idx + r * (int64_t)k;
-        if (nend < kSmallLen) {
-            k2_stream<KeyT, true, false, true>(W, keys, off, len, stream, nullptr, n0);
-            for (uint32_t j = lane; j < k; j += 64) update_slot(keys, off, n0, nend, j, ((const uint32_t*)tab)[j], sk, si);
+    for (int64_t b = (int64_t)blockIdx.x * kWaves + W.wave; b < B; b += wave_stride) {
+        Segment g;
+        if (!read_segment(g, offsets, ids, bases, state_next, b, S)) continue;
+        const uint64_t stream = stream_base + (uint64_t)g.r;
+        KeyT* sk = state_keys + g.r * (int64_t)k;
+        int64_t* si = state_idx + g.r * (int64_t)k;
+        if (g.nend < kSmallLen) {
+            k2_stream<KeyT, true, false, true>(W, keys, g.off, g.len, stream, nullptr, g.n0);
+            for (uint32_t j = lane; j < k; j += 64)
+                update_slot(keys, g.off, g.n0, g.nend, j, ((const uint32_t*)W.tab)[j], sk, si);
         } else {
-            k2_stream<KeyT, false, false, true>(W, keys, off, len, stream, nullptr, n0);
-            for (uint32_t j = lane; j < k; j += 64) update_slot(keys, off, n0, nend, j, ((const uint64_t*)tab)[j], sk, si);
+            k2_stream<KeyT, false, false, true>(W, keys, g.off, g.len, stream, nullptr, g.n0);
+            for (uint32_t j = lane; j < k; j += 64)
+                update_slot(keys, g.off, g.n0, g.nend, j, ((const uint64_t*)W.tab)[j], sk, si);
         }
-        if (lane == 0 && state_next[r] < nend) state_next[r] = nend;
+        if (lane == 0 && state_next[g.r] < g.nend) state_next[g.r] = g.nend;
         __builtin_amdgcn_wave_barrier();  // the table is read before the next segment zeroes it
     }
 }
@@ -507,6 +538,18 @@ constexpr uint32_t kWGMinK = 512;  // smaller k keep one wave per stream (C3: k 
 
 __host__ __device__ constexpr size_t lds_bytes_wg(uint32_t k, size_t tab_entry, bool GT) {
     return kLutBytes + (size_t)kWavesWG * (kStashBytes + kQueueBytes) + (GT ? 0 : (size_t)k * tab_entry);
+}
+
+// the workgroup form's frame: per wave stash | FIFO, then the one table the waves share -- after the
+// eight waves' rings, or (GT) the workgroup's slice of the global scratch gtab
+template <bool GT = false, typename TabT = unsigned long long>
+__device__ __forceinline__ Wave wg_frame(unsigned char* lds, uint32_t k, uint32_t k0, uint32_t k1, uint32_t fifo_cap,
+                                         TabT* gtab = nullptr) {
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes);
+    TabT* tab = GT ? gtab + (size_t)blockIdx.x * k
+                   : (TabT*)(lds + kLutBytes + (size_t)kWavesWG * (kStashBytes + kQueueBytes));
+    return make_wave(lds, base, tab, wave, lane, k, k0, k1, fifo_cap);
 }
 
 // RES (k2_segmented_update_wg): the segment holds the stream's indices [n0, n0 + len), as in k2_stream.
@@ -640,22 +683,9 @@ __global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_wg(const KeyT* __r
                                                                  int64_t* __restrict__ counts, uint32_t fifo_cap,
                                                                  TabT* __restrict__ gtab) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    uint16_t* lut = (uint16_t*)lds;
-    const uint64_t dense_lim = 256ull * k;
-    for (uint32_t g = threadIdx.x; g < kLut; g += blockDim.x) {
-        const uint64_t i0 = (uint64_t)g << 4;
-        uint32_t T;
-        if (i0 + 1 >= dense_lim) T = 0;
-        else if (dense_lim + i0 <= 0xFFFFFFFFull) T = std::min<uint32_t>(256u, (uint32_t)(dense_lim + i0) / (uint32_t)(i0 + 1));
-        else T = block_threshold(i0, dense_lim);
-        lut[g] = (uint16_t)T;
-    }
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes);
-    TabT* tab = GT ? gtab + (size_t)blockIdx.x * k
-                   : (TabT*)(lds + kLutBytes + (size_t)kWavesWG * (kStashBytes + kQueueBytes));
-    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), nullptr, lut, lane, k,
-                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    build_lut((uint16_t*)lds, 256ull * k);
+    const Wave W = wg_frame<GT>(lds, k, k0, k1, fifo_cap, gtab);
+    TabT* tab = (TabT*)W.tab;
     const uint32_t nthr = 64u * kWavesWG;
     for (int64_t s = blockIdx.x; s < S; s += gridDim.x) {
         const int64_t off = offsets[s], len = offsets[s + 1] - off;
@@ -663,8 +693,8 @@ __global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_wg(const KeyT* __r
             for (uint32_t j = threadIdx.x; j < k; j += nthr) tab[j] = 0;
         __syncthreads();  // the table is zero (GT: the previous stream's gather left it so)
         const uint64_t stream = stream_base + (uint64_t)s;
-        if (len < kSmallLen) k2_part<TabT, true, GT>(W, tab, len, stream, wave);
-        else k2_part<TabT, false, GT>(W, tab, len, stream, wave);
+        if (len < kSmallLen) k2_part<TabT, true, GT>(W, tab, len, stream, W.wave);
+        else k2_part<TabT, false, GT>(W, tab, len, stream, W.wave);
         if constexpr (GT) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // this wave's table atomics
         __syncthreads();
         if constexpr (GT) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // every wave's, before the gather
@@ -673,7 +703,8 @@ __global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_wg(const KeyT* __r
             TabT wi;
             if constexpr (GT) wi = __hip_atomic_exchange(&tab[j], (TabT)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else wi = tab[j];
-            o[j] = wi ? keys[off + (int64_t)wi] : ((int64_t)j < len ? keys[off + j] : (KeyT)0);
+            const int64_t at = slot_source(wi, j, off, len);
+            o[j] = at >= 0 ? keys[at] : (KeyT)0;
         }
         if (threadIdx.x == 0) counts[s] = len < (int64_t)k ? len : (int64_t)k;
         __syncthreads();  // the gather has read the table before the next stream zeroes it
@@ -691,49 +722,39 @@ __global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_update_wg(
     int64_t* __restrict__ state_next, uint32_t fifo_cap) {
     using TabT = unsigned long long;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    uint16_t* lut = (uint16_t*)lds;
-    const uint64_t dense_lim = 256ull * k;
-    build_lut(lut, dense_lim);
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes);
-    TabT* tab = (TabT*)(lds + kLutBytes + (size_t)kWavesWG * (kStashBytes + kQueueBytes));
-    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), nullptr, lut, lane, k,
-                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    build_lut((uint16_t*)lds, 256ull * k);
+    const Wave W = wg_frame(lds, k, k0, k1, fifo_cap);
+    TabT* tab = (TabT*)W.tab;
     const uint32_t nthr = 64u * kWavesWG;
     for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
-        // workgroup-uniform: every thread reads the same words (state_next[r] before anyone writes it)
-        const int64_t off = uniform64(offsets[b]), len = uniform64(offsets[b + 1]) - off;
-        const int64_t r = ids ? uniform64(ids[b]) : b;
-        if (len <= 0 || r < 0 || r >= S) continue;
-        const int64_t n0 = uniform64(bases ? bases[b] : state_next[r]);
-        if (n0 < 0) continue;
-        const int64_t nend = n0 + len;
+        Segment g;
+        if (!read_segment(g, offsets, ids, bases, state_next, b, S)) continue;
         for (uint32_t j = threadIdx.x; j < k; j += nthr) tab[j] = 0;
         __syncthreads();  // the table is zero, the lut built, and n0 read by every wave
-        const uint64_t stream = stream_base + (uint64_t)r;
-        if (nend < kSmallLen) k2_part<TabT, true, false, true>(W, tab, len, stream, wave, n0);
-        else k2_part<TabT, false, false, true>(W, tab, len, stream, wave, n0);
+        const uint64_t stream = stream_base + (uint64_t)g.r;
+        if (g.nend < kSmallLen) k2_part<TabT, true, false, true>(W, tab, g.len, stream, W.wave, g.n0);
+        else k2_part<TabT, false, false, true>(W, tab, g.len, stream, W.wave, g.n0);
         __syncthreads();
-        KeyT* sk = state_keys + r * (int64_t)k;
-        int64_t* si = state_idx + r * (int64_t)k;
-        for (uint32_t j = threadIdx.x; j < k; j += nthr) update_slot(keys, off, n0, nend, j, tab[j], sk, si);
-        if (threadIdx.x == 0 && state_next[r] < nend) state_next[r] = nend;
+        KeyT* sk = state_keys + g.r * (int64_t)k;
+        int64_t* si = state_idx + g.r * (int64_t)k;
+        for (uint32_t j = threadIdx.x; j < k; j += nthr) update_slot(keys, g.off, g.n0, g.nend, j, tab[j], sk, si);
+        if (threadIdx.x == 0 && state_next[g.r] < g.nend) state_next[g.r] = g.nend;
         __syncthreads();  // the write-back has read the table before the next segment zeroes it
     }
 }
 
 // rsv_sample_segmented_merge: per (row, slot) the part with the largest idx, if it beats the row's;
 // next = the max over the row and the parts.  parts: [P][S][k], [P][S][k], [P][S].
-template <typename KeyT>
-__global__ __launch_bounds__(256) void k2_segmented_merge(const KeyT* part_keys, const int64_t* part_idx,
-                                                          const int64_t* part_next, int32_t P, int64_t S, uint32_t k,
-                                                          KeyT* state_keys, int64_t* state_idx, int64_t* state_next) {
-    // (no __restrict__: a state merged into itself names the same memory twice)
+// The pick for entry t = (row, slot) of S k: the part with the largest idx if it beats the state's (-1:
+// none), and state_idx[t] takes it; the thread of a row's first slot also moves the row's next to the max.
+// Only this thread reads or writes the entry's idx.  (No __restrict__ here or in the kernels: a state merged
+// into itself names the same memory twice.)
+template <typename Move>
+__device__ __forceinline__ int32_t merge_pick(const int64_t* part_idx, const int64_t* part_next, int32_t P, int64_t S,
+                                              uint32_t k, int64_t t, int64_t* state_idx, int64_t* state_next,
+                                              Move move) {
     const int64_t total = S * (int64_t)k;
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= total) return;
-    const int64_t cur = state_idx[t];
-    int64_t best = cur;
+    int64_t best = state_idx[t];
     int32_t bp = -1;
     for (int32_t p = 0; p < P; ++p) {
         const int64_t pi = part_idx[(int64_t)p * total + t];
@@ -743,16 +764,28 @@ __global__ __launch_bounds__(256) void k2_segmented_merge(const KeyT* part_keys,
         }
     }
     if (bp >= 0) {
-        state_keys[t] = part_keys[(int64_t)bp * total + t];
+        move(bp);
         state_idx[t] = best;
     }
-    if (t % k == 0) {  // the row's first slot also takes its next
+    if (t % k == 0) {
         const int64_t r = t / k;
         const int64_t cn = state_next[r];
         int64_t n = cn;
         for (int32_t p = 0; p < P; ++p) n = std::max<int64_t>(n, part_next[(int64_t)p * S + r]);
         if (n > cn) state_next[r] = n;
     }
+    return bp;
+}
+
+template <typename KeyT>
+__global__ __launch_bounds__(256) void k2_segmented_merge(const KeyT* part_keys, const int64_t* part_idx,
+                                                          const int64_t* part_next, int32_t P, int64_t S, uint32_t k,
+                                                          KeyT* state_keys, int64_t* state_idx, int64_t* state_next) {
+    const int64_t total = S * (int64_t)k;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    merge_pick(part_idx, part_next, P, S, k, t, state_idx, state_next,
+               [&](int32_t bp) { state_keys[t] = part_keys[(int64_t)bp * total + t]; });
 }
 
 // ---- byte keys: the streams' elements are rows of W bytes (java.util.UUID: W = 16) ----------------
@@ -822,31 +855,25 @@ __global__ __launch_bounds__(64 * kWaves) void k2_segmented_rows(const unsigned 
                                                                  uint64_t stream_base, unsigned char* __restrict__ out,
                                                                  int64_t* __restrict__ counts, uint32_t fifo_cap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    uint16_t* lut = (uint16_t*)lds;
-    const uint64_t dense_lim = 256ull * k;
-    build_lut(lut, dense_lim);
+    build_lut((uint16_t*)lds, 256ull * k);
     __syncthreads();
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes + (size_t)k * 8);
-    void* tab = base + kStashBytes + kQueueBytes;
-    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), tab, lut, lane, k,
-                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    const Wave W = wave_frame(lds, k, k0, k1, fifo_cap);
+    const uint32_t lane = W.lane;
+    const void* tab = W.tab;
     const uint64_t Wb = (uint64_t)C * sizeof(G);
     const PairStep p0 = pair_step(lane, 64, C);
     const int64_t wave_stride = (int64_t)gridDim.x * kWaves;
     G pv = G{};       // DEFER: the previous stream's granule, in flight
     G* po = nullptr;  // and where it goes
-    for (int64_t s = (int64_t)blockIdx.x * kWaves + wave; s < S; s += wave_stride) {
+    for (int64_t s = (int64_t)blockIdx.x * kWaves + W.wave; s < S; s += wave_stride) {
         const int64_t off = uniform64(offsets[s]);
         const int64_t len = std::max<int64_t>(uniform64(offsets[s + 1]) - off, 0);
         const uint64_t stream = stream_base + (uint64_t)s;
         const bool small = len < kSmallLen;
         if (small) k2_stream<int64_t, true, false, true>(W, nullptr, off, len, stream, nullptr, 0);
         else k2_stream<int64_t, false, false, true>(W, nullptr, off, len, stream, nullptr, 0);
-        // slot j's row: its last writer, else row j of the stream, else none
         auto src_of = [&](uint32_t j) -> int64_t {
-            const uint64_t wi = small ? (uint64_t)((const uint32_t*)tab)[j] : ((const uint64_t*)tab)[j];
-            return wi ? off + (int64_t)wi : ((int64_t)j < len ? off + (int64_t)j : -1);
+            return slot_source(small ? (uint64_t)((const uint32_t*)tab)[j] : ((const uint64_t*)tab)[j], j, off, len);
         };
         unsigned char* o = out + (uint64_t)s * k * Wb;
         if constexpr (DEFER) {
@@ -876,15 +903,9 @@ __global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_rows_wg(
     uint32_t k0, uint32_t k1, uint64_t stream_base, unsigned char* __restrict__ out, int64_t* __restrict__ counts,
     uint32_t fifo_cap, TabT* __restrict__ gtab) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    uint16_t* lut = (uint16_t*)lds;
-    const uint64_t dense_lim = 256ull * k;
-    build_lut(lut, dense_lim);
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes);
-    TabT* tab = GTAB ? gtab + (size_t)blockIdx.x * k
-                     : (TabT*)(lds + kLutBytes + (size_t)kWavesWG * (kStashBytes + kQueueBytes));
-    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), nullptr, lut, lane, k,
-                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    build_lut((uint16_t*)lds, 256ull * k);
+    const Wave W = wg_frame<GTAB>(lds, k, k0, k1, fifo_cap, gtab);
+    TabT* tab = (TabT*)W.tab;
     const uint32_t nthr = 64u * kWavesWG;
     const uint64_t Wb = (uint64_t)C * sizeof(G);
     const PairStep p0 = pair_step(threadIdx.x, nthr, C);
@@ -895,8 +916,8 @@ __global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_rows_wg(
             for (uint32_t j = threadIdx.x; j < k; j += nthr) tab[j] = 0;
         __syncthreads();  // the table is zero (GTAB: the previous stream's second pass left it so)
         const uint64_t stream = stream_base + (uint64_t)s;
-        if (len < kSmallLen) k2_part<TabT, true, GTAB, true>(W, tab, len, stream, wave, 0);
-        else k2_part<TabT, false, GTAB, true>(W, tab, len, stream, wave, 0);
+        if (len < kSmallLen) k2_part<TabT, true, GTAB, true>(W, tab, len, stream, W.wave, 0);
+        else k2_part<TabT, false, GTAB, true>(W, tab, len, stream, W.wave, 0);
         if constexpr (GTAB) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // this wave's table atomics
         __syncthreads();
         if constexpr (GTAB) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // every wave's, before the gather
@@ -904,7 +925,7 @@ __global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_rows_wg(
             TabT wi;
             if constexpr (GTAB) wi = __hip_atomic_load(&tab[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else wi = tab[j];
-            return wi ? off + (int64_t)wi : ((int64_t)j < len ? off + (int64_t)j : -1);
+            return slot_source(wi, j, off, len);
         };
         gather_rows<G, true>(rows, out + (uint64_t)s * k * Wb, k, C, p0, src_of);
         if (threadIdx.x == 0) counts[s] = len < (int64_t)k ? len : (int64_t)k;
@@ -942,42 +963,34 @@ __global__ __launch_bounds__(64 * kWaves) void k2_segmented_rows_update(
     uint64_t stream_base, unsigned char* __restrict__ state_rows, int64_t* __restrict__ state_idx,
     int64_t* __restrict__ state_next, uint32_t fifo_cap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    uint16_t* lut = (uint16_t*)lds;
-    const uint64_t dense_lim = 256ull * k;
-    build_lut(lut, dense_lim);
+    build_lut((uint16_t*)lds, 256ull * k);
     __syncthreads();
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes + (size_t)k * 8);
-    void* tab = base + kStashBytes + kQueueBytes;
-    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), tab, lut, lane, k,
-                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    const Wave W = wave_frame(lds, k, k0, k1, fifo_cap);
+    const uint32_t lane = W.lane;
+    void* tab = W.tab;
     const uint64_t Wb = (uint64_t)C * sizeof(G);
     const PairStep p0 = pair_step(lane, 64, C);
     const int64_t wave_stride = (int64_t)gridDim.x * kWaves;
-    for (int64_t b = (int64_t)blockIdx.x * kWaves + wave; b < B; b += wave_stride) {
-        const int64_t off = uniform64(offsets[b]), len = uniform64(offsets[b + 1]) - off;
-        const int64_t r = ids ? uniform64(ids[b]) : b;
-        if (len <= 0 || r < 0 || r >= S) continue;
-        const int64_t n0 = uniform64(bases ? bases[b] : state_next[r]);
-        if (n0 < 0) continue;
-        const int64_t nend = n0 + len;
-        const uint64_t stream = stream_base + (uint64_t)r;
-        int64_t* si = state_idx + r * (int64_t)k;
-        const bool small = nend < kSmallLen;
+    for (int64_t b = (int64_t)blockIdx.x * kWaves + W.wave; b < B; b += wave_stride) {
+        Segment g;
+        if (!read_segment(g, offsets, ids, bases, state_next, b, S)) continue;
+        const uint64_t stream = stream_base + (uint64_t)g.r;
+        int64_t* si = state_idx + g.r * (int64_t)k;
+        const bool small = g.nend < kSmallLen;
         if (small) {
-            k2_stream<int64_t, true, false, true>(W, nullptr, off, len, stream, nullptr, n0);
-            for (uint32_t j = lane; j < k; j += 64) update_slot_rows((uint32_t*)tab, n0, nend, j, si);
+            k2_stream<int64_t, true, false, true>(W, nullptr, g.off, g.len, stream, nullptr, g.n0);
+            for (uint32_t j = lane; j < k; j += 64) update_slot_rows((uint32_t*)tab, g.n0, g.nend, j, si);
         } else {
-            k2_stream<int64_t, false, false, true>(W, nullptr, off, len, stream, nullptr, n0);
-            for (uint32_t j = lane; j < k; j += 64) update_slot_rows((uint64_t*)tab, n0, nend, j, si);
+            k2_stream<int64_t, false, false, true>(W, nullptr, g.off, g.len, stream, nullptr, g.n0);
+            for (uint32_t j = lane; j < k; j += 64) update_slot_rows((uint64_t*)tab, g.n0, g.nend, j, si);
         }
         __builtin_amdgcn_wave_barrier();
         auto src_of = [&](uint32_t j) -> int64_t {
             const uint64_t e = small ? (uint64_t)((const uint32_t*)tab)[j] : ((const uint64_t*)tab)[j];
-            return e ? off + (int64_t)e - 1 : -1;
+            return e ? g.off + (int64_t)e - 1 : -1;
         };
-        gather_rows<G, false>(rows, state_rows + (uint64_t)r * k * Wb, k, C, p0, src_of);
-        if (lane == 0 && state_next[r] < nend) state_next[r] = nend;
+        gather_rows<G, false>(rows, state_rows + (uint64_t)g.r * k * Wb, k, C, p0, src_of);
+        if (lane == 0 && state_next[g.r] < g.nend) state_next[g.r] = g.nend;
         __builtin_amdgcn_wave_barrier();  // the table is read before the next segment zeroes it
     }
 }
@@ -991,40 +1004,30 @@ __global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_rows_update_wg(
     int64_t* __restrict__ state_next, uint32_t fifo_cap) {
     using TabT = unsigned long long;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    uint16_t* lut = (uint16_t*)lds;
-    const uint64_t dense_lim = 256ull * k;
-    build_lut(lut, dense_lim);
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    unsigned char* base = lds + kLutBytes + (size_t)wave * (kStashBytes + kQueueBytes);
-    TabT* tab = (TabT*)(lds + kLutBytes + (size_t)kWavesWG * (kStashBytes + kQueueBytes));
-    const Wave W{(u32x4*)base, (uint16_t*)(base + kStashBytes), nullptr, lut, lane, k,
-                 k0, k1, dense_lim, std::min<uint32_t>(std::max<uint32_t>(fifo_cap, 128u), kQCap)};
+    build_lut((uint16_t*)lds, 256ull * k);
+    const Wave W = wg_frame(lds, k, k0, k1, fifo_cap);
+    TabT* tab = (TabT*)W.tab;
     const uint32_t nthr = 64u * kWavesWG;
     const uint64_t Wb = (uint64_t)C * sizeof(G);
     const PairStep p0 = pair_step(threadIdx.x, nthr, C);
     for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
-        // workgroup-uniform: every thread reads the same words (state_next[r] before anyone writes it)
-        const int64_t off = uniform64(offsets[b]), len = uniform64(offsets[b + 1]) - off;
-        const int64_t r = ids ? uniform64(ids[b]) : b;
-        if (len <= 0 || r < 0 || r >= S) continue;
-        const int64_t n0 = uniform64(bases ? bases[b] : state_next[r]);
-        if (n0 < 0) continue;
-        const int64_t nend = n0 + len;
+        Segment g;
+        if (!read_segment(g, offsets, ids, bases, state_next, b, S)) continue;
         for (uint32_t j = threadIdx.x; j < k; j += nthr) tab[j] = 0;
         __syncthreads();  // the table is zero, the lut built, and n0 read by every wave
-        const uint64_t stream = stream_base + (uint64_t)r;
-        if (nend < kSmallLen) k2_part<TabT, true, false, true>(W, tab, len, stream, wave, n0);
-        else k2_part<TabT, false, false, true>(W, tab, len, stream, wave, n0);
+        const uint64_t stream = stream_base + (uint64_t)g.r;
+        if (g.nend < kSmallLen) k2_part<TabT, true, false, true>(W, tab, g.len, stream, W.wave, g.n0);
+        else k2_part<TabT, false, false, true>(W, tab, g.len, stream, W.wave, g.n0);
         __syncthreads();
-        int64_t* si = state_idx + r * (int64_t)k;
-        for (uint32_t j = threadIdx.x; j < k; j += nthr) update_slot_rows(tab, n0, nend, j, si);
+        int64_t* si = state_idx + g.r * (int64_t)k;
+        for (uint32_t j = threadIdx.x; j < k; j += nthr) update_slot_rows(tab, g.n0, g.nend, j, si);
         __syncthreads();  // every slot's entry names its row (or none)
         auto src_of = [&](uint32_t j) -> int64_t {
             const uint64_t e = tab[j];
-            return e ? off + (int64_t)e - 1 : -1;
+            return e ? g.off + (int64_t)e - 1 : -1;
         };
-        gather_rows<G, false>(rows, state_rows + (uint64_t)r * k * Wb, k, C, p0, src_of);
-        if (threadIdx.x == 0 && state_next[r] < nend) state_next[r] = nend;
+        gather_rows<G, false>(rows, state_rows + (uint64_t)g.r * k * Wb, k, C, p0, src_of);
+        if (threadIdx.x == 0 && state_next[g.r] < g.nend) state_next[g.r] = g.nend;
         __syncthreads();  // the write-back has read the table before the next segment zeroes it
     }
 }
@@ -1037,31 +1040,10 @@ __global__ __launch_bounds__(256) void k2_segmented_rows_merge(const unsigned ch
                                                                const int64_t* part_next, int32_t P, int64_t S,
                                                                uint32_t k, uint32_t C, unsigned char* state_rows,
                                                                int64_t* state_idx, int64_t* state_next) {
-    // (no __restrict__: a state merged into itself names the same memory twice)
     __shared__ int32_t win[256];
     const int64_t total = S * (int64_t)k;
     const int64_t t0 = (int64_t)blockIdx.x * 256, t = t0 + threadIdx.x;
-    int32_t bp = -1;
-    if (t < total) {
-        const int64_t cur = state_idx[t];
-        int64_t best = cur;
-        for (int32_t p = 0; p < P; ++p) {
-            const int64_t pi = part_idx[(int64_t)p * total + t];
-            if (pi > best) {
-                best = pi;
-                bp = p;
-            }
-        }
-        if (bp >= 0) state_idx[t] = best;
-        if (t % k == 0) {  // the row's first slot also takes its next
-            const int64_t r = t / k;
-            const int64_t cn = state_next[r];
-            int64_t n = cn;
-            for (int32_t p = 0; p < P; ++p) n = std::max<int64_t>(n, part_next[(int64_t)p * S + r]);
-            if (n > cn) state_next[r] = n;
-        }
-    }
-    win[threadIdx.x] = bp;
+    win[threadIdx.x] = t < total ? merge_pick(part_idx, part_next, P, S, k, t, state_idx, state_next, [](int32_t) {}) : -1;
     __syncthreads();
     const uint32_t here = (uint32_t)std::min<int64_t>(256, total - t0);
     // source row of entry t0 + j: entry t0 + j of part win[j]

@@ -1606,11 +1606,41 @@ rsv_status rsv_merge_packed(rsv_sampler* s, const int64_t* rows_dev, int32_t par
     return RSV_OK;
 }
 
+// k and key_width of the six K2 entry points (fn: the entry point's name, for the messages; long_fn: for
+// the three over byte keys, their counterpart for 4- and 8-byte keys, else NULL; state: the four resumed
+// ones, whose k is bounded)
+static rsv_status check_segsample_shape(const char* fn, const char* long_fn, int32_t k, int32_t key_width,
+                                        bool state) {
+    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
+    if (state && k > (int32_t)kSegSampleStateMaxK)
+        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " holds k <= " + std::to_string(kSegSampleStateMaxK) +
+                                           " per stream; use separate handles beyond");
+    if (!long_fn)
+        return key_width == 4 || key_width == 8 ? RSV_OK : fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be 4 or 8");
+    if (key_width == 4 || key_width == 8)
+        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " takes byte keys; " + long_fn + " takes 4- and 8-byte keys");
+    if (key_width < 16 || key_width > 256 || key_width % 8 != 0)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be a multiple of 8 in 16..256");
+    return RSV_OK;
+}
+
+// the counts of the two update and the two merge entry points, after a shape check that left st RSV_OK;
+// true: the call returns st -- an error, or RSV_OK because there is nothing to do
+static bool segsample_update_done(int64_t num_segments, int64_t num_states, const void* ids_dev, rsv_status& st) {
+    if (num_segments < 0 || num_states < 0) st = fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
+    else if (!ids_dev && num_segments > num_states)
+        st = fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
+    return st || num_segments == 0 || num_states == 0;
+}
+static bool segsample_merge_done(int32_t parts, int64_t num_states, rsv_status& st) {
+    if (parts < 0 || num_states < 0) st = fail(RSV_E_ILLEGAL_ARGUMENT, "negative part or state count");
+    return st || parts == 0 || num_states == 0;
+}
+
 rsv_status rsv_sample_segmented(const void* keys_dev, const int64_t* offsets_dev, int64_t num_streams,
                                 int32_t key_width, int32_t k, uint64_t seed, uint64_t stream_base, void* out_dev,
                                 int64_t* counts_dev, void* hip_stream) {
-    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
-    if (key_width != 4 && key_width != 8) return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be 4 or 8");
+    if (rsv_status st = check_segsample_shape("rsv_sample_segmented", nullptr, k, key_width, false)) return st;
     if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
     if (num_streams == 0) return RSV_OK;
     if (!offsets_dev || !out_dev || !counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
@@ -1620,26 +1650,13 @@ rsv_status rsv_sample_segmented(const void* keys_dev, const int64_t* offsets_dev
     return RSV_OK;
 }
 
-// k and key_width of the two resumed K2 entry points (fn: the entry point's name, for the messages)
-static rsv_status check_segstate_shape(const char* fn, int32_t k, int32_t key_width) {
-    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
-    if (k > (int32_t)kSegSampleStateMaxK)
-        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " holds k <= " + std::to_string(kSegSampleStateMaxK) +
-                                           " per stream; use separate handles beyond");
-    if (key_width != 4 && key_width != 8) return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be 4 or 8");
-    return RSV_OK;
-}
-
 rsv_status rsv_sample_segmented_update(const void* keys_dev, const int64_t* offsets_dev, const int64_t* stream_ids_dev,
                                        const int64_t* bases_dev, int64_t num_segments, int64_t num_states,
                                        int32_t key_width, int32_t k, uint64_t seed, uint64_t stream_base,
                                        void* state_keys_dev, int64_t* state_idx_dev, int64_t* state_next_dev,
                                        void* hip_stream) {
-    if (rsv_status st = check_segstate_shape("rsv_sample_segmented_update", k, key_width)) return st;
-    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
-    if (!stream_ids_dev && num_segments > num_states)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
-    if (num_segments == 0 || num_states == 0) return RSV_OK;
+    rsv_status st = check_segsample_shape("rsv_sample_segmented_update", nullptr, k, key_width, true);
+    if (st || segsample_update_done(num_segments, num_states, stream_ids_dev, st)) return st;
     // keys_dev is not checked: a launch whose segments are all empty has no keys
     if (!offsets_dev || !state_keys_dev || !state_idx_dev || !state_next_dev)
         return fail(RSV_E_NULL_POINTER, "NULL buffer");
@@ -1654,9 +1671,8 @@ rsv_status rsv_sample_segmented_merge(const void* part_keys_dev, const int64_t* 
                                       const int64_t* part_next_dev, int32_t parts, int64_t num_states,
                                       int32_t key_width, int32_t k, void* state_keys_dev, int64_t* state_idx_dev,
                                       int64_t* state_next_dev, void* hip_stream) {
-    if (rsv_status st = check_segstate_shape("rsv_sample_segmented_merge", k, key_width)) return st;
-    if (parts < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative part or state count");
-    if (parts == 0 || num_states == 0) return RSV_OK;
+    rsv_status st = check_segsample_shape("rsv_sample_segmented_merge", nullptr, k, key_width, true);
+    if (st || segsample_merge_done(parts, num_states, st)) return st;
     if (!part_keys_dev || !part_idx_dev || !part_next_dev || !state_keys_dev || !state_idx_dev || !state_next_dev)
         return fail(RSV_E_NULL_POINTER, "NULL buffer");
     RSV_HIP_TRY(launch_segmented_merge(part_keys_dev, key_width, part_idx_dev, part_next_dev, parts, num_states,
@@ -1665,25 +1681,10 @@ rsv_status rsv_sample_segmented_merge(const void* part_keys_dev, const int64_t* 
     return RSV_OK;
 }
 
-// k and key_width of the three K2 entry points over byte keys (fn: the entry point's name, long_fn: its
-// counterpart for 4- and 8-byte keys, for the messages; state: the two resumed ones, whose k is bounded)
-static rsv_status check_segsample_rows_shape(const char* fn, const char* long_fn, int32_t k, int32_t key_width,
-                                             bool state) {
-    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
-    if (state && k > (int32_t)kSegSampleStateMaxK)
-        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " holds k <= " + std::to_string(kSegSampleStateMaxK) +
-                                           " per stream; use separate handles beyond");
-    if (key_width == 4 || key_width == 8)
-        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " takes byte keys; " + long_fn + " takes 4- and 8-byte keys");
-    if (key_width < 16 || key_width > 256 || key_width % 8 != 0)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be a multiple of 8 in 16..256");
-    return RSV_OK;
-}
-
 rsv_status rsv_sample_segmented_rows(const void* rows_dev, const int64_t* offsets_dev, int64_t num_streams,
                                      int32_t key_width, int32_t k, uint64_t seed, uint64_t stream_base,
                                      void* out_rows_dev, int64_t* counts_dev, void* hip_stream) {
-    if (rsv_status st = check_segsample_rows_shape("rsv_sample_segmented_rows", "rsv_sample_segmented", k, key_width, false))
+    if (rsv_status st = check_segsample_shape("rsv_sample_segmented_rows", "rsv_sample_segmented", k, key_width, false))
         return st;
     if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
     if (num_streams == 0) return RSV_OK;
@@ -1702,13 +1703,9 @@ rsv_status rsv_sample_segmented_rows_update(const void* rows_dev, const int64_t*
                                             int64_t num_segments, int64_t num_states, int32_t key_width, int32_t k,
                                             uint64_t seed, uint64_t stream_base, void* state_rows_dev,
                                             int64_t* state_idx_dev, int64_t* state_next_dev, void* hip_stream) {
-    if (rsv_status st = check_segsample_rows_shape("rsv_sample_segmented_rows_update", "rsv_sample_segmented_update", k,
-                                                   key_width, true))
-        return st;
-    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
-    if (!stream_ids_dev && num_segments > num_states)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
-    if (num_segments == 0 || num_states == 0) return RSV_OK;
+    rsv_status st =
+        check_segsample_shape("rsv_sample_segmented_rows_update", "rsv_sample_segmented_update", k, key_width, true);
+    if (st || segsample_update_done(num_segments, num_states, stream_ids_dev, st)) return st;
     // rows_dev is not checked: a launch whose segments are all empty has no rows
     if (!offsets_dev || !state_rows_dev || !state_idx_dev || !state_next_dev)
         return fail(RSV_E_NULL_POINTER, "NULL buffer");
@@ -1725,11 +1722,9 @@ rsv_status rsv_sample_segmented_rows_merge(const void* part_rows_dev, const int6
                                            const int64_t* part_next_dev, int32_t parts, int64_t num_states,
                                            int32_t key_width, int32_t k, void* state_rows_dev, int64_t* state_idx_dev,
                                            int64_t* state_next_dev, void* hip_stream) {
-    if (rsv_status st = check_segsample_rows_shape("rsv_sample_segmented_rows_merge", "rsv_sample_segmented_merge", k,
-                                                   key_width, true))
-        return st;
-    if (parts < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative part or state count");
-    if (parts == 0 || num_states == 0) return RSV_OK;
+    rsv_status st =
+        check_segsample_shape("rsv_sample_segmented_rows_merge", "rsv_sample_segmented_merge", k, key_width, true);
+    if (st || segsample_merge_done(parts, num_states, st)) return st;
     if (!part_rows_dev || !part_idx_dev || !part_next_dev || !state_rows_dev || !state_idx_dev || !state_next_dev)
         return fail(RSV_E_NULL_POINTER, "NULL buffer");
     if (((uintptr_t)part_rows_dev | (uintptr_t)state_rows_dev) & 7)

@@ -34,6 +34,13 @@
 // rows of 16..256 bytes.  The same element loops find the winners without reading a row; separate
 // kernels (k2_segmented_rows*, rsv_k2.h) then gather whole rows, lanes side by side on a row's 16- or
 // 8-byte granules, with 64-bit byte offsets.  The key-typed kernels above are not instantiated for rows.
+//
+// What the nine kernels and six launchers share exists once.  Device (rsv_k2.h): build_lut, the frames
+// wave_frame / wg_frame (the Wave over the workgroup's LDS and its winner table), read_segment (an update's
+// segment header and its skip rules), slot_source (the stateless slot rule) and merge_pick.  Host (below):
+// SeedWords, wave_grid / wg_grid, tables_fit_u32, with_global_table (gt_acquire .. gt_release around a
+// launch), with_key / with_granule (each kernel launch is written once, in a generic lambda), launch_wg
+// (the stateless workgroup form of both families), launch_update and merge_grid.
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -113,69 +120,84 @@ uint32_t env_fifo_cap() {
     return fifo_cap;
 }
 
-template <typename KeyT, typename TabT>
-hipError_t launch_wg(const KeyT* keys, const int64_t* offsets, int64_t S, uint32_t k, const DrawParams& dp,
-                     KeyT* out, int64_t* counts, hipStream_t st, uint32_t fifo_cap) {
-    const uint32_t k0 = (uint32_t)dp.seed, k1 = (uint32_t)(dp.seed >> 32);
-    const size_t lds = k2::lds_bytes_wg(k, sizeof(TabT), false);
-    if (lds <= k2::kLdsMax) {
-        // as many workgroups as the CUs hold at once, twice over (streams are taken grid-stride)
-        const uint64_t per_cu = std::max<uint64_t>(1, k2::kLdsMax / lds);
-        const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)S, 256ull * per_cu * 2);
-        hipLaunchKernelGGL((k2_segmented_wg<KeyT, TabT, false>), dim3(grid), dim3(64 * kWavesWG), lds, st, keys,
-                           offsets, S, k, k0, k1, dp.stream, out, counts, fifo_cap, (TabT*)nullptr);
-        return hipGetLastError();
-    }
+// ---- the launch plan: what every launcher below shares -------------------------------------------
+// the Philox key words of a launch
+struct SeedWords {
+    uint32_t k0, k1;
+    explicit SeedWords(const DrawParams& dp) : k0((uint32_t)dp.seed), k1((uint32_t)(dp.seed >> 32)) {}
+};
+
+// The wave form's grid over n streams or segments: up to 128 four-wave workgroups per CU over the launch
+// (C3: 8 streams per wave): tools/micro_k2 G (r03ai) 1.78 ms at 4096 workgroups, 1.71 at 16384, 1.65 at
+// 32768, 1.66-1.68 at 65536, 1.84 at one stream per wave (262144: every workgroup rebuilds the threshold table)
+unsigned wave_grid(int64_t n) {
+    return (unsigned)std::min<uint64_t>(((uint64_t)n + kWaves - 1) / kWaves, 256ull * 128);
+}
+
+// the workgroup form's grid: as many workgroups as the CUs hold at once, twice over (taken grid-stride)
+unsigned wg_grid(int64_t n, size_t lds) {
+    const uint64_t per_cu = std::max<uint64_t>(1, k2::kLdsMax / lds);
+    return (unsigned)std::min<uint64_t>((uint64_t)n, 256ull * per_cu * 2);
+}
+
+// every index fits 32 bits when the streams together span < 2^32 elements: u32 tables (one host read)
+hipError_t tables_fit_u32(const int64_t* offsets, int64_t S, hipStream_t st, bool* fit) {
+    int64_t ends[2] = {0, 0};
+    RSV_HIP_RET(hipMemcpyAsync(&ends[0], offsets, 8, hipMemcpyDeviceToHost, st));
+    RSV_HIP_RET(hipMemcpyAsync(&ends[1], offsets + S, 8, hipMemcpyDeviceToHost, st));
+    RSV_HIP_RET(hipStreamSynchronize(st));
+    *fit = ends[1] - ends[0] < ((int64_t)1 << 32);
+    return hipSuccess;
+}
+
+// the global-table path: launch(table) under g_gt_mu between gt_acquire and gt_release; the launch's error
+template <typename Launch>
+hipError_t with_global_table(size_t bytes, hipStream_t st, Launch launch) {
     int dev = 0;
     RSV_HIP_RET(hipGetDevice(&dev));
-    const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)S, 512);
-    const size_t bytes = (size_t)grid * k * sizeof(TabT);
     std::lock_guard<std::mutex> lk(g_gt_mu);
     void* gt = nullptr;
     bool priv = false;
     RSV_HIP_RET(gt_acquire(dev, bytes, st, &gt, &priv));
-    hipLaunchKernelGGL((k2_segmented_wg<KeyT, TabT, true>), dim3(grid), dim3(64 * kWavesWG),
-                       k2::lds_bytes_wg(k, sizeof(TabT), true), st, keys, offsets, S, k, k0, k1, dp.stream, out,
-                       counts, fifo_cap, (TabT*)gt);
+    launch(gt);
     const hipError_t e = hipGetLastError();
     gt_release(dev, st, priv, gt);
     return e;
 }
-}  // namespace
 
-hipError_t launch_segmented(const void* keys, int key_width, const int64_t* offsets, int64_t S, uint32_t k,
-                            const DrawParams& dp, void* out, int64_t* counts, hipStream_t st) {
-    if (S <= 0) return hipSuccess;
-    const uint32_t fifo_cap = env_fifo_cap();
-    if (k >= k2::kWGMinK) {  // one workgroup per stream
-        // every index fits 32 bits when the streams together span < 2^32 elements: u32 tables
-        int64_t ends[2] = {0, 0};
-        RSV_HIP_RET(hipMemcpyAsync(&ends[0], offsets, 8, hipMemcpyDeviceToHost, st));
-        RSV_HIP_RET(hipMemcpyAsync(&ends[1], offsets + S, 8, hipMemcpyDeviceToHost, st));
-        RSV_HIP_RET(hipStreamSynchronize(st));
-        const bool t32 = ends[1] - ends[0] < ((int64_t)1 << 32);
-        if (key_width == 8)
-            return t32 ? launch_wg<int64_t, uint32_t>((const int64_t*)keys, offsets, S, k, dp, (int64_t*)out, counts, st, fifo_cap)
-                       : launch_wg<int64_t, unsigned long long>((const int64_t*)keys, offsets, S, k, dp, (int64_t*)out,
-                                                                counts, st, fifo_cap);
-        return t32 ? launch_wg<int32_t, uint32_t>((const int32_t*)keys, offsets, S, k, dp, (int32_t*)out, counts, st, fifo_cap)
-                   : launch_wg<int32_t, unsigned long long>((const int32_t*)keys, offsets, S, k, dp, (int32_t*)out,
-                                                            counts, st, fifo_cap);
+// f(KeyT{}) for the key width, f(G{}) for the rows' granule: each kernel launch below is written once
+template <typename F>
+hipError_t with_key(int key_width, F f) {
+    return key_width == 8 ? f(int64_t{}) : f(int32_t{});
+}
+template <typename F>
+hipError_t with_granule(bool vec16, F f) {
+    return vec16 ? f(uint4{}) : f(uint64_t{});
+}
+// 16-byte granules where every row of every buffer sits on a 16-byte boundary, else 8-byte ones
+bool rows_vec16(int key_width, const void* a, const void* b) {
+    return key_width % 16 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0;
+}
+
+// The stateless workgroup form (k >= kWGMinK) of either kernel family: go(GT, grid, lds, table) launches
+// the kernel's <TabT, GT> instantiation -- the table in LDS while it fits, else in the global scratch.
+template <typename TabT, typename Go>
+hipError_t launch_wg_tab(int64_t S, uint32_t k, hipStream_t st, Go go) {
+    const size_t lds = k2::lds_bytes_wg(k, sizeof(TabT), false);
+    if (lds <= k2::kLdsMax) {
+        go(std::false_type{}, wg_grid(S, lds), lds, (TabT*)nullptr);
+        return hipGetLastError();
     }
-    const size_t lds = k2::lds_bytes(k);
-    const uint32_t k0 = (uint32_t)dp.seed, k1 = (uint32_t)(dp.seed >> 32);
-    // up to 128 four-wave workgroups per CU over the launch (C3: 8 streams per wave): tools/micro_k2 G
-    // (r03ai) 1.78 ms at 4096 workgroups, 1.71 at 16384, 1.65 at 32768, 1.66-1.68 at 65536, 1.84 at
-    // one stream per wave (262144: every workgroup rebuilds the threshold table)
-    const uint64_t blocks = ((uint64_t)S + kWaves - 1) / kWaves;
-    const unsigned grid = (unsigned)std::min<uint64_t>(blocks, 256ull * 128);
-    if (key_width == 8)
-        hipLaunchKernelGGL(k2_segmented<int64_t>, dim3(grid), dim3(64 * kWaves), lds, st, (const int64_t*)keys,
-                           offsets, S, k, k0, k1, dp.stream, (int64_t*)out, counts, fifo_cap);
-    else
-        hipLaunchKernelGGL(k2_segmented<int32_t>, dim3(grid), dim3(64 * kWaves), lds, st, (const int32_t*)keys,
-                           offsets, S, k, k0, k1, dp.stream, (int32_t*)out, counts, fifo_cap);
-    return hipGetLastError();
+    const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)S, 512);
+    return with_global_table((size_t)grid * k * sizeof(TabT), st, [&](void* gt) {
+        go(std::true_type{}, grid, k2::lds_bytes_wg(k, sizeof(TabT), true), (TabT*)gt);
+    });
+}
+template <typename Go>
+hipError_t launch_wg(const int64_t* offsets, int64_t S, uint32_t k, hipStream_t st, Go go) {
+    bool t32 = false;
+    RSV_HIP_RET(tables_fit_u32(offsets, S, st, &t32));
+    return t32 ? launch_wg_tab<uint32_t>(S, k, st, go) : launch_wg_tab<unsigned long long>(S, k, st, go);
 }
 
 // the largest k whose 64-bit winner table fits one workgroup's LDS beside the waves' rings
@@ -183,28 +205,47 @@ static_assert(k2::lds_bytes_wg(kSegSampleStateMaxK, 8, false) <= k2::kLdsMax &&
                   k2::lds_bytes_wg(kSegSampleStateMaxK + 1, 8, false) > k2::kLdsMax,
               "kSegSampleStateMaxK is the LDS limit of k2_segmented_update_wg");
 
-namespace {
-template <typename KeyT>
-hipError_t launch_update(const KeyT* keys, const int64_t* offsets, const int64_t* ids, const int64_t* bases, int64_t B,
-                         int64_t S, uint32_t k, const DrawParams& dp, KeyT* state_keys, int64_t* state_idx,
-                         int64_t* state_next, hipStream_t st) {
-    const uint32_t k0 = (uint32_t)dp.seed, k1 = (uint32_t)(dp.seed >> 32);
-    const uint32_t fifo_cap = env_fifo_cap();
-    if (k >= k2::kWGMinK) {  // one workgroup per segment, grids as launch_wg
+// The resumed launch of either family: wg(grid, lds) launches the workgroup form (k >= kWGMinK, one workgroup
+// per segment, 64-bit table in LDS), wave(grid, lds) the wave form.
+template <typename Wg, typename Wave>
+hipError_t launch_update(int64_t B, uint32_t k, Wg wg, Wave wave) {
+    if (k >= k2::kWGMinK) {
         const size_t lds = k2::lds_bytes_wg(k, 8, false);
-        const uint64_t per_cu = std::max<uint64_t>(1, k2::kLdsMax / lds);
-        const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)B, 256ull * per_cu * 2);
-        hipLaunchKernelGGL(k2_segmented_update_wg<KeyT>, dim3(grid), dim3(64 * kWavesWG), lds, st, keys, offsets, ids,
-                           bases, B, S, k, k0, k1, dp.stream, state_keys, state_idx, state_next, fifo_cap);
-        return hipGetLastError();
+        wg(wg_grid(B, lds), lds);
+    } else {
+        wave(wave_grid(B), k2::lds_bytes(k));
     }
-    const uint64_t blocks = ((uint64_t)B + kWaves - 1) / kWaves;  // grids as launch_segmented
-    const unsigned grid = (unsigned)std::min<uint64_t>(blocks, 256ull * 128);
-    hipLaunchKernelGGL(k2_segmented_update<KeyT>, dim3(grid), dim3(64 * kWaves), k2::lds_bytes(k), st, keys, offsets,
-                       ids, bases, B, S, k, k0, k1, dp.stream, state_keys, state_idx, state_next, fifo_cap);
     return hipGetLastError();
 }
+
+// one thread per (row, slot) entry, 256 a workgroup
+hipError_t merge_grid(int64_t num_states, uint32_t k, unsigned* grid) {
+    const uint64_t blocks = ((uint64_t)num_states * k + 255) / 256;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    *grid = (unsigned)blocks;
+    return hipSuccess;
+}
 }  // namespace
+
+hipError_t launch_segmented(const void* keys, int key_width, const int64_t* offsets, int64_t S, uint32_t k,
+                            const DrawParams& dp, void* out, int64_t* counts, hipStream_t st) {
+    if (S <= 0) return hipSuccess;
+    const uint32_t fifo_cap = env_fifo_cap();
+    const SeedWords sw(dp);
+    return with_key(key_width, [&](auto key) {
+        using KeyT = decltype(key);
+        if (k >= k2::kWGMinK)  // one workgroup per stream
+            return launch_wg(offsets, S, k, st, [&](auto gt, unsigned grid, size_t lds, auto* tab) {
+                using TabT = std::remove_pointer_t<decltype(tab)>;
+                hipLaunchKernelGGL((k2_segmented_wg<KeyT, TabT, decltype(gt)::value>), dim3(grid), dim3(64 * kWavesWG),
+                                   lds, st, (const KeyT*)keys, offsets, S, k, sw.k0, sw.k1, dp.stream, (KeyT*)out,
+                                   counts, fifo_cap, tab);
+            });
+        hipLaunchKernelGGL(k2_segmented<KeyT>, dim3(wave_grid(S)), dim3(64 * kWaves), k2::lds_bytes(k), st,
+                           (const KeyT*)keys, offsets, S, k, sw.k0, sw.k1, dp.stream, (KeyT*)out, counts, fifo_cap);
+        return hipGetLastError();
+    });
+}
 
 hipError_t launch_segmented_update(const void* keys, int key_width, const int64_t* offsets, const int64_t* stream_ids,
                                    const int64_t* bases, int64_t num_segments, int64_t num_states, uint32_t k,
@@ -212,161 +253,108 @@ hipError_t launch_segmented_update(const void* keys, int key_width, const int64_
                                    hipStream_t st) {
     if (num_segments <= 0 || num_states <= 0) return hipSuccess;
     if (k > kSegSampleStateMaxK) return hipErrorInvalidValue;
-    if (key_width == 8)
-        return launch_update<int64_t>((const int64_t*)keys, offsets, stream_ids, bases, num_segments, num_states, k, dp,
-                                      (int64_t*)state_keys, state_idx, state_next, st);
-    return launch_update<int32_t>((const int32_t*)keys, offsets, stream_ids, bases, num_segments, num_states, k, dp,
-                                  (int32_t*)state_keys, state_idx, state_next, st);
+    const SeedWords sw(dp);
+    const uint32_t fifo_cap = env_fifo_cap();
+    return with_key(key_width, [&](auto key) {
+        using KeyT = decltype(key);
+        auto launch = [&](auto kernel, int waves) {
+            return [&, kernel, waves](unsigned grid, size_t lds) {
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, st, (const KeyT*)keys, offsets, stream_ids,
+                                   bases, num_segments, num_states, k, sw.k0, sw.k1, dp.stream, (KeyT*)state_keys,
+                                   state_idx, state_next, fifo_cap);
+            };
+        };
+        return launch_update(num_segments, k, launch(k2_segmented_update_wg<KeyT>, kWavesWG),
+                             launch(k2_segmented_update<KeyT>, kWaves));
+    });
 }
 
 hipError_t launch_segmented_merge(const void* part_keys, int key_width, const int64_t* part_idx,
                                   const int64_t* part_next, int32_t parts, int64_t num_states, uint32_t k,
                                   void* state_keys, int64_t* state_idx, int64_t* state_next, hipStream_t st) {
     if (parts <= 0 || num_states <= 0) return hipSuccess;
-    const uint64_t blocks = ((uint64_t)num_states * k + 255) / 256;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (key_width == 8)
-        hipLaunchKernelGGL(k2_segmented_merge<int64_t>, dim3((unsigned)blocks), dim3(256), 0, st,
-                           (const int64_t*)part_keys, part_idx, part_next, parts, num_states, k, (int64_t*)state_keys,
-                           state_idx, state_next);
-    else
-        hipLaunchKernelGGL(k2_segmented_merge<int32_t>, dim3((unsigned)blocks), dim3(256), 0, st,
-                           (const int32_t*)part_keys, part_idx, part_next, parts, num_states, k, (int32_t*)state_keys,
-                           state_idx, state_next);
-    return hipGetLastError();
-}
-
-// ---- byte keys (rows) ----------------------------------------------------------------------------
-namespace {
-// 16-byte granules where every row of every buffer sits on a 16-byte boundary, else 8-byte ones
-bool rows_vec16(int key_width, const void* a, const void* b) {
-    return key_width % 16 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0;
-}
-
-template <typename G, typename TabT>
-hipError_t launch_rows_wg(const unsigned char* rows, uint32_t C, const int64_t* offsets, int64_t S, uint32_t k,
-                          const DrawParams& dp, unsigned char* out, int64_t* counts, hipStream_t st,
-                          uint32_t fifo_cap) {
-    const uint32_t k0 = (uint32_t)dp.seed, k1 = (uint32_t)(dp.seed >> 32);
-    const size_t lds = k2::lds_bytes_wg(k, sizeof(TabT), false);
-    if (lds <= k2::kLdsMax) {  // grids as launch_wg
-        const uint64_t per_cu = std::max<uint64_t>(1, k2::kLdsMax / lds);
-        const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)S, 256ull * per_cu * 2);
-        hipLaunchKernelGGL((k2_segmented_rows_wg<G, TabT, false>), dim3(grid), dim3(64 * kWavesWG), lds, st, rows,
-                           offsets, S, k, C, k0, k1, dp.stream, out, counts, fifo_cap, (TabT*)nullptr);
+    unsigned grid = 0;
+    RSV_HIP_RET(merge_grid(num_states, k, &grid));
+    return with_key(key_width, [&](auto key) {
+        using KeyT = decltype(key);
+        hipLaunchKernelGGL(k2_segmented_merge<KeyT>, dim3(grid), dim3(256), 0, st, (const KeyT*)part_keys, part_idx,
+                           part_next, parts, num_states, k, (KeyT*)state_keys, state_idx, state_next);
         return hipGetLastError();
-    }
-    int dev = 0;
-    RSV_HIP_RET(hipGetDevice(&dev));
-    const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)S, 512);
-    const size_t bytes = (size_t)grid * k * sizeof(TabT);
-    std::lock_guard<std::mutex> lk(g_gt_mu);
-    void* gt = nullptr;
-    bool priv = false;
-    RSV_HIP_RET(gt_acquire(dev, bytes, st, &gt, &priv));
-    hipLaunchKernelGGL((k2_segmented_rows_wg<G, TabT, true>), dim3(grid), dim3(64 * kWavesWG),
-                       k2::lds_bytes_wg(k, sizeof(TabT), true), st, rows, offsets, S, k, C, k0, k1, dp.stream, out,
-                       counts, fifo_cap, (TabT*)gt);
-    const hipError_t e = hipGetLastError();
-    gt_release(dev, st, priv, gt);
-    return e;
+    });
 }
 
-template <typename G>
-hipError_t launch_rows(const unsigned char* rows, int key_width, const int64_t* offsets, int64_t S, uint32_t k,
-                       const DrawParams& dp, unsigned char* out, int64_t* counts, hipStream_t st) {
-    const uint32_t C = (uint32_t)key_width / (uint32_t)sizeof(G);
-    const uint32_t fifo_cap = env_fifo_cap();
-    if (k >= k2::kWGMinK) {  // one workgroup per stream; u32 tables by the rule of launch_segmented
-        int64_t ends[2] = {0, 0};
-        RSV_HIP_RET(hipMemcpyAsync(&ends[0], offsets, 8, hipMemcpyDeviceToHost, st));
-        RSV_HIP_RET(hipMemcpyAsync(&ends[1], offsets + S, 8, hipMemcpyDeviceToHost, st));
-        RSV_HIP_RET(hipStreamSynchronize(st));
-        if (ends[1] - ends[0] < ((int64_t)1 << 32))
-            return launch_rows_wg<G, uint32_t>(rows, C, offsets, S, k, dp, out, counts, st, fifo_cap);
-        return launch_rows_wg<G, unsigned long long>(rows, C, offsets, S, k, dp, out, counts, st, fifo_cap);
-    }
-    const uint32_t k0 = (uint32_t)dp.seed, k1 = (uint32_t)(dp.seed >> 32);
-    const uint64_t blocks = ((uint64_t)S + kWaves - 1) / kWaves;  // grids as launch_segmented
-    const unsigned grid = (unsigned)std::min<uint64_t>(blocks, 256ull * 128);
-    // one (slot, granule) pair per lane: the gather is deferred past the next stream's draws (C3 with UUID
-    // rows: 1.79 ms against 1.85 ms plain, profiles/segmented_rows/bench.json).  RSV_K2_ROWS_DEFER=0 (read
-    // once per process) keeps the plain gather, for that A/B in tools/bench_segmented_rows.py.
-    static const bool defer = [] {
-        const char* e = std::getenv("RSV_K2_ROWS_DEFER");
-        return !e || std::atoi(e) != 0;
-    }();
-    if (defer && (uint64_t)k * C <= 64)
-        hipLaunchKernelGGL((k2_segmented_rows<G, true>), dim3(grid), dim3(64 * kWaves), k2::lds_bytes(k), st, rows,
-                           offsets, S, k, C, k0, k1, dp.stream, out, counts, fifo_cap);
-    else
-        hipLaunchKernelGGL((k2_segmented_rows<G, false>), dim3(grid), dim3(64 * kWaves), k2::lds_bytes(k), st, rows,
-                           offsets, S, k, C, k0, k1, dp.stream, out, counts, fifo_cap);
-    return hipGetLastError();
-}
-
-template <typename G>
-hipError_t launch_rows_update(const unsigned char* rows, int key_width, const int64_t* offsets, const int64_t* ids,
-                              const int64_t* bases, int64_t B, int64_t S, uint32_t k, const DrawParams& dp,
-                              unsigned char* state_rows, int64_t* state_idx, int64_t* state_next, hipStream_t st) {
-    const uint32_t C = (uint32_t)key_width / (uint32_t)sizeof(G);
-    const uint32_t k0 = (uint32_t)dp.seed, k1 = (uint32_t)(dp.seed >> 32);
-    const uint32_t fifo_cap = env_fifo_cap();
-    if (k >= k2::kWGMinK) {  // grids as launch_update
-        const size_t lds = k2::lds_bytes_wg(k, 8, false);
-        const uint64_t per_cu = std::max<uint64_t>(1, k2::kLdsMax / lds);
-        const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)B, 256ull * per_cu * 2);
-        hipLaunchKernelGGL(k2_segmented_rows_update_wg<G>, dim3(grid), dim3(64 * kWavesWG), lds, st, rows, offsets,
-                           ids, bases, B, S, k, C, k0, k1, dp.stream, state_rows, state_idx, state_next, fifo_cap);
-        return hipGetLastError();
-    }
-    const uint64_t blocks = ((uint64_t)B + kWaves - 1) / kWaves;
-    const unsigned grid = (unsigned)std::min<uint64_t>(blocks, 256ull * 128);
-    hipLaunchKernelGGL(k2_segmented_rows_update<G>, dim3(grid), dim3(64 * kWaves), k2::lds_bytes(k), st, rows, offsets,
-                       ids, bases, B, S, k, C, k0, k1, dp.stream, state_rows, state_idx, state_next, fifo_cap);
-    return hipGetLastError();
-}
-}  // namespace
-
-hipError_t launch_segmented_rows(const void* rows, int key_width, const int64_t* offsets, int64_t S, uint32_t k,
+// ---- byte keys (rows): C granules of sizeof(G) bytes a row ---------------------------------------
+hipError_t launch_segmented_rows(const void* rows_, int key_width, const int64_t* offsets, int64_t S, uint32_t k,
                                  const DrawParams& dp, void* out_rows, int64_t* counts, hipStream_t st) {
     if (S <= 0) return hipSuccess;
-    if (rows_vec16(key_width, rows, out_rows))
-        return launch_rows<uint4>((const unsigned char*)rows, key_width, offsets, S, k, dp, (unsigned char*)out_rows,
-                                  counts, st);
-    return launch_rows<uint64_t>((const unsigned char*)rows, key_width, offsets, S, k, dp, (unsigned char*)out_rows,
-                                 counts, st);
+    const unsigned char* rows = (const unsigned char*)rows_;
+    unsigned char* out = (unsigned char*)out_rows;
+    return with_granule(rows_vec16(key_width, rows, out), [&](auto granule) {
+        using G = decltype(granule);
+        const uint32_t C = (uint32_t)key_width / (uint32_t)sizeof(G);
+        const uint32_t fifo_cap = env_fifo_cap();
+        const SeedWords sw(dp);
+        if (k >= k2::kWGMinK)  // one workgroup per stream; u32 tables by the rule of launch_segmented
+            return launch_wg(offsets, S, k, st, [&](auto gt, unsigned grid, size_t lds, auto* tab) {
+                using TabT = std::remove_pointer_t<decltype(tab)>;
+                hipLaunchKernelGGL((k2_segmented_rows_wg<G, TabT, decltype(gt)::value>), dim3(grid),
+                                   dim3(64 * kWavesWG), lds, st, rows, offsets, S, k, C, sw.k0, sw.k1, dp.stream, out,
+                                   counts, fifo_cap, tab);
+            });
+        // one (slot, granule) pair per lane: the gather is deferred past the next stream's draws (C3 with UUID
+        // rows: 1.79 ms against 1.85 ms plain, profiles/segmented_rows/bench.json).  RSV_K2_ROWS_DEFER=0 (read
+        // once per process) keeps the plain gather, for that A/B in tools/bench_segmented_rows.py.
+        static const bool defer = [] {
+            const char* e = std::getenv("RSV_K2_ROWS_DEFER");
+            return !e || std::atoi(e) != 0;
+        }();
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(wave_grid(S)), dim3(64 * kWaves), k2::lds_bytes(k), st, rows, offsets, S, k,
+                               C, sw.k0, sw.k1, dp.stream, out, counts, fifo_cap);
+            return hipGetLastError();
+        };
+        return defer && (uint64_t)k * C <= 64 ? launch(k2_segmented_rows<G, true>) : launch(k2_segmented_rows<G, false>);
+    });
 }
 
-hipError_t launch_segmented_rows_update(const void* rows, int key_width, const int64_t* offsets,
+hipError_t launch_segmented_rows_update(const void* rows_, int key_width, const int64_t* offsets,
                                         const int64_t* stream_ids, const int64_t* bases, int64_t num_segments,
-                                        int64_t num_states, uint32_t k, const DrawParams& dp, void* state_rows,
+                                        int64_t num_states, uint32_t k, const DrawParams& dp, void* state_rows_,
                                         int64_t* state_idx, int64_t* state_next, hipStream_t st) {
     if (num_segments <= 0 || num_states <= 0) return hipSuccess;
     if (k > kSegSampleStateMaxK) return hipErrorInvalidValue;
-    if (rows_vec16(key_width, rows, state_rows))
-        return launch_rows_update<uint4>((const unsigned char*)rows, key_width, offsets, stream_ids, bases,
-                                         num_segments, num_states, k, dp, (unsigned char*)state_rows, state_idx,
-                                         state_next, st);
-    return launch_rows_update<uint64_t>((const unsigned char*)rows, key_width, offsets, stream_ids, bases, num_segments,
-                                        num_states, k, dp, (unsigned char*)state_rows, state_idx, state_next, st);
+    const unsigned char* rows = (const unsigned char*)rows_;
+    unsigned char* state_rows = (unsigned char*)state_rows_;
+    return with_granule(rows_vec16(key_width, rows, state_rows), [&](auto granule) {
+        using G = decltype(granule);
+        const uint32_t C = (uint32_t)key_width / (uint32_t)sizeof(G);
+        const SeedWords sw(dp);
+        const uint32_t fifo_cap = env_fifo_cap();
+        auto launch = [&](auto kernel, int waves) {
+            return [&, kernel, waves](unsigned grid, size_t lds) {
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, st, rows, offsets, stream_ids, bases,
+                                   num_segments, num_states, k, C, sw.k0, sw.k1, dp.stream, state_rows, state_idx,
+                                   state_next, fifo_cap);
+            };
+        };
+        return launch_update(num_segments, k, launch(k2_segmented_rows_update_wg<G>, kWavesWG),
+                             launch(k2_segmented_rows_update<G>, kWaves));
+    });
 }
 
 hipError_t launch_segmented_rows_merge(const void* part_rows, int key_width, const int64_t* part_idx,
                                        const int64_t* part_next, int32_t parts, int64_t num_states, uint32_t k,
                                        void* state_rows, int64_t* state_idx, int64_t* state_next, hipStream_t st) {
     if (parts <= 0 || num_states <= 0) return hipSuccess;
-    const uint64_t blocks = ((uint64_t)num_states * k + 255) / 256;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (rows_vec16(key_width, part_rows, state_rows))
-        hipLaunchKernelGGL(k2_segmented_rows_merge<uint4>, dim3((unsigned)blocks), dim3(256), 0, st,
-                           (const unsigned char*)part_rows, part_idx, part_next, parts, num_states, k,
-                           (uint32_t)key_width / 16u, (unsigned char*)state_rows, state_idx, state_next);
-    else
-        hipLaunchKernelGGL(k2_segmented_rows_merge<uint64_t>, dim3((unsigned)blocks), dim3(256), 0, st,
-                           (const unsigned char*)part_rows, part_idx, part_next, parts, num_states, k,
-                           (uint32_t)key_width / 8u, (unsigned char*)state_rows, state_idx, state_next);
-    return hipGetLastError();
+    unsigned grid = 0;
+    RSV_HIP_RET(merge_grid(num_states, k, &grid));
+    return with_granule(rows_vec16(key_width, part_rows, state_rows), [&](auto granule) {
+        using G = decltype(granule);
+        hipLaunchKernelGGL(k2_segmented_rows_merge<G>, dim3(grid), dim3(256), 0, st, (const unsigned char*)part_rows,
+                           part_idx, part_next, parts, num_states, k, (uint32_t)key_width / (uint32_t)sizeof(G),
+                           (unsigned char*)state_rows, state_idx, state_next);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace rsv
