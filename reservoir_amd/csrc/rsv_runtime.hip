@@ -1580,7 +1580,11 @@ rsv_status rsv_merge_packed(rsv_sampler* s, const int64_t* rows_dev, int32_t par
     touch(s);
     if (rsv_status st = flush_stage(s)) return st;
     if (rsv_status st = ensure_slots(s)) return st;
-    if (total_count > s->count) s->count = total_count;
+    if (total_count > s->count) {
+        // a publication holds min(count, k) keys: once the count crosses k it covers too few (rsv_seek)
+        if (std::min<int64_t>(total_count, s->k) != std::min<int64_t>(s->count, s->k)) s->pub_valid = false;
+        s->count = total_count;
+    }
     if (parts > 0) {
         bool fused = false;
         if (s->k <= kFusedPublishMaxK && s->kw <= 8) {  // merge + publish in one dispatch
