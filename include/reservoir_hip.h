@@ -144,7 +144,9 @@ rsv_status rsv_sample_batch(rsv_sampler* s, const void* keys, int64_t n, int32_t
  * elements that end up in the reservoir need `map`.  slot_offsets_host[k] receives, per slot, the
  * offset in [0, n) of the element that now holds it (fill phase S:253-255 included), or -1 where
  * the slot did not change.  The caller maps exactly those elements (seq(offset)) and passes their
- * keys to rsv_fill_slots; until then every other call on the handle returns RSV_E_ILLEGAL_STATE.
+ * keys to rsv_fill_slots; until then (or rsv_abort_indexed / rsv_commit_indexed) every other sampling,
+ * staging, result, seek, export and merge call on the handle returns RSV_E_ILLEGAL_STATE and leaves
+ * it as it was (the plumbing calls -- see "Plumbing calls" below -- are still taken).
  * ELEMENTS samplers only (Sampler.distinct maps every element: its sampleAll is the trait default,
  * S:50).  One K1 pass over the index range, k x 8 B back over PCIe -- no key crosses the link.
  * `map` then runs once per slot that changed, on its final holder: for a pure map the reservoir is
@@ -194,8 +196,8 @@ rsv_status rsv_commit_indexed(rsv_sampler* s);
  * returns RSV_E_ILLEGAL_STATE.  mem says where `hashes` live (host hashes travel through pinned
  * staging); n == 0 is a valid empty batch; *n_cand receives the candidate count.  The call returns
  * with its device work done, on a caller stream too.  Until rsv_candidates_commit or
- * rsv_candidates_abort every call but those two, rsv_candidates_read, rsv_is_open, rsv_count and
- * rsv_destroy returns RSV_E_ILLEGAL_STATE.  Multi-GPU merging of such samplers is not provided. */
+ * rsv_candidates_abort every call but those two, rsv_candidates_read, rsv_is_open, rsv_count,
+ * rsv_get_stream and rsv_destroy returns RSV_E_ILLEGAL_STATE.  Multi-GPU merging of such samplers is not provided. */
 rsv_status rsv_distinct_candidates(rsv_sampler* s, const int64_t* hashes, int64_t n, int32_t mem, int64_t* n_cand);
 /* The pending batch's candidates into host buffers of cap entries: offsets strictly ascending in
  * [0, n), the scrambled hash of each beside it (the elemHash of S:396).  The same for any order the
@@ -215,7 +217,9 @@ rsv_status rsv_candidates_abort(rsv_sampler* s);
  * min(count, k) keys (ELEMENTS: slot order, which is part of the reference result) or the distinct
  * set (DISTINCT: ascending scrambled hash; the reference's order is HashSet order) into host
  * memory `out` of `cap` keys, and the count into *out_n.  Single-use samplers close (S:345-350):
- * any later call but rsv_is_open returns RSV_E_ILLEGAL_STATE. */
+ * every later sampling, staging, result, seek, export, merge and distinct-info / log call returns
+ * RSV_E_ILLEGAL_STATE (checkOpen comes before any other work, S:185-186); the plumbing calls below
+ * stay valid until rsv_destroy. */
 rsv_status rsv_result(rsv_sampler* s, void* out, int64_t cap, int64_t* out_n);
 /* Same, into device memory (no host round trip of the keys). */
 rsv_status rsv_result_device(rsv_sampler* s, void* out_dev, int64_t cap, int64_t* out_n);
@@ -230,6 +234,16 @@ void       rsv_host_release(void* buf);
 
 int32_t    rsv_is_open(const rsv_sampler* s); /* Sampler.isOpen (S:67, S:193, S:380) */
 int64_t    rsv_count(const rsv_sampler* s);   /* elements sampled so far (S:203) */
+
+/* Plumbing calls: rsv_is_open, rsv_count, rsv_get_stream, rsv_set_stream, rsv_set_resolve_stream,
+ * rsv_synchronize, rsv_profile_enable, rsv_profile_read and rsv_destroy neither read nor change the
+ * sample, so the lifecycle does not gate them: they are taken on a closed single-use handle (a
+ * caller still synchronizes, reads its kernel times or hands the stream back after result()), while
+ * keys are owed after rsv_sample_indexed, and after rsv_commit_indexed.  The one exception is a
+ * pending candidate batch (rsv_distinct_candidates): until its commit or abort the calls among them
+ * that return a status -- rsv_set_stream, rsv_set_resolve_stream, rsv_synchronize, rsv_profile_* --
+ * return RSV_E_ILLEGAL_STATE, as that call's text says.  rsv_count includes the keys staged by
+ * rsv_sample / rsv_stage_commit; a closed handle keeps reporting its final count. */
 
 /* Streams: every handle owns a non-blocking HIP stream; a caller may substitute its own.  On the
  * handle's own stream every call returns with its device work finished (ownership of caller

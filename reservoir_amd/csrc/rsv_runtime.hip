@@ -122,12 +122,27 @@ struct AlgoLState {  // RandomElements' private state (Sampler.scala:199-205)
 
 using namespace rsv;
 
+static_assert(__BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__ && sizeof(bool) == 1, "rsv_sampler::gate reads four bools as a word");
+constexpr uint32_t kGateReady = 1;  // bytes {open = 1, keys_owed = 0, keys_external = 0, cand_pending = 0}
+
 struct rsv_sampler {
     rsv_config cfg{};
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    bool open = true;
+    // The lifecycle flags, also readable as one word: rsv_sample / rsv_stage_acquire / rsv_stage_commit
+    // go ahead iff `gate == kGateReady` (open, no keys owed, slots hold keys, no candidate batch) -- one
+    // load and compare per element; every other state goes through check_keyed for its message.
+    //   keys_owed      rsv_sample_indexed: the caller still owes the new holders' keys (rsv_fill_slots)
+    //   keys_external  rsv_commit_indexed / rsv_distinct_candidates: the caller keeps the elements (any
+    //                  JVM B); the slots hold no keys
+    //   cand_pending   rsv_distinct_candidates: the caller owes a commit or abort
+    union {
+        struct {
+            bool open, keys_owed, keys_external, cand_pending;
+        };
+        uint32_t gate = 1;  // open
+    };
     int64_t count = 0;
     int kw = 8;
     uint32_t k = 0;
@@ -147,12 +162,8 @@ struct rsv_sampler {
     int64_t* ev_pos_d = nullptr;
     int32_t* ev_slot_d = nullptr;
     int64_t ev_cap = 0;
-    // index-only batches (rsv_sample_indexed): per slot the batch offset of its new element, and
-    // whether the caller still owes those elements' keys (rsv_fill_slots)
+    // index-only batches (rsv_sample_indexed): per slot the batch offset of its new element
     int64_t* idx_offs_d = nullptr;
-    bool keys_owed = false;
-    // rsv_commit_indexed: the caller keeps the elements (any JVM B); the slots hold no keys
-    bool keys_external = false;
     // rsv_abort_indexed: the slot indices before the pending index-only batch, and its start
     int64_t* idx_bak_d = nullptr;
     bool idx_fresh = false;
@@ -175,7 +186,6 @@ struct rsv_sampler {
     // distinct for any B (rsv_distinct_candidates): the hash-only candidate pass; the caller keeps the
     // elements (keys_external) and owes a commit or abort while cand_pending
     ObjDistinct* obj = nullptr;
-    bool cand_pending = false;
     int64_t cand_batch = 0;  // the pending batch's element count
     // host staging: per-element calls and host batches
     // per-element sample(): two pinned staging buffers; a full one is flushed asynchronously
@@ -1003,7 +1013,7 @@ static rsv_status stage_slow(rsv_sampler* s, bool pre) {
 
 rsv_status rsv_sample(rsv_sampler* s, const void* key, const int64_t* hash) {
     // per-element hot path (the akka operator calls this per element): no HIP call here
-    if (!s || !s->open || s->keys_external) return check_keyed(s);
+    if (!s || s->gate != kGateReady) return check_keyed(s);
     if (!key) return fail(RSV_E_NULL_POINTER, "key is NULL");
     const bool pre = s->hash_kind == kHashPrecomputed && s->cfg.kind == RSV_KIND_DISTINCT;
     if (pre && !hash) return fail(RSV_E_NULL_POINTER, "hash is NULL for RSV_HASH_PRECOMPUTED");
@@ -1020,7 +1030,7 @@ rsv_status rsv_sample(rsv_sampler* s, const void* key, const int64_t* hash) {
 }
 
 rsv_status rsv_stage_acquire(rsv_sampler* s, void** keys_out, int64_t** hashes_out, int64_t* capacity) {
-    if (!s || !s->open || s->keys_external) return check_keyed(s);
+    if (!s || s->gate != kGateReady) return check_keyed(s);
     if (!keys_out || !capacity) return fail(RSV_E_NULL_POINTER, "keys_out/capacity is NULL");
     const bool pre = s->hash_kind == kHashPrecomputed && s->cfg.kind == RSV_KIND_DISTINCT;
     if (s->stage_n == 0 || s->stage_n == s->stage_cap) {
@@ -1034,7 +1044,7 @@ rsv_status rsv_stage_acquire(rsv_sampler* s, void** keys_out, int64_t** hashes_o
 }
 
 rsv_status rsv_stage_commit(rsv_sampler* s, int64_t n) {
-    if (!s || !s->open || s->keys_external) return check_keyed(s);
+    if (!s || s->gate != kGateReady) return check_keyed(s);
     if (n < 0 || n > s->stage_cap - s->stage_n)
         return fail(RSV_E_ILLEGAL_ARGUMENT, "commit exceeds the acquired staging capacity");
     s->stage_n += n;
@@ -1236,6 +1246,10 @@ static rsv_status result_impl(rsv_sampler* s, void* out, int64_t cap, int64_t* o
         m = std::min<int64_t>(s->count, (int64_t)s->k);  // resultImpl, Sampler.scala:318-331
         if (m > cap) return fail(RSV_E_ILLEGAL_ARGUMENT, "result buffer too small");
         if (m && !out && !take) return fail(RSV_E_NULL_POINTER, "out is NULL");
+        // a count that came from rsv_seek alone: the slots were never written, and a recycled block
+        // still holds its last sampler's keys -- the result is m empty (zero) slots
+        if (m)
+            if (rsv_status st = ensure_slots(s)) return st;
         src = s->slot_key;
         if (m && !out && take) out = s->result_h;  // checked: a published result (see rsv_result_take)
         if (m && device_out) {
