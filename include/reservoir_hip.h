@@ -456,7 +456,7 @@ rsv_status rsv_sample_segmented_rows_merge(const void* part_rows_dev, const int6
  * out_hashes_dev when not NULL), counts_dev[s] = min(k, D_s), slots beyond it zero.  That is the
  * reference's set whenever no two distinct keys share the final maximum hash (always under an
  * injective hash), whatever the arrival order.  The reference's arrival-order tie replay
- * (RSV_DISTINCT_ORDERED) is not provided here: such callers keep separate handles.
+ * (RSV_DISTINCT_ORDERED) is rsv_distinct_segmented_ordered below.
  * hash_kind: IDENTITY, JAVA_LONG, JAVA_INT, DEFAULT (JAVA_INT for key_width 4, JAVA_LONG for 8), or
  * PRECOMPUTED with hashes_dev, one int64 per key, indexed like keys_dev (NULL otherwise).
  * key_width 4 or 8 (byte keys: RSV_E_UNSUPPORTED); 1 <= k <= 4096 (larger: RSV_E_UNSUPPORTED).
@@ -466,6 +466,27 @@ rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_de
                                   int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind, uint64_t seed,
                                   uint64_t stream_base, void* out_keys_dev, int64_t* out_hashes_dev,
                                   int64_t* counts_dev, void* hip_stream);
+
+/* Segmented distinct in the reference's order (RSV_DISTINCT_ORDERED): inputs, seeding, hash kinds, key
+ * widths and k as rsv_distinct_segmented.  Stream s ends holding exactly the set a RandomValues instance
+ * (S:383-412) holds after sample() over keys_dev[offsets[s] .. offsets[s+1]) in that order, for any hash:
+ * where more than k distinct keys have a hash <= the set's maximum hash M, the members with h = M are the
+ * ones the reference's heap keeps (arrival order and scala 2.13 PriorityQueue's tie behaviour), not the
+ * smallest keys.  The reference's own result order is a HashSet's and unspecified; the output is written
+ * as rsv_distinct_segmented writes it: ascending by (h, key), counts_dev[s] = min(k, D_s), zeros beyond.
+ * tied_dev[num_streams] (required; it is also the channel between the launch's two kernels):
+ * tied_dev[s] = 1 iff the set is full and some distinct key of the stream outside the bottom-k by (h, key)
+ * has hash M -- rsv_distinct_info.tied per stream, exact also for M = INT64_MAX or INT64_MIN -- else 0.  A
+ * stream with tied_dev[s] == 0 is bit-identical to rsv_distinct_segmented's row.
+ * out_hashes_dev may be NULL.  Byte keys: RSV_E_UNSUPPORTED; 1 <= k <= 4096 (larger:
+ * RSV_E_UNSUPPORTED).  Stateless and stream-ordered on hip_stream: no host wait, no allocation.
+ * Not provided in ordered form: byte-key rows (rsv_distinct_segmented_rows), resumed state and merge (a
+ * state of k entries cannot carry the heap's history), and k > 4096: such callers keep separate handles. */
+rsv_status rsv_distinct_segmented_ordered(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
+                                          int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
+                                          uint64_t seed, uint64_t stream_base, void* out_keys_dev,
+                                          int64_t* out_hashes_dev, int64_t* counts_dev, int32_t* tied_dev,
+                                          void* hip_stream);
 
 /* Segmented distinct over fixed-width byte keys (java.util.UUID, case classes of primitives): what
  * rsv_distinct_segmented is for 4- and 8-byte keys.  Stream s is rows [offsets[s], offsets[s+1]) of

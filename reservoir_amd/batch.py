@@ -136,6 +136,43 @@ def distinct_segmented(keys, offsets, k: int, seed: int, stream_base: int = 0, h
     return out, out_h, counts
 
 
+def distinct_segmented_ordered(keys, offsets, k: int, seed: int, stream_base: int = 0, hash: str = "default",
+                               hashes=None):
+    """distinct_segmented in the reference's order: exact for any hash, the tie bucket included.
+
+    Returns (out_keys[S, k], out_hashes[S, k], counts[S], tied[S]) device tensors (tied int32).  Stream s
+    holds the set a single Sampler.distinct(k, seed=seed + stream_base + s, order="ordered") fed the same
+    keys in the same order holds -- the reference's RandomValues -- written ascending by (scrambled hash,
+    key), slots beyond counts[s] zero.  tied[s] is 1 iff the set is full and a distinct key outside the
+    bottom-k by (hash, key) has the set's maximum hash; where it is 0 the row is distinct_segmented's.
+    hash / hashes and k as distinct_segmented.
+    """
+    import torch
+
+    L = N.load()
+    keys, offsets, hashes = _segd_inputs(torch, keys, offsets, hashes)
+    if hashes is not None:
+        kind = N.HASH_PRECOMPUTED
+    elif hash in _SEG_HASH:
+        kind = _SEG_HASH[hash]
+    else:
+        raise N.IllegalArgumentException(f"unknown hash {hash!r}")
+    S = offsets.numel() - 1
+    kk = max(int(k), 0)
+    out = torch.empty((max(S, 0), kk), dtype=keys.dtype, device=keys.device)
+    out_h = torch.empty((max(S, 0), kk), dtype=torch.int64, device=keys.device)
+    counts = torch.empty(max(S, 0), dtype=torch.int64, device=keys.device)
+    tied = torch.empty(max(S, 0), dtype=torch.int32, device=keys.device)
+    if S <= 0:
+        return out, out_h, counts, tied
+    N.check(L.rsv_distinct_segmented_ordered(
+        C.c_void_p(keys.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
+        C.c_void_p(offsets.data_ptr()), S, keys.element_size(), k, kind, seed & (2**64 - 1),
+        stream_base & (2**64 - 1), C.c_void_p(out.data_ptr()), C.c_void_p(out_h.data_ptr()),
+        C.c_void_p(counts.data_ptr()), C.c_void_p(tied.data_ptr()), _stream_ptr(torch, keys.device)))
+    return out, out_h, counts, tied
+
+
 def _rows_inputs(torch, rows, offsets, dtypes=None):
     """rows / offsets of a call over byte keys (dtypes: the row dtypes it takes, None: any), checked and
     contiguous; returns (rows, offsets, width)."""

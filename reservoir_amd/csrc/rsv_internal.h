@@ -178,6 +178,12 @@ constexpr uint32_t kSegDistinctMaxK = 4096;
 hipError_t launch_segdistinct(const void* keys, int key_width, const int64_t* hashes, const int64_t* offsets, int64_t S,
                               uint32_t k, int hash_kind, uint64_t seed0, void* out_keys, int64_t* out_hashes,
                               int64_t* counts, hipStream_t st);
+// K5 ordered (rsv_segdistinct.hip): launch_segdistinct with tied[s] = 1 iff the set is full and a distinct key
+// outside it has its maximum hash, then a second kernel on the same stream that replays RandomValues over the tied
+// streams in arrival order and rewrites their rows (ascending by (h, key) like the others).  No allocation.
+hipError_t launch_segdistinct_ordered(const void* keys, int key_width, const int64_t* hashes, const int64_t* offsets,
+                                      int64_t S, uint32_t k, int hash_kind, uint64_t seed0, void* out_keys,
+                                      int64_t* out_hashes, int64_t* counts, int32_t* tied, hipStream_t st);
 // K5 over byte keys (rsv_segdistinct.hip, the same element loop and forms): rows of key_width bytes (16..256, a
 // multiple of 8; rows and out_rows 8-byte aligned), the bottom-k by (scrambled hash, row words unsigned).
 // hashes: one per row, or null for UUID.hashCode of 16-byte rows.

@@ -1753,7 +1753,7 @@ rsv_status rsv_sample_segmented_rows_merge(const void* part_rows_dev, const int6
     return RSV_OK;
 }
 
-// k and key_width of the three K5 entry points (fn: the entry point's name, for the messages)
+// k and key_width of the four K5 entry points over 4- and 8-byte keys (fn: the entry point's name, for the messages)
 static rsv_status check_segdistinct_shape(const char* fn, int32_t k, int32_t key_width) {
     if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
     if (k > (int32_t)kSegDistinctMaxK)
@@ -1788,6 +1788,26 @@ rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_de
     RSV_HIP_TRY(launch_segdistinct(keys_dev, key_width, hk == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr, offsets_dev,
                                    num_streams, (uint32_t)k, hk, seed + stream_base, out_keys_dev, out_hashes_dev,
                                    counts_dev, (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
+rsv_status rsv_distinct_segmented_ordered(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
+                                          int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
+                                          uint64_t seed, uint64_t stream_base, void* out_keys_dev,
+                                          int64_t* out_hashes_dev, int64_t* counts_dev, int32_t* tied_dev,
+                                          void* hip_stream) {
+    // rsv_distinct_segmented's checks in its order; tied_dev with the other output buffers
+    int hk;
+    if (rsv_status st = check_segdistinct_shape("rsv_distinct_segmented_ordered", k, key_width)) return st;
+    if (rsv_status st = resolve_segdistinct_hash(hash_kind, key_width, hk)) return st;
+    if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
+    if (num_streams == 0) return RSV_OK;
+    if (!offsets_dev || !out_keys_dev || !counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (!tied_dev) return fail(RSV_E_NULL_POINTER, "rsv_distinct_segmented_ordered needs tied_dev");
+    if (hk == RSV_HASH_PRECOMPUTED && !hashes_dev) return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
+    RSV_HIP_TRY(launch_segdistinct_ordered(keys_dev, key_width, hk == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr,
+                                           offsets_dev, num_streams, (uint32_t)k, hk, seed + stream_base, out_keys_dev,
+                                           out_hashes_dev, counts_dev, tied_dev, (hipStream_t)hip_stream));
     return RSV_OK;
 }
 

@@ -3,8 +3,11 @@
 // No reference counterpart; = S separate RandomValues instances (Sampler.scala:383-412), each seeded
 // with java.util.Random(seed + stream_base + s), in the engine's set order (RSV_DISTINCT_SET): stream
 // s keeps the min(k, D_s) distinct keys with the smallest (scrambled hash, key), written ascending.
-// The reference's arrival-order tie replay (RSV_DISTINCT_ORDERED) is out of scope here: a caller
-// that needs it for a colliding hash keeps separate handles.
+// rsv_distinct_segmented_ordered (the last section of this file) is the same launch followed by a
+// replay of the streams whose boundary hash bucket is oversubscribed: there the members of that
+// bucket are the reference's, chosen by arrival order and the heap's tie behaviour
+// (RSV_DISTINCT_ORDERED), not the smallest keys.  Not provided in ordered form: byte-key rows, resumed
+// state and merge (k entries cannot carry the heap's history), k > 4096.
 //
 // One TEAM of NT threads per stream, streams taken grid-stride.  The team holds P 16-byte entries
 // (h, key) in LDS: the current set [0, m) ascending by (h, key), and behind it the candidates
@@ -154,6 +157,10 @@ struct Keys : KeyOrd {
         t.Th = se[k - 1].h;
         t.Tk = se[k - 1].key;
     }
+    // what the loop refuses is of no interest here (TiedKeys notes it)
+    static __device__ __forceinline__ void refuse(int64_t, const Team&) {}
+    template <int NT>
+    static __device__ __forceinline__ void trimmed(const Ent*, uint32_t, uint32_t, const Team&) {}
 };
 
 // Byte keys: where an entry's second word (its ref) finds its row of W8 words.  One source, the stateless
@@ -255,6 +262,9 @@ struct Rows : RowOrd<TWO> {
         t.Tk = se[k - 1].key;
         if (threadIdx.x < this->W8) s_trow[threadIdx.x] = this->at(t.Tk)[threadIdx.x];
     }
+    static __device__ __forceinline__ void refuse(int64_t, const Team&) {}
+    template <int NT>
+    static __device__ __forceinline__ void trimmed(const Ent*, uint32_t, uint32_t, const Team&) {}
 };
 
 // Sort + dedup + trim of the team's first n entries; returns the new set size min(k, distinct).
@@ -341,7 +351,10 @@ __device__ __forceinline__ void take_piece(Ent* __restrict__ se, uint32_t* __res
             if (base + (int64_t)u * NT >= hi) break;  // uniform: the tail chunk's empty steps
             if (t.n_tot + NT > P || (t.m < k && t.n_tot >= 4 * k)) {
                 t.m = merge_set<NT>(se, t.n_tot, k, s_scan, src);
-                if (t.m == k) src.set_T(se, k, t);
+                if (t.m == k) {
+                    src.set_T(se, k, t);
+                    src.template trimmed<NT>(se, k, t.n_tot, t);
+                }
                 __syncthreads();  // T is read before the appends below overwrite anything
                 if (tid == 0) *s_cnt = t.m;
                 t.n_tot = t.m;
@@ -349,6 +362,7 @@ __device__ __forceinline__ void take_piece(Ent* __restrict__ se, uint32_t* __res
             }
             const int64_t h = src.h_of(key[u], hv[u]);
             const bool pass = i < hi && src.admits(h, key[u], t);
+            if (i < hi && !pass) src.refuse(h, t);
             const uint64_t mask = __ballot(pass);
             if (mask) {
                 const uint32_t lead = (uint32_t)(__ffsll((long long)mask) - 1);  // the wave's first admitting lane
@@ -623,6 +637,201 @@ __global__ __launch_bounds__(NT) void segrowstate_kernel(const uint64_t* in_rows
     }
 }
 
+// ---- Ordered (rsv_distinct_segmented_ordered) ----
+// Once RandomValues' heap is full its maximum M is the k-th smallest hash over the distinct keys seen
+// and it holds every key with h < M, so its set is the bottom-k by (h, key) unless more than k distinct
+// keys have h <= M: only then does the arrival order decide who of the bucket h = M stays.  Two kernels:
+// K5 as above, which also finds those streams (tied), and a replay of RandomValues for them alone.
+//
+// Kernel 1.  TiedKeys is Keys<KeyT, true> that also notes, per lane, whether the team refused an element
+// whose h is the current T.h: an element that fails `admits` ((h, key) > T), or an entry a merge trims
+// (the entries above the new T among se[k, n): an entry of distinct rank >= k sits at a sorted position
+// >= k, which the compaction does not write).  The note is dropped when a merge lowers T.h.  A refused
+// element is a distinct key outside the final set, for T only falls; and a distinct key x outside the
+// final set with h(x) = M, the final maximum, is refused at its first occurrence at the latest, at a
+// time when M <= T.h <= h(x), so T.h = M then and ever after and the note stays.  Hence
+//   tied = (m == k && some lane holds a note),
+// exactly, whatever M is: below k entries T is the pad and nothing is refused.  This says what "the
+// minimum h of everything refused equals se[k-1].h" says (a refused h is never below T.h) at one
+// v_cndmask per step: the compare h == T.h is the admission test's own.  Keeping the minimum itself cost
+// 7 VALU per step (DESIGN.md 5c.3 has both measurements).
+template <typename KeyT>
+struct TiedKeys : Keys<KeyT, true> {
+    mutable bool at_T;
+    __device__ __forceinline__ void refuse(int64_t h, const Team& t) const { at_T |= h == t.Th; }
+    __device__ __forceinline__ void set_T(const Ent* se, uint32_t k, Team& t) const {
+        const int64_t was = t.Th;
+        Keys<KeyT, true>::set_T(se, k, t);
+        if (t.Th != was) at_T = false;
+    }
+    // behind set_T, and before the barrier that lets the appends go on
+    template <int NT>
+    __device__ __forceinline__ void trimmed(const Ent* se, uint32_t k, uint32_t n, const Team& t) const {
+        for (uint32_t i = k + threadIdx.x; i < n; i += NT) {
+            const Ent e = se[i];
+            at_T |= e.h == t.Th && e.key > t.Tk;
+        }
+    }
+};
+
+template <typename KeyT, int NT>
+__global__ __launch_bounds__(NT) void segdistinct_tied_kernel(const KeyT* __restrict__ keys, const int64_t* __restrict__ hashes,
+                                                              const int64_t* __restrict__ offsets, int64_t S, uint32_t k,
+                                                              uint32_t P, int hash_kind, uint64_t seed0,
+                                                              KeyT* __restrict__ out_keys, int64_t* __restrict__ out_hashes,
+                                                              int64_t* __restrict__ counts, int32_t* __restrict__ tied) {
+    extern __shared__ __align__(16) unsigned char seg_lds[];
+    Ent* const se = (Ent*)seg_lds;
+    __shared__ uint32_t s_cnt;
+    __shared__ uint32_t s_scan[NT / 64 > 1 ? NT / 64 : 1];
+    const uint32_t tid = threadIdx.x;
+
+    for (int64_t s = blockIdx.x; s < S; s += gridDim.x) {
+        int64_t r0, r1;
+        java_r0r1(seed0 + (uint64_t)s, r0, r1);
+        __syncthreads();  // the previous stream's output reads are done
+        if (tid == 0) s_cnt = 0;
+        __syncthreads();
+        Team t{0, 0, kMaxI64, kMaxI64, false};
+        const TiedKeys<KeyT> src{{{}, keys, hashes, hash_kind, r0, r1}, false};
+        take_piece<TiedKeys<KeyT>, NT>(se, &s_cnt, s_scan, src, offsets[s], offsets[s + 1], k, P, t);
+        if (t.n_tot != t.m) {  // the last merge, here for what it trims
+            const uint32_t n = t.n_tot;
+            t.m = merge_set<NT>(se, n, k, s_scan, KeyOrd{});
+            if (t.m == k) {
+                src.set_T(se, k, t);
+                src.template trimmed<NT>(se, k, n, t);
+            }
+            t.n_tot = t.m;
+        }
+        const int noted = __syncthreads_or(src.at_T);
+        if (tid == 0) tied[s] = t.m == k && noted;
+        finish_row<KeyT, NT, true>(se, s_scan, t, k, s, out_keys, out_hashes, counts);
+    }
+}
+
+// lane l's value as a scalar (l uniform): two v_readlane, no LDS round trip
+__device__ __forceinline__ int64_t read_lane(int64_t v, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), l);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// Kernel 2: RandomValues (Sampler.scala:394-409) over the tied streams, one wave per stream.  A wave
+// reads the tied words of W consecutive streams at once and replays those that are set, one after the
+// other.  The heap is rsv_host_values.h's, 1-indexed in se[0, k) (entry j at se[j - 1]): scala 2.13
+// mutable.PriorityQueue's addOne/fixUp (sift up while parent < child) and dequeue/fixDown (last entry to
+// the root, sink to the larger child, left on ties, stop when parent >= child), ordered by h alone.
+// The stream is walked in arrival order, 64 elements a step (kU steps loaded ahead).  Of a step, the
+// first lane whose element passes the current test (size < k, or h < maxHash) is taken (read_lane), its
+// key looked up among the heap's keys by all lanes (elements.contains), and admitted by lane 0 if absent; then the
+// lanes behind it are tested again, against the new maxHash.  maxHash never rises once the heap is full
+// and below that every element passes, so a lane that failed once fails for good and the lanes taken are
+// in arrival order.  The barriers order lane 0's heap writes and the other lanes' reads; with one wave
+// per workgroup they cost no wait.  At the end the k entries are sorted by (h, key) and written over the
+// row kernel 1 left; count and tied stay.
+template <typename KeyT>
+__global__ __launch_bounds__(64) void segdistinct_replay_kernel(const KeyT* __restrict__ keys, const int64_t* __restrict__ hashes,
+                                                                const int64_t* __restrict__ offsets, int64_t S, uint32_t k,
+                                                                uint32_t W, int hash_kind, uint64_t seed0,
+                                                                KeyT* __restrict__ out_keys, int64_t* __restrict__ out_hashes,
+                                                                const int32_t* __restrict__ tied) {
+    extern __shared__ __align__(16) unsigned char seg_lds[];
+    Ent* const se = (Ent*)seg_lds;
+    __shared__ uint32_t s_scan[1];
+    const uint32_t lane = threadIdx.x;
+    const int64_t groups = (S + W - 1) / W;
+
+    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+        const int64_t sl = g * W + lane;
+        uint64_t todo = __ballot(lane < W && sl < S && tied[sl] != 0);
+        while (todo) {
+            const int64_t s = g * W + (__ffsll((long long)todo) - 1);
+            todo &= todo - 1;
+            const int64_t lo = offsets[s], hi = offsets[s + 1];
+            int64_t r0, r1;
+            java_r0r1(seed0 + (uint64_t)s, r0, r1);
+            const Keys<KeyT, true> src{{}, keys, hashes, hash_kind, r0, r1};
+            uint32_t n = 0;              // heap size (uniform)
+            int64_t maxh = INT64_MIN;    // the root's h once anything is in
+            __syncthreads();             // the previous stream's output reads are done
+            for (int64_t base = lo; base < hi; base += 64 * kU) {
+                int64_t key[kU], hv[kU];
+#pragma unroll
+                for (int u = 0; u < kU; ++u) {
+                    const int64_t i = base + (int64_t)u * 64 + lane;
+                    key[u] = 0;
+                    hv[u] = 0;
+                    if (i < hi) src.load(i, key[u], hv[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < kU; ++u) {
+                    const int64_t i = base + (int64_t)u * 64 + lane;
+                    if (base + (int64_t)u * 64 >= hi) break;  // uniform
+                    const int64_t h = src.h_of(key[u], hv[u]);
+                    bool pend = i < hi;
+                    for (;;) {
+                        const uint64_t mask = __ballot(pend && (n < k || h < maxh));
+                        if (!mask) break;
+                        const int l = __ffsll((long long)mask) - 1;
+                        if ((int)lane == l) pend = false;
+                        const int64_t ck = read_lane(key[u], l), ch = read_lane(h, l);
+                        // elements.contains: n / 64 reads per lane, eight in flight
+                        bool found = false;
+                        const uint32_t full = n >> 6;
+                        uint32_t r = 0;
+                        for (; r + 8 <= full; r += 8) {
+                            int64_t mk[8];
+#pragma unroll
+                            for (int x = 0; x < 8; ++x) mk[x] = se[(r + x) * 64 + lane].key;
+#pragma unroll
+                            for (int x = 0; x < 8; ++x) found |= mk[x] == ck;
+                        }
+                        for (uint32_t j = r * 64 + lane; j < n; j += 64) found |= se[j].key == ck;
+                        if (__ballot(found)) continue;  // a member
+                        if (lane == 0) {
+                            uint32_t nn = n;
+                            if (nn == k) {  // dequeue: the root leaves
+                                const Ent last = se[nn - 1];
+                                --nn;
+                                if (nn) {
+                                    uint32_t q = 1;
+                                    while (2 * q <= nn) {
+                                        uint32_t c = 2 * q;
+                                        if (c + 1 <= nn && se[c - 1].h < se[c].h) ++c;
+                                        if (last.h >= se[c - 1].h) break;
+                                        se[q - 1] = se[c - 1];
+                                        q = c;
+                                    }
+                                    se[q - 1] = last;
+                                }
+                            }
+                            uint32_t q = nn + 1;  // addOne
+                            while (q > 1 && se[(q >> 1) - 1].h < ch) {
+                                se[q - 1] = se[(q >> 1) - 1];
+                                q >>= 1;
+                            }
+                            se[q - 1] = Ent{ch, ck};
+                        }
+                        if (n < k) ++n;
+                        __syncthreads();
+                        maxh = se[0].h;
+                        __syncthreads();
+                    }
+                }
+            }
+            const uint32_t m = merge_set<64>(se, n, k, s_scan, KeyOrd{});
+            __syncthreads();
+            const int64_t ob = s * (int64_t)k;
+            for (uint32_t i = lane; i < m; i += 64) {
+                const Ent e = se[i];
+                out_keys[ob + i] = (KeyT)e.key;
+                if (out_hashes) out_hashes[ob + i] = e.h;
+            }
+        }
+    }
+}
+
 // The forms: f(KeyT{}, NT as an integral_constant, P) for the key width and k of a launch.
 template <typename KeyT, typename F>
 hipError_t with_form_of(uint32_t k, F& f) {
@@ -663,6 +872,38 @@ hipError_t launch_segdistinct(const void* keys, int key_width, const int64_t* ha
         constexpr int NT = decltype(nt)::value;
         return launch_teams(segdistinct_kernel<KeyT, NT>, NT, S, P, st, (const KeyT*)keys, hashes, offsets, S, k, P,
                             hash_kind, seed0, (KeyT*)out_keys, out_hashes, counts);
+    });
+}
+
+hipError_t launch_segdistinct_ordered(const void* keys, int key_width, const int64_t* hashes, const int64_t* offsets,
+                                      int64_t S, uint32_t k, int hash_kind, uint64_t seed0, void* out_keys,
+                                      int64_t* out_hashes, int64_t* counts, int32_t* tied, hipStream_t st) {
+    if (S <= 0) return hipSuccess;
+    return with_form(key_width, k, [&](auto key, auto nt, uint32_t P) {
+        using KeyT = decltype(key);
+        constexpr int NT = decltype(nt)::value;
+        const hipError_t e = launch_teams(segdistinct_tied_kernel<KeyT, NT>, NT, S, P, st, (const KeyT*)keys, hashes, offsets,
+                                          S, k, P, hash_kind, seed0, (KeyT*)out_keys, out_hashes, counts, tied);
+        if (e != hipSuccess) return e;
+        // the replay: one wave and pow2ceil(k) entries (the heap, and the pads of its final sort) per
+        // stream in flight.  A wave looks at W consecutive tied words per step: 64 when there are streams
+        // enough to fill the grid that way, fewer when not, so that few streams still spread over the CUs.
+        uint32_t P2 = 2;
+        while (P2 < k) P2 <<= 1;
+        const size_t lds = (size_t)P2 * 16;
+        auto* const replay = segdistinct_replay_kernel<KeyT>;
+        if (lds + 256 > 64 * 1024) {
+            const hipError_t a = hipFuncSetAttribute((const void*)replay, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (a != hipSuccess) return a;
+        }
+        const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>((160 * 1024) / (lds + 256), 32));
+        const uint64_t cap = 256ull * per_cu * 4;
+        uint32_t W = 1;
+        while (W < 64 && (uint64_t)S / (2 * W) >= cap) W <<= 1;
+        const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)S + W - 1) / W, cap);
+        hipLaunchKernelGGL(replay, dim3(grid), dim3(64), lds, st, (const KeyT*)keys, hashes, offsets, S, k, W, hash_kind, seed0,
+                           (KeyT*)out_keys, out_hashes, (const int32_t*)tied);
+        return hipGetLastError();
     });
 }
 
