@@ -480,8 +480,9 @@ rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_de
  * stream with tied_dev[s] == 0 is bit-identical to rsv_distinct_segmented's row.
  * out_hashes_dev may be NULL.  Byte keys: RSV_E_UNSUPPORTED; 1 <= k <= 4096 (larger:
  * RSV_E_UNSUPPORTED).  Stateless and stream-ordered on hip_stream: no host wait, no allocation.
- * Not provided in ordered form: byte-key rows (rsv_distinct_segmented_rows), resumed state and merge (a
- * state of k entries cannot carry the heap's history), and k > 4096: such callers keep separate handles. */
+ * Byte-key rows in this order: rsv_distinct_segmented_rows_ordered below.  Not provided in ordered form:
+ * resumed state and merge (a state of k entries cannot carry the heap's history), and k > 4096: such callers
+ * keep separate handles. */
 rsv_status rsv_distinct_segmented_ordered(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
                                           int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
                                           uint64_t seed, uint64_t stream_base, void* out_keys_dev,
@@ -512,6 +513,30 @@ rsv_status rsv_distinct_segmented_rows(const void* rows_dev, const int64_t* hash
                                        int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
                                        uint64_t seed, uint64_t stream_base, void* out_rows_dev,
                                        int64_t* out_hashes_dev, int64_t* counts_dev, void* hip_stream);
+
+/* Segmented distinct over byte keys in the reference's order (RSV_DISTINCT_ORDERED): what
+ * rsv_distinct_segmented_ordered is for 4- and 8-byte keys.  Inputs, seeding, hash kinds (PRECOMPUTED at any
+ * width, DEFAULT = UUID.hashCode at key_width 16), key widths, k, the alignment of rows_dev and out_rows_dev
+ * and every check are rsv_distinct_segmented_rows': the same bad arguments give the same status in the same
+ * order.  Stream s ends holding exactly the rows a RandomValues instance (S:383-412) over byte keys holds
+ * after sample() over rows [offsets[s], offsets[s+1]) in that order, equality being equality of all bytes --
+ * for any hash, UUID.hashCode's 32 bits included: where more than k distinct rows have a hash <= the set's
+ * maximum hash M, the members with h = M are the ones the reference's heap keeps (arrival order and scala
+ * 2.13 PriorityQueue's tie behaviour), not the smallest rows.  The output is laid out as
+ * rsv_distinct_segmented_rows writes it: rows ascending by (h, words as unsigned 64-bit values, word 0
+ * first), their h into out_hashes_dev when not NULL, counts_dev[s] = min(k, D_s), rows and hashes beyond
+ * the count zero.
+ * tied_dev[num_streams] (required, RSV_E_NULL_POINTER; it is also the channel between the launch's two
+ * kernels): tied_dev[s] = 1 iff the set is full and some distinct row of the stream outside the bottom-k by
+ * (h, row) has hash M, exact also for M = INT64_MAX or INT64_MIN, else 0.  A stream with tied_dev[s] == 0 is
+ * bit-identical to rsv_distinct_segmented_rows' row block.
+ * Stateless and stream-ordered on hip_stream: no host wait, no allocation.  Resumed state, merge and
+ * k > 4096 have no ordered form. */
+rsv_status rsv_distinct_segmented_rows_ordered(const void* rows_dev, const int64_t* hashes_dev,
+                                               const int64_t* offsets_dev, int64_t num_streams, int32_t key_width,
+                                               int32_t k, int32_t hash_kind, uint64_t seed, uint64_t stream_base,
+                                               void* out_rows_dev, int64_t* out_hashes_dev, int64_t* counts_dev,
+                                               int32_t* tied_dev, void* hip_stream);
 
 /* Segmented distinct, resumed: long-lived distinct samplers advanced by one launch per batch.  The
  * state is the caller's device memory: state_keys_dev[num_states*k] (key_width values),

@@ -6,6 +6,7 @@ libreservoir_hip.so.  Every function raises if the engine is unavailable.
     sample_segmented  -- K2: S independent samplers in one launch (one wave per stream)
     distinct_segmented -- K5: S independent Sampler.distinct streams in one launch (bottom-k per stream)
     distinct_segmented_rows -- K5 over fixed-width byte keys (UUIDs): rows in, the winning rows out
+    distinct_segmented_rows_ordered -- the same in the reference's order (exact under UUID.hashCode's ties)
     SegmentedDistinct -- K5 resumed: the same S streams as caller-held state, advanced by one launch
                          per micro-batch (update) and combined across launches, GPUs and ranks (merge)
     SegmentedDistinctRows -- K5 resumed over byte keys: the rows move inside the caller-held state (update, merge)
@@ -231,6 +232,40 @@ def distinct_segmented_rows(rows, offsets, k: int, seed: int, stream_base: int =
         seed & (2**64 - 1), stream_base & (2**64 - 1), C.c_void_p(out.data_ptr()), C.c_void_p(out_h.data_ptr()),
         C.c_void_p(counts.data_ptr()), _stream_ptr(torch, rows.device)))
     return out, out_h, counts
+
+
+def distinct_segmented_rows_ordered(rows, offsets, k: int, seed: int, stream_base: int = 0, hash: str = "default",
+                                    hashes=None):
+    """distinct_segmented_rows in the reference's order: exact for any hash, the tie bucket included.
+
+    rows, offsets, hash / hashes and k as distinct_segmented_rows.  Returns (out_rows uint8 [S, k, W],
+    out_hashes int64 [S, k], counts int64 [S], tied int32 [S]) device tensors.  Stream s holds the set a
+    single Sampler.distinct(k, key_type="bytesW", seed=seed + stream_base + s, order="ordered") fed the same
+    rows in the same order holds -- the reference's RandomValues over byte keys -- written ascending by
+    (scrambled hash, row words), rows and hashes beyond counts[s] zero.  tied[s] is 1 iff the set is full and
+    a distinct row outside the bottom-k by (hash, row) has the set's maximum hash; where it is 0 the row
+    block is distinct_segmented_rows'.  Under the default hash of 16-byte rows (UUID.hashCode, 32 bits) ties
+    are what this call is for.
+    """
+    import torch
+
+    L = N.load()
+    rows, offsets, hashes = _segd_rows_inputs(torch, rows, offsets, hash, hashes)
+    W = rows.shape[1] * rows.element_size()
+    S = offsets.numel() - 1
+    kk = max(int(k), 0)
+    out = torch.empty((max(S, 0), kk, W), dtype=torch.uint8, device=rows.device)
+    out_h = torch.empty((max(S, 0), kk), dtype=torch.int64, device=rows.device)
+    counts = torch.empty(max(S, 0), dtype=torch.int64, device=rows.device)
+    tied = torch.empty(max(S, 0), dtype=torch.int32, device=rows.device)
+    if S <= 0:
+        return out, out_h, counts, tied
+    N.check(L.rsv_distinct_segmented_rows_ordered(
+        C.c_void_p(rows.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
+        C.c_void_p(offsets.data_ptr()), S, W, k, N.HASH_PRECOMPUTED if hashes is not None else N.HASH_DEFAULT,
+        seed & (2**64 - 1), stream_base & (2**64 - 1), C.c_void_p(out.data_ptr()), C.c_void_p(out_h.data_ptr()),
+        C.c_void_p(counts.data_ptr()), C.c_void_p(tied.data_ptr()), _stream_ptr(torch, rows.device)))
+    return out, out_h, counts, tied
 
 
 def _check_rows_width(what: str, long_what: str, width: int) -> None:

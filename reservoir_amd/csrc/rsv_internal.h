@@ -190,6 +190,12 @@ hipError_t launch_segdistinct_ordered(const void* keys, int key_width, const int
 hipError_t launch_segdistinct_rows(const void* rows, int key_width, const int64_t* hashes, const int64_t* offsets,
                                    int64_t S, uint32_t k, uint64_t seed0, void* out_rows, int64_t* out_hashes,
                                    int64_t* counts, hipStream_t st);
+// K5 over byte keys, ordered (rsv_segdistinct.hip): launch_segdistinct_rows with tied[s] as for
+// launch_segdistinct_ordered ("key" read as "row"), then the replay of RandomValues over the tied streams on the
+// same stream, entries (h, row index), rows read from `rows` on equal hashes only.  No allocation.
+hipError_t launch_segdistinct_rows_ordered(const void* rows, int key_width, const int64_t* hashes, const int64_t* offsets,
+                                           int64_t S, uint32_t k, uint64_t seed0, void* out_rows, int64_t* out_hashes,
+                                           int64_t* counts, int32_t* tied, hipStream_t st);
 // K5 resumed (rsv_segdistinct.hip, the same element loop and forms): the teams started from the caller's state rows
 // (keys[num_states*k], hashes, counts; ascending by (h, key) as launch_segdistinct writes them) and
 // written back in place.  update: segment b into row stream_ids[b] (null: row b), seeded seed0 + row;

@@ -1857,6 +1857,29 @@ rsv_status rsv_distinct_segmented_rows(const void* rows_dev, const int64_t* hash
     return RSV_OK;
 }
 
+rsv_status rsv_distinct_segmented_rows_ordered(const void* rows_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
+                                               int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
+                                               uint64_t seed, uint64_t stream_base, void* out_rows_dev,
+                                               int64_t* out_hashes_dev, int64_t* counts_dev, int32_t* tied_dev,
+                                               void* hip_stream) {
+    // rsv_distinct_segmented_rows' checks in its order; tied_dev with the other output buffers
+    if (rsv_status st = check_segrows_shape("rsv_distinct_segmented_rows_ordered", "rsv_distinct_segmented_ordered", k, key_width))
+        return st;
+    if (rsv_status st = check_segrows_hash(hash_kind, key_width)) return st;
+    if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
+    if (num_streams == 0) return RSV_OK;
+    if (!offsets_dev || !out_rows_dev || !counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (!tied_dev) return fail(RSV_E_NULL_POINTER, "rsv_distinct_segmented_rows_ordered needs tied_dev");
+    if (hash_kind == RSV_HASH_PRECOMPUTED && !hashes_dev)
+        return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
+    if (((uintptr_t)rows_dev | (uintptr_t)out_rows_dev) & 7)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "rows_dev and out_rows_dev must be 8-byte aligned");
+    RSV_HIP_TRY(launch_segdistinct_rows_ordered(rows_dev, key_width, hash_kind == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr,
+                                                offsets_dev, num_streams, (uint32_t)k, seed + stream_base, out_rows_dev,
+                                                out_hashes_dev, counts_dev, tied_dev, (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
 rsv_status rsv_distinct_segmented_update(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
                                          const int64_t* stream_ids_dev, int64_t num_segments, int64_t num_states,
                                          int32_t key_width, int32_t k, int32_t hash_kind, uint64_t seed,

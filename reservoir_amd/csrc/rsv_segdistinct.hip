@@ -6,8 +6,9 @@
 // rsv_distinct_segmented_ordered (the last section of this file) is the same launch followed by a
 // replay of the streams whose boundary hash bucket is oversubscribed: there the members of that
 // bucket are the reference's, chosen by arrival order and the heap's tie behaviour
-// (RSV_DISTINCT_ORDERED), not the smallest keys.  Not provided in ordered form: byte-key rows, resumed
-// state and merge (k entries cannot carry the heap's history), k > 4096.
+// (RSV_DISTINCT_ORDERED), not the smallest keys; rsv_distinct_segmented_rows_ordered is that for byte-key
+// rows.  Not provided in ordered form: resumed state and merge (k entries cannot carry the heap's
+// history), k > 4096.
 //
 // One TEAM of NT threads per stream, streams taken grid-stride.  The team holds P 16-byte entries
 // (h, key) in LDS: the current set [0, m) ascending by (h, key), and behind it the candidates
@@ -832,6 +833,219 @@ __global__ __launch_bounds__(64) void segdistinct_replay_kernel(const KeyT* __re
     }
 }
 
+// ---- Ordered over byte keys (rsv_distinct_segmented_rows_ordered) ----
+// The argument above with "key" read as "row": once the heap is full its maximum M is the k-th smallest
+// hash over the distinct rows seen and it holds every row with h < M, so its set is the bottom-k by
+// (h, row words) unless more than k distinct rows have h <= M.  Kernel 1 is segrows_kernel with TiedRows,
+// which is Rows<false, true> that also notes, per lane, whether the team refused an element whose h is the
+// current T.h.  A lane that fails `admits` at h = T.h holds a row strictly above T's row (an equal row and an
+// equal ref pass), so it is a distinct row outside the current set, and outside the final one, for T only
+// falls.  A merge trims the entries above the new T among se[k, n): the compaction writes below k only, so
+// se[k, n) is what the sort left there, and an entry of distinct rank >= k sits at a sorted position >= k.
+// Of those positions the ones below T's own hold repeats of members, which may share T.h with a row below
+// T's: the note wants (h == T.h and row > T's row), not "row differs".  Equal refs are settled before any row
+// is addressed.  The note is dropped when a merge lowers T.h.  A distinct row x outside the final set with
+// h(x) = M is refused at its first occurrence at the latest, or trimmed, at a time when M <= T.h <= h(x), so
+// T.h = M then and ever after and the note stays.  Hence tied = (m == k && some lane holds a note), exactly,
+// whatever M is: below k entries T is the pad (INT64_MAX, -1), which admits everything.
+// Rows::set_T writes s_trow from the threads below W8 and no barrier stands between it and trimmed, so
+// trimmed reads T's row where set_T read it: at(T.Tk) in global memory.
+struct TiedRows : Rows<false, true> {
+    mutable bool at_T;
+    __device__ __forceinline__ void refuse(int64_t h, const Team& t) const { at_T |= h == t.Th; }
+    __device__ __forceinline__ void set_T(const Ent* se, uint32_t k, Team& t) const {
+        const int64_t was = t.Th;
+        Rows<false, true>::set_T(se, k, t);
+        if (t.Th != was) at_T = false;
+    }
+    // behind set_T, and before the barrier that lets the appends go on
+    template <int NT>
+    __device__ __forceinline__ void trimmed(const Ent* se, uint32_t k, uint32_t n, const Team& t) const {
+        for (uint32_t i = k + threadIdx.x; i < n; i += NT) {
+            const Ent e = se[i];
+            if (e.h != t.Th || e.key == t.Tk || e.key < 0 || t.Tk < 0) continue;
+            const uint64_t* const r = this->at(e.key);
+            const uint64_t* const tr = this->at(t.Tk);
+            for (uint32_t w = 0; w < this->W8; ++w) {
+                const uint64_t x = r[w], y = tr[w];
+                if (x != y) {
+                    at_T |= x > y;
+                    break;
+                }
+            }
+        }
+    }
+};
+
+template <int NT>
+__global__ __launch_bounds__(NT) void segrows_tied_kernel(const uint64_t* __restrict__ rows, const int64_t* __restrict__ hashes,
+                                                          const int64_t* __restrict__ offsets, int64_t S, uint32_t W8,
+                                                          uint32_t k, uint32_t P, uint64_t seed0,
+                                                          uint64_t* __restrict__ out_rows, int64_t* __restrict__ out_hashes,
+                                                          int64_t* __restrict__ counts, int32_t* __restrict__ tied) {
+    extern __shared__ __align__(16) unsigned char seg_lds[];
+    Ent* const se = (Ent*)seg_lds;
+    __shared__ uint32_t s_cnt;
+    __shared__ uint32_t s_scan[NT / 64 > 1 ? NT / 64 : 1];
+    __shared__ uint64_t s_trow[32];  // kMaxRowWords
+    const uint32_t tid = threadIdx.x;
+    const bool vec16 = ((uintptr_t)rows & 15) == 0;
+
+    for (int64_t s = blockIdx.x; s < S; s += gridDim.x) {
+        int64_t r0, r1;
+        java_r0r1(seed0 + (uint64_t)s, r0, r1);
+        __syncthreads();  // the previous stream's output reads are done
+        if (tid == 0) s_cnt = 0;
+        __syncthreads();
+        Team t{0, 0, kMaxI64, -1, false};
+        const TiedRows src{{{{rows, W8}}, hashes, vec16, r0, r1, s_trow}, false};
+        take_piece<TiedRows, NT>(se, &s_cnt, s_scan, src, offsets[s], offsets[s + 1], k, P, t);
+        if (t.n_tot != t.m) {  // the last merge, here also for what it trims
+            const uint32_t n = t.n_tot;
+            t.m = merge_set<NT>(se, n, k, s_scan, src);
+            if (t.m == k) {
+                src.set_T(se, k, t);
+                src.template trimmed<NT>(se, k, n, t);
+            }
+            t.n_tot = t.m;
+        }
+        const int noted = __syncthreads_or(src.at_T);
+        if (tid == 0) tied[s] = t.m == k && noted;
+        const int64_t ob = s * (int64_t)k;
+        for (uint32_t x = tid; x < k * W8; x += NT) {  // k * W8 <= 4096 * 32
+            const uint32_t j = x / W8, w = x - j * W8;
+            out_rows[ob * W8 + x] = j < t.m ? rows[se[j].key * (int64_t)W8 + w] : 0;
+        }
+        if (out_hashes)
+            for (uint32_t i = tid; i < k; i += NT) out_hashes[ob + i] = i < t.m ? se[i].h : 0;
+        if (tid == 0) counts[s] = t.m;
+    }
+}
+
+// Kernel 2 over byte keys: segdistinct_replay_kernel with entries (h, ref), ref the row's index into rows:
+// the same grouping of tied words, heap, walk and serialised admission; no row is staged in LDS.
+// elements.contains: equal rows carry equal hashes (the caller's contract), so a member can only be an
+// entry whose h is the candidate's.  All lanes scan the heap's h, eight 8-byte reads in flight; only an
+// entry with the candidate's h goes further: its ref is read, an equal ref is the candidate's own row,
+// otherwise the two rows are read from global memory and compared word by word.  At the end the entries are sorted by (h, row words)
+// and the m rows gathered over what kernel 1 wrote, lanes over (entry, word); count and tied stay.
+__global__ __launch_bounds__(64) void segrows_replay_kernel(const uint64_t* __restrict__ rows, const int64_t* __restrict__ hashes,
+                                                            const int64_t* __restrict__ offsets, int64_t S, uint32_t W8,
+                                                            uint32_t k, uint32_t W, uint64_t seed0,
+                                                            uint64_t* __restrict__ out_rows, int64_t* __restrict__ out_hashes,
+                                                            const int32_t* __restrict__ tied) {
+    extern __shared__ __align__(16) unsigned char seg_lds[];
+    Ent* const se = (Ent*)seg_lds;
+    __shared__ uint32_t s_scan[1];
+    const uint32_t lane = threadIdx.x;
+    const int64_t groups = (S + W - 1) / W;
+    const bool vec16 = ((uintptr_t)rows & 15) == 0;
+
+    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+        const int64_t sl = g * W + lane;
+        uint64_t todo = __ballot(lane < W && sl < S && tied[sl] != 0);
+        while (todo) {
+            const int64_t s = g * W + (__ffsll((long long)todo) - 1);
+            todo &= todo - 1;
+            const int64_t lo = offsets[s], hi = offsets[s + 1];
+            int64_t r0, r1;
+            java_r0r1(seed0 + (uint64_t)s, r0, r1);
+            const Rows<false, true> src{{{rows, W8}}, hashes, vec16, r0, r1, nullptr};  // no T here: admits is not used
+            const RowOrd<false>& ord = src;
+            // equality of two rows of the input (refs >= 0; W8 >= 2): the first two words of both in flight
+            // together, so a UUID costs one round trip, not one per word
+            const auto same_row = [&](int64_t a, int64_t b) {
+                if (a == b) return true;
+                const uint64_t* const ra = src.at(a);
+                const uint64_t* const rb = src.at(b);
+                const uint64_t a0 = ra[0], a1 = ra[1], b0 = rb[0], b1 = rb[1];
+                if (a0 != b0 || a1 != b1) return false;
+                for (uint32_t w = 2; w < W8; ++w)
+                    if (ra[w] != rb[w]) return false;
+                return true;
+            };
+            uint32_t n = 0;            // heap size (uniform)
+            int64_t maxh = INT64_MIN;  // the root's h once anything is in
+            __syncthreads();           // the previous stream's output reads are done
+            for (int64_t base = lo; base < hi; base += 64 * kU) {
+                int64_t ref[kU], hv[kU];
+#pragma unroll
+                for (int u = 0; u < kU; ++u) {
+                    const int64_t i = base + (int64_t)u * 64 + lane;
+                    ref[u] = 0;
+                    hv[u] = 0;
+                    if (i < hi) src.load(i, ref[u], hv[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < kU; ++u) {
+                    const int64_t i = base + (int64_t)u * 64 + lane;
+                    if (base + (int64_t)u * 64 >= hi) break;  // uniform
+                    const int64_t h = src.h_of(ref[u], hv[u]);
+                    bool pend = i < hi;
+                    for (;;) {
+                        const uint64_t mask = __ballot(pend && (n < k || h < maxh));
+                        if (!mask) break;
+                        const int l = __ffsll((long long)mask) - 1;
+                        if ((int)lane == l) pend = false;
+                        const Ent c{read_lane(h, l), base + (int64_t)u * 64 + l};  // the candidate: (h, its row's index)
+                        bool found = false;
+                        const uint32_t full = n >> 6;
+                        uint32_t r = 0;
+                        for (; r + 8 <= full; r += 8) {
+                            int64_t mh[8];
+#pragma unroll
+                            for (int x = 0; x < 8; ++x) mh[x] = se[(r + x) * 64 + lane].h;
+#pragma unroll
+                            for (int x = 0; x < 8; ++x)
+                                if (mh[x] == c.h) found |= same_row(se[(r + x) * 64 + lane].key, c.key);
+                        }
+                        for (uint32_t j = r * 64 + lane; j < n; j += 64)
+                            if (se[j].h == c.h) found |= same_row(se[j].key, c.key);
+                        if (__ballot(found)) continue;  // a member
+                        if (lane == 0) {
+                            uint32_t nn = n;
+                            if (nn == k) {  // dequeue: the root leaves
+                                const Ent last = se[nn - 1];
+                                --nn;
+                                if (nn) {
+                                    uint32_t q = 1;
+                                    while (2 * q <= nn) {
+                                        uint32_t ch = 2 * q;
+                                        if (ch + 1 <= nn && se[ch - 1].h < se[ch].h) ++ch;
+                                        if (last.h >= se[ch - 1].h) break;
+                                        se[q - 1] = se[ch - 1];
+                                        q = ch;
+                                    }
+                                    se[q - 1] = last;
+                                }
+                            }
+                            uint32_t q = nn + 1;  // addOne
+                            while (q > 1 && se[(q >> 1) - 1].h < c.h) {
+                                se[q - 1] = se[(q >> 1) - 1];
+                                q >>= 1;
+                            }
+                            se[q - 1] = c;
+                        }
+                        if (n < k) ++n;
+                        __syncthreads();
+                        maxh = se[0].h;
+                        __syncthreads();
+                    }
+                }
+            }
+            const uint32_t m = merge_set<64>(se, n, k, s_scan, ord);
+            __syncthreads();
+            const int64_t ob = s * (int64_t)k;
+            for (uint32_t x = lane; x < m * W8; x += 64) {  // m * W8 <= 4096 * 32
+                const uint32_t j = x / W8, w = x - j * W8;
+                out_rows[ob * W8 + x] = rows[se[j].key * (int64_t)W8 + w];
+            }
+            if (out_hashes)
+                for (uint32_t i = lane; i < m; i += 64) out_hashes[ob + i] = se[i].h;
+        }
+    }
+}
+
 // The forms: f(KeyT{}, NT as an integral_constant, P) for the key width and k of a launch.
 template <typename KeyT, typename F>
 hipError_t with_form_of(uint32_t k, F& f) {
@@ -861,6 +1075,31 @@ hipError_t launch_teams(void (*kernel)(Params...), int nt, int64_t teams, uint32
     return hipGetLastError();
 }
 
+// The replay of the tied streams: one wave and pow2ceil(k) entries (the heap, and the pads of its final sort)
+// per stream in flight.  A wave looks at W consecutive tied words per step: 64 when there are streams enough to
+// fill the grid that way, fewer when not, so that few streams still spread over the CUs.
+struct ReplayPlan {
+    size_t lds;
+    uint32_t W;
+    unsigned grid;
+};
+
+hipError_t plan_replay(const void* kernel, int64_t S, uint32_t k, ReplayPlan& p) {
+    uint32_t P2 = 2;
+    while (P2 < k) P2 <<= 1;
+    p.lds = (size_t)P2 * 16;
+    if (p.lds + 256 > 64 * 1024) {
+        const hipError_t a = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+        if (a != hipSuccess) return a;
+    }
+    const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>((160 * 1024) / (p.lds + 256), 32));
+    const uint64_t cap = 256ull * per_cu * 4;
+    p.W = 1;
+    while (p.W < 64 && (uint64_t)S / (2 * p.W) >= cap) p.W <<= 1;
+    p.grid = (unsigned)std::min<uint64_t>(((uint64_t)S + p.W - 1) / p.W, cap);
+    return hipSuccess;
+}
+
 }  // namespace
 
 hipError_t launch_segdistinct(const void* keys, int key_width, const int64_t* hashes, const int64_t* offsets, int64_t S,
@@ -885,24 +1124,11 @@ hipError_t launch_segdistinct_ordered(const void* keys, int key_width, const int
         const hipError_t e = launch_teams(segdistinct_tied_kernel<KeyT, NT>, NT, S, P, st, (const KeyT*)keys, hashes, offsets,
                                           S, k, P, hash_kind, seed0, (KeyT*)out_keys, out_hashes, counts, tied);
         if (e != hipSuccess) return e;
-        // the replay: one wave and pow2ceil(k) entries (the heap, and the pads of its final sort) per
-        // stream in flight.  A wave looks at W consecutive tied words per step: 64 when there are streams
-        // enough to fill the grid that way, fewer when not, so that few streams still spread over the CUs.
-        uint32_t P2 = 2;
-        while (P2 < k) P2 <<= 1;
-        const size_t lds = (size_t)P2 * 16;
+        ReplayPlan rp;
         auto* const replay = segdistinct_replay_kernel<KeyT>;
-        if (lds + 256 > 64 * 1024) {
-            const hipError_t a = hipFuncSetAttribute((const void*)replay, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (a != hipSuccess) return a;
-        }
-        const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>((160 * 1024) / (lds + 256), 32));
-        const uint64_t cap = 256ull * per_cu * 4;
-        uint32_t W = 1;
-        while (W < 64 && (uint64_t)S / (2 * W) >= cap) W <<= 1;
-        const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)S + W - 1) / W, cap);
-        hipLaunchKernelGGL(replay, dim3(grid), dim3(64), lds, st, (const KeyT*)keys, hashes, offsets, S, k, W, hash_kind, seed0,
-                           (KeyT*)out_keys, out_hashes, (const int32_t*)tied);
+        if (const hipError_t a = plan_replay((const void*)replay, S, k, rp); a != hipSuccess) return a;
+        hipLaunchKernelGGL(replay, dim3(rp.grid), dim3(64), rp.lds, st, (const KeyT*)keys, hashes, offsets, S, k, rp.W, hash_kind,
+                           seed0, (KeyT*)out_keys, out_hashes, (const int32_t*)tied);
         return hipGetLastError();
     });
 }
@@ -915,6 +1141,25 @@ hipError_t launch_segdistinct_rows(const void* rows, int key_width, const int64_
         constexpr int NT = decltype(nt)::value;
         return launch_teams(segrows_kernel<NT>, NT, S, P, st, (const uint64_t*)rows, hashes, offsets, S,
                             (uint32_t)key_width / 8, k, P, seed0, (uint64_t*)out_rows, out_hashes, counts);
+    };
+    return with_form_of<int64_t>(k, f);
+}
+
+hipError_t launch_segdistinct_rows_ordered(const void* rows, int key_width, const int64_t* hashes, const int64_t* offsets,
+                                           int64_t S, uint32_t k, uint64_t seed0, void* out_rows, int64_t* out_hashes,
+                                           int64_t* counts, int32_t* tied, hipStream_t st) {
+    if (S <= 0) return hipSuccess;
+    const uint32_t W8 = (uint32_t)key_width / 8;
+    auto f = [&](int64_t, auto nt, uint32_t P) {
+        constexpr int NT = decltype(nt)::value;
+        const hipError_t e = launch_teams(segrows_tied_kernel<NT>, NT, S, P, st, (const uint64_t*)rows, hashes, offsets, S, W8,
+                                          k, P, seed0, (uint64_t*)out_rows, out_hashes, counts, tied);
+        if (e != hipSuccess) return e;
+        ReplayPlan rp;
+        if (const hipError_t a = plan_replay((const void*)segrows_replay_kernel, S, k, rp); a != hipSuccess) return a;
+        hipLaunchKernelGGL(segrows_replay_kernel, dim3(rp.grid), dim3(64), rp.lds, st, (const uint64_t*)rows, hashes, offsets,
+                           S, W8, k, rp.W, seed0, (uint64_t*)out_rows, out_hashes, (const int32_t*)tied);
+        return hipGetLastError();
     };
     return with_form_of<int64_t>(k, f);
 }
