@@ -480,9 +480,10 @@ rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_de
  * stream with tied_dev[s] == 0 is bit-identical to rsv_distinct_segmented's row.
  * out_hashes_dev may be NULL.  Byte keys: RSV_E_UNSUPPORTED; 1 <= k <= 4096 (larger:
  * RSV_E_UNSUPPORTED).  Stateless and stream-ordered on hip_stream: no host wait, no allocation.
- * Byte-key rows in this order: rsv_distinct_segmented_rows_ordered below.  Not provided in ordered form:
- * resumed state and merge (a state of k entries cannot carry the heap's history), and k > 4096: such callers
- * keep separate handles. */
+ * Byte-key rows in this order: rsv_distinct_segmented_rows_ordered below.  Resumed from caller-held state:
+ * rsv_distinct_segmented_ordered_update below -- a state of k entries kept sorted cannot carry the heap's
+ * history, a state of k entries kept in the queue's array order is the heap, and that is its state.  Not
+ * provided in ordered form: merge, resumed byte-key rows, and k > 4096: such callers keep separate handles. */
 rsv_status rsv_distinct_segmented_ordered(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
                                           int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
                                           uint64_t seed, uint64_t stream_base, void* out_keys_dev,
@@ -530,8 +531,8 @@ rsv_status rsv_distinct_segmented_rows(const void* rows_dev, const int64_t* hash
  * kernels): tied_dev[s] = 1 iff the set is full and some distinct row of the stream outside the bottom-k by
  * (h, row) has hash M, exact also for M = INT64_MAX or INT64_MIN, else 0.  A stream with tied_dev[s] == 0 is
  * bit-identical to rsv_distinct_segmented_rows' row block.
- * Stateless and stream-ordered on hip_stream: no host wait, no allocation.  Resumed state, merge and
- * k > 4096 have no ordered form. */
+ * Stateless and stream-ordered on hip_stream: no host wait, no allocation.  Resumed byte-key rows, merge and
+ * k > 4096 have no ordered form (4- and 8-byte keys resume with rsv_distinct_segmented_ordered_update). */
 rsv_status rsv_distinct_segmented_rows_ordered(const void* rows_dev, const int64_t* hashes_dev,
                                                const int64_t* offsets_dev, int64_t num_streams, int32_t key_width,
                                                int32_t k, int32_t hash_kind, uint64_t seed, uint64_t stream_base,
@@ -564,6 +565,46 @@ rsv_status rsv_distinct_segmented_update(const void* keys_dev, const int64_t* ha
                                          int32_t key_width, int32_t k, int32_t hash_kind, uint64_t seed,
                                          uint64_t stream_base, void* state_keys_dev, int64_t* state_hashes_dev,
                                          int64_t* state_counts_dev, void* hip_stream);
+
+/* Segmented distinct in the reference's order, resumed: what rsv_distinct_segmented_update is for the engine's
+ * set order, for RSV_DISTINCT_ORDERED.  The state is the caller's device memory: state_keys_dev[num_states*k]
+ * (key_width values), state_hashes_dev[num_states*k] (int64, required: the heap is ordered by them) and
+ * state_counts_dev[num_states] (int64).  Row r holds counts[r] entries in scala 2.13 mutable.PriorityQueue
+ * array order: entry j of the 1-indexed queue of a RandomValues instance (S:383-412) sits in slot j - 1, its
+ * scrambled hash beside it; a row with counts[r] == 0 is the empty sampler, whatever its slots hold.  That
+ * array and its length are the whole sampler: RandomValues' set holds the array's keys, its maxHash is the
+ * root's hash at every moment (below k entries the running maximum, which a max-heap keeps at its root), and
+ * addOne/fixUp and dequeue/fixDown are functions of the array alone.
+ * THIS IS NOT THE LAYOUT OF rsv_distinct_segmented_update.  A row sorted ascending by (h, key) -- what
+ * rsv_distinct_segmented, rsv_distinct_segmented_ordered and rsv_distinct_segmented_update write -- is not a
+ * valid ordered state (sorted ascending it is not even a max-heap, and sorted descending it is another heap
+ * than the reference's, which continues differently in exactly the tied streams); the two kinds of state must
+ * not be mixed, and neither call accepts the other's rows.  Start a state with zeroed counts.
+ * Segment b = keys_dev[offsets[b] .. offsets[b+1]) goes into row r = stream_ids_dev[b], or r = b when
+ * stream_ids_dev is NULL (then num_segments <= num_states).  Row r is seeded as
+ * java.util.Random(seed + stream_base + r); hash kinds, key widths (4 and 8; byte keys: RSV_E_UNSUPPORTED) and
+ * 1 <= k <= 4096 as rsv_distinct_segmented_ordered.  Afterwards row r is exactly the array a RandomValues
+ * instance holds after sample() over everything the row has been fed, across all launches, in that order, for
+ * any hash; a fresh state fed a whole stream in one launch therefore holds the set
+ * rsv_distinct_segmented_ordered returns (sort the row by (h, key) to compare).
+ * The ids of one launch must be distinct (two segments on one row race: the caller's contract); a segment
+ * whose id lies outside [0, num_states) is skipped.  Rows that no segment names, and rows whose segment is
+ * empty, are not touched; a row in which nothing was admitted is not written at all; a row that is written
+ * gets zeros beyond its count.  A row's count is clamped into [0, k] before use and nothing else read from
+ * the state indexes memory: a row that is not a heap gives an unspecified set, never an out-of-range access.
+ * The checks run before any device call, in rsv_distinct_segmented_update's order; state_hashes_dev NULL is
+ * RSV_E_NULL_POINTER with the parameter named in rsv_last_error.
+ * No merge: two heaps over disjoint parts of a stream do not determine the reference's heap over the whole
+ * stream (who of the bucket at the maximum hash stays depends on the order in which all of it arrived).
+ * Callers of the set order keep rsv_distinct_segmented_merge.  Byte-key rows are not provided in this form.
+ * Stateless and stream-ordered on hip_stream: no host wait, no allocation.  All pointers are device
+ * pointers. */
+rsv_status rsv_distinct_segmented_ordered_update(const void* keys_dev, const int64_t* hashes_dev,
+                                                 const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                                 int64_t num_segments, int64_t num_states, int32_t key_width,
+                                                 int32_t k, int32_t hash_kind, uint64_t seed, uint64_t stream_base,
+                                                 void* state_keys_dev, int64_t* state_hashes_dev,
+                                                 int64_t* state_counts_dev, void* hip_stream);
 
 /* Combine of segmented distinct states: part_* are `parts` states laid back to back
  * ([parts][num_states][k] keys and hashes, [parts][num_states] counts: what an all-gather of every

@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "rsv_distinct_segmented_rows_update", "rsv_distinct_segmented_rows_merge",
     "rsv_sample_segmented_rows", "rsv_sample_segmented_rows_update", "rsv_sample_segmented_rows_merge",
     "rsv_distinct_segmented_ordered", "rsv_distinct_segmented_rows_ordered",
+    "rsv_distinct_segmented_ordered_update",
 )
 
 
@@ -144,6 +145,7 @@ def load():
     L.rsv_distinct_segmented_rows.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_distinct_segmented_rows_ordered.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp, vp]
     L.rsv_distinct_segmented_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
+    L.rsv_distinct_segmented_ordered_update.argtypes = L.rsv_distinct_segmented_update.argtypes
     L.rsv_distinct_segmented_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
     L.rsv_distinct_segmented_rows_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_distinct_segmented_rows_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
@@ -182,7 +184,7 @@ def load():
                  "rsv_distinct_segmented_rows_update", "rsv_distinct_segmented_rows_merge",
                  "rsv_sample_segmented_rows", "rsv_sample_segmented_rows_update",
                  "rsv_sample_segmented_rows_merge", "rsv_distinct_segmented_ordered",
-                 "rsv_distinct_segmented_rows_ordered"):
+                 "rsv_distinct_segmented_rows_ordered", "rsv_distinct_segmented_ordered_update"):
         getattr(L, name).restype = i32
     if L.rsv_abi_version() != 1:
         raise ImportError("libreservoir_hip.so ABI version mismatch")

@@ -9,6 +9,7 @@ libreservoir_hip.so.  Every function raises if the engine is unavailable.
     distinct_segmented_rows_ordered -- the same in the reference's order (exact under UUID.hashCode's ties)
     SegmentedDistinct -- K5 resumed: the same S streams as caller-held state, advanced by one launch
                          per micro-batch (update) and combined across launches, GPUs and ranks (merge)
+    SegmentedDistinctOrdered -- the ordered form resumed: the state rows are the reference's heap arrays (update)
     SegmentedDistinctRows -- K5 resumed over byte keys: the rows move inside the caller-held state (update, merge)
     SegmentedSampler  -- K2 resumed: S Sampler.apply streams as caller-held state (keys, idx, next), fed in
                          pieces from any start index (update) and combined per slot by largest index (merge)
@@ -458,6 +459,91 @@ class SegmentedDistinct(_SegmentedState):
 
         L = N.load()
         return self._merge(torch, L.rsv_distinct_segmented_merge, SegmentedDistinct, (part_keys, part_hashes, part_counts))
+
+
+class SegmentedDistinctOrdered(_SegmentedState):
+    """S long-lived Sampler.distinct streams in the reference's order, advanced by one launch per batch.
+
+    What SegmentedDistinct is for the set order, for order="ordered": exact for any hash, the tie bucket included.
+    The state is three device tensors keys (S, k), hashes (S, k), counts (S,), and row s is the reference's
+    RandomValues itself: counts[s] entries in scala 2.13 mutable.PriorityQueue array order (entry j of the
+    1-indexed queue in slot j - 1, its scrambled hash beside it), seeded like a single
+    Sampler.distinct(k, seed=seed + stream_base + s, order="ordered").  Fed a stream in any number of update()
+    calls, a row is the array the reference holds after the same elements in the same order.  This is NOT
+    SegmentedDistinct's layout: a sorted row is not a valid ordered state, and the two kinds of state must not be
+    mixed; result() gives the rows sorted.  Only the counts are zero-filled: a row with count 0 is empty whatever
+    its slots hold, and every row an update writes has zeros beyond its count.  hash="precomputed":
+    update(hashes=...).  There is no merge.  Everything runs on torch's current stream.
+    """
+
+    _NAME, _TENSORS, _MAX_K = "SegmentedDistinctOrdered", ("keys", "hashes", "counts"), _SEG_DISTINCT_MAX_K
+
+    def __init__(self, num_streams: int, k: int, seed: int, stream_base: int = 0, hash: str = "default",
+                 dtype=None, device=None):
+        import torch
+
+        N.load()
+        dtype = torch.int64 if dtype is None else dtype
+        if dtype not in (torch.int64, torch.int32):
+            raise N.IllegalArgumentException("keys must be int64/int32")
+        if hash == "precomputed":
+            self._kind = N.HASH_PRECOMPUTED
+        elif hash in _SEG_HASH:
+            self._kind = _SEG_HASH[hash]
+        else:
+            raise N.IllegalArgumentException(f"unknown hash {hash!r}")
+        dev = self._init_state(torch, num_streams, k, seed, stream_base, device)
+        self.keys = torch.empty((self.num_streams, self.k), dtype=dtype, device=dev)
+        self.hashes = torch.empty((self.num_streams, self.k), dtype=torch.int64, device=dev)
+        self.counts = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
+
+    def update(self, keys, offsets, stream_ids=None, hashes=None, check_ids: bool = True):
+        """Segment b = keys[offsets[b]:offsets[b+1]] into row stream_ids[b] (None: row b), in arrival order.
+
+        The ids of one call must be distinct and inside [0, num_streams).  check_ids=True verifies
+        that on the device before the launch (one host wait) and raises IllegalArgumentException;
+        check_ids=False keeps the call stream-ordered and leaves the contract to the caller.
+        Rows that no segment names, or whose segment is empty, are not touched, and a row in which
+        nothing was admitted is not written.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        keys, offsets, hashes = _segd_inputs(torch, keys, offsets, hashes, state=self)
+        seg = self._segments(torch, offsets, check_ids, stream_ids)
+        if seg is None:
+            return self
+        B, stream_ids = seg
+        N.check(L.rsv_distinct_segmented_ordered_update(
+            C.c_void_p(keys.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
+            C.c_void_p(offsets.data_ptr()), C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
+            B, self.num_streams, keys.element_size(), self.k, self._kind, self.seed, self.stream_base,
+            C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.hashes.data_ptr()), C.c_void_p(self.counts.data_ptr()),
+            _stream_ptr(torch, self.keys.device)))
+        return self
+
+    def result(self):
+        """(keys (S, k), hashes (S, k), counts (S,)) in distinct_segmented_ordered's layout: every row ascending
+        by (scrambled hash, key), zeros beyond its count.  New tensors; the state is left as it is."""
+        import torch
+
+        counts = self.counts.clamp(0, self.k)
+        valid = torch.arange(self.k, device=self.keys.device)[None, :] < counts[:, None]
+        # by key, then stably by hash, then stably the valid entries first: ascending by (h, key) in front
+        order = torch.argsort(self.keys.masked_fill(~valid, 0), dim=1, stable=True)
+        order = order.gather(1, torch.argsort(self.hashes.gather(1, order), dim=1, stable=True))
+        order = order.gather(1, torch.argsort((~valid).gather(1, order).to(torch.int8), dim=1, stable=True))
+        keep = valid.gather(1, order)
+        zero_k = torch.zeros((), dtype=self.keys.dtype, device=self.keys.device)
+        zero_h = torch.zeros((), dtype=torch.int64, device=self.keys.device)
+        return (torch.where(keep, self.keys.gather(1, order), zero_k),
+                torch.where(keep, self.hashes.gather(1, order), zero_h), counts)
+
+    def merge(self, *parts, **kw):
+        """Not provided: two heaps over parts of a stream do not determine the reference's heap over the whole."""
+        raise N.ReservoirError(
+            "SegmentedDistinctOrdered has no merge: two heaps over disjoint parts of a stream do not determine the "
+            "reference's heap over the whole stream; SegmentedDistinct.merge combines states in the set order")
 
 
 class SegmentedDistinctRows(_SegmentedState):

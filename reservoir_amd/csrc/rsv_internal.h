@@ -207,6 +207,14 @@ hipError_t launch_segdistinct_update(const void* keys, int key_width, const int6
 hipError_t launch_segdistinct_merge(const void* part_keys, int key_width, const int64_t* part_hashes,
                                     const int64_t* part_counts, int32_t parts, int64_t num_states, uint32_t k,
                                     void* state_keys, int64_t* state_hashes, int64_t* state_counts, hipStream_t st);
+// K5 ordered, resumed (rsv_segdistinct.hip): the state rows hold RandomValues' heap, counts[r] entries (h, key) in
+// scala 2.13 mutable.PriorityQueue array order (entry j of the 1-indexed queue in slot j - 1), not ascending; one
+// wave per segment continues the reference from them and writes them back in array order.  Segments, ids and
+// seeding as launch_segdistinct_update.  No allocation.
+hipError_t launch_segdistinct_ordered_update(const void* keys, int key_width, const int64_t* hashes, const int64_t* offsets,
+                                             const int64_t* stream_ids, int64_t num_segments, int64_t num_states,
+                                             uint32_t k, int hash_kind, uint64_t seed0, void* state_keys,
+                                             int64_t* state_hashes, int64_t* state_counts, hipStream_t st);
 // K5 resumed over byte keys (rsv_segdistinct.hip): the state is rows[num_states*k] of key_width bytes, hashes,
 // counts, as launch_segdistinct_rows writes them, moved in place.  rows / part_rows ([parts][num_states][k] rows)
 // and state_rows 8-byte aligned, and no input may alias the state.  hashes as for launch_segdistinct_rows.

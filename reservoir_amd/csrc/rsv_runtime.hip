@@ -1903,6 +1903,32 @@ rsv_status rsv_distinct_segmented_update(const void* keys_dev, const int64_t* ha
     return RSV_OK;
 }
 
+rsv_status rsv_distinct_segmented_ordered_update(const void* keys_dev, const int64_t* hashes_dev,
+                                                 const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                                 int64_t num_segments, int64_t num_states, int32_t key_width,
+                                                 int32_t k, int32_t hash_kind, uint64_t seed, uint64_t stream_base,
+                                                 void* state_keys_dev, int64_t* state_hashes_dev,
+                                                 int64_t* state_counts_dev, void* hip_stream) {
+    // rsv_distinct_segmented_update's checks in its order; state_hashes_dev by name, behind the other buffers
+    int hk;
+    if (rsv_status st = check_segdistinct_shape("rsv_distinct_segmented_ordered_update", k, key_width)) return st;
+    if (rsv_status st = resolve_segdistinct_hash(hash_kind, key_width, hk)) return st;
+    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
+    if (!stream_ids_dev && num_segments > num_states)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
+    if (num_segments == 0 || num_states == 0) return RSV_OK;
+    // keys_dev is not checked: a launch whose segments are all empty has no keys
+    if (!offsets_dev || !state_keys_dev || !state_counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (!state_hashes_dev)
+        return fail(RSV_E_NULL_POINTER, "rsv_distinct_segmented_ordered_update needs state_hashes_dev: the heap is ordered by them");
+    if (hk == RSV_HASH_PRECOMPUTED && !hashes_dev) return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
+    RSV_HIP_TRY(launch_segdistinct_ordered_update(keys_dev, key_width, hk == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr,
+                                                  offsets_dev, stream_ids_dev, num_segments, num_states, (uint32_t)k, hk,
+                                                  seed + stream_base, state_keys_dev, state_hashes_dev,
+                                                  state_counts_dev, (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
 rsv_status rsv_distinct_segmented_merge(const void* part_keys_dev, const int64_t* part_hashes_dev,
                                         const int64_t* part_counts_dev, int32_t parts, int64_t num_states,
                                         int32_t key_width, int32_t k, void* state_keys_dev, int64_t* state_hashes_dev,

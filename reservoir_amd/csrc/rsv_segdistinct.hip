@@ -7,8 +7,11 @@
 // replay of the streams whose boundary hash bucket is oversubscribed: there the members of that
 // bucket are the reference's, chosen by arrival order and the heap's tie behaviour
 // (RSV_DISTINCT_ORDERED), not the smallest keys; rsv_distinct_segmented_rows_ordered is that for byte-key
-// rows.  Not provided in ordered form: resumed state and merge (k entries cannot carry the heap's
-// history), k > 4096.
+// rows.  rsv_distinct_segmented_ordered_update resumes the ordered form from caller-held state: k entries
+// kept sorted cannot carry the heap's history, k entries kept in the queue's array
+// order are the heap, and that is the state there.  Not provided in ordered form:
+// merge (two heaps over parts of a stream do not determine the heap over the whole), resumed byte-key
+// rows, k > 4096.
 //
 // One TEAM of NT threads per stream, streams taken grid-stride.  The team holds P 16-byte entries
 // (h, key) in LDS: the current set [0, m) ascending by (h, key), and behind it the candidates
@@ -718,6 +721,91 @@ __device__ __forceinline__ int64_t read_lane(int64_t v, int l) {
     return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
+// RandomValues.sample over the elements [lo, hi) of src in arrival order, by one wave, on the heap se[0, n) with
+// maxh its root's h (INT64_MIN while it is empty): what the comment at segdistinct_replay_kernel says of its
+// walk.  The one piece of device code both ordered kernels run per stream (segdistinct_replay_kernel from an
+// empty heap, segdistinct_heap_kernel from the caller's); with NOTE it returns whether anything was admitted (the
+// replay has no use for that).  The heap is left as the last admission wrote it, behind a barrier.
+template <bool NOTE, typename KeyT>
+__device__ __forceinline__ bool replay_walk(Ent* const se, const Keys<KeyT, true> src, int64_t lo, int64_t hi, uint32_t k,
+                                            uint32_t& n_io, int64_t& maxh_io) {
+    // (locals, written back at the end: with them the replay kernel compiles to the instructions it had when
+    // this loop stood in its body; through the references it did not)
+    uint32_t n = n_io;
+    int64_t maxh = maxh_io;
+    const uint32_t lane = threadIdx.x;
+    bool admitted = false;
+    for (int64_t base = lo; base < hi; base += 64 * kU) {
+        int64_t key[kU], hv[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int64_t i = base + (int64_t)u * 64 + lane;
+            key[u] = 0;
+            hv[u] = 0;
+            if (i < hi) src.load(i, key[u], hv[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int64_t i = base + (int64_t)u * 64 + lane;
+            if (base + (int64_t)u * 64 >= hi) break;  // uniform
+            const int64_t h = src.h_of(key[u], hv[u]);
+            bool pend = i < hi;
+            for (;;) {
+                const uint64_t mask = __ballot(pend && (n < k || h < maxh));
+                if (!mask) break;
+                const int l = __ffsll((long long)mask) - 1;
+                if ((int)lane == l) pend = false;
+                const int64_t ck = read_lane(key[u], l), ch = read_lane(h, l);
+                // elements.contains: n / 64 reads per lane, eight in flight
+                bool found = false;
+                const uint32_t full = n >> 6;
+                uint32_t r = 0;
+                for (; r + 8 <= full; r += 8) {
+                    int64_t mk[8];
+#pragma unroll
+                    for (int x = 0; x < 8; ++x) mk[x] = se[(r + x) * 64 + lane].key;
+#pragma unroll
+                    for (int x = 0; x < 8; ++x) found |= mk[x] == ck;
+                }
+                for (uint32_t j = r * 64 + lane; j < n; j += 64) found |= se[j].key == ck;
+                if (__ballot(found)) continue;  // a member
+                if (lane == 0) {
+                    uint32_t nn = n;
+                    if (nn == k) {  // dequeue: the root leaves
+                        const Ent last = se[nn - 1];
+                        --nn;
+                        if (nn) {
+                            uint32_t q = 1;
+                            while (2 * q <= nn) {
+                                uint32_t c = 2 * q;
+                                if (c + 1 <= nn && se[c - 1].h < se[c].h) ++c;
+                                if (last.h >= se[c - 1].h) break;
+                                se[q - 1] = se[c - 1];
+                                q = c;
+                            }
+                            se[q - 1] = last;
+                        }
+                    }
+                    uint32_t q = nn + 1;  // addOne
+                    while (q > 1 && se[(q >> 1) - 1].h < ch) {
+                        se[q - 1] = se[(q >> 1) - 1];
+                        q >>= 1;
+                    }
+                    se[q - 1] = Ent{ch, ck};
+                }
+                if (n < k) ++n;
+                if constexpr (NOTE) admitted = true;
+                __syncthreads();
+                maxh = se[0].h;
+                __syncthreads();
+            }
+        }
+    }
+    n_io = n;
+    maxh_io = maxh;
+    return admitted;
+}
+
 // Kernel 2: RandomValues (Sampler.scala:394-409) over the tied streams, one wave per stream.  A wave
 // reads the tied words of W consecutive streams at once and replays those that are set, one after the
 // other.  The heap is rsv_host_values.h's, 1-indexed in se[0, k) (entry j at se[j - 1]): scala 2.13
@@ -756,71 +844,7 @@ __global__ __launch_bounds__(64) void segdistinct_replay_kernel(const KeyT* __re
             uint32_t n = 0;              // heap size (uniform)
             int64_t maxh = INT64_MIN;    // the root's h once anything is in
             __syncthreads();             // the previous stream's output reads are done
-            for (int64_t base = lo; base < hi; base += 64 * kU) {
-                int64_t key[kU], hv[kU];
-#pragma unroll
-                for (int u = 0; u < kU; ++u) {
-                    const int64_t i = base + (int64_t)u * 64 + lane;
-                    key[u] = 0;
-                    hv[u] = 0;
-                    if (i < hi) src.load(i, key[u], hv[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < kU; ++u) {
-                    const int64_t i = base + (int64_t)u * 64 + lane;
-                    if (base + (int64_t)u * 64 >= hi) break;  // uniform
-                    const int64_t h = src.h_of(key[u], hv[u]);
-                    bool pend = i < hi;
-                    for (;;) {
-                        const uint64_t mask = __ballot(pend && (n < k || h < maxh));
-                        if (!mask) break;
-                        const int l = __ffsll((long long)mask) - 1;
-                        if ((int)lane == l) pend = false;
-                        const int64_t ck = read_lane(key[u], l), ch = read_lane(h, l);
-                        // elements.contains: n / 64 reads per lane, eight in flight
-                        bool found = false;
-                        const uint32_t full = n >> 6;
-                        uint32_t r = 0;
-                        for (; r + 8 <= full; r += 8) {
-                            int64_t mk[8];
-#pragma unroll
-                            for (int x = 0; x < 8; ++x) mk[x] = se[(r + x) * 64 + lane].key;
-#pragma unroll
-                            for (int x = 0; x < 8; ++x) found |= mk[x] == ck;
-                        }
-                        for (uint32_t j = r * 64 + lane; j < n; j += 64) found |= se[j].key == ck;
-                        if (__ballot(found)) continue;  // a member
-                        if (lane == 0) {
-                            uint32_t nn = n;
-                            if (nn == k) {  // dequeue: the root leaves
-                                const Ent last = se[nn - 1];
-                                --nn;
-                                if (nn) {
-                                    uint32_t q = 1;
-                                    while (2 * q <= nn) {
-                                        uint32_t c = 2 * q;
-                                        if (c + 1 <= nn && se[c - 1].h < se[c].h) ++c;
-                                        if (last.h >= se[c - 1].h) break;
-                                        se[q - 1] = se[c - 1];
-                                        q = c;
-                                    }
-                                    se[q - 1] = last;
-                                }
-                            }
-                            uint32_t q = nn + 1;  // addOne
-                            while (q > 1 && se[(q >> 1) - 1].h < ch) {
-                                se[q - 1] = se[(q >> 1) - 1];
-                                q >>= 1;
-                            }
-                            se[q - 1] = Ent{ch, ck};
-                        }
-                        if (n < k) ++n;
-                        __syncthreads();
-                        maxh = se[0].h;
-                        __syncthreads();
-                    }
-                }
-            }
+            replay_walk<false>(se, src, lo, hi, k, n, maxh);
             const uint32_t m = merge_set<64>(se, n, k, s_scan, KeyOrd{});
             __syncthreads();
             const int64_t ob = s * (int64_t)k;
@@ -830,6 +854,58 @@ __global__ __launch_bounds__(64) void segdistinct_replay_kernel(const KeyT* __re
                 if (out_hashes) out_hashes[ob + i] = e.h;
             }
         }
+    }
+}
+
+// ---- Ordered, resumed (rsv_distinct_segmented_ordered_update) ----
+// RandomValues' whole state is the queue's array, a set of the array's keys, and maxHash, which at every moment
+// is the root's h: below k entries the running maximum, which a max-heap keeps at its root, at k entries
+// samples.head._2.  addOne/fixUp and dequeue/fixDown are functions of the array alone.  So the row's count and
+// its entries (h, key) in array order -- entry j of the 1-indexed queue in slot j - 1 -- are the sampler, and
+// replay_walk from them is the reference going on.  A row kept sorted is a heap too, but another one: its later
+// dequeues move other entries, and the bucket at the maximum hash ends with other members.
+// One wave per segment, segments grid-stride; row r = ids[b] (or b), seeded seed0 + r.
+//   prologue   n = clamp(counts[r], 0, k); the row's pairs into se[0, n) as they lie; maxh = se[0].h when n > 0.
+//   walk       replay_walk, segdistinct_replay_kernel's own.
+//   epilogue   only if something was admitted: se[0, n) back as they lie, zeros up to k, the count.  No sort.
+// Nothing read from the state or from the ids indexes memory unclamped, and the walk addresses se below
+// max(n, 1) <= k only (parents and children of positions <= n), whatever the entries hold: a row that is no heap
+// gives an unspecified set at the same addresses.
+template <typename KeyT>
+__global__ __launch_bounds__(64) void segdistinct_heap_kernel(const KeyT* __restrict__ keys, const int64_t* __restrict__ hashes,
+                                                              const int64_t* __restrict__ offsets,
+                                                              const int64_t* __restrict__ ids, int64_t num_segments,
+                                                              int64_t num_states, uint32_t k, int hash_kind, uint64_t seed0,
+                                                              KeyT* state_keys, int64_t* state_hashes, int64_t* state_counts) {
+    extern __shared__ __align__(16) unsigned char seg_lds[];
+    Ent* const se = (Ent*)seg_lds;
+    const uint32_t lane = threadIdx.x;
+
+    for (int64_t b = blockIdx.x; b < num_segments; b += gridDim.x) {
+        // everything that decides the control flow below is uniform over the wave
+        int64_t r = b;
+        if (ids) r = ids[b];
+        if (r < 0 || r >= num_states) continue;  // an id outside the state: no row is addressed
+        const int64_t lo = offsets[b], hi = offsets[b + 1];
+        if (hi <= lo) continue;  // an empty segment leaves its row as it is
+        const int64_t ob = r * (int64_t)k;
+        const int64_t c0 = state_counts[r];
+        uint32_t n = c0 <= 0 ? 0u : (c0 >= (int64_t)k ? k : (uint32_t)c0);
+        __syncthreads();  // the previous row's output reads are done
+        for (uint32_t i = lane; i < n; i += 64) se[i] = Ent{state_hashes[ob + i], (int64_t)state_keys[ob + i]};
+        __syncthreads();
+        int64_t maxh = INT64_MIN;
+        if (n) maxh = se[0].h;
+        int64_t r0, r1;
+        java_r0r1(seed0 + (uint64_t)r, r0, r1);
+        const Keys<KeyT, true> src{{}, keys, hashes, hash_kind, r0, r1};
+        if (!replay_walk<true>(se, src, lo, hi, k, n, maxh)) continue;  // nothing admitted: the row stands as it is
+        for (uint32_t i = lane; i < k; i += 64) {
+            const Ent e = i < n ? se[i] : Ent{0, 0};
+            state_keys[ob + i] = (KeyT)e.key;
+            state_hashes[ob + i] = e.h;
+        }
+        if (lane == 0) state_counts[r] = n;
     }
 }
 
@@ -1084,16 +1160,24 @@ struct ReplayPlan {
     unsigned grid;
 };
 
-hipError_t plan_replay(const void* kernel, int64_t S, uint32_t k, ReplayPlan& p) {
+// (the part both ordered launches share: the LDS of one wave's heap, the attribute above 64 KB, and `cap`, the
+// waves the 256 CUs hold at once, four times over)
+hipError_t plan_heap_waves(const void* kernel, uint32_t k, size_t& lds, uint64_t& cap) {
     uint32_t P2 = 2;
     while (P2 < k) P2 <<= 1;
-    p.lds = (size_t)P2 * 16;
-    if (p.lds + 256 > 64 * 1024) {
-        const hipError_t a = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    lds = (size_t)P2 * 16;
+    if (lds + 256 > 64 * 1024) {
+        const hipError_t a = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (a != hipSuccess) return a;
     }
-    const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>((160 * 1024) / (p.lds + 256), 32));
-    const uint64_t cap = 256ull * per_cu * 4;
+    const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>((160 * 1024) / (lds + 256), 32));
+    cap = 256ull * per_cu * 4;
+    return hipSuccess;
+}
+
+hipError_t plan_replay(const void* kernel, int64_t S, uint32_t k, ReplayPlan& p) {
+    uint64_t cap;
+    if (const hipError_t a = plan_heap_waves(kernel, k, p.lds, cap); a != hipSuccess) return a;
     p.W = 1;
     while (p.W < 64 && (uint64_t)S / (2 * p.W) >= cap) p.W <<= 1;
     p.grid = (unsigned)std::min<uint64_t>(((uint64_t)S + p.W - 1) / p.W, cap);
@@ -1176,6 +1260,27 @@ hipError_t launch_segdistinct_update(const void* keys, int key_width, const int6
                             offsets, stream_ids, (const int64_t*)nullptr, num_segments, num_states, (int32_t)0, k, P,
                             hash_kind, seed0, (KeyT*)state_keys, state_hashes, state_counts);
     });
+}
+
+// The resumed ordered launch: plan_replay's LDS and grid with one segment per wave (W = 1: there is no tied word
+// to read, every segment is walked).
+hipError_t launch_segdistinct_ordered_update(const void* keys, int key_width, const int64_t* hashes, const int64_t* offsets,
+                                             const int64_t* stream_ids, int64_t num_segments, int64_t num_states,
+                                             uint32_t k, int hash_kind, uint64_t seed0, void* state_keys,
+                                             int64_t* state_hashes, int64_t* state_counts, hipStream_t st) {
+    if (num_segments <= 0 || num_states <= 0) return hipSuccess;
+    auto go = [&](auto key) {
+        using KeyT = decltype(key);
+        auto* const kernel = segdistinct_heap_kernel<KeyT>;
+        size_t lds;
+        uint64_t cap;
+        if (const hipError_t a = plan_heap_waves((const void*)kernel, k, lds, cap); a != hipSuccess) return a;
+        const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)num_segments, cap);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, st, (const KeyT*)keys, hashes, offsets, stream_ids,
+                           num_segments, num_states, k, hash_kind, seed0, (KeyT*)state_keys, state_hashes, state_counts);
+        return hipGetLastError();
+    };
+    return key_width == 8 ? go(int64_t{}) : go(int32_t{});
 }
 
 hipError_t launch_segdistinct_merge(const void* part_keys, int key_width, const int64_t* part_hashes,

@@ -83,6 +83,11 @@ class RandomValues:
     def __contains__(self, elem) -> bool:
         return elem in self._elements
 
+    def heap(self):
+        """``(elements, hashes)`` in the queue's array order: entry j of the 1-indexed queue at index j - 1.
+        New lists; the sampler is left as it is."""
+        return self._e[1:], self._h[1:]
+
     def result(self) -> list:
         """The set's elements, ascending by scrambled hash (the reference's order is HashSet order)."""
         order = sorted(range(1, len(self._h)), key=self._h.__getitem__)
