@@ -482,8 +482,9 @@ rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_de
  * RSV_E_UNSUPPORTED).  Stateless and stream-ordered on hip_stream: no host wait, no allocation.
  * Byte-key rows in this order: rsv_distinct_segmented_rows_ordered below.  Resumed from caller-held state:
  * rsv_distinct_segmented_ordered_update below -- a state of k entries kept sorted cannot carry the heap's
- * history, a state of k entries kept in the queue's array order is the heap, and that is its state.  Not
- * provided in ordered form: merge, resumed byte-key rows, and k > 4096: such callers keep separate handles. */
+ * history, a state of k entries kept in the queue's array order is the heap, and that is its state
+ * (rsv_distinct_segmented_rows_ordered_update for byte-key rows).  Not provided in ordered form: merge and
+ * k > 4096: such callers keep separate handles. */
 rsv_status rsv_distinct_segmented_ordered(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
                                           int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
                                           uint64_t seed, uint64_t stream_base, void* out_keys_dev,
@@ -531,8 +532,8 @@ rsv_status rsv_distinct_segmented_rows(const void* rows_dev, const int64_t* hash
  * kernels): tied_dev[s] = 1 iff the set is full and some distinct row of the stream outside the bottom-k by
  * (h, row) has hash M, exact also for M = INT64_MAX or INT64_MIN, else 0.  A stream with tied_dev[s] == 0 is
  * bit-identical to rsv_distinct_segmented_rows' row block.
- * Stateless and stream-ordered on hip_stream: no host wait, no allocation.  Resumed byte-key rows, merge and
- * k > 4096 have no ordered form (4- and 8-byte keys resume with rsv_distinct_segmented_ordered_update). */
+ * Stateless and stream-ordered on hip_stream: no host wait, no allocation.  Resumed from caller-held state:
+ * rsv_distinct_segmented_rows_ordered_update below.  Merge and k > 4096 have no ordered form. */
 rsv_status rsv_distinct_segmented_rows_ordered(const void* rows_dev, const int64_t* hashes_dev,
                                                const int64_t* offsets_dev, int64_t num_streams, int32_t key_width,
                                                int32_t k, int32_t hash_kind, uint64_t seed, uint64_t stream_base,
@@ -596,7 +597,8 @@ rsv_status rsv_distinct_segmented_update(const void* keys_dev, const int64_t* ha
  * RSV_E_NULL_POINTER with the parameter named in rsv_last_error.
  * No merge: two heaps over disjoint parts of a stream do not determine the reference's heap over the whole
  * stream (who of the bucket at the maximum hash stays depends on the order in which all of it arrived).
- * Callers of the set order keep rsv_distinct_segmented_merge.  Byte-key rows are not provided in this form.
+ * Callers of the set order keep rsv_distinct_segmented_merge.  Byte-key rows in this form:
+ * rsv_distinct_segmented_rows_ordered_update below.
  * Stateless and stream-ordered on hip_stream: no host wait, no allocation.  All pointers are device
  * pointers. */
 rsv_status rsv_distinct_segmented_ordered_update(const void* keys_dev, const int64_t* hashes_dev,
@@ -667,6 +669,60 @@ rsv_status rsv_distinct_segmented_rows_merge(const void* part_rows_dev, const in
                                              const int64_t* part_counts_dev, int32_t parts, int64_t num_states,
                                              int32_t key_width, int32_t k, void* state_rows_dev,
                                              int64_t* state_hashes_dev, int64_t* state_counts_dev, void* hip_stream);
+
+/* Segmented distinct over byte keys in the reference's order, resumed: what rsv_distinct_segmented_ordered_update
+ * is for 4- and 8-byte keys, and what rsv_distinct_segmented_rows_update is for the engine's set order.  The state
+ * is the queue's array of a RandomValues instance (S:383-412) over byte keys, and as on the JVM the array holds
+ * references: the rows stay where they were put.  It is the caller's device memory, four parts per row r:
+ *   state_rows_dev[num_states*k]    rows of key_width bytes (8-byte aligned).  Storage only: the order of the k
+ *                                   slots of a row's block means nothing.
+ *   state_hashes_dev[num_states*k]  int64, in scala 2.13 mutable.PriorityQueue array order: the scrambled hash of
+ *                                   entry j of the 1-indexed queue sits at position j - 1.
+ *   state_slots_dev[num_states*k]   int32, same positions: the row of the entry at position p lies in slot
+ *                                   slots[r*k + p] of row r's own block, at state_rows_dev[(r*k + slot) * key_width].
+ *   state_counts_dev[num_states]    int64: the queue's length; 0 is the empty sampler, whatever the rest holds.
+ * Slot rule (part of the contract): an admission that grows the heap from n to n + 1 entries takes slot n; an
+ * admission into a full heap takes the slot of the root it evicts.  So a row with n < k entries uses exactly the
+ * slots 0..n-1, a full row's slots are a permutation of 0..k-1, no surviving row is ever moved, and the whole
+ * state -- hashes, slots, counts and the rows in their slots -- is a function of what the row has been fed, in
+ * that order, however it was cut into launches.  The array, its length and the rows it refers to are the whole
+ * sampler, for the reason given at rsv_distinct_segmented_ordered_update.
+ * THIS IS NOT rsv_distinct_segmented_rows_update's layout.  A row block sorted ascending by (h, words) with its
+ * hashes beside it -- what rsv_distinct_segmented_rows, rsv_distinct_segmented_rows_ordered and
+ * rsv_distinct_segmented_rows_update write -- is not a valid ordered state, with or without slots 0..k-1 added:
+ * it is another heap than the reference's and continues differently in exactly the tied streams.  The two kinds
+ * of state must not be mixed.  Start a state with zeroed counts.
+ * Segment b = rows [offsets[b], offsets[b+1]) of rows_dev goes into row r = stream_ids_dev[b], or r = b when
+ * stream_ids_dev is NULL (then num_segments <= num_states).  Row r is seeded as
+ * java.util.Random(seed + stream_base + r); key widths, hash kinds (PRECOMPUTED with hashes_dev, or DEFAULT =
+ * UUID.hashCode at key_width 16), 1 <= k <= 4096 and the equal-rows-equal-hashes contract as
+ * rsv_distinct_segmented_rows_ordered.  Afterwards row r is exactly the array a RandomValues instance holds after
+ * sample() over everything the row has been fed, across all launches, in that order, for any hash; a fresh state
+ * fed a whole stream in one launch holds the set rsv_distinct_segmented_rows_ordered returns (gather the rows by
+ * their slots and sort by (h, words) to compare).
+ * A launch writes into the row block only the rows it admitted that are still members at its end, each into its
+ * slot; hashes and slots are written over [0, k) with zeros beyond the count.  A row in which nothing was admitted
+ * is not written at all.  Row slots [count, k) are zeroed whenever the row was empty before or its count had to
+ * be clamped; a row that held entries keeps what it had there, which is zero in every state this entry point
+ * wrote.  The ids of one launch must be distinct (two segments on one row race: the caller's contract); a
+ * segment whose id lies outside [0, num_states) is skipped.  Rows that no segment names, and rows whose segment
+ * is empty, are not touched.  rows_dev and hashes_dev must not overlap the state (the caller's contract);
+ * rows_dev may be NULL when every segment is empty.
+ * A row's count is clamped into [0, k] and every slot below k before use, and nothing else read from the state
+ * addresses memory: slots out of range or repeated, a row that is no heap and a wrong count give an unspecified
+ * set, never an out-of-range access.
+ * The checks run before any device call and are rsv_distinct_segmented_rows_update's in its order (the same bad
+ * arguments give the same status); state_slots_dev NULL is RSV_E_NULL_POINTER with the parameter named in
+ * rsv_last_error.  No merge, for the reason given at rsv_distinct_segmented_ordered_update: callers of the set
+ * order keep rsv_distinct_segmented_rows_merge.
+ * Stateless and stream-ordered on hip_stream: no host wait, no allocation.  All pointers are device pointers. */
+rsv_status rsv_distinct_segmented_rows_ordered_update(const void* rows_dev, const int64_t* hashes_dev,
+                                                      const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                                      int64_t num_segments, int64_t num_states, int32_t key_width,
+                                                      int32_t k, int32_t hash_kind, uint64_t seed, uint64_t stream_base,
+                                                      void* state_rows_dev, int64_t* state_hashes_dev,
+                                                      int32_t* state_slots_dev, int64_t* state_counts_dev,
+                                                      void* hip_stream);
 
 /* Event replay (K1'): apply eviction events (1-based position, slot) -- the
  * `samples(rand.nextInt(k)) = map(element)` writes of S:243-246 -- for elements at global indices

@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = (
     "rsv_distinct_segmented_rows_update", "rsv_distinct_segmented_rows_merge",
     "rsv_sample_segmented_rows", "rsv_sample_segmented_rows_update", "rsv_sample_segmented_rows_merge",
     "rsv_distinct_segmented_ordered", "rsv_distinct_segmented_rows_ordered",
-    "rsv_distinct_segmented_ordered_update",
+    "rsv_distinct_segmented_ordered_update", "rsv_distinct_segmented_rows_ordered_update",
 )
 
 
@@ -148,6 +148,8 @@ def load():
     L.rsv_distinct_segmented_ordered_update.argtypes = L.rsv_distinct_segmented_update.argtypes
     L.rsv_distinct_segmented_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
     L.rsv_distinct_segmented_rows_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
+    L.rsv_distinct_segmented_rows_ordered_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, u64, u64, vp, vp, vp,
+                                                             vp, vp]
     L.rsv_distinct_segmented_rows_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
     L.rsv_replay_events.argtypes = [vp, i64, i32, i64, vp, vp, i64, i32, vp, vp]
     L.rsv_export_draws.argtypes = [u64, u64, u64, i64, vp, vp]
@@ -184,7 +186,8 @@ def load():
                  "rsv_distinct_segmented_rows_update", "rsv_distinct_segmented_rows_merge",
                  "rsv_sample_segmented_rows", "rsv_sample_segmented_rows_update",
                  "rsv_sample_segmented_rows_merge", "rsv_distinct_segmented_ordered",
-                 "rsv_distinct_segmented_rows_ordered", "rsv_distinct_segmented_ordered_update"):
+                 "rsv_distinct_segmented_rows_ordered", "rsv_distinct_segmented_ordered_update",
+                 "rsv_distinct_segmented_rows_ordered_update"):
         getattr(L, name).restype = i32
     if L.rsv_abi_version() != 1:
         raise ImportError("libreservoir_hip.so ABI version mismatch")

@@ -11,6 +11,8 @@ libreservoir_hip.so.  Every function raises if the engine is unavailable.
                          per micro-batch (update) and combined across launches, GPUs and ranks (merge)
     SegmentedDistinctOrdered -- the ordered form resumed: the state rows are the reference's heap arrays (update)
     SegmentedDistinctRows -- K5 resumed over byte keys: the rows move inside the caller-held state (update, merge)
+    SegmentedDistinctRowsOrdered -- the ordered form resumed over byte keys: the heap arrays hold (hash, slot) and
+                         the rows stay in their slots of the caller-held state (update)
     SegmentedSampler  -- K2 resumed: S Sampler.apply streams as caller-held state (keys, idx, next), fed in
                          pieces from any start index (update) and combined per slot by largest index (merge)
     sample_segmented_rows -- K2 over fixed-width byte keys (UUIDs): rows in, each slot's winning row out
@@ -277,9 +279,10 @@ def _check_rows_width(what: str, long_what: str, width: int) -> None:
 
 
 class _SegmentedState:
-    """What the four caller-held states share: the constructor's checks, the segment side of update() and
-    the argument handling of merge().  A subclass names its three tensors (_TENSORS: the payload keys (S, k) or
-    rows (S, k, width), the per-slot and the per-row tensor), itself and its cap on k for the messages (_NAME,
+    """What the caller-held states share: the constructor's checks, the segment side of update() and
+    the argument handling of merge().  A subclass names its tensors (_TENSORS: the payload keys (S, k) or
+    rows (S, k, width) first, then the per-slot tensors -- one, or two where the slots hold references -- and the
+    per-row tensor; merge() is for the classes with three), itself and its cap on k for the messages (_NAME,
     _MAX_K; _LONG: a rows class's counterpart for 4- and 8-byte keys), what merge(other) compares (_identity(),
     _SAME in the message), and makes its own native calls."""
 
@@ -623,6 +626,106 @@ class SegmentedDistinctRows(_SegmentedState):
         L = N.load()
         return self._merge(torch, L.rsv_distinct_segmented_rows_merge, SegmentedDistinctRows,
                            (part_rows, part_hashes, part_counts))
+
+
+class SegmentedDistinctRowsOrdered(_SegmentedState):
+    """SegmentedDistinctOrdered over fixed-width byte keys (java.util.UUID, case classes of primitives).
+
+    What SegmentedDistinctRows is for the set order, for order="ordered": exact for any hash, UUID.hashCode's 32
+    bits included.  The state is four device tensors, and row s is the reference's RandomValues itself, its queue's
+    array holding references as on the JVM: hashes int64 (S, k) and slots int32 (S, k) are counts[s] entries in
+    scala 2.13 mutable.PriorityQueue array order (entry j of the 1-indexed queue at position j - 1), and the row of
+    the entry at position p is rows[s, slots[s, p]]; rows uint8 (S, k, width) is storage whose order means nothing;
+    counts int64 (S,).  An admission that grows the heap from n entries takes slot n, one into a full heap takes the
+    slot of the root it evicts, so no surviving row ever moves and the whole state is a function of what a row was
+    fed, in that order, however it was cut into update() calls.  Row s is seeded like a single
+    Sampler.distinct(k, key_type="bytesW", seed=seed + stream_base + s, order="ordered").  This is NOT
+    SegmentedDistinctRows' layout, and the two kinds of state must not be mixed; result() gives the rows sorted.
+    Only the counts are zero-filled: a row with count 0 is empty whatever the rest holds.  width: a multiple of 8 in
+    16..256.  hash="default" is UUID.hashCode (width 16 only); hash="precomputed": update(hashes=...).  There is no
+    merge.  Everything runs on torch's current stream.
+    """
+
+    _NAME, _LONG, _MAX_K = "SegmentedDistinctRowsOrdered", "SegmentedDistinctOrdered", _SEG_DISTINCT_MAX_K
+    _TENSORS = ("rows", "hashes", "slots", "counts")
+
+    def _check_width(self, width) -> None:
+        super()._check_width(width)
+        if self._hash == "default" and width != 16:
+            raise N.ReservoirError("hash='default' is UUID.hashCode: width 16 only")
+
+    def __init__(self, num_streams: int, k: int, width: int, seed: int, stream_base: int = 0, hash: str = "default",
+                 device=None):
+        import torch
+
+        N.load()
+        if hash not in ("default", "precomputed"):
+            raise N.IllegalArgumentException(f"unknown hash {hash!r}")
+        self._hash = hash
+        dev = self._init_state(torch, num_streams, k, seed, stream_base, device, width)
+        self.rows = torch.empty((self.num_streams, self.k, self.width), dtype=torch.uint8, device=dev)
+        self.hashes = torch.empty((self.num_streams, self.k), dtype=torch.int64, device=dev)
+        self.slots = torch.empty((self.num_streams, self.k), dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
+
+    def update(self, rows, offsets, stream_ids=None, hashes=None, check_ids: bool = True):
+        """Segment b = rows[offsets[b]:offsets[b+1]] into row stream_ids[b] (None: row b), in arrival order.
+
+        rows: uint8 (n, width) or int64 (n, width / 8), as distinct_segmented_rows takes them; they must
+        not overlap the state.  stream_ids and check_ids as SegmentedDistinct.update.  Rows that no
+        segment names, or whose segment is empty, are not touched, and a row in which nothing was admitted
+        is not written.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        if hashes is not None and self._hash != "precomputed":
+            raise N.IllegalArgumentException("hashes= needs hash='precomputed'")
+        rows, offsets, hashes = _segd_rows_inputs(torch, rows, offsets, self._hash, hashes)
+        self._check_same_device(rows, offsets)
+        seg = self._segments(torch, offsets, check_ids, stream_ids)
+        if seg is None:
+            return self
+        B, stream_ids = seg
+        N.check(L.rsv_distinct_segmented_rows_ordered_update(
+            C.c_void_p(rows.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
+            C.c_void_p(offsets.data_ptr()), C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
+            B, self.num_streams, self.width, self.k, N.HASH_PRECOMPUTED if hashes is not None else N.HASH_DEFAULT,
+            self.seed, self.stream_base, C.c_void_p(self.rows.data_ptr()), C.c_void_p(self.hashes.data_ptr()),
+            C.c_void_p(self.slots.data_ptr()), C.c_void_p(self.counts.data_ptr()), _stream_ptr(torch, self.rows.device)))
+        return self
+
+    def result(self):
+        """(rows uint8 (S, k, width), hashes (S, k), counts (S,)) in distinct_segmented_rows_ordered's layout: every
+        row block ascending by (scrambled hash, words as unsigned little-endian 64-bit values, word 0 first), zeros
+        beyond its count.  New tensors; the state is left as it is, and nothing waits for the device."""
+        import torch
+
+        S, k, W8 = self.num_streams, self.k, self.width // 8
+        dev = self.rows.device
+        counts = self.counts.clamp(0, k)
+        valid = torch.arange(k, device=dev)[None, :] < counts[:, None]
+        # the rows in array order; unsigned order of a word = signed order of the word with its top bit flipped
+        slots = self.slots.clamp(0, k - 1).to(torch.int64)
+        words = self.rows.view(torch.int64).gather(1, slots[:, :, None].expand(S, k, W8))
+        ordw = (words ^ torch.iinfo(torch.int64).min).masked_fill(~valid[:, :, None], 0)
+        # stably by the last word up to word 0, then by hash, then the valid entries first
+        order = torch.arange(k, device=dev)[None, :].expand(S, k)
+        for w in range(W8 - 1, -1, -1):
+            order = order.gather(1, torch.argsort(ordw[:, :, w].gather(1, order), dim=1, stable=True))
+        order = order.gather(1, torch.argsort(self.hashes.gather(1, order), dim=1, stable=True))
+        order = order.gather(1, torch.argsort((~valid).gather(1, order).to(torch.int8), dim=1, stable=True))
+        keep = valid.gather(1, order)
+        zero = torch.zeros((), dtype=torch.int64, device=dev)
+        out = torch.where(keep[:, :, None], words.gather(1, order[:, :, None].expand(S, k, W8)), zero)
+        return (out.contiguous().view(torch.uint8).reshape(S, k, self.width),
+                torch.where(keep, self.hashes.gather(1, order), zero), counts)
+
+    def merge(self, *parts, **kw):
+        """Not provided: two heaps over parts of a stream do not determine the reference's heap over the whole."""
+        raise N.ReservoirError(
+            "SegmentedDistinctRowsOrdered has no merge: two heaps over disjoint parts of a stream do not determine the "
+            "reference's heap over the whole stream; SegmentedDistinctRows.merge combines states in the set order")
 
 
 _SEG_SAMPLE_STATE_MAX_K = 15104  # rsv_internal.h kSegSampleStateMaxK

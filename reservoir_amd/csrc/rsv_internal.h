@@ -215,6 +215,16 @@ hipError_t launch_segdistinct_ordered_update(const void* keys, int key_width, co
                                              const int64_t* stream_ids, int64_t num_segments, int64_t num_states,
                                              uint32_t k, int hash_kind, uint64_t seed0, void* state_keys,
                                              int64_t* state_hashes, int64_t* state_counts, hipStream_t st);
+// K5 ordered, resumed over byte keys (rsv_segdistinct.hip): the heap array holds references.  hashes and slots
+// [num_states*k] are the queue's array order as for launch_segdistinct_ordered_update, the row of the entry at
+// position p lies in slot slots[p] of the row's block of state_rows (storage, in no order; an admission takes slot
+// n when the heap grows from n, else the evicted root's).  rows and state_rows 8-byte aligned, no input may alias
+// the state.  hashes as for launch_segdistinct_rows.  No allocation.
+hipError_t launch_segdistinct_rows_ordered_update(const void* rows, int key_width, const int64_t* hashes,
+                                                  const int64_t* offsets, const int64_t* stream_ids, int64_t num_segments,
+                                                  int64_t num_states, uint32_t k, uint64_t seed0, void* state_rows,
+                                                  int64_t* state_hashes, int32_t* state_slots, int64_t* state_counts,
+                                                  hipStream_t st);
 // K5 resumed over byte keys (rsv_segdistinct.hip): the state is rows[num_states*k] of key_width bytes, hashes,
 // counts, as launch_segdistinct_rows writes them, moved in place.  rows / part_rows ([parts][num_states][k] rows)
 // and state_rows 8-byte aligned, and no input may alias the state.  hashes as for launch_segdistinct_rows.

@@ -1973,6 +1973,39 @@ rsv_status rsv_distinct_segmented_rows_update(const void* rows_dev, const int64_
     return RSV_OK;
 }
 
+rsv_status rsv_distinct_segmented_rows_ordered_update(const void* rows_dev, const int64_t* hashes_dev,
+                                                      const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                                      int64_t num_segments, int64_t num_states, int32_t key_width,
+                                                      int32_t k, int32_t hash_kind, uint64_t seed, uint64_t stream_base,
+                                                      void* state_rows_dev, int64_t* state_hashes_dev,
+                                                      int32_t* state_slots_dev, int64_t* state_counts_dev,
+                                                      void* hip_stream) {
+    // rsv_distinct_segmented_rows_update's checks in its order; state_slots_dev by name, behind the other buffers
+    if (rsv_status st = check_segrows_shape("rsv_distinct_segmented_rows_ordered_update", "rsv_distinct_segmented_ordered_update",
+                                            k, key_width))
+        return st;
+    if (rsv_status st = check_segrows_hash(hash_kind, key_width)) return st;
+    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
+    if (!stream_ids_dev && num_segments > num_states)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
+    if (num_segments == 0 || num_states == 0) return RSV_OK;
+    // rows_dev is not checked: a launch whose segments are all empty has no rows
+    if (!offsets_dev || !state_rows_dev || !state_hashes_dev || !state_counts_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (!state_slots_dev)
+        return fail(RSV_E_NULL_POINTER,
+                    "rsv_distinct_segmented_rows_ordered_update needs state_slots_dev: the heap's entries find their rows by them");
+    if (hash_kind == RSV_HASH_PRECOMPUTED && !hashes_dev)
+        return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
+    if (((uintptr_t)rows_dev | (uintptr_t)state_rows_dev) & 7)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "rows_dev and state_rows_dev must be 8-byte aligned");
+    RSV_HIP_TRY(launch_segdistinct_rows_ordered_update(
+        rows_dev, key_width, hash_kind == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr, offsets_dev, stream_ids_dev,
+        num_segments, num_states, (uint32_t)k, seed + stream_base, state_rows_dev, state_hashes_dev, state_slots_dev,
+        state_counts_dev, (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
 rsv_status rsv_distinct_segmented_rows_merge(const void* part_rows_dev, const int64_t* part_hashes_dev,
                                              const int64_t* part_counts_dev, int32_t parts, int64_t num_states,
                                              int32_t key_width, int32_t k, void* state_rows_dev,

@@ -9,9 +9,10 @@
 // (RSV_DISTINCT_ORDERED), not the smallest keys; rsv_distinct_segmented_rows_ordered is that for byte-key
 // rows.  rsv_distinct_segmented_ordered_update resumes the ordered form from caller-held state: k entries
 // kept sorted cannot carry the heap's history, k entries kept in the queue's array
-// order are the heap, and that is the state there.  Not provided in ordered form:
-// merge (two heaps over parts of a stream do not determine the heap over the whole), resumed byte-key
-// rows, k > 4096.
+// order are the heap, and that is the state there; rsv_distinct_segmented_rows_ordered_update
+// is that for byte-key rows, the array holding (hash, slot) and the rows staying in their slots of the row's
+// block.  Not provided in ordered form: merge (two heaps over parts of a stream do not
+// determine the heap over the whole), k > 4096.
 //
 // One TEAM of NT threads per stream, streams taken grid-stride.  The team holds P 16-byte entries
 // (h, key) in LDS: the current set [0, m) ascending by (h, key), and behind it the candidates
@@ -998,6 +999,128 @@ __global__ __launch_bounds__(NT) void segrows_tied_kernel(const uint64_t* __rest
     }
 }
 
+// What a heap entry's second word is in the two ordered kernels over rows.  Stateless (STATE = false): the row's
+// index into rows.  Resumed (STATE = true): every entry also carries the storage slot of its row in the state
+// block, so that lane 0's sift moves it along in the same 16 bytes: a state entry is
+// kStateRef | slot, an entry admitted from the input is slot << kSlotShift | row index (slot < 4096, indices far
+// below 2^48).  row_of and slot_of are the only places that take such a word apart; RowSrc<true>::at clamps the
+// slot of a state entry below k before it addresses anything.
+constexpr int kSlotShift = 48;
+constexpr int64_t kRowIndexMask = (1LL << kSlotShift) - 1;
+
+template <bool STATE>
+__device__ __forceinline__ const uint64_t* row_of(const RowSrc<STATE>& src, int64_t ref) {
+    if constexpr (STATE)
+        return src.at((ref & kStateRef) ? ref : (ref & kRowIndexMask));
+    else
+        return src.at(ref);
+}
+// (below k whatever the entry holds: a state entry's slot was clamped when it entered LDS, an input entry's is a
+// heap size below k or the slot of a root)
+__device__ __forceinline__ uint32_t slot_of(int64_t ref, uint32_t k) {
+    const uint64_t j = (ref & kStateRef) ? (uint64_t)(ref & (kStateRef - 1)) : (uint64_t)ref >> kSlotShift;
+    return j < k ? (uint32_t)j : k - 1;
+}
+
+// RandomValues.sample over the rows [lo, hi) of src's input in arrival order, by one wave, on the heap se[0, n)
+// with maxh its root's h (INT64_MIN while it is empty): replay_walk for byte keys, what the comment at
+// segrows_replay_kernel says of its walk.  The one piece of device code both ordered kernels over rows run per
+// stream (segrows_replay_kernel from an empty heap, segrows_heap_kernel from the caller's); it returns whether
+// anything was admitted.  With STATE an admission takes its slot by the rule: the heap's size when it grows, the
+// evicted root's slot when it is full.  The heap is left as the last admission wrote it, behind a barrier.
+template <bool STATE>
+__device__ __forceinline__ bool rows_replay_walk(Ent* const se, const Rows<STATE, true> src, int64_t lo, int64_t hi,
+                                                 uint32_t k, uint32_t& n_io, int64_t& maxh_io) {
+    uint32_t n = n_io;
+    int64_t maxh = maxh_io;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t W8 = src.W8;
+    bool admitted = false;
+    // equality of a heap entry's row and row c of the input (W8 >= 2): the first two words of both in flight
+    // together, so a UUID costs one round trip, not one per word
+    const auto same_row = [&](int64_t ref, int64_t c) {
+        const uint64_t* const ra = row_of<STATE>(src, ref);
+        const uint64_t* const rb = src.rows + c * (int64_t)W8;
+        if (ra == rb) return true;
+        const uint64_t a0 = ra[0], a1 = ra[1], b0 = rb[0], b1 = rb[1];
+        if (a0 != b0 || a1 != b1) return false;
+        for (uint32_t w = 2; w < W8; ++w)
+            if (ra[w] != rb[w]) return false;
+        return true;
+    };
+    for (int64_t base = lo; base < hi; base += 64 * kU) {
+        int64_t ref[kU], hv[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int64_t i = base + (int64_t)u * 64 + lane;
+            ref[u] = 0;
+            hv[u] = 0;
+            if (i < hi) src.load(i, ref[u], hv[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int64_t i = base + (int64_t)u * 64 + lane;
+            if (base + (int64_t)u * 64 >= hi) break;  // uniform
+            const int64_t h = src.h_of(ref[u], hv[u]);
+            bool pend = i < hi;
+            for (;;) {
+                const uint64_t mask = __ballot(pend && (n < k || h < maxh));
+                if (!mask) break;
+                const int l = __ffsll((long long)mask) - 1;
+                if ((int)lane == l) pend = false;
+                Ent c{read_lane(h, l), base + (int64_t)u * 64 + l};  // the candidate: (h, its row's index)
+                bool found = false;
+                const uint32_t full = n >> 6;
+                uint32_t r = 0;
+                for (; r + 8 <= full; r += 8) {
+                    int64_t mh[8];
+#pragma unroll
+                    for (int x = 0; x < 8; ++x) mh[x] = se[(r + x) * 64 + lane].h;
+#pragma unroll
+                    for (int x = 0; x < 8; ++x)
+                        if (mh[x] == c.h) found |= same_row(se[(r + x) * 64 + lane].key, c.key);
+                }
+                for (uint32_t j = r * 64 + lane; j < n; j += 64)
+                    if (se[j].h == c.h) found |= same_row(se[j].key, c.key);
+                if (__ballot(found)) continue;  // a member
+                if (lane == 0) {
+                    uint32_t nn = n;
+                    if constexpr (STATE) c.key |= (int64_t)(nn == k ? slot_of(se[0].key, k) : nn) << kSlotShift;
+                    if (nn == k) {  // dequeue: the root leaves
+                        const Ent last = se[nn - 1];
+                        --nn;
+                        if (nn) {
+                            uint32_t q = 1;
+                            while (2 * q <= nn) {
+                                uint32_t ch = 2 * q;
+                                if (ch + 1 <= nn && se[ch - 1].h < se[ch].h) ++ch;
+                                if (last.h >= se[ch - 1].h) break;
+                                se[q - 1] = se[ch - 1];
+                                q = ch;
+                            }
+                            se[q - 1] = last;
+                        }
+                    }
+                    uint32_t q = nn + 1;  // addOne
+                    while (q > 1 && se[(q >> 1) - 1].h < c.h) {
+                        se[q - 1] = se[(q >> 1) - 1];
+                        q >>= 1;
+                    }
+                    se[q - 1] = c;
+                }
+                if (n < k) ++n;
+                admitted = true;
+                __syncthreads();
+                maxh = se[0].h;
+                __syncthreads();
+            }
+        }
+    }
+    n_io = n;
+    maxh_io = maxh;
+    return admitted;
+}
+
 // Kernel 2 over byte keys: segdistinct_replay_kernel with entries (h, ref), ref the row's index into rows:
 // the same grouping of tied words, heap, walk and serialised admission; no row is staged in LDS.
 // elements.contains: equal rows carry equal hashes (the caller's contract), so a member can only be an
@@ -1028,87 +1151,10 @@ __global__ __launch_bounds__(64) void segrows_replay_kernel(const uint64_t* __re
             java_r0r1(seed0 + (uint64_t)s, r0, r1);
             const Rows<false, true> src{{{rows, W8}}, hashes, vec16, r0, r1, nullptr};  // no T here: admits is not used
             const RowOrd<false>& ord = src;
-            // equality of two rows of the input (refs >= 0; W8 >= 2): the first two words of both in flight
-            // together, so a UUID costs one round trip, not one per word
-            const auto same_row = [&](int64_t a, int64_t b) {
-                if (a == b) return true;
-                const uint64_t* const ra = src.at(a);
-                const uint64_t* const rb = src.at(b);
-                const uint64_t a0 = ra[0], a1 = ra[1], b0 = rb[0], b1 = rb[1];
-                if (a0 != b0 || a1 != b1) return false;
-                for (uint32_t w = 2; w < W8; ++w)
-                    if (ra[w] != rb[w]) return false;
-                return true;
-            };
             uint32_t n = 0;            // heap size (uniform)
             int64_t maxh = INT64_MIN;  // the root's h once anything is in
             __syncthreads();           // the previous stream's output reads are done
-            for (int64_t base = lo; base < hi; base += 64 * kU) {
-                int64_t ref[kU], hv[kU];
-#pragma unroll
-                for (int u = 0; u < kU; ++u) {
-                    const int64_t i = base + (int64_t)u * 64 + lane;
-                    ref[u] = 0;
-                    hv[u] = 0;
-                    if (i < hi) src.load(i, ref[u], hv[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < kU; ++u) {
-                    const int64_t i = base + (int64_t)u * 64 + lane;
-                    if (base + (int64_t)u * 64 >= hi) break;  // uniform
-                    const int64_t h = src.h_of(ref[u], hv[u]);
-                    bool pend = i < hi;
-                    for (;;) {
-                        const uint64_t mask = __ballot(pend && (n < k || h < maxh));
-                        if (!mask) break;
-                        const int l = __ffsll((long long)mask) - 1;
-                        if ((int)lane == l) pend = false;
-                        const Ent c{read_lane(h, l), base + (int64_t)u * 64 + l};  // the candidate: (h, its row's index)
-                        bool found = false;
-                        const uint32_t full = n >> 6;
-                        uint32_t r = 0;
-                        for (; r + 8 <= full; r += 8) {
-                            int64_t mh[8];
-#pragma unroll
-                            for (int x = 0; x < 8; ++x) mh[x] = se[(r + x) * 64 + lane].h;
-#pragma unroll
-                            for (int x = 0; x < 8; ++x)
-                                if (mh[x] == c.h) found |= same_row(se[(r + x) * 64 + lane].key, c.key);
-                        }
-                        for (uint32_t j = r * 64 + lane; j < n; j += 64)
-                            if (se[j].h == c.h) found |= same_row(se[j].key, c.key);
-                        if (__ballot(found)) continue;  // a member
-                        if (lane == 0) {
-                            uint32_t nn = n;
-                            if (nn == k) {  // dequeue: the root leaves
-                                const Ent last = se[nn - 1];
-                                --nn;
-                                if (nn) {
-                                    uint32_t q = 1;
-                                    while (2 * q <= nn) {
-                                        uint32_t ch = 2 * q;
-                                        if (ch + 1 <= nn && se[ch - 1].h < se[ch].h) ++ch;
-                                        if (last.h >= se[ch - 1].h) break;
-                                        se[q - 1] = se[ch - 1];
-                                        q = ch;
-                                    }
-                                    se[q - 1] = last;
-                                }
-                            }
-                            uint32_t q = nn + 1;  // addOne
-                            while (q > 1 && se[(q >> 1) - 1].h < c.h) {
-                                se[q - 1] = se[(q >> 1) - 1];
-                                q >>= 1;
-                            }
-                            se[q - 1] = c;
-                        }
-                        if (n < k) ++n;
-                        __syncthreads();
-                        maxh = se[0].h;
-                        __syncthreads();
-                    }
-                }
-            }
+            rows_replay_walk<false>(se, src, lo, hi, k, n, maxh);
             const uint32_t m = merge_set<64>(se, n, k, s_scan, ord);
             __syncthreads();
             const int64_t ob = s * (int64_t)k;
@@ -1119,6 +1165,79 @@ __global__ __launch_bounds__(64) void segrows_replay_kernel(const uint64_t* __re
             if (out_hashes)
                 for (uint32_t i = lane; i < m; i += 64) out_hashes[ob + i] = se[i].h;
         }
+    }
+}
+
+// ---- Ordered over byte keys, resumed (rsv_distinct_segmented_rows_ordered_update) ----
+// segdistinct_heap_kernel's argument does not ask what a key is: the queue's array in array order is the sampler.
+// What the array holds here is what it holds on the JVM, references: the row block state_rows[r] is storage whose
+// order means nothing, hashes[r][p] and slots[r][p] are position p of the array, and the row of that entry lies in
+// slot slots[r][p] of the block.  An admission that grows the heap from n to n + 1 takes slot n, one into a full
+// heap takes the slot of the root it evicts: below k the slots in use are {0..n-1}, at k a permutation, and no
+// surviving row ever moves.
+// One wave per segment, segments grid-stride; row r = ids[b] (or b), seeded seed0 + r.
+//   prologue   n = clamp(counts[r], 0, k); entry p into se[p] as (hashes[p], kStateRef | slot), the slot clamped
+//              below k; maxh = se[0].h when n > 0.  No row is read.
+//   walk       rows_replay_walk, segrows_replay_kernel's own; rows are read from the input or from a state slot
+//              only for entries with the candidate's hash.
+//   epilogue   only if something was admitted: hashes and slots of se[0, n) as they lie and zeros up to k, then for
+//              every entry that refers to the input its row into its slot, lanes over (entry, word), then the count.
+//              No sort and no staged move: the rows read are the input's, and the slots written are the ones no
+//              surviving state entry names (a grown heap's new slots, or slots of evicted roots), so nothing is
+//              read after it was overwritten and no member's row is touched.  Slots [n, k) of the block are zeroed
+//              when the row was empty before or its count had to be clamped (the caller's bytes), else they are
+//              the kernel's own zeros already.
+// Nothing read from the state or from the ids indexes memory unclamped: the count into [0, k], every slot below k,
+// an id outside [0, num_states) skips the segment.  Repeated or out-of-range slots, a row that is no heap and a
+// wrong count give an unspecified set at the same addresses.
+__global__ __launch_bounds__(64) void segrows_heap_kernel(const uint64_t* in_rows, const int64_t* __restrict__ hashes,
+                                                          const int64_t* __restrict__ offsets,
+                                                          const int64_t* __restrict__ ids, int64_t num_segments,
+                                                          int64_t num_states, uint32_t W8, uint32_t k, uint64_t seed0,
+                                                          uint64_t* state_rows, int64_t* state_hashes,
+                                                          int32_t* state_slots, int64_t* state_counts) {
+    extern __shared__ __align__(16) unsigned char seg_lds[];
+    Ent* const se = (Ent*)seg_lds;
+    const uint32_t lane = threadIdx.x;
+    const bool vec16 = ((uintptr_t)in_rows & 15) == 0;
+
+    for (int64_t b = blockIdx.x; b < num_segments; b += gridDim.x) {
+        // everything that decides the control flow below is uniform over the wave
+        int64_t r = b;
+        if (ids) r = ids[b];
+        if (r < 0 || r >= num_states) continue;  // an id outside the state: no row is addressed
+        const int64_t lo = offsets[b], hi = offsets[b + 1];
+        if (hi <= lo) continue;  // an empty segment leaves its row as it is
+        const int64_t ob = r * (int64_t)k;
+        uint64_t* const srow = state_rows + ob * (int64_t)W8;
+        const int64_t c0 = state_counts[r];
+        const uint32_t n0 = c0 <= 0 ? 0u : (c0 >= (int64_t)k ? k : (uint32_t)c0);
+        uint32_t n = n0;
+        __syncthreads();  // the previous row's output reads are done
+        for (uint32_t i = lane; i < n; i += 64) {
+            const uint32_t j = (uint32_t)state_slots[ob + i];  // a negative slot is a large one
+            se[i] = Ent{state_hashes[ob + i], kStateRef | (int64_t)(j < k ? j : k - 1)};
+        }
+        __syncthreads();
+        int64_t maxh = INT64_MIN;
+        if (n) maxh = se[0].h;
+        int64_t r0, r1;
+        java_r0r1(seed0 + (uint64_t)r, r0, r1);
+        const Rows<true, true> src{{{in_rows, W8, srow, k}}, hashes, vec16, r0, r1, nullptr};  // no T here
+        if (!rows_replay_walk<true>(se, src, lo, hi, k, n, maxh)) continue;  // nothing admitted: the row stands as it is
+        if (n0 == 0 || c0 != (int64_t)n0)
+            for (uint32_t x = n * W8 + lane; x < k * W8; x += 64) srow[x] = 0;  // k * W8 <= 4096 * 32
+        for (uint32_t i = lane; i < k; i += 64) {
+            const Ent e = i < n ? se[i] : Ent{0, 0};
+            state_hashes[ob + i] = e.h;
+            state_slots[ob + i] = i < n ? (int32_t)slot_of(e.key, k) : 0;
+        }
+        for (uint32_t x = lane; x < n * W8; x += 64) {
+            const uint32_t j = x / W8, w = x - j * W8;
+            const int64_t ref = se[j].key;
+            if (!(ref & kStateRef)) srow[slot_of(ref, k) * W8 + w] = in_rows[(ref & kRowIndexMask) * (int64_t)W8 + w];
+        }
+        if (lane == 0) state_counts[r] = n;
     }
 }
 
@@ -1281,6 +1400,24 @@ hipError_t launch_segdistinct_ordered_update(const void* keys, int key_width, co
         return hipGetLastError();
     };
     return key_width == 8 ? go(int64_t{}) : go(int32_t{});
+}
+
+// The resumed ordered launch over byte keys: launch_segdistinct_ordered_update's plan (one segment per wave, the
+// heap's 16-byte entries carry their slots, so the LDS is the same).
+hipError_t launch_segdistinct_rows_ordered_update(const void* rows, int key_width, const int64_t* hashes,
+                                                  const int64_t* offsets, const int64_t* stream_ids, int64_t num_segments,
+                                                  int64_t num_states, uint32_t k, uint64_t seed0, void* state_rows,
+                                                  int64_t* state_hashes, int32_t* state_slots, int64_t* state_counts,
+                                                  hipStream_t st) {
+    if (num_segments <= 0 || num_states <= 0) return hipSuccess;
+    size_t lds;
+    uint64_t cap;
+    if (const hipError_t a = plan_heap_waves((const void*)segrows_heap_kernel, k, lds, cap); a != hipSuccess) return a;
+    const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)num_segments, cap);
+    hipLaunchKernelGGL(segrows_heap_kernel, dim3(grid), dim3(64), lds, st, (const uint64_t*)rows, hashes, offsets,
+                       stream_ids, num_segments, num_states, (uint32_t)key_width / 8, k, seed0, (uint64_t*)state_rows,
+                       state_hashes, state_slots, state_counts);
+    return hipGetLastError();
 }
 
 hipError_t launch_segdistinct_merge(const void* part_keys, int key_width, const int64_t* part_hashes,
