@@ -105,6 +105,45 @@ def _check_stream_ids(torch, stream_ids, S: int) -> None:
         raise N.IllegalArgumentException("stream_ids repeat a row within one update")
 
 
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _segd_kind(hash, precomputed: bool) -> int:
+    """The hash kind of a K5 call over 4- and 8-byte keys."""
+    if precomputed:
+        return N.HASH_PRECOMPUTED
+    if hash in _SEG_HASH:
+        return _SEG_HASH[hash]
+    raise N.IllegalArgumentException(f"unknown hash {hash!r}")
+
+
+def _segd_stateless(torch, fn, data, hashes, offsets, width, k, kind, seed, stream_base, out_dtype, ordered):
+    """The outputs and the native call (fn) of the four stateless K5 functions.  data: keys, or rows of `width`
+    bytes each, for which out is (S, k, width); ordered: a fourth output, tied (S,) int32."""
+    S = offsets.numel() - 1
+    # the kernel writes every slot or row block (zeros beyond the count) and every count: no zero-fill
+    kk = max(int(k), 0)
+    out = torch.empty((max(S, 0), kk) + ((width,) if data.dim() == 2 else ()), dtype=out_dtype, device=data.device)
+    res = [out, torch.empty((max(S, 0), kk), dtype=torch.int64, device=data.device),
+           torch.empty(max(S, 0), dtype=torch.int64, device=data.device)]
+    if ordered:
+        res.append(torch.empty(max(S, 0), dtype=torch.int32, device=data.device))
+    if S > 0:
+        N.check(fn(_ptr(data), _ptr(hashes), _ptr(offsets), S, width, k, kind, seed & (2**64 - 1),
+                   stream_base & (2**64 - 1), *(_ptr(t) for t in res), _stream_ptr(torch, data.device)))
+    return tuple(res)
+
+
+def _segd_keys_stateless(fn, keys, offsets, k, seed, stream_base, hash, hashes, ordered):
+    import torch
+
+    keys, offsets, hashes = _segd_inputs(torch, keys, offsets, hashes)
+    kind = _segd_kind(hash, hashes is not None)
+    return _segd_stateless(torch, fn, keys, hashes, offsets, keys.element_size(), k, kind, seed, stream_base,
+                           keys.dtype, ordered)
+
+
 def distinct_segmented(keys, offsets, k: int, seed: int, stream_base: int = 0, hash: str = "default", hashes=None):
     """Distinct-sample each of S streams keys[offsets[s]:offsets[s+1]] independently (bottom-k).
 
@@ -114,30 +153,7 @@ def distinct_segmented(keys, offsets, k: int, seed: int, stream_base: int = 0, h
     keys holds.  hash: "default" | "identity" | "java_long" | "java_int"; hashes= (one int64 per
     key, a device tensor) means precomputed hashes.  1 <= k <= 4096.
     """
-    import torch
-
-    L = N.load()
-    keys, offsets, hashes = _segd_inputs(torch, keys, offsets, hashes)
-    if hashes is not None:
-        kind = N.HASH_PRECOMPUTED
-    elif hash in _SEG_HASH:
-        kind = _SEG_HASH[hash]
-    else:
-        raise N.IllegalArgumentException(f"unknown hash {hash!r}")
-    S = offsets.numel() - 1
-    # the kernel writes every slot (empty ones as 0) and every count: no zero-fill
-    kk = max(int(k), 0)
-    out = torch.empty((max(S, 0), kk), dtype=keys.dtype, device=keys.device)
-    out_h = torch.empty((max(S, 0), kk), dtype=torch.int64, device=keys.device)
-    counts = torch.empty(max(S, 0), dtype=torch.int64, device=keys.device)
-    if S <= 0:
-        return out, out_h, counts
-    N.check(L.rsv_distinct_segmented(
-        C.c_void_p(keys.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
-        C.c_void_p(offsets.data_ptr()), S, keys.element_size(), k, kind, seed & (2**64 - 1),
-        stream_base & (2**64 - 1), C.c_void_p(out.data_ptr()), C.c_void_p(out_h.data_ptr()),
-        C.c_void_p(counts.data_ptr()), _stream_ptr(torch, keys.device)))
-    return out, out_h, counts
+    return _segd_keys_stateless(N.load().rsv_distinct_segmented, keys, offsets, k, seed, stream_base, hash, hashes, False)
 
 
 def distinct_segmented_ordered(keys, offsets, k: int, seed: int, stream_base: int = 0, hash: str = "default",
@@ -151,30 +167,8 @@ def distinct_segmented_ordered(keys, offsets, k: int, seed: int, stream_base: in
     bottom-k by (hash, key) has the set's maximum hash; where it is 0 the row is distinct_segmented's.
     hash / hashes and k as distinct_segmented.
     """
-    import torch
-
-    L = N.load()
-    keys, offsets, hashes = _segd_inputs(torch, keys, offsets, hashes)
-    if hashes is not None:
-        kind = N.HASH_PRECOMPUTED
-    elif hash in _SEG_HASH:
-        kind = _SEG_HASH[hash]
-    else:
-        raise N.IllegalArgumentException(f"unknown hash {hash!r}")
-    S = offsets.numel() - 1
-    kk = max(int(k), 0)
-    out = torch.empty((max(S, 0), kk), dtype=keys.dtype, device=keys.device)
-    out_h = torch.empty((max(S, 0), kk), dtype=torch.int64, device=keys.device)
-    counts = torch.empty(max(S, 0), dtype=torch.int64, device=keys.device)
-    tied = torch.empty(max(S, 0), dtype=torch.int32, device=keys.device)
-    if S <= 0:
-        return out, out_h, counts, tied
-    N.check(L.rsv_distinct_segmented_ordered(
-        C.c_void_p(keys.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
-        C.c_void_p(offsets.data_ptr()), S, keys.element_size(), k, kind, seed & (2**64 - 1),
-        stream_base & (2**64 - 1), C.c_void_p(out.data_ptr()), C.c_void_p(out_h.data_ptr()),
-        C.c_void_p(counts.data_ptr()), C.c_void_p(tied.data_ptr()), _stream_ptr(torch, keys.device)))
-    return out, out_h, counts, tied
+    return _segd_keys_stateless(N.load().rsv_distinct_segmented_ordered, keys, offsets, k, seed, stream_base, hash,
+                                hashes, True)
 
 
 def _rows_inputs(torch, rows, offsets, dtypes=None):
@@ -203,6 +197,15 @@ def _segd_rows_inputs(torch, rows, offsets, hash, hashes):
     return rows, offsets, hashes
 
 
+def _segd_rows_stateless(fn, rows, offsets, k, seed, stream_base, hash, hashes, ordered):
+    import torch
+
+    rows, offsets, hashes = _segd_rows_inputs(torch, rows, offsets, hash, hashes)
+    kind = N.HASH_PRECOMPUTED if hashes is not None else N.HASH_DEFAULT
+    return _segd_stateless(torch, fn, rows, hashes, offsets, rows.shape[1] * rows.element_size(), k, kind, seed,
+                           stream_base, torch.uint8, ordered)
+
+
 def distinct_segmented_rows(rows, offsets, k: int, seed: int, stream_base: int = 0, hash: str = "default", hashes=None):
     """distinct_segmented over fixed-width byte keys (java.util.UUID, case classes of primitives).
 
@@ -216,25 +219,8 @@ def distinct_segmented_rows(rows, offsets, k: int, seed: int, stream_base: int =
     zero -- the set a single Sampler.distinct(k, key_type="bytesW", seed=seed + stream_base + s,
     order="set") fed the same rows holds.  1 <= k <= 4096.
     """
-    import torch
-
-    L = N.load()
-    rows, offsets, hashes = _segd_rows_inputs(torch, rows, offsets, hash, hashes)
-    W = rows.shape[1] * rows.element_size()
-    S = offsets.numel() - 1
-    # the kernel writes every row block (zeros beyond the count) and every count: no zero-fill
-    kk = max(int(k), 0)
-    out = torch.empty((max(S, 0), kk, W), dtype=torch.uint8, device=rows.device)
-    out_h = torch.empty((max(S, 0), kk), dtype=torch.int64, device=rows.device)
-    counts = torch.empty(max(S, 0), dtype=torch.int64, device=rows.device)
-    if S <= 0:
-        return out, out_h, counts
-    N.check(L.rsv_distinct_segmented_rows(
-        C.c_void_p(rows.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
-        C.c_void_p(offsets.data_ptr()), S, W, k, N.HASH_PRECOMPUTED if hashes is not None else N.HASH_DEFAULT,
-        seed & (2**64 - 1), stream_base & (2**64 - 1), C.c_void_p(out.data_ptr()), C.c_void_p(out_h.data_ptr()),
-        C.c_void_p(counts.data_ptr()), _stream_ptr(torch, rows.device)))
-    return out, out_h, counts
+    return _segd_rows_stateless(N.load().rsv_distinct_segmented_rows, rows, offsets, k, seed, stream_base, hash, hashes,
+                                False)
 
 
 def distinct_segmented_rows_ordered(rows, offsets, k: int, seed: int, stream_base: int = 0, hash: str = "default",
@@ -250,25 +236,8 @@ def distinct_segmented_rows_ordered(rows, offsets, k: int, seed: int, stream_bas
     block is distinct_segmented_rows'.  Under the default hash of 16-byte rows (UUID.hashCode, 32 bits) ties
     are what this call is for.
     """
-    import torch
-
-    L = N.load()
-    rows, offsets, hashes = _segd_rows_inputs(torch, rows, offsets, hash, hashes)
-    W = rows.shape[1] * rows.element_size()
-    S = offsets.numel() - 1
-    kk = max(int(k), 0)
-    out = torch.empty((max(S, 0), kk, W), dtype=torch.uint8, device=rows.device)
-    out_h = torch.empty((max(S, 0), kk), dtype=torch.int64, device=rows.device)
-    counts = torch.empty(max(S, 0), dtype=torch.int64, device=rows.device)
-    tied = torch.empty(max(S, 0), dtype=torch.int32, device=rows.device)
-    if S <= 0:
-        return out, out_h, counts, tied
-    N.check(L.rsv_distinct_segmented_rows_ordered(
-        C.c_void_p(rows.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
-        C.c_void_p(offsets.data_ptr()), S, W, k, N.HASH_PRECOMPUTED if hashes is not None else N.HASH_DEFAULT,
-        seed & (2**64 - 1), stream_base & (2**64 - 1), C.c_void_p(out.data_ptr()), C.c_void_p(out_h.data_ptr()),
-        C.c_void_p(counts.data_ptr()), C.c_void_p(tied.data_ptr()), _stream_ptr(torch, rows.device)))
-    return out, out_h, counts, tied
+    return _segd_rows_stateless(N.load().rsv_distinct_segmented_rows_ordered, rows, offsets, k, seed, stream_base, hash,
+                                hashes, True)
 
 
 def _check_rows_width(what: str, long_what: str, width: int) -> None:
@@ -389,7 +358,90 @@ class _SegmentedState:
         return self
 
 
-class SegmentedDistinct(_SegmentedState):
+class _DistinctState(_SegmentedState):
+    """What the four K5 states share: the cap on k, the allocation of the state (_TENSORS[0], the payload, by the
+    subclass's base; hashes int64 and, where there are any, slots int32, (S, k); only the counts zero-filled) and the
+    native call of update(), whose entry points (_UPDATE) take the state's tensors last, in _TENSORS' order."""
+
+    _MAX_K = _SEG_DISTINCT_MAX_K
+    _UPDATE = ""
+
+    def _alloc(self, torch, dev, payload_shape, payload_dtype) -> None:
+        setattr(self, self._TENSORS[0], torch.empty(payload_shape, dtype=payload_dtype, device=dev))
+        for name in self._TENSORS[1:-1]:
+            dtype = torch.int32 if name == "slots" else torch.int64
+            setattr(self, name, torch.empty((self.num_streams, self.k), dtype=dtype, device=dev))
+        self.counts = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
+
+    def _launch_update(self, torch, data, hashes, offsets, check_ids, stream_ids, kind):
+        seg = self._segments(torch, offsets, check_ids, stream_ids)
+        if seg is None:
+            return self
+        B, stream_ids = seg
+        state = self._state()
+        N.check(getattr(N.load(), self._UPDATE)(
+            _ptr(data), _ptr(hashes), _ptr(offsets), _ptr(stream_ids), B, self.num_streams, self._key_width(), self.k,
+            kind, self.seed, self.stream_base, *(_ptr(t) for t in state), _stream_ptr(torch, state[0].device)))
+        return self
+
+
+class _DistinctKeysState(_DistinctState):
+    """The two states over 4- and 8-byte keys: hash parsing, dtype check, allocation; update() but for its docstring."""
+
+    _TENSORS = ("keys", "hashes", "counts")
+
+    def __init__(self, num_streams: int, k: int, seed: int, stream_base: int = 0, hash: str = "default",
+                 dtype=None, device=None):
+        import torch
+
+        N.load()
+        dtype = torch.int64 if dtype is None else dtype
+        if dtype not in (torch.int64, torch.int32):
+            raise N.IllegalArgumentException("keys must be int64/int32")
+        self._kind = _segd_kind(hash, hash == "precomputed")
+        dev = self._init_state(torch, num_streams, k, seed, stream_base, device)
+        self._alloc(torch, dev, (self.num_streams, self.k), dtype)
+
+    def _update(self, keys, offsets, stream_ids, hashes, check_ids):
+        import torch
+
+        N.load()
+        keys, offsets, hashes = _segd_inputs(torch, keys, offsets, hashes, state=self)
+        return self._launch_update(torch, keys, hashes, offsets, check_ids, stream_ids, self._kind)
+
+
+class _DistinctRowsState(_DistinctState):
+    """The two states over byte keys: the hash check, _check_width, allocation; update() but for its docstring."""
+
+    def _check_width(self, width) -> None:
+        super()._check_width(width)
+        if self._hash == "default" and width != 16:
+            raise N.ReservoirError("hash='default' is UUID.hashCode: width 16 only")
+
+    def __init__(self, num_streams: int, k: int, width: int, seed: int, stream_base: int = 0, hash: str = "default",
+                 device=None):
+        import torch
+
+        N.load()
+        if hash not in ("default", "precomputed"):
+            raise N.IllegalArgumentException(f"unknown hash {hash!r}")
+        self._hash = hash
+        dev = self._init_state(torch, num_streams, k, seed, stream_base, device, width)
+        self._alloc(torch, dev, (self.num_streams, self.k, self.width), torch.uint8)
+
+    def _update(self, rows, offsets, stream_ids, hashes, check_ids):
+        import torch
+
+        N.load()
+        if hashes is not None and self._hash != "precomputed":
+            raise N.IllegalArgumentException("hashes= needs hash='precomputed'")
+        rows, offsets, hashes = _segd_rows_inputs(torch, rows, offsets, self._hash, hashes)
+        self._check_same_device(rows, offsets)
+        return self._launch_update(torch, rows, hashes, offsets, check_ids, stream_ids,
+                                   N.HASH_PRECOMPUTED if hashes is not None else N.HASH_DEFAULT)
+
+
+class SegmentedDistinct(_DistinctKeysState):
     """S long-lived Sampler.distinct streams advanced by one launch per batch (K5 resumed).
 
     The state is three device tensors in distinct_segmented's layout: keys (S, k), hashes (S, k),
@@ -401,30 +453,11 @@ class SegmentedDistinct(_SegmentedState):
     Everything runs on torch's current stream.
     """
 
-    _NAME, _TENSORS, _MAX_K = "SegmentedDistinct", ("keys", "hashes", "counts"), _SEG_DISTINCT_MAX_K
+    _NAME, _UPDATE = "SegmentedDistinct", "rsv_distinct_segmented_update"
     _SAME = "seed, stream_base and hash"
 
     def _identity(self):
         return self.num_streams, self.k, self.seed, self.stream_base, self._kind
-
-    def __init__(self, num_streams: int, k: int, seed: int, stream_base: int = 0, hash: str = "default",
-                 dtype=None, device=None):
-        import torch
-
-        N.load()
-        dtype = torch.int64 if dtype is None else dtype
-        if dtype not in (torch.int64, torch.int32):
-            raise N.IllegalArgumentException("keys must be int64/int32")
-        if hash == "precomputed":
-            self._kind = N.HASH_PRECOMPUTED
-        elif hash in _SEG_HASH:
-            self._kind = _SEG_HASH[hash]
-        else:
-            raise N.IllegalArgumentException(f"unknown hash {hash!r}")
-        dev = self._init_state(torch, num_streams, k, seed, stream_base, device)
-        self.keys = torch.empty((self.num_streams, self.k), dtype=dtype, device=dev)
-        self.hashes = torch.empty((self.num_streams, self.k), dtype=torch.int64, device=dev)
-        self.counts = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
 
     def update(self, keys, offsets, stream_ids=None, hashes=None, check_ids: bool = True):
         """Segment b = keys[offsets[b]:offsets[b+1]] into row stream_ids[b] (None: row b).
@@ -434,21 +467,7 @@ class SegmentedDistinct(_SegmentedState):
         check_ids=False keeps the call stream-ordered and leaves the contract to the caller.
         Rows that no segment names, or whose segment is empty, are not touched.  Returns self.
         """
-        import torch
-
-        L = N.load()
-        keys, offsets, hashes = _segd_inputs(torch, keys, offsets, hashes, state=self)
-        seg = self._segments(torch, offsets, check_ids, stream_ids)
-        if seg is None:
-            return self
-        B, stream_ids = seg
-        N.check(L.rsv_distinct_segmented_update(
-            C.c_void_p(keys.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
-            C.c_void_p(offsets.data_ptr()), C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
-            B, self.num_streams, keys.element_size(), self.k, self._kind, self.seed, self.stream_base,
-            C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.hashes.data_ptr()), C.c_void_p(self.counts.data_ptr()),
-            _stream_ptr(torch, self.keys.device)))
-        return self
+        return self._update(keys, offsets, stream_ids, hashes, check_ids)
 
     def merge(self, part_keys, part_hashes=None, part_counts=None):
         """Row s becomes the bottom-k of (row s u row s of every part).
@@ -464,7 +483,7 @@ class SegmentedDistinct(_SegmentedState):
         return self._merge(torch, L.rsv_distinct_segmented_merge, SegmentedDistinct, (part_keys, part_hashes, part_counts))
 
 
-class SegmentedDistinctOrdered(_SegmentedState):
+class SegmentedDistinctOrdered(_DistinctKeysState):
     """S long-lived Sampler.distinct streams in the reference's order, advanced by one launch per batch.
 
     What SegmentedDistinct is for the set order, for order="ordered": exact for any hash, the tie bucket included.
@@ -479,26 +498,7 @@ class SegmentedDistinctOrdered(_SegmentedState):
     update(hashes=...).  There is no merge.  Everything runs on torch's current stream.
     """
 
-    _NAME, _TENSORS, _MAX_K = "SegmentedDistinctOrdered", ("keys", "hashes", "counts"), _SEG_DISTINCT_MAX_K
-
-    def __init__(self, num_streams: int, k: int, seed: int, stream_base: int = 0, hash: str = "default",
-                 dtype=None, device=None):
-        import torch
-
-        N.load()
-        dtype = torch.int64 if dtype is None else dtype
-        if dtype not in (torch.int64, torch.int32):
-            raise N.IllegalArgumentException("keys must be int64/int32")
-        if hash == "precomputed":
-            self._kind = N.HASH_PRECOMPUTED
-        elif hash in _SEG_HASH:
-            self._kind = _SEG_HASH[hash]
-        else:
-            raise N.IllegalArgumentException(f"unknown hash {hash!r}")
-        dev = self._init_state(torch, num_streams, k, seed, stream_base, device)
-        self.keys = torch.empty((self.num_streams, self.k), dtype=dtype, device=dev)
-        self.hashes = torch.empty((self.num_streams, self.k), dtype=torch.int64, device=dev)
-        self.counts = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
+    _NAME, _UPDATE = "SegmentedDistinctOrdered", "rsv_distinct_segmented_ordered_update"
 
     def update(self, keys, offsets, stream_ids=None, hashes=None, check_ids: bool = True):
         """Segment b = keys[offsets[b]:offsets[b+1]] into row stream_ids[b] (None: row b), in arrival order.
@@ -509,21 +509,7 @@ class SegmentedDistinctOrdered(_SegmentedState):
         Rows that no segment names, or whose segment is empty, are not touched, and a row in which
         nothing was admitted is not written.  Returns self.
         """
-        import torch
-
-        L = N.load()
-        keys, offsets, hashes = _segd_inputs(torch, keys, offsets, hashes, state=self)
-        seg = self._segments(torch, offsets, check_ids, stream_ids)
-        if seg is None:
-            return self
-        B, stream_ids = seg
-        N.check(L.rsv_distinct_segmented_ordered_update(
-            C.c_void_p(keys.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
-            C.c_void_p(offsets.data_ptr()), C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
-            B, self.num_streams, keys.element_size(), self.k, self._kind, self.seed, self.stream_base,
-            C.c_void_p(self.keys.data_ptr()), C.c_void_p(self.hashes.data_ptr()), C.c_void_p(self.counts.data_ptr()),
-            _stream_ptr(torch, self.keys.device)))
-        return self
+        return self._update(keys, offsets, stream_ids, hashes, check_ids)
 
     def result(self):
         """(keys (S, k), hashes (S, k), counts (S,)) in distinct_segmented_ordered's layout: every row ascending
@@ -549,7 +535,7 @@ class SegmentedDistinctOrdered(_SegmentedState):
             "reference's heap over the whole stream; SegmentedDistinct.merge combines states in the set order")
 
 
-class SegmentedDistinctRows(_SegmentedState):
+class SegmentedDistinctRows(_DistinctRowsState):
     """SegmentedDistinct over fixed-width byte keys (java.util.UUID, case classes of primitives).
 
     The state is three device tensors in distinct_segmented_rows' layout: rows uint8 (S, k, width),
@@ -563,29 +549,11 @@ class SegmentedDistinctRows(_SegmentedState):
     Everything runs on torch's current stream.
     """
 
-    _NAME, _LONG, _MAX_K = "SegmentedDistinctRows", "SegmentedDistinct", _SEG_DISTINCT_MAX_K
+    _NAME, _LONG, _UPDATE = "SegmentedDistinctRows", "SegmentedDistinct", "rsv_distinct_segmented_rows_update"
     _TENSORS, _SAME = ("rows", "hashes", "counts"), "width, seed, stream_base and hash"
 
     def _identity(self):
         return self.num_streams, self.k, self.width, self.seed, self.stream_base, self._hash
-
-    def _check_width(self, width) -> None:
-        super()._check_width(width)
-        if self._hash == "default" and width != 16:
-            raise N.ReservoirError("hash='default' is UUID.hashCode: width 16 only")
-
-    def __init__(self, num_streams: int, k: int, width: int, seed: int, stream_base: int = 0, hash: str = "default",
-                 device=None):
-        import torch
-
-        N.load()
-        if hash not in ("default", "precomputed"):
-            raise N.IllegalArgumentException(f"unknown hash {hash!r}")
-        self._hash = hash
-        dev = self._init_state(torch, num_streams, k, seed, stream_base, device, width)
-        self.rows = torch.empty((self.num_streams, self.k, self.width), dtype=torch.uint8, device=dev)
-        self.hashes = torch.empty((self.num_streams, self.k), dtype=torch.int64, device=dev)
-        self.counts = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
 
     def update(self, rows, offsets, stream_ids=None, hashes=None, check_ids: bool = True):
         """Segment b = rows[offsets[b]:offsets[b+1]] into row stream_ids[b] (None: row b).
@@ -594,24 +562,7 @@ class SegmentedDistinctRows(_SegmentedState):
         not overlap the state.  stream_ids and check_ids as SegmentedDistinct.update.  Rows that no
         segment names, or whose segment is empty, are not touched.  Returns self.
         """
-        import torch
-
-        L = N.load()
-        if hashes is not None and self._hash != "precomputed":
-            raise N.IllegalArgumentException("hashes= needs hash='precomputed'")
-        rows, offsets, hashes = _segd_rows_inputs(torch, rows, offsets, self._hash, hashes)
-        self._check_same_device(rows, offsets)
-        seg = self._segments(torch, offsets, check_ids, stream_ids)
-        if seg is None:
-            return self
-        B, stream_ids = seg
-        N.check(L.rsv_distinct_segmented_rows_update(
-            C.c_void_p(rows.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
-            C.c_void_p(offsets.data_ptr()), C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
-            B, self.num_streams, self.width, self.k, N.HASH_PRECOMPUTED if hashes is not None else N.HASH_DEFAULT,
-            self.seed, self.stream_base, C.c_void_p(self.rows.data_ptr()), C.c_void_p(self.hashes.data_ptr()),
-            C.c_void_p(self.counts.data_ptr()), _stream_ptr(torch, self.rows.device)))
-        return self
+        return self._update(rows, offsets, stream_ids, hashes, check_ids)
 
     def merge(self, part_rows, part_hashes=None, part_counts=None):
         """Row s becomes the bottom-k of (row s u row s of every part).
@@ -628,7 +579,7 @@ class SegmentedDistinctRows(_SegmentedState):
                            (part_rows, part_hashes, part_counts))
 
 
-class SegmentedDistinctRowsOrdered(_SegmentedState):
+class SegmentedDistinctRowsOrdered(_DistinctRowsState):
     """SegmentedDistinctOrdered over fixed-width byte keys (java.util.UUID, case classes of primitives).
 
     What SegmentedDistinctRows is for the set order, for order="ordered": exact for any hash, UUID.hashCode's 32
@@ -646,27 +597,8 @@ class SegmentedDistinctRowsOrdered(_SegmentedState):
     merge.  Everything runs on torch's current stream.
     """
 
-    _NAME, _LONG, _MAX_K = "SegmentedDistinctRowsOrdered", "SegmentedDistinctOrdered", _SEG_DISTINCT_MAX_K
-    _TENSORS = ("rows", "hashes", "slots", "counts")
-
-    def _check_width(self, width) -> None:
-        super()._check_width(width)
-        if self._hash == "default" and width != 16:
-            raise N.ReservoirError("hash='default' is UUID.hashCode: width 16 only")
-
-    def __init__(self, num_streams: int, k: int, width: int, seed: int, stream_base: int = 0, hash: str = "default",
-                 device=None):
-        import torch
-
-        N.load()
-        if hash not in ("default", "precomputed"):
-            raise N.IllegalArgumentException(f"unknown hash {hash!r}")
-        self._hash = hash
-        dev = self._init_state(torch, num_streams, k, seed, stream_base, device, width)
-        self.rows = torch.empty((self.num_streams, self.k, self.width), dtype=torch.uint8, device=dev)
-        self.hashes = torch.empty((self.num_streams, self.k), dtype=torch.int64, device=dev)
-        self.slots = torch.empty((self.num_streams, self.k), dtype=torch.int32, device=dev)
-        self.counts = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
+    _NAME, _LONG = "SegmentedDistinctRowsOrdered", "SegmentedDistinctOrdered"
+    _TENSORS, _UPDATE = ("rows", "hashes", "slots", "counts"), "rsv_distinct_segmented_rows_ordered_update"
 
     def update(self, rows, offsets, stream_ids=None, hashes=None, check_ids: bool = True):
         """Segment b = rows[offsets[b]:offsets[b+1]] into row stream_ids[b] (None: row b), in arrival order.
@@ -676,24 +608,7 @@ class SegmentedDistinctRowsOrdered(_SegmentedState):
         segment names, or whose segment is empty, are not touched, and a row in which nothing was admitted
         is not written.  Returns self.
         """
-        import torch
-
-        L = N.load()
-        if hashes is not None and self._hash != "precomputed":
-            raise N.IllegalArgumentException("hashes= needs hash='precomputed'")
-        rows, offsets, hashes = _segd_rows_inputs(torch, rows, offsets, self._hash, hashes)
-        self._check_same_device(rows, offsets)
-        seg = self._segments(torch, offsets, check_ids, stream_ids)
-        if seg is None:
-            return self
-        B, stream_ids = seg
-        N.check(L.rsv_distinct_segmented_rows_ordered_update(
-            C.c_void_p(rows.data_ptr()), C.c_void_p(hashes.data_ptr()) if hashes is not None else None,
-            C.c_void_p(offsets.data_ptr()), C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
-            B, self.num_streams, self.width, self.k, N.HASH_PRECOMPUTED if hashes is not None else N.HASH_DEFAULT,
-            self.seed, self.stream_base, C.c_void_p(self.rows.data_ptr()), C.c_void_p(self.hashes.data_ptr()),
-            C.c_void_p(self.slots.data_ptr()), C.c_void_p(self.counts.data_ptr()), _stream_ptr(torch, self.rows.device)))
-        return self
+        return self._update(rows, offsets, stream_ids, hashes, check_ids)
 
     def result(self):
         """(rows uint8 (S, k, width), hashes (S, k), counts (S,)) in distinct_segmented_rows_ordered's layout: every

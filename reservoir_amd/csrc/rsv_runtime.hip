@@ -1753,41 +1753,114 @@ rsv_status rsv_sample_segmented_rows_merge(const void* part_rows_dev, const int6
     return RSV_OK;
 }
 
-// k and key_width of the four K5 entry points over 4- and 8-byte keys (fn: the entry point's name, for the messages)
-static rsv_status check_segdistinct_shape(const char* fn, int32_t k, int32_t key_width) {
+// ---- K5: the ten rsv_distinct_segmented* entry points ----
+// What an entry point tells its checker about itself, and what the checker tells it (hk, st).  There are three
+// checkers, one per kind of call (stateless, update, merge); each holds that kind's checks once, in the one order they
+// fire in.
+struct SegDistinctCall {
+    const char* fn;                 // the entry point's name, for the messages
+    const char* long_fn = nullptr;  // over byte keys: its counterpart for 4- and 8-byte keys; NULL: it is that one
+    const char* needs = nullptr;    // the one more pointer it requires, as its message names it; NULL: none
+    const void* needed = nullptr;   // that pointer
+    int hk = RSV_HASH_PRECOMPUTED;  // the hash kind, resolved (a merge takes its hashes as stored)
+    rsv_status st = RSV_OK;         // what the call returns when its checker says it is done
+    bool rows() const { return long_fn != nullptr; }
+};
+
+static rsv_status check_segdistinct_shape(const SegDistinctCall& c, int32_t k, int32_t key_width) {
     if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
     if (k > (int32_t)kSegDistinctMaxK)
-        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " holds k <= " + std::to_string(kSegDistinctMaxK) +
+        return fail(RSV_E_UNSUPPORTED, std::string(c.fn) + " holds k <= " + std::to_string(kSegDistinctMaxK) +
                                            " per stream; use separate handles beyond");
-    if (key_width > 8 && key_width <= 256 && key_width % 8 == 0)
-        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " takes 4- and 8-byte keys, not byte keys");
-    if (key_width != 4 && key_width != 8) return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be 4 or 8");
+    if (!c.rows()) {
+        if (key_width > 8 && key_width <= 256 && key_width % 8 == 0)
+            return fail(RSV_E_UNSUPPORTED, std::string(c.fn) + " takes 4- and 8-byte keys, not byte keys");
+        if (key_width != 4 && key_width != 8) return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be 4 or 8");
+        return RSV_OK;
+    }
+    if (key_width == 4 || key_width == 8)
+        return fail(RSV_E_UNSUPPORTED, std::string(c.fn) + " takes byte keys; " + c.long_fn + " takes 4- and 8-byte keys");
+    if (key_width < 16 || key_width > 256 || key_width % 8 != 0)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be a multiple of 8 in 16..256");
     return RSV_OK;
 }
 
-// the hash kind of the two K5 entry points that hash: its range, and RSV_HASH_DEFAULT resolved by key width
-static rsv_status resolve_segdistinct_hash(int32_t hash_kind, int32_t key_width, int& hk) {
+// the hash kind of the entry points that hash: its range; RSV_HASH_DEFAULT resolved by key width for 4- and 8-byte
+// keys; over byte keys PRECOMPUTED, or DEFAULT (UUID.hashCode) at key_width 16
+static rsv_status resolve_segdistinct_hash(SegDistinctCall& c, int32_t hash_kind, int32_t key_width) {
     if (hash_kind < RSV_HASH_DEFAULT || hash_kind > RSV_HASH_PRECOMPUTED)
         return fail(RSV_E_ILLEGAL_ARGUMENT, "unknown hash kind");
-    hk = hash_kind != RSV_HASH_DEFAULT ? hash_kind : key_width == 4 ? RSV_HASH_JAVA_INT : RSV_HASH_JAVA_LONG;
+    c.hk = hash_kind;
+    if (!c.rows()) {
+        if (hash_kind == RSV_HASH_DEFAULT) c.hk = key_width == 4 ? RSV_HASH_JAVA_INT : RSV_HASH_JAVA_LONG;
+        return RSV_OK;
+    }
+    if (hash_kind != RSV_HASH_DEFAULT && hash_kind != RSV_HASH_PRECOMPUTED)
+        return fail(RSV_E_UNSUPPORTED, "byte keys take RSV_HASH_PRECOMPUTED, or RSV_HASH_DEFAULT (UUID.hashCode) at key_width 16");
+    if (hash_kind == RSV_HASH_DEFAULT && key_width != 16)
+        return fail(RSV_E_UNSUPPORTED, "RSV_HASH_DEFAULT is UUID.hashCode: key_width 16 only");
     return RSV_OK;
+}
+
+// the pointers, behind the counts: the buffers every call of the kind needs (present: none of them is NULL; the keys
+// or rows of a stateless or update call are not among them: a launch whose streams are all empty has none), the one
+// more the entry point names, hashes_dev under RSV_HASH_PRECOMPUTED (otherwise the launch gets NULL for it), and over
+// byte keys the alignment of the two row buffers, last
+static rsv_status check_segdistinct_buffers(const SegDistinctCall& c, bool present, const int64_t*& hashes_dev,
+                                            const void* rows_in, const void* rows_out, const char* unaligned) {
+    if (!present) return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (c.needs && !c.needed) return fail(RSV_E_NULL_POINTER, std::string(c.fn) + " needs " + c.needs);
+    if (c.hk != RSV_HASH_PRECOMPUTED) hashes_dev = nullptr;
+    else if (!hashes_dev) return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
+    if (c.rows() && (((uintptr_t)rows_in | (uintptr_t)rows_out) & 7)) return fail(RSV_E_ILLEGAL_ARGUMENT, unaligned);
+    return RSV_OK;
+}
+
+// The three checkers.  true: the call returns c.st -- an error, or RSV_OK because there is nothing to do.
+static bool segdistinct_stateless_done(SegDistinctCall& c, int32_t k, int32_t key_width, int32_t hash_kind,
+                                       int64_t num_streams, bool present, const int64_t*& hashes_dev, const void* in_dev,
+                                       const void* out_dev) {
+    if ((c.st = check_segdistinct_shape(c, k, key_width)) || (c.st = resolve_segdistinct_hash(c, hash_kind, key_width)))
+        return true;
+    if (num_streams < 0) c.st = fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
+    if (c.st || num_streams == 0) return true;
+    c.st = check_segdistinct_buffers(c, present, hashes_dev, in_dev, out_dev, "rows_dev and out_rows_dev must be 8-byte aligned");
+    return c.st != RSV_OK;
+}
+
+static bool segdistinct_update_done(SegDistinctCall& c, int32_t k, int32_t key_width, int32_t hash_kind,
+                                    int64_t num_segments, int64_t num_states, const void* ids_dev, bool present,
+                                    const int64_t*& hashes_dev, const void* in_dev, const void* state_dev) {
+    if ((c.st = check_segdistinct_shape(c, k, key_width)) || (c.st = resolve_segdistinct_hash(c, hash_kind, key_width)))
+        return true;
+    if (num_segments < 0 || num_states < 0) c.st = fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
+    else if (!ids_dev && num_segments > num_states)
+        c.st = fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
+    if (c.st || num_segments == 0 || num_states == 0) return true;
+    c.st = check_segdistinct_buffers(c, present, hashes_dev, in_dev, state_dev, "rows_dev and state_rows_dev must be 8-byte aligned");
+    return c.st != RSV_OK;
+}
+
+static bool segdistinct_merge_done(SegDistinctCall& c, int32_t k, int32_t key_width, int32_t parts, int64_t num_states,
+                                   bool present, const int64_t* part_hashes_dev, const void* part_dev, const void* state_dev) {
+    if ((c.st = check_segdistinct_shape(c, k, key_width))) return true;
+    if (parts < 0 || num_states < 0) c.st = fail(RSV_E_ILLEGAL_ARGUMENT, "negative part or state count");
+    if (c.st || parts == 0 || num_states == 0) return true;
+    c.st = check_segdistinct_buffers(c, present, part_hashes_dev, part_dev, state_dev,
+                                     "part_rows_dev and state_rows_dev must be 8-byte aligned");
+    return c.st != RSV_OK;
 }
 
 rsv_status rsv_distinct_segmented(const void* keys_dev, const int64_t* hashes_dev, const int64_t* offsets_dev,
                                   int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind, uint64_t seed,
                                   uint64_t stream_base, void* out_keys_dev, int64_t* out_hashes_dev,
                                   int64_t* counts_dev, void* hip_stream) {
-    int hk;
-    if (rsv_status st = check_segdistinct_shape("rsv_distinct_segmented", k, key_width)) return st;
-    if (rsv_status st = resolve_segdistinct_hash(hash_kind, key_width, hk)) return st;
-    if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
-    if (num_streams == 0) return RSV_OK;
-    // keys_dev is not checked: a launch whose streams are all empty has no keys
-    if (!offsets_dev || !out_keys_dev || !counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
-    if (hk == RSV_HASH_PRECOMPUTED && !hashes_dev) return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
-    RSV_HIP_TRY(launch_segdistinct(keys_dev, key_width, hk == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr, offsets_dev,
-                                   num_streams, (uint32_t)k, hk, seed + stream_base, out_keys_dev, out_hashes_dev,
-                                   counts_dev, (hipStream_t)hip_stream));
+    SegDistinctCall c{"rsv_distinct_segmented"};
+    if (segdistinct_stateless_done(c, k, key_width, hash_kind, num_streams, offsets_dev && out_keys_dev && counts_dev,
+                                   hashes_dev, keys_dev, out_keys_dev))
+        return c.st;
+    RSV_HIP_TRY(launch_segdistinct(keys_dev, key_width, hashes_dev, offsets_dev, num_streams, (uint32_t)k, c.hk,
+                                   seed + stream_base, out_keys_dev, out_hashes_dev, counts_dev, (hipStream_t)hip_stream));
     return RSV_OK;
 }
 
@@ -1796,43 +1869,13 @@ rsv_status rsv_distinct_segmented_ordered(const void* keys_dev, const int64_t* h
                                           uint64_t seed, uint64_t stream_base, void* out_keys_dev,
                                           int64_t* out_hashes_dev, int64_t* counts_dev, int32_t* tied_dev,
                                           void* hip_stream) {
-    // rsv_distinct_segmented's checks in its order; tied_dev with the other output buffers
-    int hk;
-    if (rsv_status st = check_segdistinct_shape("rsv_distinct_segmented_ordered", k, key_width)) return st;
-    if (rsv_status st = resolve_segdistinct_hash(hash_kind, key_width, hk)) return st;
-    if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
-    if (num_streams == 0) return RSV_OK;
-    if (!offsets_dev || !out_keys_dev || !counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
-    if (!tied_dev) return fail(RSV_E_NULL_POINTER, "rsv_distinct_segmented_ordered needs tied_dev");
-    if (hk == RSV_HASH_PRECOMPUTED && !hashes_dev) return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
-    RSV_HIP_TRY(launch_segdistinct_ordered(keys_dev, key_width, hk == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr,
-                                           offsets_dev, num_streams, (uint32_t)k, hk, seed + stream_base, out_keys_dev,
-                                           out_hashes_dev, counts_dev, tied_dev, (hipStream_t)hip_stream));
-    return RSV_OK;
-}
-
-// k and key_width of the three K5 entry points over byte keys (fn: the entry point's name, long_fn: its
-// counterpart for 4- and 8-byte keys, for the messages)
-static rsv_status check_segrows_shape(const char* fn, const char* long_fn, int32_t k, int32_t key_width) {
-    if (k <= 0 || k > kMaxSize) return fail(RSV_E_ILLEGAL_ARGUMENT, "k out of range");
-    if (k > (int32_t)kSegDistinctMaxK)
-        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " holds k <= " + std::to_string(kSegDistinctMaxK) +
-                                           " per stream; use separate handles beyond");
-    if (key_width == 4 || key_width == 8)
-        return fail(RSV_E_UNSUPPORTED, std::string(fn) + " takes byte keys; " + long_fn + " takes 4- and 8-byte keys");
-    if (key_width < 16 || key_width > 256 || key_width % 8 != 0)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "key_width must be a multiple of 8 in 16..256");
-    return RSV_OK;
-}
-
-// the hash kind of the two that hash: PRECOMPUTED, or DEFAULT (UUID.hashCode) at key_width 16
-static rsv_status check_segrows_hash(int32_t hash_kind, int32_t key_width) {
-    if (hash_kind < RSV_HASH_DEFAULT || hash_kind > RSV_HASH_PRECOMPUTED)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "unknown hash kind");
-    if (hash_kind != RSV_HASH_DEFAULT && hash_kind != RSV_HASH_PRECOMPUTED)
-        return fail(RSV_E_UNSUPPORTED, "byte keys take RSV_HASH_PRECOMPUTED, or RSV_HASH_DEFAULT (UUID.hashCode) at key_width 16");
-    if (hash_kind == RSV_HASH_DEFAULT && key_width != 16)
-        return fail(RSV_E_UNSUPPORTED, "RSV_HASH_DEFAULT is UUID.hashCode: key_width 16 only");
+    SegDistinctCall c{"rsv_distinct_segmented_ordered", nullptr, "tied_dev", tied_dev};
+    if (segdistinct_stateless_done(c, k, key_width, hash_kind, num_streams, offsets_dev && out_keys_dev && counts_dev,
+                                   hashes_dev, keys_dev, out_keys_dev))
+        return c.st;
+    RSV_HIP_TRY(launch_segdistinct_ordered(keys_dev, key_width, hashes_dev, offsets_dev, num_streams, (uint32_t)k, c.hk,
+                                           seed + stream_base, out_keys_dev, out_hashes_dev, counts_dev, tied_dev,
+                                           (hipStream_t)hip_stream));
     return RSV_OK;
 }
 
@@ -1840,20 +1883,13 @@ rsv_status rsv_distinct_segmented_rows(const void* rows_dev, const int64_t* hash
                                        int64_t num_streams, int32_t key_width, int32_t k, int32_t hash_kind,
                                        uint64_t seed, uint64_t stream_base, void* out_rows_dev,
                                        int64_t* out_hashes_dev, int64_t* counts_dev, void* hip_stream) {
-    // the checks in rsv_distinct_segmented's order: k, key_width, hash_kind, num_streams, pointers
-    if (rsv_status st = check_segrows_shape("rsv_distinct_segmented_rows", "rsv_distinct_segmented", k, key_width)) return st;
-    if (rsv_status st = check_segrows_hash(hash_kind, key_width)) return st;
-    if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
-    if (num_streams == 0) return RSV_OK;
-    // rows_dev is not checked: a launch whose streams are all empty has no rows
-    if (!offsets_dev || !out_rows_dev || !counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
-    if (hash_kind == RSV_HASH_PRECOMPUTED && !hashes_dev)
-        return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
-    if (((uintptr_t)rows_dev | (uintptr_t)out_rows_dev) & 7)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "rows_dev and out_rows_dev must be 8-byte aligned");
-    RSV_HIP_TRY(launch_segdistinct_rows(rows_dev, key_width, hash_kind == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr,
-                                        offsets_dev, num_streams, (uint32_t)k, seed + stream_base, out_rows_dev,
-                                        out_hashes_dev, counts_dev, (hipStream_t)hip_stream));
+    SegDistinctCall c{"rsv_distinct_segmented_rows", "rsv_distinct_segmented"};
+    if (segdistinct_stateless_done(c, k, key_width, hash_kind, num_streams, offsets_dev && out_rows_dev && counts_dev,
+                                   hashes_dev, rows_dev, out_rows_dev))
+        return c.st;
+    RSV_HIP_TRY(launch_segdistinct_rows(rows_dev, key_width, hashes_dev, offsets_dev, num_streams, (uint32_t)k,
+                                        seed + stream_base, out_rows_dev, out_hashes_dev, counts_dev,
+                                        (hipStream_t)hip_stream));
     return RSV_OK;
 }
 
@@ -1862,21 +1898,13 @@ rsv_status rsv_distinct_segmented_rows_ordered(const void* rows_dev, const int64
                                                uint64_t seed, uint64_t stream_base, void* out_rows_dev,
                                                int64_t* out_hashes_dev, int64_t* counts_dev, int32_t* tied_dev,
                                                void* hip_stream) {
-    // rsv_distinct_segmented_rows' checks in its order; tied_dev with the other output buffers
-    if (rsv_status st = check_segrows_shape("rsv_distinct_segmented_rows_ordered", "rsv_distinct_segmented_ordered", k, key_width))
-        return st;
-    if (rsv_status st = check_segrows_hash(hash_kind, key_width)) return st;
-    if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
-    if (num_streams == 0) return RSV_OK;
-    if (!offsets_dev || !out_rows_dev || !counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
-    if (!tied_dev) return fail(RSV_E_NULL_POINTER, "rsv_distinct_segmented_rows_ordered needs tied_dev");
-    if (hash_kind == RSV_HASH_PRECOMPUTED && !hashes_dev)
-        return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
-    if (((uintptr_t)rows_dev | (uintptr_t)out_rows_dev) & 7)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "rows_dev and out_rows_dev must be 8-byte aligned");
-    RSV_HIP_TRY(launch_segdistinct_rows_ordered(rows_dev, key_width, hash_kind == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr,
-                                                offsets_dev, num_streams, (uint32_t)k, seed + stream_base, out_rows_dev,
-                                                out_hashes_dev, counts_dev, tied_dev, (hipStream_t)hip_stream));
+    SegDistinctCall c{"rsv_distinct_segmented_rows_ordered", "rsv_distinct_segmented_ordered", "tied_dev", tied_dev};
+    if (segdistinct_stateless_done(c, k, key_width, hash_kind, num_streams, offsets_dev && out_rows_dev && counts_dev,
+                                   hashes_dev, rows_dev, out_rows_dev))
+        return c.st;
+    RSV_HIP_TRY(launch_segdistinct_rows_ordered(rows_dev, key_width, hashes_dev, offsets_dev, num_streams, (uint32_t)k,
+                                                seed + stream_base, out_rows_dev, out_hashes_dev, counts_dev, tied_dev,
+                                                (hipStream_t)hip_stream));
     return RSV_OK;
 }
 
@@ -1885,21 +1913,14 @@ rsv_status rsv_distinct_segmented_update(const void* keys_dev, const int64_t* ha
                                          int32_t key_width, int32_t k, int32_t hash_kind, uint64_t seed,
                                          uint64_t stream_base, void* state_keys_dev, int64_t* state_hashes_dev,
                                          int64_t* state_counts_dev, void* hip_stream) {
-    int hk;
-    if (rsv_status st = check_segdistinct_shape("rsv_distinct_segmented_update", k, key_width)) return st;
-    if (rsv_status st = resolve_segdistinct_hash(hash_kind, key_width, hk)) return st;
-    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
-    if (!stream_ids_dev && num_segments > num_states)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
-    if (num_segments == 0 || num_states == 0) return RSV_OK;
-    // keys_dev is not checked: a launch whose segments are all empty has no keys
-    if (!offsets_dev || !state_keys_dev || !state_hashes_dev || !state_counts_dev)
-        return fail(RSV_E_NULL_POINTER, "NULL buffer");
-    if (hk == RSV_HASH_PRECOMPUTED && !hashes_dev) return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
-    RSV_HIP_TRY(launch_segdistinct_update(keys_dev, key_width, hk == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr,
-                                          offsets_dev, stream_ids_dev, num_segments, num_states, (uint32_t)k, hk,
-                                          seed + stream_base, state_keys_dev, state_hashes_dev, state_counts_dev,
-                                          (hipStream_t)hip_stream));
+    SegDistinctCall c{"rsv_distinct_segmented_update"};
+    if (segdistinct_update_done(c, k, key_width, hash_kind, num_segments, num_states, stream_ids_dev,
+                                offsets_dev && state_keys_dev && state_hashes_dev && state_counts_dev, hashes_dev,
+                                keys_dev, state_keys_dev))
+        return c.st;
+    RSV_HIP_TRY(launch_segdistinct_update(keys_dev, key_width, hashes_dev, offsets_dev, stream_ids_dev, num_segments,
+                                          num_states, (uint32_t)k, c.hk, seed + stream_base, state_keys_dev,
+                                          state_hashes_dev, state_counts_dev, (hipStream_t)hip_stream));
     return RSV_OK;
 }
 
@@ -1909,23 +1930,16 @@ rsv_status rsv_distinct_segmented_ordered_update(const void* keys_dev, const int
                                                  int32_t k, int32_t hash_kind, uint64_t seed, uint64_t stream_base,
                                                  void* state_keys_dev, int64_t* state_hashes_dev,
                                                  int64_t* state_counts_dev, void* hip_stream) {
-    // rsv_distinct_segmented_update's checks in its order; state_hashes_dev by name, behind the other buffers
-    int hk;
-    if (rsv_status st = check_segdistinct_shape("rsv_distinct_segmented_ordered_update", k, key_width)) return st;
-    if (rsv_status st = resolve_segdistinct_hash(hash_kind, key_width, hk)) return st;
-    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
-    if (!stream_ids_dev && num_segments > num_states)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
-    if (num_segments == 0 || num_states == 0) return RSV_OK;
-    // keys_dev is not checked: a launch whose segments are all empty has no keys
-    if (!offsets_dev || !state_keys_dev || !state_counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
-    if (!state_hashes_dev)
-        return fail(RSV_E_NULL_POINTER, "rsv_distinct_segmented_ordered_update needs state_hashes_dev: the heap is ordered by them");
-    if (hk == RSV_HASH_PRECOMPUTED && !hashes_dev) return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
-    RSV_HIP_TRY(launch_segdistinct_ordered_update(keys_dev, key_width, hk == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr,
-                                                  offsets_dev, stream_ids_dev, num_segments, num_states, (uint32_t)k, hk,
-                                                  seed + stream_base, state_keys_dev, state_hashes_dev,
-                                                  state_counts_dev, (hipStream_t)hip_stream));
+    // state_hashes_dev by name, behind the other buffers
+    SegDistinctCall c{"rsv_distinct_segmented_ordered_update", nullptr,
+                            "state_hashes_dev: the heap is ordered by them", state_hashes_dev};
+    if (segdistinct_update_done(c, k, key_width, hash_kind, num_segments, num_states, stream_ids_dev,
+                                offsets_dev && state_keys_dev && state_counts_dev, hashes_dev, keys_dev, state_keys_dev))
+        return c.st;
+    RSV_HIP_TRY(launch_segdistinct_ordered_update(keys_dev, key_width, hashes_dev, offsets_dev, stream_ids_dev,
+                                                  num_segments, num_states, (uint32_t)k, c.hk, seed + stream_base,
+                                                  state_keys_dev, state_hashes_dev, state_counts_dev,
+                                                  (hipStream_t)hip_stream));
     return RSV_OK;
 }
 
@@ -1933,12 +1947,12 @@ rsv_status rsv_distinct_segmented_merge(const void* part_keys_dev, const int64_t
                                         const int64_t* part_counts_dev, int32_t parts, int64_t num_states,
                                         int32_t key_width, int32_t k, void* state_keys_dev, int64_t* state_hashes_dev,
                                         int64_t* state_counts_dev, void* hip_stream) {
-    if (rsv_status st = check_segdistinct_shape("rsv_distinct_segmented_merge", k, key_width)) return st;
-    if (parts < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative part or state count");
-    if (parts == 0 || num_states == 0) return RSV_OK;
-    if (!part_keys_dev || !part_hashes_dev || !part_counts_dev || !state_keys_dev || !state_hashes_dev ||
-        !state_counts_dev)
-        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    SegDistinctCall c{"rsv_distinct_segmented_merge"};
+    if (segdistinct_merge_done(c, k, key_width, parts, num_states,
+                               part_keys_dev && part_hashes_dev && part_counts_dev && state_keys_dev &&
+                                   state_hashes_dev && state_counts_dev,
+                               part_hashes_dev, part_keys_dev, state_keys_dev))
+        return c.st;
     RSV_HIP_TRY(launch_segdistinct_merge(part_keys_dev, key_width, part_hashes_dev, part_counts_dev, parts, num_states,
                                          (uint32_t)k, state_keys_dev, state_hashes_dev, state_counts_dev,
                                          (hipStream_t)hip_stream));
@@ -1951,25 +1965,14 @@ rsv_status rsv_distinct_segmented_rows_update(const void* rows_dev, const int64_
                                               int32_t hash_kind, uint64_t seed, uint64_t stream_base,
                                               void* state_rows_dev, int64_t* state_hashes_dev,
                                               int64_t* state_counts_dev, void* hip_stream) {
-    if (rsv_status st = check_segrows_shape("rsv_distinct_segmented_rows_update", "rsv_distinct_segmented_update", k, key_width))
-        return st;
-    if (rsv_status st = check_segrows_hash(hash_kind, key_width)) return st;
-    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
-    if (!stream_ids_dev && num_segments > num_states)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
-    if (num_segments == 0 || num_states == 0) return RSV_OK;
-    // rows_dev is not checked: a launch whose segments are all empty has no rows
-    if (!offsets_dev || !state_rows_dev || !state_hashes_dev || !state_counts_dev)
-        return fail(RSV_E_NULL_POINTER, "NULL buffer");
-    if (hash_kind == RSV_HASH_PRECOMPUTED && !hashes_dev)
-        return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
-    if (((uintptr_t)rows_dev | (uintptr_t)state_rows_dev) & 7)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "rows_dev and state_rows_dev must be 8-byte aligned");
-    RSV_HIP_TRY(launch_segdistinct_rows_update(rows_dev, key_width,
-                                               hash_kind == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr, offsets_dev,
-                                               stream_ids_dev, num_segments, num_states, (uint32_t)k,
-                                               seed + stream_base, state_rows_dev, state_hashes_dev, state_counts_dev,
-                                               (hipStream_t)hip_stream));
+    SegDistinctCall c{"rsv_distinct_segmented_rows_update", "rsv_distinct_segmented_update"};
+    if (segdistinct_update_done(c, k, key_width, hash_kind, num_segments, num_states, stream_ids_dev,
+                                offsets_dev && state_rows_dev && state_hashes_dev && state_counts_dev, hashes_dev,
+                                rows_dev, state_rows_dev))
+        return c.st;
+    RSV_HIP_TRY(launch_segdistinct_rows_update(rows_dev, key_width, hashes_dev, offsets_dev, stream_ids_dev, num_segments,
+                                               num_states, (uint32_t)k, seed + stream_base, state_rows_dev,
+                                               state_hashes_dev, state_counts_dev, (hipStream_t)hip_stream));
     return RSV_OK;
 }
 
@@ -1980,29 +1983,17 @@ rsv_status rsv_distinct_segmented_rows_ordered_update(const void* rows_dev, cons
                                                       void* state_rows_dev, int64_t* state_hashes_dev,
                                                       int32_t* state_slots_dev, int64_t* state_counts_dev,
                                                       void* hip_stream) {
-    // rsv_distinct_segmented_rows_update's checks in its order; state_slots_dev by name, behind the other buffers
-    if (rsv_status st = check_segrows_shape("rsv_distinct_segmented_rows_ordered_update", "rsv_distinct_segmented_ordered_update",
-                                            k, key_width))
-        return st;
-    if (rsv_status st = check_segrows_hash(hash_kind, key_width)) return st;
-    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
-    if (!stream_ids_dev && num_segments > num_states)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
-    if (num_segments == 0 || num_states == 0) return RSV_OK;
-    // rows_dev is not checked: a launch whose segments are all empty has no rows
-    if (!offsets_dev || !state_rows_dev || !state_hashes_dev || !state_counts_dev)
-        return fail(RSV_E_NULL_POINTER, "NULL buffer");
-    if (!state_slots_dev)
-        return fail(RSV_E_NULL_POINTER,
-                    "rsv_distinct_segmented_rows_ordered_update needs state_slots_dev: the heap's entries find their rows by them");
-    if (hash_kind == RSV_HASH_PRECOMPUTED && !hashes_dev)
-        return fail(RSV_E_NULL_POINTER, "RSV_HASH_PRECOMPUTED needs hashes_dev");
-    if (((uintptr_t)rows_dev | (uintptr_t)state_rows_dev) & 7)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "rows_dev and state_rows_dev must be 8-byte aligned");
-    RSV_HIP_TRY(launch_segdistinct_rows_ordered_update(
-        rows_dev, key_width, hash_kind == RSV_HASH_PRECOMPUTED ? hashes_dev : nullptr, offsets_dev, stream_ids_dev,
-        num_segments, num_states, (uint32_t)k, seed + stream_base, state_rows_dev, state_hashes_dev, state_slots_dev,
-        state_counts_dev, (hipStream_t)hip_stream));
+    // state_slots_dev by name, behind the other buffers
+    SegDistinctCall c{"rsv_distinct_segmented_rows_ordered_update", "rsv_distinct_segmented_ordered_update",
+                            "state_slots_dev: the heap's entries find their rows by them", state_slots_dev};
+    if (segdistinct_update_done(c, k, key_width, hash_kind, num_segments, num_states, stream_ids_dev,
+                                offsets_dev && state_rows_dev && state_hashes_dev && state_counts_dev, hashes_dev,
+                                rows_dev, state_rows_dev))
+        return c.st;
+    RSV_HIP_TRY(launch_segdistinct_rows_ordered_update(rows_dev, key_width, hashes_dev, offsets_dev, stream_ids_dev,
+                                                       num_segments, num_states, (uint32_t)k, seed + stream_base,
+                                                       state_rows_dev, state_hashes_dev, state_slots_dev,
+                                                       state_counts_dev, (hipStream_t)hip_stream));
     return RSV_OK;
 }
 
@@ -2010,15 +2001,12 @@ rsv_status rsv_distinct_segmented_rows_merge(const void* part_rows_dev, const in
                                              const int64_t* part_counts_dev, int32_t parts, int64_t num_states,
                                              int32_t key_width, int32_t k, void* state_rows_dev,
                                              int64_t* state_hashes_dev, int64_t* state_counts_dev, void* hip_stream) {
-    if (rsv_status st = check_segrows_shape("rsv_distinct_segmented_rows_merge", "rsv_distinct_segmented_merge", k, key_width))
-        return st;
-    if (parts < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative part or state count");
-    if (parts == 0 || num_states == 0) return RSV_OK;
-    if (!part_rows_dev || !part_hashes_dev || !part_counts_dev || !state_rows_dev || !state_hashes_dev ||
-        !state_counts_dev)
-        return fail(RSV_E_NULL_POINTER, "NULL buffer");
-    if (((uintptr_t)part_rows_dev | (uintptr_t)state_rows_dev) & 7)
-        return fail(RSV_E_ILLEGAL_ARGUMENT, "part_rows_dev and state_rows_dev must be 8-byte aligned");
+    SegDistinctCall c{"rsv_distinct_segmented_rows_merge", "rsv_distinct_segmented_merge"};
+    if (segdistinct_merge_done(c, k, key_width, parts, num_states,
+                               part_rows_dev && part_hashes_dev && part_counts_dev && state_rows_dev &&
+                                   state_hashes_dev && state_counts_dev,
+                               part_hashes_dev, part_rows_dev, state_rows_dev))
+        return c.st;
     RSV_HIP_TRY(launch_segdistinct_rows_merge(part_rows_dev, key_width, part_hashes_dev, part_counts_dev, parts,
                                               num_states, (uint32_t)k, state_rows_dev, state_hashes_dev,
                                               state_counts_dev, (hipStream_t)hip_stream));
