@@ -65,6 +65,83 @@ __global__ __launch_bounds__(kBlock) void k1_last_writer(DrawKey dk, uint32_t k,
         k1_body_q<kK1Win, false>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], sch.W1, sch.A, sch.B);
 }
 
+// ---- the slot rule ----------------------------------------------------------------------------
+// What the batch [base, base + n) does to slot j, given the batch's last writer wi = win[j] (0: none).
+// The first case that holds:
+//   winner  wi != 0: the last eviction into slot j in this batch (Sampler.scala:243-246) -- the slot
+//           takes element wi, and the caller clears win[j]
+//   fill    base <= j < base + n: the fill phase (Sampler.scala:253-255) -- the slot takes element j
+//   empty   fresh (the first batch of a handle whose slots were never initialised): idx -1, key zero
+//   keep    the slot keeps what it holds
+// The rule calls exactly one of
+//   take(off, idx, winner)  winner, fill: the element at offset `off` of the batch, the slot's new slot_idx
+//   empty(idx)              the empty slot's slot_idx
+//   keep()
+// so a form's code for a case stands in the branch of that case, as when each kernel spelled the
+// cases out.  Two things kept k1_resolve_publish<long> at its 51 VGPRs: the rule calls back instead of
+// returning the case as a value (53), and callbacks that only store capture by value -- behind a
+// by-reference closure the pointers lose __restrict__, which keys and indices of one type need (57).
+// Every resolve form below goes through this function; none spells the cases out again.
+template <typename Take, typename Empty, typename Keep>
+__device__ __forceinline__ void slot_rule(int64_t j, unsigned long long wi, int64_t base, int64_t n, int fresh,
+                                          Take&& take, Empty&& empty, Keep&& keep) {
+    if (wi) take((int64_t)wi - base, (int64_t)wi, true);
+    else if (j >= base && j < base + n) take(j - base, j, false);
+    else if (fresh) empty((int64_t)-1);
+    else keep();
+}
+
+// The registers-first resolve + publication by one 256-thread workgroup, R slots per lane (k <= 256 R):
+// all R winner loads are issued before any key load, and every load before any store; then the first
+// m final slot keys go to coherent host memory `dst` and `gen` to the host flag.  kAgentWin: win[] was
+// written by other workgroups of this launch (k1_resolve_publish), so it is read with agent-scope
+// atomic loads -- a plain load there may be served from a stale line.
+template <typename KeyT, int R, bool kAgentWin>
+__device__ __forceinline__ void resolve_registers_first(const KeyT* __restrict__ keys, int64_t base, int64_t n,
+                                                        uint32_t k, unsigned long long* __restrict__ win,
+                                                        KeyT* __restrict__ slot_key, int64_t* __restrict__ slot_idx,
+                                                        int fresh, int64_t m, KeyT* dst, uint32_t* flag, uint32_t gen) {
+    unsigned long long wi[R];
+    KeyT v[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const uint32_t j = threadIdx.x + r * kBlock;
+        if (j >= k) wi[r] = 0ull;
+        else if (kAgentWin) wi[r] = __hip_atomic_load(&win[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else wi[r] = win[j];
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int64_t j = threadIdx.x + r * kBlock;
+        if (j >= k) continue;
+        KeyT x;
+        slot_rule(
+            j, wi[r], base, n, fresh, [&](int64_t off, int64_t, bool) { x = keys[off]; }, [&](int64_t) { x = 0; },
+            [&] { x = slot_key[j]; });
+        v[r] = x;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int64_t j = threadIdx.x + r * kBlock;
+        if (j >= k) continue;
+        const KeyT x = v[r];
+        slot_rule(
+            j, wi[r], base, n, fresh,
+            [=](int64_t, int64_t idx, bool winner) {
+                slot_key[j] = x;
+                slot_idx[j] = idx;
+                if (winner) win[j] = 0;
+            },
+            [=](int64_t idx) {
+                slot_key[j] = 0;
+                slot_idx[j] = idx;
+            },
+            [] {});
+        if (j < m) dst[j] = x;
+    }
+    publish_flag(flag, gen);
+}
+
 // K1 + resolve_publish in one dispatch (single-launch batches, k <= kK1FusedMaxK): every
 // workgroup takes a ticket after its winner atomics; the last one -- which then sees all of them --
 // runs the resolve over the k slots (all loads of a lane issued before any store) and publishes
@@ -107,105 +184,52 @@ __global__ __launch_bounds__(kBlock) void k1_resolve_publish(DrawKey dk, uint32_
     __syncthreads();
     if (!last) return;  // workgroup-uniform
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    constexpr int R = kK1FusedMaxK / kBlock;
-    unsigned long long wi[R];
-    KeyT v[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint32_t j = threadIdx.x + r * kBlock;
-        wi[r] = j < k ? __hip_atomic_load(&win[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int64_t j = threadIdx.x + r * kBlock;
-        if (j >= k) continue;
-        if (wi[r]) v[r] = keys[(int64_t)wi[r] - base];
-        else if (j >= base && j < base + n) v[r] = keys[j - base];
-        else if (fresh) v[r] = 0;
-        else v[r] = slot_key[j];
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int64_t j = threadIdx.x + r * kBlock;
-        if (j >= k) continue;
-        if (wi[r]) {
-            slot_key[j] = v[r];
-            slot_idx[j] = (int64_t)wi[r];
-            win[j] = 0;
-        } else if (j >= base && j < base + n) {
-            slot_key[j] = v[r];
-            slot_idx[j] = j;
-        } else if (fresh) {
-            slot_key[j] = 0;
-            slot_idx[j] = -1;
-        }
-        if (j < m) dst[j] = v[r];
-    }
-    publish_flag(flag, gen);
+    resolve_registers_first<KeyT, kK1FusedMaxK / kBlock, true>(keys, base, n, k, win, slot_key, slot_idx, fresh, m, dst,
+                                                               flag, gen);
 }
 
-// Per slot j: the batch's last writer (win[j], then cleared), else the fill of j < k from this
-// batch, else -- first batch of a handle whose slots were never initialised (`fresh`) -- empty.
-template <typename KeyT>
-__global__ __launch_bounds__(kBlock) void resolve_kernel(const KeyT* __restrict__ keys, int64_t base,
-                                                         int64_t n, uint32_t k,
-                                                         unsigned long long* __restrict__ win,
-                                                         KeyT* __restrict__ slot_key,
-                                                         int64_t* __restrict__ slot_idx, int fresh) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= k) return;
-    const unsigned long long wi = win[j];
-    if (wi) {  // last eviction into slot j in this batch (Sampler.scala:243-246)
-        slot_key[j] = keys[(int64_t)wi - base];
-        if (slot_idx) slot_idx[j] = (int64_t)wi;
-        win[j] = 0;
-    } else if ((int64_t)j >= base && (int64_t)j < base + n) {  // fill phase (Sampler.scala:253-255)
-        slot_key[j] = keys[j - base];
-        if (slot_idx) slot_idx[j] = j;
-    } else if (fresh) {
-        slot_key[j] = 0;
-        if (slot_idx) slot_idx[j] = -1;
+// The batch's resolve of 4- / 8-byte keys: the slot rule per slot j, the keys gathered from the batch.
+// kPublish: one workgroup (reservoirs of <= 8192 keys) that also writes the first m final slot keys
+// straight into coherent host memory and publishes `gen` in the host flag with a system-scope release
+// (as publish_kernel); else one slot per thread of a k-wide grid, with m / dst / flag / gen unused.
+// The two forms have different launch bounds, so the publication is a compile-time case: the
+// one-workgroup form is what bench.py's two-dispatch step runs.  slot_idx is null only for
+// rsv_replay_events (a caller's bare reservoir, never published).
+// j + stride stays below 2^32: k < 2^31, and no grid is wider than k rounded up to the block.
+template <typename KeyT, bool kPublish>
+__global__ __launch_bounds__(kPublish ? 1024 : kBlock) void resolve_kernel(const KeyT* __restrict__ keys, int64_t base,
+                                                                         int64_t n, uint32_t k,
+                                                                         unsigned long long* __restrict__ win,
+                                                                         KeyT* __restrict__ slot_key,
+                                                                         int64_t* __restrict__ slot_idx, int fresh,
+                                                                         int64_t m, KeyT* dst, uint32_t* flag,
+                                                                         uint32_t gen) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < k; j += stride) {
+        KeyT v = 0;
+        slot_rule(
+            j, win[j], base, n, fresh,
+            [&](int64_t off, int64_t idx, bool winner) {
+                slot_key[j] = v = keys[off];
+                if (kPublish || slot_idx) slot_idx[j] = idx;
+                if (winner) win[j] = 0;
+            },
+            [=](int64_t idx) {
+                slot_key[j] = 0;
+                if (kPublish || slot_idx) slot_idx[j] = idx;
+            },
+            [&] {
+                if (kPublish) v = slot_key[j];
+            });
+        if (kPublish && (int64_t)j < m) dst[j] = v;
     }
+    if (kPublish) publish_flag(flag, gen);
 }
 
-// resolve + publish in one dispatch (reservoirs of <= 8192 keys): one workgroup walks the k slots
-// as resolve_kernel does, writes the first m final slot keys straight into coherent host memory,
-// then publishes `gen` in the host flag with a system-scope release (as publish_kernel).
-template <typename KeyT>
-__global__ __launch_bounds__(1024) void resolve_publish_kernel(const KeyT* __restrict__ keys, int64_t base,
-                                                               int64_t n, uint32_t k,
-                                                               unsigned long long* __restrict__ win,
-                                                               KeyT* __restrict__ slot_key,
-                                                               int64_t* __restrict__ slot_idx, int fresh,
-                                                               int64_t m, KeyT* dst, uint32_t* flag, uint32_t gen) {
-    for (uint32_t j = threadIdx.x; j < k; j += blockDim.x) {
-        const unsigned long long wi = win[j];
-        KeyT v;
-        if (wi) {
-            v = keys[(int64_t)wi - base];
-            slot_key[j] = v;
-            slot_idx[j] = (int64_t)wi;
-            win[j] = 0;
-        } else if ((int64_t)j >= base && (int64_t)j < base + n) {
-            v = keys[j - base];
-            slot_key[j] = v;
-            slot_idx[j] = j;
-        } else if (fresh) {
-            v = 0;
-            slot_key[j] = 0;
-            slot_idx[j] = -1;
-        } else {
-            v = slot_key[j];
-        }
-        if ((int64_t)j < m) dst[j] = v;
-    }
-    publish_flag(flag, gen);
-}
-
-// resolve_publish_kernel for one 256-thread workgroup with R slots per lane, all R winner loads
-// issued before any key gather (k <= 256 R).  For a resolve forked onto a second stream beside the
-// next batch's K1 (rsv_set_resolve_stream): 4 waves fit beside K1's six workgroups on a CU, where
-// the 1024-thread form's 16 waves displace one of them (K1's first-generation schedule then ends late).
+// The publishing resolve as one 256-thread workgroup (k <= 256 R).  For a resolve forked onto a second
+// stream beside the next batch's K1 (rsv_set_resolve_stream): 4 waves fit beside K1's six workgroups on
+// a CU, where the 1024-thread form's 16 waves displace one of them (K1's first-generation schedule then
+// ends late).
 template <typename KeyT, int R>
 __global__ __launch_bounds__(kBlock) void resolve_publish_small_kernel(const KeyT* __restrict__ keys, int64_t base,
                                                                        int64_t n, uint32_t k,
@@ -213,40 +237,7 @@ __global__ __launch_bounds__(kBlock) void resolve_publish_small_kernel(const Key
                                                                        KeyT* __restrict__ slot_key,
                                                                        int64_t* __restrict__ slot_idx, int fresh,
                                                                        int64_t m, KeyT* dst, uint32_t* flag, uint32_t gen) {
-    unsigned long long wi[R];
-    KeyT v[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint32_t j = threadIdx.x + r * kBlock;
-        wi[r] = j < k ? win[j] : 0ull;
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int64_t j = threadIdx.x + r * kBlock;
-        if (j >= k) continue;
-        if (wi[r]) v[r] = keys[(int64_t)wi[r] - base];
-        else if (j >= base && j < base + n) v[r] = keys[j - base];
-        else if (fresh) v[r] = 0;
-        else v[r] = slot_key[j];
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int64_t j = threadIdx.x + r * kBlock;
-        if (j >= k) continue;
-        if (wi[r]) {
-            slot_key[j] = v[r];
-            slot_idx[j] = (int64_t)wi[r];
-            win[j] = 0;
-        } else if (j >= base && j < base + n) {
-            slot_key[j] = v[r];
-            slot_idx[j] = j;
-        } else if (fresh) {
-            slot_key[j] = 0;
-            slot_idx[j] = -1;
-        }
-        if (j < m) dst[j] = v[r];
-    }
-    publish_flag(flag, gen);
+    resolve_registers_first<KeyT, R, false>(keys, base, n, k, win, slot_key, slot_idx, fresh, m, dst, flag, gen);
 }
 
 __global__ __launch_bounds__(kBlock) void replay_kernel(const int64_t* __restrict__ ev_pos,
@@ -269,25 +260,95 @@ __global__ __launch_bounds__(kBlock) void export_draws_kernel(DrawKey dk, uint64
     out[t] = exact_j(dk, i, level0_byte(w, (uint32_t)(i & 15)));
 }
 
+// ---- the merge rule (multi-GPU combine of exported reservoirs) ---------------------------------
+// Where part p's index and key for slot j live -- index(p, j), and take(p, j, slot_key) moves the key
+// into the slot.  Strided arrays (rsv_merge: idx_parts[p][part_len], key_parts[p][part_len]):
 template <typename KeyT>
-__global__ __launch_bounds__(kBlock) void merge_slots_kernel(const int64_t* __restrict__ idx_parts,
-                                                             const KeyT* __restrict__ key_parts,
-                                                             int32_t parts, int64_t part_len,
-                                                             uint32_t k, int64_t* __restrict__ slot_idx,
-                                                             KeyT* __restrict__ slot_key) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= k) return;
-    int64_t best = slot_idx[j];
-    KeyT key = slot_key[j];
+struct StridedParts {
+    using Key = KeyT;
+    const int64_t* idx;
+    const KeyT* key;
+    int64_t part_len;
+    __device__ int64_t index(int32_t p, uint32_t j) const { return idx[(int64_t)p * part_len + j]; }
+    __device__ void take(int32_t p, uint32_t j, KeyT* slot_key) const { slot_key[j] = key[(int64_t)p * part_len + j]; }
+};
+
+// packed multi-GPU rows, `stride` words apart: [slot_idx(k) | keys widened to int64 (k)]
+template <typename KeyT>
+struct PackedRows {
+    using Key = KeyT;
+    const int64_t* rows;
+    int64_t stride;
+    uint32_t k;
+    __device__ int64_t index(int32_t p, uint32_t j) const { return rows[(int64_t)p * stride + j]; }
+    __device__ void take(int32_t p, uint32_t j, KeyT* slot_key) const {
+        slot_key[j] = (KeyT)rows[(int64_t)p * stride + k + j];
+    }
+};
+
+// the same two layouts for fixed-width byte keys, `words` 32-bit words each, moved word by word
+// (packed rows: [slot_idx(k) | k keys of `words` words])
+struct StridedWideParts {
+    using Key = uint32_t;
+    const int64_t* idx;
+    const uint32_t* key;
+    int64_t part_len;
+    uint32_t words;
+    __device__ int64_t index(int32_t p, uint32_t j) const { return idx[(int64_t)p * part_len + j]; }
+    __device__ void take(int32_t p, uint32_t j, uint32_t* slot_key) const {
+        const uint32_t* src = key + ((size_t)p * part_len + j) * words;
+        for (uint32_t q = 0; q < words; ++q) slot_key[(size_t)j * words + q] = src[q];
+    }
+};
+
+struct PackedWideRows {
+    using Key = uint32_t;
+    const int64_t* rows;
+    int64_t stride;
+    uint32_t k, words;
+    __device__ int64_t index(int32_t p, uint32_t j) const { return rows[(int64_t)p * stride + j]; }
+    __device__ void take(int32_t p, uint32_t j, uint32_t* slot_key) const {
+        const uint32_t* src = (const uint32_t*)(rows + (int64_t)p * stride + k) + (size_t)j * words;
+        for (uint32_t q = 0; q < words; ++q) slot_key[(size_t)j * words + q] = src[q];
+    }
+};
+
+// The rule: a part's larger index is the later writer.  The first part whose index for slot j is above
+// `best` and above every other part's wins: its number is returned and `best` becomes its index.  -1:
+// the slot keeps what it holds (no part, none newer, or a tie -- equal indices carry equal keys).
+template <typename Src>
+__device__ __forceinline__ int32_t merge_winner(const Src& src, int32_t parts, uint32_t j, int64_t& best) {
+    int32_t from = -1;
     for (int32_t p = 0; p < parts; ++p) {
-        const int64_t idx = idx_parts[(int64_t)p * part_len + j];
+        const int64_t idx = src.index(p, j);
         if (idx > best) {
             best = idx;
-            key = key_parts[(int64_t)p * part_len + j];
+            from = p;
         }
     }
-    slot_idx[j] = best;
-    slot_key[j] = key;
+    return from;
+}
+
+// The merge of `parts` parts into the slots.  kPublish (k <= 8192, Int / Long keys): one workgroup that
+// also publishes the first m slot keys, the multi-GPU combine's last step before result(), as the
+// publishing resolve_kernel is for a batch; else one slot per thread of a k-wide grid.
+template <typename Src, bool kPublish>
+__global__ __launch_bounds__(kPublish ? 1024 : kBlock) void merge_kernel(Src src, int32_t parts, uint32_t k,
+                                                                       int64_t* __restrict__ slot_idx,
+                                                                       typename Src::Key* __restrict__ slot_key,
+                                                                       int64_t m, typename Src::Key* dst,
+                                                                       uint32_t* flag, uint32_t gen) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < k; j += stride) {
+        int64_t best = slot_idx[j];
+        const int32_t from = merge_winner(src, parts, j, best);
+        if (from >= 0) {
+            slot_idx[j] = best;
+            src.take(from, j, slot_key);
+        }
+        if (kPublish && (int64_t)j < m) dst[j] = slot_key[j];
+    }
+    if (kPublish) publish_flag(flag, gen);
 }
 
 // packed multi-GPU row: [slot_idx(k) | keys widened to int64 (k)]
@@ -301,61 +362,10 @@ __global__ __launch_bounds__(kBlock) void export_packed_kernel(const int64_t* __
     row[k + j] = (int64_t)slot_key[j];
 }
 
-template <typename KeyT>
-__global__ __launch_bounds__(kBlock) void merge_packed_kernel(const int64_t* __restrict__ rows, int32_t parts,
-                                                              int64_t stride, uint32_t k,
-                                                              int64_t* __restrict__ slot_idx,
-                                                              KeyT* __restrict__ slot_key) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= k) return;
-    int64_t best = slot_idx[j];
-    KeyT key = slot_key[j];
-    for (int32_t p = 0; p < parts; ++p) {
-        const int64_t* r = rows + (int64_t)p * stride;
-        const int64_t idx = r[j];
-        if (idx > best) {
-            best = idx;
-            key = (KeyT)r[k + j];
-        }
-    }
-    slot_idx[j] = best;
-    slot_key[j] = key;
-}
-
-// merge of packed rows + publication in one dispatch (k <= 8192, Int/Long keys): the multi-GPU
-// combine's last step before result(), as resolve_publish_kernel is for a batch
-template <typename KeyT>
-__global__ __launch_bounds__(1024) void merge_packed_publish_kernel(const int64_t* __restrict__ rows, int32_t parts,
-                                                                    int64_t stride, uint32_t k,
-                                                                    int64_t* __restrict__ slot_idx,
-                                                                    KeyT* __restrict__ slot_key, int64_t m, KeyT* dst,
-                                                                    uint32_t* flag, uint32_t gen) {
-    for (uint32_t j = threadIdx.x; j < k; j += blockDim.x) {
-        int64_t best = slot_idx[j];
-        KeyT key = slot_key[j];
-        bool moved = false;
-        for (int32_t p = 0; p < parts; ++p) {
-            const int64_t* r = rows + (int64_t)p * stride;
-            const int64_t idx = r[j];
-            if (idx > best) {
-                best = idx;
-                key = (KeyT)r[k + j];
-                moved = true;
-            }
-        }
-        if (moved) {
-            slot_idx[j] = best;
-            slot_key[j] = key;
-        }
-        if ((int64_t)j < m) dst[j] = key;
-    }
-    publish_flag(flag, gen);
-}
-
 // ---- fixed-width byte keys (key_width a multiple of 8 above 8: UUIDs, composite keys) ----------
 // The element sampler never looks inside a key, so wide keys only change the copies: each slot's
-// key is `words` 32-bit words, moved word by word.  Same slot logic as resolve_kernel /
-// resolve_publish_kernel (one kernel; `dst` non-null = publish, launched as one workgroup).
+// key is `words` 32-bit words, moved word by word.  The slot rule as in resolve_kernel (one kernel;
+// `dst` non-null = publish, launched as one workgroup).
 __global__ __launch_bounds__(1024) void resolve_wide_kernel(const uint32_t* __restrict__ keys, int64_t base,
                                                             int64_t n, uint32_t k, uint32_t words,
                                                             unsigned long long* __restrict__ win,
@@ -364,49 +374,25 @@ __global__ __launch_bounds__(1024) void resolve_wide_kernel(const uint32_t* __re
                                                             uint32_t* dst, uint32_t* flag, uint32_t gen) {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < k; j += stride) {
-        const unsigned long long wi = win[j];
-        const uint32_t* src = nullptr;
-        if (wi) {
-            src = keys + (size_t)((int64_t)wi - base) * words;
-            if (slot_idx) slot_idx[j] = (int64_t)wi;
-            win[j] = 0;
-        } else if ((int64_t)j >= base && (int64_t)j < base + n) {
-            src = keys + (size_t)(j - base) * words;
-            if (slot_idx) slot_idx[j] = j;
-        } else if (fresh && slot_idx) {
-            slot_idx[j] = -1;
-        }
+        const uint32_t* src = nullptr;  // the batch's key for the slot, if it takes one
+        bool write = true;              // all cases but keep rewrite the slot's key
+        slot_rule(
+            j, win[j], base, n, fresh,
+            [&](int64_t off, int64_t idx, bool winner) {
+                src = keys + (size_t)off * words;
+                slot_idx[j] = idx;
+                if (winner) win[j] = 0;
+            },
+            [=](int64_t idx) { slot_idx[j] = idx; }, [&] { write = false; });
         uint32_t* o = slot_key + (size_t)j * words;
         const bool out = dst && (int64_t)j < m;
         for (uint32_t q = 0; q < words; ++q) {
-            const uint32_t v = src ? src[q] : (fresh ? 0u : o[q]);
-            if (src || fresh) o[q] = v;
+            const uint32_t v = src ? src[q] : (write ? 0u : o[q]);
+            if (write) o[q] = v;
             if (out) dst[(size_t)j * words + q] = v;
         }
     }
     if (dst) publish_flag(flag, gen);
-}
-
-__global__ __launch_bounds__(kBlock) void merge_slots_wide_kernel(const int64_t* __restrict__ idx_parts,
-                                                                  const uint32_t* __restrict__ key_parts,
-                                                                  int32_t parts, int64_t part_len, uint32_t k,
-                                                                  uint32_t words, int64_t* __restrict__ slot_idx,
-                                                                  uint32_t* __restrict__ slot_key) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= k) return;
-    int64_t best = slot_idx[j];
-    int32_t from = -1;
-    for (int32_t p = 0; p < parts; ++p) {
-        const int64_t idx = idx_parts[(int64_t)p * part_len + j];
-        if (idx > best) {
-            best = idx;
-            from = p;
-        }
-    }
-    if (from < 0) return;
-    slot_idx[j] = best;
-    const uint32_t* src = key_parts + ((size_t)from * part_len + j) * words;
-    for (uint32_t q = 0; q < words; ++q) slot_key[(size_t)j * words + q] = src[q];
 }
 
 // packed rows of wide keys: [slot_idx(k) | k keys of `words` 32-bit words]
@@ -420,33 +406,12 @@ __global__ __launch_bounds__(kBlock) void export_packed_wide_kernel(const int64_
     for (uint32_t q = 0; q < words; ++q) o[q] = slot_key[(size_t)j * words + q];
 }
 
-__global__ __launch_bounds__(kBlock) void merge_packed_wide_kernel(const int64_t* __restrict__ rows, int32_t parts,
-                                                                   int64_t stride, uint32_t k, uint32_t words,
-                                                                   int64_t* __restrict__ slot_idx,
-                                                                   uint32_t* __restrict__ slot_key) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= k) return;
-    int64_t best = slot_idx[j];
-    int32_t from = -1;
-    for (int32_t p = 0; p < parts; ++p) {
-        const int64_t idx = rows[(int64_t)p * stride + j];
-        if (idx > best) {
-            best = idx;
-            from = p;
-        }
-    }
-    if (from < 0) return;
-    slot_idx[j] = best;
-    const uint32_t* src = (const uint32_t*)(rows + (int64_t)from * stride + k) + (size_t)j * words;
-    for (uint32_t q = 0; q < words; ++q) slot_key[(size_t)j * words + q] = src[q];
-}
-
 inline DrawKey make_key(const DrawParams& dp) {
     return DrawKey{(uint32_t)dp.seed, (uint32_t)(dp.seed >> 32), (uint32_t)dp.stream,
                    (uint32_t)(dp.stream >> 32)};
 }
 
-inline unsigned grid_for(uint64_t items, unsigned cap) {
+inline unsigned grid_for(uint64_t items, unsigned cap = ~0u) {
     uint64_t b = (items + kBlock - 1) / kBlock;
     if (b < 1) b = 1;
     return (unsigned)(b < cap ? b : cap);
@@ -486,6 +451,19 @@ inline unsigned k1_plan(uint64_t n_groups, K1Sched& sch) {
     return (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
 }
 
+// f(KeyT{}) with the key type of a 4- / 8-byte key_width (f launches a kernel); the launch's error
+template <typename F>
+hipError_t with_key_type(int key_width, F&& f) {
+    if (key_width == 8) f(int64_t{});
+    else f(int32_t{});
+    return hipGetLastError();
+}
+
+// threads of a one-workgroup form over k slots: whole waves, at most 1024
+inline unsigned one_group_threads(uint32_t k) {
+    return std::min<unsigned>(1024, std::max<unsigned>(64, (k + 63) / 64 * 64));
+}
+
 }  // namespace
 
 hipError_t launch_k1_last_writer(const DrawParams& dp, uint32_t k, uint64_t lo, uint64_t hi,
@@ -515,43 +493,42 @@ bool k1_fused_ok(uint64_t lo, uint64_t hi, uint32_t k, int key_width) {
     return g_end - g_begin <= (1ull << 31) && g_end <= ((g_begin >> 32) + 1) << 32;
 }
 
-hipError_t launch_k1_resolve_publish(const DrawParams& dp, uint32_t k, uint64_t lo, uint64_t hi,
-                                     unsigned long long* batch_win, uint32_t* ticket, const void* keys,
-                                     int key_width, int64_t base, int64_t n, void* slot_key, int64_t* slot_idx,
-                                     bool fresh, int64_t m, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen,
-                                     hipStream_t st) {
-    if (!k1_fused_ok(lo, hi, k, key_width)) return hipErrorInvalidValue;
+hipError_t launch_k1_resolve_publish(const DrawParams& dp, uint64_t lo, uint64_t hi, const SlotBlock& sb,
+                                     uint32_t* ticket, const Batch& b, const Publication& pub, hipStream_t st) {
+    if (!k1_fused_ok(lo, hi, sb.k, sb.key_width)) return hipErrorInvalidValue;
     const uint64_t g_begin = lo >> 4, n_groups = ((hi + 15) >> 4) - g_begin;
     K1Sched sch;
     const unsigned grid = k1_plan(n_groups, sch);
-    if (key_width == 8)
-        hipLaunchKernelGGL(k1_resolve_publish<int64_t>, dim3(grid), dim3(kBlock), 0, st, make_key(dp), k, lo, hi,
-                           g_begin, n_groups, batch_win, ticket, (const int64_t*)keys, base, n, (int64_t*)slot_key,
-                           slot_idx, (int)fresh, m, (int64_t*)dst_host_dev, flag_dev, gen, sch);
-    else
-        hipLaunchKernelGGL(k1_resolve_publish<int32_t>, dim3(grid), dim3(kBlock), 0, st, make_key(dp), k, lo, hi,
-                           g_begin, n_groups, batch_win, ticket, (const int32_t*)keys, base, n, (int32_t*)slot_key,
-                           slot_idx, (int)fresh, m, (int32_t*)dst_host_dev, flag_dev, gen, sch);
-    return hipGetLastError();
+    return with_key_type(sb.key_width, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k1_resolve_publish<T>, dim3(grid), dim3(kBlock), 0, st, make_key(dp), sb.k, lo, hi, g_begin,
+                           n_groups, sb.win, ticket, (const T*)b.keys, b.base, b.n, (T*)sb.slot_key, sb.slot_idx,
+                           (int)b.fresh, pub.m, (T*)pub.dst, pub.flag, pub.gen, sch);
+    });
 }
 
-hipError_t launch_resolve(const void* keys, int key_width, int64_t base, int64_t n, uint32_t k,
-                          unsigned long long* batch_win, void* slot_key, int64_t* slot_idx, bool fresh,
-                          hipStream_t st) {
-    const unsigned grid = (unsigned)((k + kBlock - 1) / kBlock);
-    if (key_width > 8) {
-        hipLaunchKernelGGL(resolve_wide_kernel, dim3(std::min<unsigned>(grid, 256 * 64)), dim3(kBlock), 0, st,
-                           (const uint32_t*)keys, base, n, k, (uint32_t)key_width / 4, batch_win, (uint32_t*)slot_key,
-                           slot_idx, (int)fresh, (int64_t)0, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u);
+hipError_t launch_resolve(const SlotBlock& sb, const Batch& b, const Publication& pub, hipStream_t st, bool small) {
+    const uint32_t k = sb.k;
+    if (sb.key_width > 8) {  // one kernel: a k-wide grid (capped, it strides), or one publishing workgroup
+        const unsigned grid = pub.dst ? 1 : grid_for(k, 256 * 64);
+        hipLaunchKernelGGL(resolve_wide_kernel, dim3(grid), dim3(pub.dst ? one_group_threads(k) : kBlock), 0, st,
+                           (const uint32_t*)b.keys, b.base, b.n, k, (uint32_t)sb.key_width / 4, sb.win,
+                           (uint32_t*)sb.slot_key, sb.slot_idx, (int)b.fresh, pub.m, (uint32_t*)pub.dst, pub.flag,
+                           pub.gen);
         return hipGetLastError();
     }
-    if (key_width == 8)
-        hipLaunchKernelGGL(resolve_kernel<int64_t>, dim3(grid), dim3(kBlock), 0, st,
-                           (const int64_t*)keys, base, n, k, batch_win, (int64_t*)slot_key, slot_idx, (int)fresh);
-    else
-        hipLaunchKernelGGL(resolve_kernel<int32_t>, dim3(grid), dim3(kBlock), 0, st,
-                           (const int32_t*)keys, base, n, k, batch_win, (int32_t*)slot_key, slot_idx, (int)fresh);
-    return hipGetLastError();
+    return with_key_type(sb.key_width, [&](auto t) {
+        using T = decltype(t);
+        auto go = [&](auto kernel, unsigned grid, unsigned threads) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, st, (const T*)b.keys, b.base, b.n, k, sb.win,
+                               (T*)sb.slot_key, sb.slot_idx, (int)b.fresh, pub.m, (T*)pub.dst, pub.flag, pub.gen);
+        };
+        if (!pub.dst) go(resolve_kernel<T, false>, grid_for(k), kBlock);
+        else if (!(small && k <= 8 * kBlock)) go(resolve_kernel<T, true>, 1, one_group_threads(k));
+        else if (k <= 2 * kBlock) go(resolve_publish_small_kernel<T, 2>, 1, kBlock);
+        else if (k <= 4 * kBlock) go(resolve_publish_small_kernel<T, 4>, 1, kBlock);
+        else go(resolve_publish_small_kernel<T, 8>, 1, kBlock);
+    });
 }
 
 // fresh handle: batch_win = 0, slot_idx = -1 (empty), slot_key = 0
@@ -571,11 +548,9 @@ __global__ __launch_bounds__(kBlock) void init_slots_kernel(uint8_t* slot_key, i
     }
 }
 
-hipError_t launch_init_slots(void* slot_key, int key_width, int64_t* slot_idx, unsigned long long* win, uint32_t k,
-                             hipStream_t st, uint32_t* ticket) {
-    const unsigned grid = (unsigned)std::min<uint64_t>((k + kBlock - 1) / kBlock, 256 * 64);
-    hipLaunchKernelGGL(init_slots_kernel, dim3(grid), dim3(kBlock), 0, st, (uint8_t*)slot_key, key_width, slot_idx,
-                       win, k, ticket);
+hipError_t launch_init_slots(const SlotBlock& sb, hipStream_t st, uint32_t* ticket) {
+    hipLaunchKernelGGL(init_slots_kernel, dim3(grid_for(sb.k, 256 * 64)), dim3(kBlock), 0, st, (uint8_t*)sb.slot_key,
+                       sb.key_width, sb.slot_idx, sb.win, sb.k, ticket);
     return hipGetLastError();
 }
 
@@ -632,70 +607,36 @@ hipError_t launch_publish(const void* src, int64_t bytes, void* dst_host_dev, ui
     return hipGetLastError();
 }
 
-hipError_t launch_resolve_publish(const void* keys, int key_width, int64_t base, int64_t n, uint32_t k,
-                                  unsigned long long* batch_win, void* slot_key, int64_t* slot_idx, bool fresh,
-                                  int64_t m, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st,
-                                  bool small) {
-    if (small && k <= 8 * kBlock && (key_width == 8 || key_width == 4)) {
-#define RSV_SMALL(T, R)                                                                                              \
-    hipLaunchKernelGGL((resolve_publish_small_kernel<T, R>), dim3(1), dim3(kBlock), 0, st, (const T*)keys, base, n, \
-                       k, batch_win, (T*)slot_key, slot_idx, (int)fresh, m, (T*)dst_host_dev, flag_dev, gen)
-        if (key_width == 8) {
-            if (k <= 2 * kBlock) RSV_SMALL(int64_t, 2);
-            else if (k <= 4 * kBlock) RSV_SMALL(int64_t, 4);
-            else RSV_SMALL(int64_t, 8);
-        } else {
-            if (k <= 2 * kBlock) RSV_SMALL(int32_t, 2);
-            else if (k <= 4 * kBlock) RSV_SMALL(int32_t, 4);
-            else RSV_SMALL(int32_t, 8);
-        }
-#undef RSV_SMALL
-        return hipGetLastError();
-    }
-    const unsigned threads = std::min<unsigned>(1024, std::max<unsigned>(64, (k + 63) / 64 * 64));
-    if (key_width > 8) {
-        hipLaunchKernelGGL(resolve_wide_kernel, dim3(1), dim3(threads), 0, st, (const uint32_t*)keys, base, n, k,
-                           (uint32_t)key_width / 4, batch_win, (uint32_t*)slot_key, slot_idx, (int)fresh, m,
-                           (uint32_t*)dst_host_dev, flag_dev, gen);
-        return hipGetLastError();
-    }
-    if (key_width == 8)
-        hipLaunchKernelGGL(resolve_publish_kernel<int64_t>, dim3(1), dim3(threads), 0, st, (const int64_t*)keys, base,
-                           n, k, batch_win, (int64_t*)slot_key, slot_idx, (int)fresh, m, (int64_t*)dst_host_dev,
-                           flag_dev, gen);
-    else
-        hipLaunchKernelGGL(resolve_publish_kernel<int32_t>, dim3(1), dim3(threads), 0, st, (const int32_t*)keys, base,
-                           n, k, batch_win, (int32_t*)slot_key, slot_idx, (int)fresh, m, (int32_t*)dst_host_dev,
-                           flag_dev, gen);
-    return hipGetLastError();
+// ---- index-only batches (rsv_sample_indexed / rsv_fill_slots) -------------------------------
+// The resolve of a batch sampled by index alone: the slot rule for slot j with no key read --
+// slot_idx[j] = the winner or the fill; returns its offset in the batch (-1: the slot took no
+// element).  The keys arrive later from the caller (fill_slots_kernel).
+__device__ __forceinline__ int64_t resolve_index_slot(uint64_t j, int64_t base, int64_t n, unsigned long long* win,
+                                                      int64_t* slot_idx, int fresh, uint8_t* slot_key, int key_width) {
+    int64_t off = -1;
+    slot_rule(
+        (int64_t)j, win[j], base, n, fresh,
+        [&](int64_t o, int64_t idx, bool winner) {
+            slot_idx[j] = idx;
+            if (winner) win[j] = 0;
+            off = o;
+        },
+        [=](int64_t idx) {
+            slot_idx[j] = idx;
+            for (int q = 0; q < key_width; ++q) slot_key[j * key_width + q] = 0;
+        },
+        [] {});
+    return off;
 }
 
-// ---- index-only batches (rsv_sample_indexed / rsv_fill_slots) -------------------------------
-// The resolve of a batch sampled by index alone: per slot j the batch's last writer (win[j]), else
-// the fill of j < k from this batch, becomes slot_idx[j], and offs[j] = its offset in the batch
-// (-1: the slot did not change).  The keys arrive later from the caller (fill_slots_kernel).
 __global__ __launch_bounds__(kBlock) void resolve_indices_kernel(int64_t base, int64_t n, uint32_t k,
                                                                  unsigned long long* __restrict__ win,
                                                                  int64_t* __restrict__ slot_idx, int fresh,
                                                                  uint8_t* __restrict__ slot_key, int key_width,
                                                                  int64_t* __restrict__ offs) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < k; j += stride) {
-        const unsigned long long wi = win[j];
-        int64_t off = -1;
-        if (wi) {  // last eviction into slot j (Sampler.scala:243-246)
-            slot_idx[j] = (int64_t)wi;
-            win[j] = 0;
-            off = (int64_t)wi - base;
-        } else if ((int64_t)j >= base && (int64_t)j < base + n) {  // fill phase (Sampler.scala:253-255)
-            slot_idx[j] = (int64_t)j;
-            off = (int64_t)j - base;
-        } else if (fresh) {
-            slot_idx[j] = -1;
-            for (int q = 0; q < key_width; ++q) slot_key[j * key_width + q] = 0;
-        }
-        offs[j] = off;
-    }
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < k; j += stride)
+        offs[j] = resolve_index_slot(j, base, n, win, slot_idx, fresh, slot_key, key_width);
 }
 
 // keys[j] (host-supplied, one per slot, slot order) into every slot the index-only batch changed
@@ -711,6 +652,13 @@ __global__ __launch_bounds__(kBlock) void fill_slots_kernel(const int64_t* __res
     }
 }
 
+// The two publishing forms below are kernels of their own, not a compile-time case of the two above.
+// Merged (resolve_indices_kernel<kPublish>: 50 -> 56 SGPRs, 14 -> 18 VGPRs; fill_slots_kernel<kPublish>
+// with the key type as a run-time branch: 28 -> 52 SGPRs, 8 -> 14 VGPRs) the winners-only host batch
+// on philox_r (tools/bench_paths.py c2h), whose latency path they are on, measured 0.11309 ms against
+// the parent's 0.11088 - 0.11230 and 0.11335 ms against 0.11080 - 0.11290 in two sessions
+// (profiles/elements_shared/refactor_ab.jsonl, "s1" and "s2").
+
 // resolve_indices_kernel + publication of offs[] into coherent host memory (flag = gen) in one
 // dispatch, for k <= kIdxPublishMaxK: the host spins on the flag instead of a D2H copy + stream
 // synchronize (the winners-only host batches and rsv_sample_indexed)
@@ -723,27 +671,15 @@ __global__ __launch_bounds__(1024) void resolve_indices_publish_kernel(int64_t b
                                                                        int64_t* __restrict__ offs, int64_t* offs_host,
                                                                        uint32_t* flag, uint32_t gen) {
     for (uint32_t j = threadIdx.x; j < k; j += blockDim.x) {
-        const unsigned long long wi = win[j];
-        int64_t off = -1;
-        if (wi) {
-            slot_idx[j] = (int64_t)wi;
-            win[j] = 0;
-            off = (int64_t)wi - base;
-        } else if ((int64_t)j >= base && (int64_t)j < base + n) {
-            slot_idx[j] = (int64_t)j;
-            off = (int64_t)j - base;
-        } else if (fresh) {
-            slot_idx[j] = -1;
-            for (int q = 0; q < key_width; ++q) slot_key[(size_t)j * key_width + q] = 0;
-        }
+        const int64_t off = resolve_index_slot(j, base, n, win, slot_idx, fresh, slot_key, key_width);
         offs[j] = off;
         offs_host[j] = off;
     }
     publish_flag(flag, gen);
 }
 
-// fill_slots_kernel + publication of the first m slot keys (resolve_publish's form) for k <= 8192
-// and 4- / 8-byte keys: the host-keyed batch's reservoir is published with its last kernel
+// fill_slots_kernel + publication of the first m slot keys (the publishing resolve_kernel's form) for
+// k <= 8192 and 4- / 8-byte keys: the host-keyed batch's reservoir is published with its last kernel
 template <typename KeyT>
 __global__ __launch_bounds__(1024) void fill_slots_publish_kernel(const int64_t* __restrict__ offs,
                                                                   const KeyT* __restrict__ keys, uint32_t k,
@@ -764,13 +700,17 @@ __global__ __launch_bounds__(1024) void fill_slots_publish_kernel(const int64_t*
 
 bool resolve_indices_publish_ok(uint32_t k) { return k <= kIdxPublishMaxK; }
 
-hipError_t launch_resolve_indices_publish(int64_t base, int64_t n, uint32_t k, unsigned long long* batch_win,
-                                          int64_t* slot_idx, bool fresh, void* slot_key, int key_width, int64_t* offs,
-                                          int64_t* offs_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st) {
-    if (k > kIdxPublishMaxK) return hipErrorInvalidValue;
-    const unsigned threads = std::min<unsigned>(1024, std::max<unsigned>(64, (k + 63) / 64 * 64));
-    hipLaunchKernelGGL(resolve_indices_publish_kernel, dim3(1), dim3(threads), 0, st, base, n, k, batch_win, slot_idx,
-                       (int)fresh, (uint8_t*)slot_key, key_width, offs, offs_host_dev, flag_dev, gen);
+hipError_t launch_resolve_indices(const SlotBlock& sb, const Batch& b, int64_t* offs, const Publication& pub,
+                                  hipStream_t st) {
+    if (!pub.dst)
+        hipLaunchKernelGGL(resolve_indices_kernel, dim3(grid_for(sb.k, 256 * 64)), dim3(kBlock), 0, st, b.base, b.n, sb.k,
+                           sb.win, sb.slot_idx, (int)b.fresh, (uint8_t*)sb.slot_key, sb.key_width, offs);
+    else if (!resolve_indices_publish_ok(sb.k))
+        return hipErrorInvalidValue;
+    else
+        hipLaunchKernelGGL(resolve_indices_publish_kernel, dim3(1), dim3(one_group_threads(sb.k)), 0, st, b.base, b.n,
+                           sb.k, sb.win, sb.slot_idx, (int)b.fresh, (uint8_t*)sb.slot_key, sb.key_width, offs,
+                           (int64_t*)pub.dst, pub.flag, pub.gen);
     return hipGetLastError();
 }
 
@@ -778,31 +718,19 @@ bool fill_slots_publish_ok(uint32_t k, int key_width) {
     return k <= kIdxPublishMaxK && (key_width == 4 || key_width == 8);
 }
 
-hipError_t launch_fill_slots_publish(const int64_t* offs, const void* keys, uint32_t k, int key_width, void* slot_key,
-                                     int64_t m, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st) {
-    if (!fill_slots_publish_ok(k, key_width)) return hipErrorInvalidValue;
-    const unsigned threads = std::min<unsigned>(1024, std::max<unsigned>(64, (k + 63) / 64 * 64));
-    if (key_width == 8)
-        hipLaunchKernelGGL(fill_slots_publish_kernel<int64_t>, dim3(1), dim3(threads), 0, st, offs,
-                           (const int64_t*)keys, k, (int64_t*)slot_key, m, (int64_t*)dst_host_dev, flag_dev, gen);
-    else
-        hipLaunchKernelGGL(fill_slots_publish_kernel<int32_t>, dim3(1), dim3(threads), 0, st, offs,
-                           (const int32_t*)keys, k, (int32_t*)slot_key, m, (int32_t*)dst_host_dev, flag_dev, gen);
-    return hipGetLastError();
-}
-
-hipError_t launch_resolve_indices(int64_t base, int64_t n, uint32_t k, unsigned long long* batch_win, int64_t* slot_idx,
-                                  bool fresh, void* slot_key, int key_width, int64_t* offs, hipStream_t st) {
-    hipLaunchKernelGGL(resolve_indices_kernel, dim3(grid_for(k, 256 * 64)), dim3(kBlock), 0, st, base, n, k, batch_win,
-                       slot_idx, (int)fresh, (uint8_t*)slot_key, key_width, offs);
-    return hipGetLastError();
-}
-
-hipError_t launch_fill_slots(const int64_t* offs, const void* keys, uint32_t k, int key_width, void* slot_key,
+hipError_t launch_fill_slots(const int64_t* offs, const void* keys, const SlotBlock& sb, const Publication& pub,
                              hipStream_t st) {
-    hipLaunchKernelGGL(fill_slots_kernel, dim3(grid_for(k, 256 * 64)), dim3(kBlock), 0, st, offs, (const uint8_t*)keys,
-                       k, key_width, (uint8_t*)slot_key);
-    return hipGetLastError();
+    if (!pub.dst) {
+        hipLaunchKernelGGL(fill_slots_kernel, dim3(grid_for(sb.k, 256 * 64)), dim3(kBlock), 0, st, offs,
+                           (const uint8_t*)keys, sb.k, sb.key_width, (uint8_t*)sb.slot_key);
+        return hipGetLastError();
+    }
+    if (!fill_slots_publish_ok(sb.k, sb.key_width)) return hipErrorInvalidValue;
+    return with_key_type(sb.key_width, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(fill_slots_publish_kernel<T>, dim3(1), dim3(one_group_threads(sb.k)), 0, st, offs,
+                           (const T*)keys, sb.k, (T*)sb.slot_key, pub.m, (T*)pub.dst, pub.flag, pub.gen);
+    });
 }
 
 hipError_t launch_replay_events(const int64_t* ev_pos, const int32_t* ev_slot, int64_t n_events,
@@ -822,70 +750,58 @@ hipError_t launch_export_draws(const DrawParams& dp, uint64_t i0, int64_t n, uin
     return hipGetLastError();
 }
 
-hipError_t launch_merge_slots(const int64_t* idx_parts, const void* key_parts, int key_width,
-                              int32_t parts, int64_t part_len, uint32_t k, int64_t* slot_idx,
-                              void* slot_key, hipStream_t st) {
-    const unsigned grid = (unsigned)((k + kBlock - 1) / kBlock);
-    if (key_width > 8) {
-        hipLaunchKernelGGL(merge_slots_wide_kernel, dim3(grid), dim3(kBlock), 0, st, idx_parts,
-                           (const uint32_t*)key_parts, parts, part_len, k, (uint32_t)key_width / 4, slot_idx,
-                           (uint32_t*)slot_key);
-        return hipGetLastError();
-    }
-    if (key_width == 8)
-        hipLaunchKernelGGL(merge_slots_kernel<int64_t>, dim3(grid), dim3(kBlock), 0, st, idx_parts,
-                           (const int64_t*)key_parts, parts, part_len, k, slot_idx, (int64_t*)slot_key);
-    else
-        hipLaunchKernelGGL(merge_slots_kernel<int32_t>, dim3(grid), dim3(kBlock), 0, st, idx_parts,
-                           (const int32_t*)key_parts, parts, part_len, k, slot_idx, (int32_t*)slot_key);
-    return hipGetLastError();
+namespace {
+
+// one merge_kernel launch over the source `src`: a k-wide grid, or the one publishing workgroup
+template <bool kPublish, typename Src>
+void launch_merge(const Src& src, int32_t parts, const SlotBlock& sb, const Publication& pub, hipStream_t st) {
+    using Key = typename Src::Key;
+    hipLaunchKernelGGL((merge_kernel<Src, kPublish>), dim3(kPublish ? 1 : grid_for(sb.k)),
+                       dim3(kPublish ? one_group_threads(sb.k) : kBlock), 0, st, src, parts, sb.k, sb.slot_idx,
+                       (Key*)sb.slot_key, pub.m, (Key*)pub.dst, pub.flag, pub.gen);
 }
 
-hipError_t launch_export_packed(const int64_t* slot_idx, const void* slot_key, int key_width, uint32_t k,
-                                int64_t* row, hipStream_t st) {
-    const unsigned grid = (unsigned)((k + kBlock - 1) / kBlock);
-    if (key_width > 8) {
-        hipLaunchKernelGGL(export_packed_wide_kernel, dim3(grid), dim3(kBlock), 0, st, slot_idx,
-                           (const uint32_t*)slot_key, k, (uint32_t)key_width / 4, row);
+}  // namespace
+
+hipError_t launch_merge_slots(const int64_t* idx_parts, const void* key_parts, int32_t parts, int64_t part_len,
+                              const SlotBlock& sb, hipStream_t st) {
+    if (sb.key_width > 8) {
+        const StridedWideParts src{idx_parts, (const uint32_t*)key_parts, part_len, (uint32_t)sb.key_width / 4};
+        launch_merge<false>(src, parts, sb, Publication{}, st);
         return hipGetLastError();
     }
-    if (key_width == 8)
-        hipLaunchKernelGGL(export_packed_kernel<int64_t>, dim3(grid), dim3(kBlock), 0, st, slot_idx,
-                           (const int64_t*)slot_key, k, row);
-    else
-        hipLaunchKernelGGL(export_packed_kernel<int32_t>, dim3(grid), dim3(kBlock), 0, st, slot_idx,
-                           (const int32_t*)slot_key, k, row);
-    return hipGetLastError();
+    return with_key_type(sb.key_width, [&](auto t) {
+        using T = decltype(t);
+        launch_merge<false>(StridedParts<T>{idx_parts, (const T*)key_parts, part_len}, parts, sb, Publication{}, st);
+    });
 }
 
-hipError_t launch_merge_packed(const int64_t* rows, int32_t parts, int64_t stride, uint32_t k, int64_t* slot_idx,
-                               void* slot_key, int key_width, hipStream_t st) {
-    const unsigned grid = (unsigned)((k + kBlock - 1) / kBlock);
-    if (key_width > 8) {
-        hipLaunchKernelGGL(merge_packed_wide_kernel, dim3(grid), dim3(kBlock), 0, st, rows, parts, stride, k,
-                           (uint32_t)key_width / 4, slot_idx, (uint32_t*)slot_key);
+hipError_t launch_export_packed(const SlotBlock& sb, int64_t* row, hipStream_t st) {
+    if (sb.key_width > 8) {
+        hipLaunchKernelGGL(export_packed_wide_kernel, dim3(grid_for(sb.k)), dim3(kBlock), 0, st, sb.slot_idx,
+                           (const uint32_t*)sb.slot_key, sb.k, (uint32_t)sb.key_width / 4, row);
         return hipGetLastError();
     }
-    if (key_width == 8)
-        hipLaunchKernelGGL(merge_packed_kernel<int64_t>, dim3(grid), dim3(kBlock), 0, st, rows, parts, stride, k,
-                           slot_idx, (int64_t*)slot_key);
-    else
-        hipLaunchKernelGGL(merge_packed_kernel<int32_t>, dim3(grid), dim3(kBlock), 0, st, rows, parts, stride, k,
-                           slot_idx, (int32_t*)slot_key);
-    return hipGetLastError();
+    return with_key_type(sb.key_width, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(export_packed_kernel<T>, dim3(grid_for(sb.k)), dim3(kBlock), 0, st, sb.slot_idx,
+                           (const T*)sb.slot_key, sb.k, row);
+    });
 }
 
-hipError_t launch_merge_packed_publish(const int64_t* rows, int32_t parts, int64_t stride, uint32_t k,
-                                       int64_t* slot_idx, void* slot_key, int key_width, int64_t m, void* dst_host_dev,
-                                       uint32_t* flag_dev, uint32_t gen, hipStream_t st) {
-    const unsigned threads = std::min<unsigned>(1024, std::max<unsigned>(64, (k + 63) / 64 * 64));
-    if (key_width == 8)
-        hipLaunchKernelGGL(merge_packed_publish_kernel<int64_t>, dim3(1), dim3(threads), 0, st, rows, parts, stride, k,
-                           slot_idx, (int64_t*)slot_key, m, (int64_t*)dst_host_dev, flag_dev, gen);
-    else
-        hipLaunchKernelGGL(merge_packed_publish_kernel<int32_t>, dim3(1), dim3(threads), 0, st, rows, parts, stride, k,
-                           slot_idx, (int32_t*)slot_key, m, (int32_t*)dst_host_dev, flag_dev, gen);
-    return hipGetLastError();
+hipError_t launch_merge_packed(const int64_t* rows, int32_t parts, int64_t stride, const SlotBlock& sb,
+                               const Publication& pub, hipStream_t st) {
+    if (sb.key_width > 8) {  // byte keys are merged without a publication (the caller never asks for one)
+        if (pub.dst) return hipErrorInvalidValue;
+        launch_merge<false>(PackedWideRows{rows, stride, sb.k, (uint32_t)sb.key_width / 4}, parts, sb, pub, st);
+        return hipGetLastError();
+    }
+    return with_key_type(sb.key_width, [&](auto t) {
+        using T = decltype(t);
+        const PackedRows<T> src{rows, stride, sb.k};
+        if (pub.dst) launch_merge<true>(src, parts, sb, pub, st);
+        else launch_merge<false>(src, parts, sb, pub, st);
+    });
 }
 
 }  // namespace rsv

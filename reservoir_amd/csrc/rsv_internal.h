@@ -87,53 +87,63 @@ struct DrawParams {
 };
 
 // ---- elements (Algorithm R, draw format R2) -------------------------------------------------
+// Argument bundles of the element launchers (plain data: no ownership, no checks).
+// A handle's slot block: batch_win[k] (0 = no writer in this batch), slot_idx[k] (-1 = empty), the keys.
+struct SlotBlock {
+    unsigned long long* win;
+    int64_t* slot_idx;
+    void* slot_key;
+    uint32_t k;
+    int key_width;
+};
+// One batch: n elements at global indices [base, base + n); keys null for an index-only batch; fresh:
+// the first batch of a handle whose slots were never initialised (untouched slots become empty).
+struct Batch {
+    const void* keys;
+    int64_t base, n;
+    bool fresh;
+};
+// What a launch publishes besides its own work: the first m slot keys (or the k offsets of an index-only
+// batch) into coherent host memory dst (device alias), then flag = gen.  dst null: no publication.
+struct Publication {
+    int64_t m = 0;
+    void* dst = nullptr;
+    uint32_t* flag = nullptr;
+    uint32_t gen = 0;
+};
+
 // K1: per-slot last writer of the index range [lo, hi) (only indices >= k can evict) into
-// batch_win[k] (0 = no writer in this batch; atomicMax keeps the largest index).
+// batch_win[k] (atomicMax keeps the largest index).
 hipError_t launch_k1_last_writer(const DrawParams& dp, uint32_t k, uint64_t lo, uint64_t hi,
                                  unsigned long long* batch_win, hipStream_t st);
-// K1 + resolve_publish as one dispatch (see launch_resolve_publish), when k1_fused_ok: a batch
-// whose range K1 covers in one launch, k <= 2048, 4- or 8-byte keys.  ticket: a zeroed device
-// word, re-armed by the launch.
+// K1 + the publishing resolve as one dispatch, when k1_fused_ok: a batch whose range K1 covers in one
+// launch, k <= 2048, 4- or 8-byte keys.  ticket: a zeroed device word, re-armed by the launch.
 bool k1_fused_ok(uint64_t lo, uint64_t hi, uint32_t k, int key_width);
-hipError_t launch_k1_resolve_publish(const DrawParams& dp, uint32_t k, uint64_t lo, uint64_t hi,
-                                     unsigned long long* batch_win, uint32_t* ticket, const void* keys,
-                                     int key_width, int64_t base, int64_t n, void* slot_key, int64_t* slot_idx,
-                                     bool fresh, int64_t m, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen,
-                                     hipStream_t st);
-// Resolve: fill phase for slots in [base, base+n) and winners of batch_win; resets batch_win.
-// slot_idx may be null.  init_slots also zeroes `ticket` when non-null.
-hipError_t launch_init_slots(void* slot_key, int key_width, int64_t* slot_idx, unsigned long long* win, uint32_t k,
-                             hipStream_t st, uint32_t* ticket = nullptr);
+hipError_t launch_k1_resolve_publish(const DrawParams& dp, uint64_t lo, uint64_t hi, const SlotBlock& sb,
+                                     uint32_t* ticket, const Batch& b, const Publication& pub, hipStream_t st);
+// init_slots also zeroes `ticket` when non-null.
+hipError_t launch_init_slots(const SlotBlock& sb, hipStream_t st, uint32_t* ticket = nullptr);
 hipError_t launch_publish(const void* src, int64_t bytes, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen,
                           hipStream_t st);
 // the same from up to 32 workgroups (large buffers); ticket_dev: a zeroed device word, re-armed
 hipError_t launch_publish_multi(const void* src, int64_t bytes, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen,
                                 uint32_t* ticket_dev, hipStream_t st);
-hipError_t launch_resolve(const void* keys, int key_width, int64_t base, int64_t n, uint32_t k,
-                          unsigned long long* batch_win, void* slot_key, int64_t* slot_idx, bool fresh,
-                          hipStream_t st);
-// resolve + publish of the first m slot keys into coherent host memory + flag = gen (k <= 8192;
-// slot_idx must be non-null); small: one 256-thread workgroup where k <= 2048 (a resolve running
-// beside K1 on a second stream)
-hipError_t launch_resolve_publish(const void* keys, int key_width, int64_t base, int64_t n, uint32_t k,
-                                  unsigned long long* batch_win, void* slot_key, int64_t* slot_idx, bool fresh,
-                                  int64_t m, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st,
-                                  bool small = false);
-// index-only batches: resolve into slot_idx with offs[k] = the batch offset of each changed slot
-// (-1: unchanged); then the caller's keys into the changed slots
-hipError_t launch_resolve_indices(int64_t base, int64_t n, uint32_t k, unsigned long long* batch_win, int64_t* slot_idx,
-                                  bool fresh, void* slot_key, int key_width, int64_t* offs, hipStream_t st);
-hipError_t launch_fill_slots(const int64_t* offs, const void* keys, uint32_t k, int key_width, void* slot_key,
-                             hipStream_t st);
-// one-dispatch forms (k <= 8192): resolve_indices + offs[] also into coherent host memory + flag = gen;
-// fill_slots + the first m slot keys into coherent host memory + flag = gen (4- / 8-byte keys)
+// Resolve: fill phase for slots in [base, base+n) and winners of batch_win; resets batch_win.  With a
+// publication (k <= 8192) one workgroup does it and publishes; small: as one 256-thread workgroup where
+// k <= 2048 (a resolve running beside K1 on a second stream).  sb.slot_idx may be null without one, for
+// 4- / 8-byte keys only.
+hipError_t launch_resolve(const SlotBlock& sb, const Batch& b, const Publication& pub, hipStream_t st,
+                          bool small = false);
+// index-only batches: resolve into slot_idx with offs[k] = the batch offset of each slot's new element
+// (-1: none), published too (pub.dst takes the k offsets, pub.m unused) when resolve_indices_publish_ok;
+// then the caller's keys into the changed slots, with the first pub.m slot keys published when
+// fill_slots_publish_ok (k <= 8192; 4- / 8-byte keys)
 bool resolve_indices_publish_ok(uint32_t k);
-hipError_t launch_resolve_indices_publish(int64_t base, int64_t n, uint32_t k, unsigned long long* batch_win,
-                                          int64_t* slot_idx, bool fresh, void* slot_key, int key_width, int64_t* offs,
-                                          int64_t* offs_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st);
+hipError_t launch_resolve_indices(const SlotBlock& sb, const Batch& b, int64_t* offs, const Publication& pub,
+                                  hipStream_t st);
 bool fill_slots_publish_ok(uint32_t k, int key_width);
-hipError_t launch_fill_slots_publish(const int64_t* offs, const void* keys, uint32_t k, int key_width, void* slot_key,
-                                     int64_t m, void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st);
+hipError_t launch_fill_slots(const int64_t* offs, const void* keys, const SlotBlock& sb, const Publication& pub,
+                             hipStream_t st);
 // K1': events (1-based pos, slot) -> batch_win
 hipError_t launch_replay_events(const int64_t* ev_pos, const int32_t* ev_slot, int64_t n_events,
                                 uint32_t k, unsigned long long* batch_win, hipStream_t st);
@@ -236,21 +246,15 @@ hipError_t launch_segdistinct_rows_merge(const void* part_rows, int key_width, c
                                          const int64_t* part_counts, int32_t parts, int64_t num_states, uint32_t k,
                                          void* state_rows, int64_t* state_hashes, int64_t* state_counts,
                                          hipStream_t st);
-// merge of exported element states: per slot max index among parts (and current state)
-hipError_t launch_merge_slots(const int64_t* idx_parts, const void* key_parts, int key_width,
-                              int32_t parts, int64_t part_len, uint32_t k, int64_t* slot_idx,
-                              void* slot_key, hipStream_t st);
+// merge of exported element states: per slot the largest index among the parts and the current state
+hipError_t launch_merge_slots(const int64_t* idx_parts, const void* key_parts, int32_t parts, int64_t part_len,
+                              const SlotBlock& sb, hipStream_t st);
 
-// packed combine rows: [slot_idx(k) | keys as int64 (k)]
-hipError_t launch_export_packed(const int64_t* slot_idx, const void* slot_key, int key_width, uint32_t k,
-                                int64_t* row, hipStream_t st);
-hipError_t launch_merge_packed(const int64_t* rows, int32_t parts, int64_t stride, uint32_t k, int64_t* slot_idx,
-                               void* slot_key, int key_width, hipStream_t st);
-
-// merge of packed rows + publication of the first m keys (k <= 8192, key_width 4 / 8)
-hipError_t launch_merge_packed_publish(const int64_t* rows, int32_t parts, int64_t stride, uint32_t k,
-                                       int64_t* slot_idx, void* slot_key, int key_width, int64_t m, void* dst_host_dev,
-                                       uint32_t* flag_dev, uint32_t gen, hipStream_t st);
+// packed combine rows: [slot_idx(k) | keys as int64 (k)] (byte keys: k keys of key_width / 4 words);
+// the merge publishes the first pub.m keys too (k <= 8192, key_width 4 / 8)
+hipError_t launch_export_packed(const SlotBlock& sb, int64_t* row, hipStream_t st);
+hipError_t launch_merge_packed(const int64_t* rows, int32_t parts, int64_t stride, const SlotBlock& sb,
+                               const Publication& pub, hipStream_t st);
 
 // ---- distinct (bottom-k over the scrambled hash) --------------------------------------------
 // The target of a speculative publication: the engine enqueues the merged set's publication into

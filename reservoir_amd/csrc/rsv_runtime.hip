@@ -352,12 +352,16 @@ rsv_status ensure_events(rsv_sampler* s, int64_t n) {
     return RSV_OK;
 }
 
+inline SlotBlock slot_block(const rsv_sampler* s) {
+    return SlotBlock{s->batch_win, s->slot_idx, s->slot_key, s->k, s->kw};
+}
+
 // slot arrays of a fresh handle: slot_key = 0, slot_idx = -1 (empty), batch_win = 0, on the
 // handle's current stream before its first use (creation itself enqueues no device work)
 rsv_status ensure_slots(rsv_sampler* s) {
     if (s->slots_init || s->cfg.kind != RSV_KIND_ELEMENTS) return RSV_OK;
     touch(s);
-    RSV_HIP_TRY(launch_init_slots(s->slot_key, s->kw, s->slot_idx, s->batch_win, s->k, s->stream, s->k1_ticket));
+    RSV_HIP_TRY(launch_init_slots(slot_block(s), s->stream, s->k1_ticket));
     s->slots_init = s->win_zero = true;
     s->pub_valid = false;
     return RSV_OK;
@@ -401,23 +405,50 @@ bool give_clean_slots(void* p, uint32_t k, int kw, int device) {
 
 constexpr int64_t kPublishMaxBytes = 1 << 20;
 
+// A publication target: `bytes` of coherent, mapped host memory and one 64-byte flag line behind it,
+// with their device aliases; the flag starts at the generation `gen` (nothing published yet).
+rsv_status alloc_flagged(size_t bytes, uint32_t gen, void** host, void** dev, uint32_t** flag, uint32_t** flag_dev) {
+    const size_t flag_off = (bytes + 63) & ~(size_t)63;
+    RSV_HIP_TRY(pool_host_alloc(host, flag_off + 64, hipHostMallocCoherent | hipHostMallocMapped));
+    RSV_HIP_TRY(hipHostGetDevicePointer(dev, *host, 0));
+    *flag = (uint32_t*)((uint8_t*)*host + flag_off);
+    *flag_dev = (uint32_t*)((uint8_t*)*dev + flag_off);
+    **flag = gen;
+    return RSV_OK;
+}
+
 rsv_status ensure_result_buffer(rsv_sampler* s) {
     if (s->result_h) return RSV_OK;
     const size_t bytes = (size_t)s->k * s->kw;
     if ((int64_t)bytes <= kPublishMaxBytes) {
-        const size_t flag_off = (bytes + 63) & ~(size_t)63;
-        RSV_HIP_TRY(pool_host_alloc(&s->result_h, flag_off + 64, hipHostMallocCoherent | hipHostMallocMapped));
-        void* dev = nullptr;
-        RSV_HIP_TRY(hipHostGetDevicePointer(&dev, s->result_h, 0));
-        s->result_dev = dev;
-        s->result_flag = (uint32_t*)((uint8_t*)s->result_h + flag_off);
-        s->result_flag_dev = (uint32_t*)((uint8_t*)dev + flag_off);
-        *s->result_flag = s->result_gen;
+        if (rsv_status st = alloc_flagged(bytes, s->result_gen, &s->result_h, &s->result_dev, &s->result_flag,
+                                          &s->result_flag_dev))
+            return st;
         s->result_publish = true;
     } else {
         RSV_HIP_TRY(pool_host_alloc(&s->result_h, bytes, hipHostMallocDefault));
     }
     return RSV_OK;
+}
+
+// The publish step of a launch that can also publish the reservoir's first min(count, k) keys.
+// begin_publish: may it (`allowed`: the form's own limit on k and key width; then a coherent result
+// buffer has to exist), and if so with which target and generation -- *pub, none when it may not.
+// record_publish, once the launch is enqueued: what result() can rely on.
+rsv_status begin_publish(rsv_sampler* s, bool allowed, int64_t count, Publication* pub) {
+    *pub = Publication{};
+    if (!allowed) return RSV_OK;
+    if (rsv_status st = ensure_result_buffer(s)) return st;
+    if (s->result_publish)
+        *pub = Publication{std::min<int64_t>(count, (int64_t)s->k), s->result_dev, s->result_flag_dev, ++s->result_gen};
+    return RSV_OK;
+}
+
+void record_publish(rsv_sampler* s, const Publication& pub) {
+    s->pub_valid = pub.dst != nullptr;
+    if (!pub.dst) return;
+    s->pub_ops = s->ops;  // the last work of this group
+    s->pub_gen = pub.gen;
 }
 
 constexpr uint32_t kFusedPublishMaxK = 8192;  // resolve_publish: one workgroup, <= 8 slots per lane
@@ -438,22 +469,70 @@ bool resolve_small() {
 rsv_status resolve_batch(rsv_sampler* s, const void* keys, int64_t base, int64_t n, bool fresh,
                          hipStream_t rst = nullptr) {
     if (!rst) rst = s->stream;
-    if (s->k <= kFusedPublishMaxK) {
-        if (rsv_status st = ensure_result_buffer(s)) return st;
-        if (s->result_publish) {
-            const uint32_t gen = ++s->result_gen;
-            const int64_t m = std::min<int64_t>(base + n, (int64_t)s->k);
-            RSV_HIP_TRY(launch_resolve_publish(keys, s->kw, base, n, s->k, s->batch_win, s->slot_key, s->slot_idx,
-                                               fresh, m, s->result_dev, s->result_flag_dev, gen, rst,
-                                               rst != s->stream && resolve_small()));
-            s->pub_ops = s->ops;  // the last work of this group
-            s->pub_gen = gen;
-            s->pub_valid = true;
-            return RSV_OK;
-        }
+    Publication pub;
+    if (rsv_status st = begin_publish(s, s->k <= kFusedPublishMaxK, base + n, &pub)) return st;
+    RSV_HIP_TRY(launch_resolve(slot_block(s), Batch{keys, base, n, fresh}, pub, rst,
+                               rst != s->stream && resolve_small()));
+    record_publish(s, pub);
+    return RSV_OK;
+}
+
+// The frame of one element batch at global indices [count, count + n).  begin: a new group of device
+// work; a never-used slot block gets its full init; *fresh says that the slots were never initialised
+// (a recycled clean block: the resolve marks the untouched ones empty); batch_win is no longer known
+// zero until the batch's resolve is enqueued, which is where end stands.
+rsv_status begin_element_batch(rsv_sampler* s, bool* fresh) {
+    touch(s);
+    if (!s->win_zero) {  // never-used block: full init
+        RSV_HIP_TRY(launch_init_slots(slot_block(s), s->stream, s->k1_ticket));
+        s->slots_init = s->win_zero = true;
     }
-    RSV_HIP_TRY(launch_resolve(keys, s->kw, base, n, s->k, s->batch_win, s->slot_key, s->slot_idx, fresh, rst));
-    s->pub_valid = false;
+    *fresh = !s->slots_init;
+    s->win_zero = false;
+    return RSV_OK;
+}
+
+void end_element_batch(rsv_sampler* s, int64_t n) {
+    s->slots_init = s->win_zero = true;
+    s->count += n;
+}
+
+// java_l: the reference's own Algorithm-L events of the batch [base, base + n) (S:261-273 skips by
+// them), computed on the host, uploaded and replayed into batch_win; *n_events of them.  stage_b >= 0:
+// the batch is staging buffer stage_b, and the uploads read that buffer's pinned event buffers -- its
+// previous flush has completed (stage_slow waited for it), and its stage_free event releases them.
+// Else they read the handle's pageable event vectors, which the next batch reuses.
+rsv_status replay_java_l(rsv_sampler* s, int64_t base, int64_t n, int stage_b, int64_t* n_events) {
+    s->ev_pos_h.clear();
+    s->ev_slot_h.clear();
+    s->algo_l.events(base, n, s->ev_pos_h, s->ev_slot_h);
+    const int64_t ne = *n_events = (int64_t)s->ev_pos_h.size();
+    if (!ne) return RSV_OK;
+    if (rsv_status st = ensure_events(s, ne)) return st;
+    const void* pos_src = s->ev_pos_h.data();
+    const void* slot_src = s->ev_slot_h.data();
+    if (stage_b >= 0) {
+        if (s->stage_ev_cap[stage_b] < ne) {
+            const int64_t cap = std::max<int64_t>(ne, 2 * s->stage_ev_cap[stage_b]);
+            pool_host_free(s->stage_ev_pos[stage_b]);
+            pool_host_free(s->stage_ev_slot[stage_b]);
+            s->stage_ev_pos[stage_b] = nullptr;
+            s->stage_ev_slot[stage_b] = nullptr;
+            s->stage_ev_cap[stage_b] = 0;
+            RSV_HIP_TRY(pool_host_alloc((void**)&s->stage_ev_pos[stage_b], cap * 8, hipHostMallocDefault));
+            RSV_HIP_TRY(pool_host_alloc((void**)&s->stage_ev_slot[stage_b], cap * 4, hipHostMallocDefault));
+            s->stage_ev_cap[stage_b] = cap;
+        }
+        memcpy(s->stage_ev_pos[stage_b], pos_src, ne * 8);
+        memcpy(s->stage_ev_slot[stage_b], slot_src, ne * 4);
+        pos_src = s->stage_ev_pos[stage_b];
+        slot_src = s->stage_ev_slot[stage_b];
+    }
+    RSV_HIP_TRY(hipMemcpyAsync(s->ev_pos_d, pos_src, ne * 8, hipMemcpyHostToDevice, s->stream));
+    RSV_HIP_TRY(hipMemcpyAsync(s->ev_slot_d, slot_src, ne * 4, hipMemcpyHostToDevice, s->stream));
+    const bool pm = prof_begin(s, s->stream);
+    RSV_HIP_TRY(launch_replay_events(s->ev_pos_d, s->ev_slot_d, ne, s->k, s->batch_win, s->stream));
+    prof_end(s, s->stream, pm);
     return RSV_OK;
 }
 
@@ -462,18 +541,8 @@ rsv_status resolve_batch(rsv_sampler* s, const void* keys, int64_t base, int64_t
 rsv_status process_device_batch(rsv_sampler* s, const void* keys, const int64_t* hashes, int64_t n,
                                 int stage_b = -1) {
     if (n <= 0) return RSV_OK;
-    touch(s);
-    const int64_t base = s->count;
-    bool fresh = false;
-    if (s->cfg.kind == RSV_KIND_ELEMENTS) {
-        if (!s->win_zero) {  // never-used block: full init
-            RSV_HIP_TRY(launch_init_slots(s->slot_key, s->kw, s->slot_idx, s->batch_win, s->k, s->stream, s->k1_ticket));
-            s->slots_init = s->win_zero = true;
-        }
-        fresh = !s->slots_init;
-        s->win_zero = false;  // until this batch's resolve is enqueued
-    }
     if (s->cfg.kind == RSV_KIND_DISTINCT) {
+        touch(s);
         // large batches publish the merged set speculatively (DistinctEngine::spec_target: set mode behind
         // its last merge, ordered mode behind the scheduled pass) -- only where a publication can
         // happen at all (a coherent result buffer of k keys); other samplers (huge k, device-only
@@ -491,38 +560,15 @@ rsv_status process_device_batch(rsv_sampler* s, const void* keys, const int64_t*
             s->pub_ops = s->ops;
             s->pub_gen = gen;
         }
-    } else if (s->cfg.engine == RSV_ENGINE_JAVA_L) {
-        s->ev_pos_h.clear();
-        s->ev_slot_h.clear();
-        s->algo_l.events(base, n, s->ev_pos_h, s->ev_slot_h);
-        const int64_t ne = (int64_t)s->ev_pos_h.size();
-        if (ne) {
-            if (rsv_status st = ensure_events(s, ne)) return st;
-            const void* pos_src = s->ev_pos_h.data();
-            const void* slot_src = s->ev_slot_h.data();
-            if (stage_b >= 0) {  // pinned: stage_b's previous flush has completed (stage_slow waited for it)
-                if (s->stage_ev_cap[stage_b] < ne) {
-                    const int64_t cap = std::max<int64_t>(ne, 2 * s->stage_ev_cap[stage_b]);
-                    pool_host_free(s->stage_ev_pos[stage_b]);
-                    pool_host_free(s->stage_ev_slot[stage_b]);
-                    s->stage_ev_pos[stage_b] = nullptr;
-                    s->stage_ev_slot[stage_b] = nullptr;
-                    s->stage_ev_cap[stage_b] = 0;
-                    RSV_HIP_TRY(pool_host_alloc((void**)&s->stage_ev_pos[stage_b], cap * 8, hipHostMallocDefault));
-                    RSV_HIP_TRY(pool_host_alloc((void**)&s->stage_ev_slot[stage_b], cap * 4, hipHostMallocDefault));
-                    s->stage_ev_cap[stage_b] = cap;
-                }
-                memcpy(s->stage_ev_pos[stage_b], pos_src, ne * 8);
-                memcpy(s->stage_ev_slot[stage_b], slot_src, ne * 4);
-                pos_src = s->stage_ev_pos[stage_b];
-                slot_src = s->stage_ev_slot[stage_b];
-            }
-            RSV_HIP_TRY(hipMemcpyAsync(s->ev_pos_d, pos_src, ne * 8, hipMemcpyHostToDevice, s->stream));
-            RSV_HIP_TRY(hipMemcpyAsync(s->ev_slot_d, slot_src, ne * 4, hipMemcpyHostToDevice, s->stream));
-            const bool pm = prof_begin(s, s->stream);
-            RSV_HIP_TRY(launch_replay_events(s->ev_pos_d, s->ev_slot_d, ne, s->k, s->batch_win, s->stream));
-            prof_end(s, s->stream, pm);
-        }
+        s->count += n;
+        return RSV_OK;
+    }
+    const int64_t base = s->count;
+    bool fresh;
+    if (rsv_status st = begin_element_batch(s, &fresh)) return st;
+    if (s->cfg.engine == RSV_ENGINE_JAVA_L) {
+        int64_t ne = 0;
+        if (rsv_status st = replay_java_l(s, base, n, stage_b, &ne)) return st;
         if (rsv_status st = resolve_batch(s, keys, base, n, fresh)) return st;
         // pageable host event vectors are reused by the next batch (a staged batch's pinned copies
         // are released by its stage_free event instead)
@@ -533,7 +579,7 @@ rsv_status process_device_batch(rsv_sampler* s, const void* keys, const int64_t*
         // Fused (one dispatch, the last workgroup resolves) for batches up to 2^27 draws, where the
         // saved dispatch is a visible share of the step; above that the two-dispatch form is faster
         // (C2: 112.5 vs 114.0 us per step, r02aa: the fused tail runs on one workgroup of the
-        // otherwise idle chip, while resolve_publish_kernel's dispatch overlaps K1's drain; round 6,
+        // otherwise idle chip, while the publishing resolve_kernel's dispatch overlaps K1's drain; round 6,
         // the two-group K1: 96.7 vs 83.0-83.7 us per launch, 97.2 vs 88.6-89.5 us per step --
         // every workgroup's ticket wait holds its slot, profiles/r06/bench_k1_fuse_ab.jsonl).
         // RSV_K1_FUSE=0 / =1 forces either form (A/B measurements).
@@ -544,21 +590,15 @@ rsv_status process_device_batch(rsv_sampler* s, const void* keys, const int64_t*
         constexpr uint64_t kFuseMaxDraws = 1ull << 27;
         const bool fuse = (fuse_mode == 1 || (fuse_mode == 2 && (hi <= lo || hi - lo <= kFuseMaxDraws))) &&
                           k1_fused_ok(lo, hi, s->k, s->kw);
-        if (fuse) {
-            if (rsv_status st = ensure_result_buffer(s)) return st;
-        }
-        if (fuse && s->result_publish) {
+        Publication pub;
+        if (rsv_status st = begin_publish(s, fuse, base + n, &pub)) return st;
+        if (pub.dst) {
             // one dispatch: K1, then the last workgroup resolves and publishes (resolve_batch's form)
-            const uint32_t gen = ++s->result_gen;
-            const int64_t m = std::min<int64_t>(base + n, (int64_t)s->k);
             const bool pm = prof_begin(s, s->stream);
-            RSV_HIP_TRY(launch_k1_resolve_publish(dp, s->k, lo, hi, s->batch_win, s->k1_ticket, keys, s->kw, base, n,
-                                                  s->slot_key, s->slot_idx, fresh, m, s->result_dev,
-                                                  s->result_flag_dev, gen, s->stream));
+            RSV_HIP_TRY(launch_k1_resolve_publish(dp, lo, hi, slot_block(s), s->k1_ticket, Batch{keys, base, n, fresh},
+                                                  pub, s->stream));
             prof_end(s, s->stream, pm);
-            s->pub_ops = s->ops;
-            s->pub_gen = gen;
-            s->pub_valid = true;
+            record_publish(s, pub);
         } else {
             const bool pm = prof_begin(s, s->stream);
             RSV_HIP_TRY(launch_k1_last_writer(dp, s->k, lo, hi, s->batch_win, s->stream));
@@ -576,8 +616,7 @@ rsv_status process_device_batch(rsv_sampler* s, const void* keys, const int64_t*
             }
         }
     }
-    if (s->cfg.kind == RSV_KIND_ELEMENTS) s->slots_init = s->win_zero = true;
-    s->count = base + n;
+    end_element_batch(s, n);
     return RSV_OK;
 }
 
@@ -617,46 +656,26 @@ rsv_status index_batch(rsv_sampler* s, int64_t n, const int64_t** offs_out) {
     if (!s->idx_bak_d) RSV_HIP_TRY(pool_device_alloc((void**)&s->idx_bak_d, (size_t)s->k * 8));
     const bool publish = resolve_indices_publish_ok(s->k);
     if (!s->offs_h) {
-        if (publish) {  // k offsets + one 64-B flag line, coherent and mapped
-            const size_t flag_off = ((size_t)s->k * 8 + 63) & ~(size_t)63;
-            RSV_HIP_TRY(pool_host_alloc((void**)&s->offs_h, flag_off + 64, hipHostMallocCoherent | hipHostMallocMapped));
-            void* dev = nullptr;
-            RSV_HIP_TRY(hipHostGetDevicePointer(&dev, s->offs_h, 0));
-            s->offs_dev = (int64_t*)dev;
-            s->offs_flag = (uint32_t*)((uint8_t*)s->offs_h + flag_off);
-            s->offs_flag_dev = (uint32_t*)((uint8_t*)dev + flag_off);
-            *s->offs_flag = s->offs_gen;
+        if (publish) {
+            if (rsv_status st = alloc_flagged((size_t)s->k * 8, s->offs_gen, (void**)&s->offs_h, (void**)&s->offs_dev,
+                                              &s->offs_flag, &s->offs_flag_dev))
+                return st;
         } else {
             RSV_HIP_TRY(pool_host_alloc((void**)&s->offs_h, (size_t)s->k * 8, hipHostMallocDefault));
         }
     }
-    touch(s);
     const int64_t base = s->count;
-    if (!s->win_zero) {  // never-used block: full init
-        RSV_HIP_TRY(launch_init_slots(s->slot_key, s->kw, s->slot_idx, s->batch_win, s->k, s->stream, s->k1_ticket));
-        s->slots_init = s->win_zero = true;
-    }
-    const bool fresh = !s->slots_init;
-    s->win_zero = false;
+    bool fresh;
+    if (rsv_status st = begin_element_batch(s, &fresh)) return st;
     // the state rsv_abort_indexed restores (a throwing `map` leaves the slots consistent)
     s->idx_fresh = fresh;
     s->idx_base = base;
     s->idx_algo_l = s->algo_l;
     if (!fresh)
         RSV_HIP_TRY(hipMemcpyAsync(s->idx_bak_d, s->slot_idx, (size_t)s->k * 8, hipMemcpyDeviceToDevice, s->stream));
-    if (s->cfg.engine == RSV_ENGINE_JAVA_L) {  // the reference's own events (S:261-273 skips by them)
-        s->ev_pos_h.clear();
-        s->ev_slot_h.clear();
-        s->algo_l.events(base, n, s->ev_pos_h, s->ev_slot_h);
-        const int64_t ne = (int64_t)s->ev_pos_h.size();
-        if (ne) {
-            if (rsv_status st = ensure_events(s, ne)) return st;
-            RSV_HIP_TRY(hipMemcpyAsync(s->ev_pos_d, s->ev_pos_h.data(), ne * 8, hipMemcpyHostToDevice, s->stream));
-            RSV_HIP_TRY(hipMemcpyAsync(s->ev_slot_d, s->ev_slot_h.data(), ne * 4, hipMemcpyHostToDevice, s->stream));
-            const bool pm = prof_begin(s, s->stream);
-            RSV_HIP_TRY(launch_replay_events(s->ev_pos_d, s->ev_slot_d, ne, s->k, s->batch_win, s->stream));
-            prof_end(s, s->stream, pm);
-        }
+    if (s->cfg.engine == RSV_ENGINE_JAVA_L) {
+        int64_t ne = 0;  // the event vectors are read by copies that precede the waits below in stream order
+        if (rsv_status st = replay_java_l(s, base, n, -1, &ne)) return st;
     } else {
         const DrawParams dp{s->cfg.seed, s->cfg.stream_id};
         const uint64_t lo = std::max<uint64_t>((uint64_t)base, s->k), hi = (uint64_t)(base + n);
@@ -664,22 +683,20 @@ rsv_status index_batch(rsv_sampler* s, int64_t n, const int64_t** offs_out) {
         RSV_HIP_TRY(launch_k1_last_writer(dp, s->k, lo, hi, s->batch_win, s->stream));
         prof_end(s, s->stream, pm);
     }
+    const Batch batch{nullptr, base, n, fresh};
     if (publish) {  // the offsets straight into coherent host memory + flag: no copy, no stream sync
         const uint32_t gen = ++s->offs_gen;
-        RSV_HIP_TRY(launch_resolve_indices_publish(base, n, s->k, s->batch_win, s->slot_idx, fresh, s->slot_key, s->kw,
-                                                   s->idx_offs_d, s->offs_dev, s->offs_flag_dev, gen, s->stream));
-        // the event vectors above were read by copies that precede the flag in stream order
+        RSV_HIP_TRY(launch_resolve_indices(slot_block(s), batch, s->idx_offs_d,
+                                           Publication{0, s->offs_dev, s->offs_flag_dev, gen}, s->stream));
         if (rsv_status st = spin_flag(s, s->offs_flag, gen, "index batch")) return st;
         if (s->offs_gen == gen) s->ops_done = s->ops;  // the publication was this handle's last work
     } else {
-        RSV_HIP_TRY(launch_resolve_indices(base, n, s->k, s->batch_win, s->slot_idx, fresh, s->slot_key, s->kw,
-                                           s->idx_offs_d, s->stream));
+        RSV_HIP_TRY(launch_resolve_indices(slot_block(s), batch, s->idx_offs_d, Publication{}, s->stream));
         RSV_HIP_TRY(hipMemcpyAsync(s->offs_h, s->idx_offs_d, (size_t)s->k * 8, hipMemcpyDeviceToHost, s->stream));
         RSV_HIP_TRY(sync_stream(s));
     }
-    s->slots_init = s->win_zero = true;
+    end_element_batch(s, n);
     s->pub_valid = false;
-    s->count = base + n;
     *offs_out = s->offs_h;
     return RSV_OK;
 }
@@ -698,22 +715,10 @@ rsv_status ensure_gather(rsv_sampler* s) {
 // kernel in stream order.
 rsv_status fill_gathered(rsv_sampler* s) {
     touch(s);
-    if (fill_slots_publish_ok(s->k, s->kw)) {
-        if (rsv_status st = ensure_result_buffer(s)) return st;
-        if (s->result_publish) {
-            const uint32_t gen = ++s->result_gen;
-            const int64_t m = std::min<int64_t>(s->count, (int64_t)s->k);
-            RSV_HIP_TRY(launch_fill_slots_publish(s->idx_offs_d, s->gath_dev, s->k, s->kw, s->slot_key, m,
-                                                  s->result_dev, s->result_flag_dev, gen, s->stream));
-            s->pub_ops = s->ops;
-            s->pub_gen = gen;
-            s->pub_valid = true;
-            s->keys_owed = false;
-            return RSV_OK;
-        }
-    }
-    RSV_HIP_TRY(launch_fill_slots(s->idx_offs_d, s->gath_dev, s->k, s->kw, s->slot_key, s->stream));
-    s->pub_valid = false;
+    Publication pub;
+    if (rsv_status st = begin_publish(s, fill_slots_publish_ok(s->k, s->kw), s->count, &pub)) return st;
+    RSV_HIP_TRY(launch_fill_slots(s->idx_offs_d, s->gath_dev, slot_block(s), pub, s->stream));
+    record_publish(s, pub);
     s->keys_owed = false;
     return RSV_OK;
 }
@@ -1112,7 +1117,7 @@ rsv_status rsv_abort_indexed(rsv_sampler* s) {
     DeviceGuard g(s->device);
     touch(s);
     if (s->idx_fresh)  // the slots were never initialised before the batch: empty them again
-        RSV_HIP_TRY(launch_init_slots(s->slot_key, s->kw, s->slot_idx, s->batch_win, s->k, s->stream, s->k1_ticket));
+        RSV_HIP_TRY(launch_init_slots(slot_block(s), s->stream, s->k1_ticket));
     else  // the changed slots still hold their old keys: their old indices make them whole again
         RSV_HIP_TRY(hipMemcpyAsync(s->slot_idx, s->idx_bak_d, (size_t)s->k * 8, hipMemcpyDeviceToDevice, s->stream));
     RSV_HIP_TRY(sync_stream(s));
@@ -1260,12 +1265,12 @@ static rsv_status result_impl(rsv_sampler* s, void* out, int64_t cap, int64_t* o
             if (s->result_publish) {  // publish kernel + flag spin (no D2H copy, no stream sync)
                 uint32_t gen = s->pub_gen;
                 if (!s->pub_valid) {  // the last batch's resolve did not publish the current slots
-                    gen = ++s->result_gen;
                     touch(s);
-                    RSV_HIP_TRY(launch_publish(src, m * s->kw, s->result_dev, s->result_flag_dev, gen, s->stream));
-                    s->pub_ops = s->ops;
-                    s->pub_gen = gen;
-                    s->pub_valid = true;
+                    Publication pub;
+                    if (rsv_status st = begin_publish(s, true, m, &pub)) return st;
+                    gen = pub.gen;
+                    RSV_HIP_TRY(launch_publish(src, m * s->kw, pub.dst, pub.flag, gen, s->stream));
+                    record_publish(s, pub);
                 }
                 if (rsv_status st = wait_flag(s, gen)) return st;
                 if (s->pub_valid && s->pub_ops == s->ops && s->result_gen == gen) s->ops_done = s->ops;
@@ -1484,8 +1489,7 @@ rsv_status rsv_merge_state(rsv_sampler* s, const int64_t* idx_dev, const void* k
         if (part_len < (int64_t)s->k) return fail(RSV_E_ILLEGAL_ARGUMENT, "part_len < k");
         if (parts > 0 && !idx_dev) return fail(RSV_E_NULL_POINTER, "idx_dev is NULL");
         if (rsv_status st = ensure_slots(s)) return st;
-        RSV_HIP_TRY(launch_merge_slots(idx_dev, keys_dev, s->kw, parts, part_len, s->k, s->slot_idx, s->slot_key,
-                                       s->stream));
+        RSV_HIP_TRY(launch_merge_slots(idx_dev, keys_dev, parts, part_len, slot_block(s), s->stream));
         s->pub_valid = false;
     }
     if (total_count > s->count) s->count = total_count;
@@ -1561,7 +1565,7 @@ rsv_status rsv_export_packed(rsv_sampler* s, int64_t* row_dev) {
         return RSV_OK;
     }
     if (rsv_status st = ensure_slots(s)) return st;
-    RSV_HIP_TRY(launch_export_packed(s->slot_idx, s->slot_key, s->kw, s->k, row_dev, s->stream));
+    RSV_HIP_TRY(launch_export_packed(slot_block(s), row_dev, s->stream));
     if (s->own_stream) RSV_HIP_TRY(sync_stream(s));
     return RSV_OK;
 }
@@ -1599,26 +1603,11 @@ rsv_status rsv_merge_packed(rsv_sampler* s, const int64_t* rows_dev, int32_t par
         if (std::min<int64_t>(total_count, s->k) != std::min<int64_t>(s->count, s->k)) s->pub_valid = false;
         s->count = total_count;
     }
-    if (parts > 0) {
-        bool fused = false;
-        if (s->k <= kFusedPublishMaxK && s->kw <= 8) {  // merge + publish in one dispatch
-            if (rsv_status st = ensure_result_buffer(s)) return st;
-            if (s->result_publish) {
-                const uint32_t gen = ++s->result_gen;
-                const int64_t m = std::min<int64_t>(s->count, (int64_t)s->k);
-                RSV_HIP_TRY(launch_merge_packed_publish(rows_dev, parts, row_stride, s->k, s->slot_idx, s->slot_key,
-                                                        s->kw, m, s->result_dev, s->result_flag_dev, gen, s->stream));
-                s->pub_gen = gen;
-                s->pub_valid = true;
-                s->pub_ops = s->ops;
-                fused = true;
-            }
-        }
-        if (!fused) {
-            RSV_HIP_TRY(launch_merge_packed(rows_dev, parts, row_stride, s->k, s->slot_idx, s->slot_key, s->kw,
-                                            s->stream));
-            s->pub_valid = false;
-        }
+    if (parts > 0) {  // for small reservoirs of Int / Long keys: merge + publish in one dispatch
+        Publication pub;
+        if (rsv_status st = begin_publish(s, s->k <= kFusedPublishMaxK && s->kw <= 8, s->count, &pub)) return st;
+        RSV_HIP_TRY(launch_merge_packed(rows_dev, parts, row_stride, slot_block(s), pub, s->stream));
+        record_publish(s, pub);
     }
     if (s->own_stream) RSV_HIP_TRY(sync_stream(s));
     return RSV_OK;
@@ -2026,7 +2015,8 @@ rsv_status rsv_replay_events(const void* keys_dev, int64_t n, int32_t key_width,
     RSV_HIP_TRY(hipMallocAsync((void**)&win, (size_t)k * 8, st));
     hipError_t e = hipMemsetAsync(win, 0, (size_t)k * 8, st);
     if (e == hipSuccess) e = launch_replay_events(ev_pos_dev, ev_slot_dev, n_events, (uint32_t)k, win, st);
-    if (e == hipSuccess) e = launch_resolve(keys_dev, key_width, base_index, n, (uint32_t)k, win, reservoir_dev, nullptr, false, st);
+    if (e == hipSuccess) e = launch_resolve(SlotBlock{win, nullptr, reservoir_dev, (uint32_t)k, key_width}, Batch{keys_dev, base_index, n, false},
+                           Publication{}, st);
     hipError_t e2 = hipFreeAsync(win, st);
     RSV_HIP_TRY(e);
     RSV_HIP_TRY(e2);

@@ -7,8 +7,8 @@
    enough winners (~ k ln(hi / lo)) to mean something; every case first asserts that on the oracle.
 2. process_device_batch (rsv_runtime.hip) resolves a batch in one of four forms, chosen by
    kK1FusedMaxK = 2048 (k1_resolve_publish, one dispatch), kFuseMaxDraws = 2^27 (above it the
-   two-dispatch form) and kFusedPublishMaxK = 8192 (resolve_publish_kernel; above it resolve_kernel
-   and a publication at result()); with a resolve stream the second dispatch is
+   two-dispatch form) and kFusedPublishMaxK = 8192 (resolve_kernel<T, true>, which publishes; above it
+   resolve_kernel<T, false> and a publication at result()); with a resolve stream the second dispatch is
    resolve_publish_small_kernel<T, 2|4|8> for k <= 512 / 1024 / 2048.  RSV_K1_FUSE=0 and
    RSV_RESOLVE_SMALL=0 force the two-dispatch and the 1024-thread forms; the engine reads them once
    per process, so those cases run in child processes.  The tests do not inspect which kernel ran.
@@ -255,7 +255,7 @@ print("resolve forms ok", checked)
                          ids=["two_dispatch", "two_dispatch_1024_threads"])
 def test_resolve_forms(cuda, oracle, env):
     """RSV_K1_FUSE=0: every batch is k1_last_writer + a resolve dispatch -- on the sampler's own stream
-    resolve_publish_kernel with min(1024, roundup64(k)) threads (k = 1 .. 8192: 64 .. 1024 threads);
+    resolve_kernel<T, true> with min(1024, roundup64(k)) threads (k = 1 .. 8192: 64 .. 1024 threads);
     with set_resolve_stream resolve_publish_small_kernel<T, 2|4|8> up to k = 2048 and the 1024-thread
     form above.  RSV_RESOLVE_SMALL=0 as well: the 1024-thread form on the resolve stream everywhere.
     long and int keys; the batches of a sampler hit every branch of the resolve kernels (fill inside

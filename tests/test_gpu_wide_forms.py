@@ -3,7 +3,7 @@
 A byte-key handle takes its own kernel at every step (rsv_elements.hip): resolve_wide_kernel in its
 publishing (one workgroup of 64..1024 threads, k <= 8192 and k * W <= 2^20 bytes) and its grid
 launch, the byte loops of resolve_indices_kernel / resolve_indices_publish_kernel / fill_slots_kernel
-(host batches), merge_slots_wide_kernel, export_packed_wide_kernel, merge_packed_wide_kernel, the wide
+(host batches), merge_kernel<StridedWideParts>, export_packed_wide_kernel, merge_kernel<PackedWideRows>, the wide
 branch of init_slots_kernel and publish_kernel over m * W bytes.  Above either limit result() no
 longer waits for a published generation: k > 8192 publishes at result(), k * W > 2^20 copies through a
 pinned buffer.

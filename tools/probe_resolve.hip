@@ -1,4 +1,4 @@
-// probe_resolve.hip -- where the ~5 us of resolve_publish_kernel go (development probe, not part of
+// probe_resolve.hip -- where the ~5 us of the publishing resolve_kernel go (development probe, not part of
 // the library).  One workgroup resolves k = 1024 slots as rsv_elements.hip does: the slot's winner
 // index (win[j]) -> its key (a random 8-B read of a 8 GB key buffer) -> slot arrays + the first m keys
 // into coherent host memory -> a system-scope release of the flag.  Variants drop one stage at a
