@@ -724,6 +724,48 @@ rsv_status rsv_distinct_segmented_rows_ordered_update(const void* rows_dev, cons
                                                       int32_t* state_slots_dev, int64_t* state_counts_dev,
                                                       void* hip_stream);
 
+/* Segmented distinct for any B (Strings, case classes, tuples): the hash-only candidate pass of
+ * rsv_distinct_candidates for many streams in one launch, on caller-held state.  The engine reads
+ * hashes_dev[i] = hash(map(x_i)) alone, 8 bytes per element, and returns per segment, in arrival order, the
+ * positions RandomValues (S:383-412) could still admit; the caller keeps one exact replica per row (heap, set,
+ * maxHash), replays the candidates' elements into it and tells the next launch the replica's size and maxHash.
+ * State, the caller's device memory: shadow_hashes_dev[num_states*k] and shadow_counts_dev[num_states] (int64).
+ * Row r holds counts[r] distinct scrambled hashes ascending, the smallest the row has returned as candidates; a
+ * row with counts[r] == 0 is the empty sampler whatever its slots hold, so a stateless call is a call on zeroed
+ * counts.  set_sizes_dev / max_hashes_dev [num_states] (both or neither: exactly one is
+ * RSV_E_ILLEGAL_ARGUMENT) are the replicas' size and maxHash as of their last replay, read once per row.
+ * Segment b = hashes_dev[offsets[b] .. offsets[b+1]) goes into row r = stream_ids_dev[b], or r = b when
+ * stream_ids_dev is NULL (then num_segments <= num_states), seeded as java.util.Random(seed + stream_base + r):
+ * h = scramble(r0, r1, hash).  While the shadow holds fewer than k values and set_sizes[r] < k (or none is
+ * given) every element is a candidate, whatever its h.  Otherwise element i is a candidate iff h_i < bound,
+ * strictly, bound being the smaller of the shadow's k-th value (when it holds k) and max_hashes[r] (when
+ * set_sizes[r] >= k).  The shadow is merged lazily, so its k-th value may lag the exact one by up to one buffer of
+ * candidates (256 / 512 / 2048 / 8192 entries for k <= 64 / 256 / 1024 / 4096): more candidates, never fewer.
+ * Every element the reference admits is among them, and replaying them in order gives the reference's heap.
+ * Candidate j of segment b is written as (absolute index into hashes_dev, h) to out_pos_dev[b*cap + j] and
+ * out_hashes_dev[b*cap + j] ([num_segments*cap] each), j ascending with the index, while j < cap;
+ * out_counts_dev[b] receives the number found, stored or not, and 0 for a skipped segment (an id outside
+ * [0, num_states), or no elements).  A segment with out_counts[b] > cap overflowed: its state row is not
+ * written, and a rerun of that segment with cap >= out_counts[b] returns exactly out_counts[b] candidates.
+ * Otherwise the row's shadow and count are advanced in place (zeros beyond the count); a row that returned no
+ * candidate is not written.  The ids of one launch must be distinct (the caller's contract); rows no segment
+ * names are not touched.  A count is clamped into [0, k] before use and nothing else read from the state indexes
+ * memory.
+ * Abort rule: the state advances in place.  A caller that may drop a batch (a throwing map) keeps a copy of the
+ * rows the launch names and puts it back: a shadow that has seen hashes the replica never sampled is no longer a
+ * valid bound.
+ * Checks, before any device call: k out of range RSV_E_ILLEGAL_ARGUMENT; k > 4096 RSV_E_UNSUPPORTED; negative
+ * counts, cap < 1 or more segments than rows without ids RSV_E_ILLEGAL_ARGUMENT; num_segments == 0 RSV_OK with
+ * nothing touched; a NULL buffer RSV_E_NULL_POINTER (hashes_dev may be NULL only when every segment is empty,
+ * the state only when num_states == 0); one of set_sizes_dev / max_hashes_dev without the other.
+ * Stateless and stream-ordered on hip_stream: no host wait, no allocation.  All pointers are device pointers. */
+rsv_status rsv_distinct_segmented_candidates(const int64_t* hashes_dev, const int64_t* offsets_dev,
+                                             const int64_t* stream_ids_dev, int64_t num_segments, int64_t num_states,
+                                             int32_t k, uint64_t seed, uint64_t stream_base, int64_t* shadow_hashes_dev,
+                                             int64_t* shadow_counts_dev, const int64_t* set_sizes_dev,
+                                             const int64_t* max_hashes_dev, int64_t* out_pos_dev, int64_t* out_hashes_dev,
+                                             int64_t cap, int64_t* out_counts_dev, void* hip_stream);
+
 /* Event replay (K1'): apply eviction events (1-based position, slot) -- the
  * `samples(rand.nextInt(k)) = map(element)` writes of S:243-246 -- for elements at global indices
  * [base_index, base_index+n) held in keys_dev, onto reservoir_dev[k] (in/out, device).  Also

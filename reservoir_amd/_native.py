@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "rsv_sample_segmented_rows", "rsv_sample_segmented_rows_update", "rsv_sample_segmented_rows_merge",
     "rsv_distinct_segmented_ordered", "rsv_distinct_segmented_rows_ordered",
     "rsv_distinct_segmented_ordered_update", "rsv_distinct_segmented_rows_ordered_update",
+    "rsv_distinct_segmented_candidates",
 )
 
 
@@ -151,6 +152,7 @@ def load():
     L.rsv_distinct_segmented_rows_ordered_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, u64, u64, vp, vp, vp,
                                                              vp, vp]
     L.rsv_distinct_segmented_rows_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
+    L.rsv_distinct_segmented_candidates.argtypes = [vp, vp, vp, i64, i64, i32, u64, u64, vp, vp, vp, vp, vp, vp, i64, vp, vp]
     L.rsv_replay_events.argtypes = [vp, i64, i32, i64, vp, vp, i64, i32, vp, vp]
     L.rsv_export_draws.argtypes = [u64, u64, u64, i64, vp, vp]
     L.rsv_profile_enable.argtypes = [vp, i32]
@@ -187,7 +189,7 @@ def load():
                  "rsv_sample_segmented_rows", "rsv_sample_segmented_rows_update",
                  "rsv_sample_segmented_rows_merge", "rsv_distinct_segmented_ordered",
                  "rsv_distinct_segmented_rows_ordered", "rsv_distinct_segmented_ordered_update",
-                 "rsv_distinct_segmented_rows_ordered_update"):
+                 "rsv_distinct_segmented_rows_ordered_update", "rsv_distinct_segmented_candidates"):
         getattr(L, name).restype = i32
     if L.rsv_abi_version() != 1:
         raise ImportError("libreservoir_hip.so ABI version mismatch")

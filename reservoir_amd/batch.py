@@ -13,6 +13,9 @@ libreservoir_hip.so.  Every function raises if the engine is unavailable.
     SegmentedDistinctRows -- K5 resumed over byte keys: the rows move inside the caller-held state (update, merge)
     SegmentedDistinctRowsOrdered -- the ordered form resumed over byte keys: the heap arrays hold (hash, slot) and
                          the rows stay in their slots of the caller-held state (update)
+    distinct_segmented_candidates -- Sampler.distinct for any B over S streams: hashes in, candidate positions out
+    SegmentedObjectDistinct -- the same as live state: a hash shadow per row on the device, a RandomValues
+                         replica per row on the host, one candidate launch per batch (update)
     SegmentedSampler  -- K2 resumed: S Sampler.apply streams as caller-held state (keys, idx, next), fed in
                          pieces from any start index (update) and combined per slot by largest index (merge)
     sample_segmented_rows -- K2 over fixed-width byte keys (UUIDs): rows in, each slot's winning row out
@@ -641,6 +644,253 @@ class SegmentedDistinctRowsOrdered(_DistinctRowsState):
         raise N.ReservoirError(
             "SegmentedDistinctRowsOrdered has no merge: two heaps over disjoint parts of a stream do not determine the "
             "reference's heap over the whole stream; SegmentedDistinctRows.merge combines states in the set order")
+
+
+# rsv_segdistinct.hip, segcand_kernel: (largest k of the form, its candidate buffer).  A bound lags the exact running
+# one by at most one buffer of candidates.
+SEGMENTED_CANDIDATE_BUFFER = ((64, 256), (256, 512), (1024, 2048), (4096, 8192))
+
+
+def segmented_candidate_buffer(k: int) -> int:
+    return next(w for top, w in SEGMENTED_CANDIDATE_BUFFER if k <= top)
+
+
+def segmented_candidate_cap(k: int, longest: int) -> int:
+    """The default cap of a candidate launch from k and the longest segment: a fresh stream of n distinct hashes
+    admits about k (1 + ln(n / k)) elements, the lazy bound adds about one buffer (measured: 578 candidates per
+    stream against 312 admissions at n = 4096, k = 64, 24 272 against 17 208 at n = 2^17, k = 4096), and a quarter
+    on top covers the spread between streams; never more than the segment holds.  Too small only costs a rerun of
+    the segments that overflowed."""
+    import math
+
+    longest = max(int(longest), 1)
+    want = int(1.25 * (k * (1.0 + math.log(max(longest / k, 1.0))) + segmented_candidate_buffer(k)))
+    return max(1, min(longest, (want + 7) & ~7))
+
+
+def distinct_segmented_candidates(hashes, offsets, k: int, seed: int, stream_base: int = 0, cap=None, stream_ids=None,
+                                  state=None):
+    """The hash-only candidate pass of Sampler.distinct for any B over S segments in one launch.
+
+    hashes: int64 device tensor, hash(map(x)) per element; offsets int64 (B + 1,).  state: None (stateless: one
+    empty row per segment, and no stream_ids) or (shadow_hashes (S, k), shadow_counts (S,), set_sizes (S,) | None,
+    max_hashes (S,) | None), int64 device tensors of which the launch advances the first two in place.  Segment b goes into row stream_ids[b] (None: row b).  cap: candidates
+    stored per segment; None takes segmented_candidate_cap(k, longest segment), which reads the offsets (one host
+    wait).  Returns (pos (B, cap), hs (B, cap), counts (B,)) device tensors: the first min(counts[b], cap) entries
+    of row b are the absolute positions, ascending, and scrambled hashes of the elements RandomValues seeded
+    seed + stream_base + row could still admit; counts[b] > cap means segment b overflowed, its row was left as it
+    was and a rerun with cap >= counts[b] returns exactly counts[b] candidates.  1 <= k <= 4096.
+    """
+    import torch
+
+    L = N.load()
+    if not (hashes.is_cuda and offsets.is_cuda):
+        raise N.IllegalArgumentException("hashes and offsets must be device tensors")
+    if hashes.dtype != torch.int64 or offsets.dtype != torch.int64 or hashes.dim() != 1:
+        raise N.IllegalArgumentException("hashes must be 1-d int64 and offsets int64")
+    dev = hashes.device
+    offsets = offsets.contiguous()
+    B = max(offsets.numel() - 1, 0)
+    # an empty tensor has no address
+    hashes = hashes.contiguous() if hashes.numel() else torch.empty(1, dtype=torch.int64, device=dev)
+    if state is None:
+        if stream_ids is not None:
+            raise N.IllegalArgumentException("stream_ids= needs state=")
+        state = (torch.empty((B, max(int(k), 0)), dtype=torch.int64, device=dev),
+                 torch.zeros(B, dtype=torch.int64, device=dev), None, None)
+    sh, sc, sizes, maxh = state
+    if (sizes is None) != (maxh is None):
+        raise N.IllegalArgumentException("set_sizes and max_hashes come together")
+    S = sc.numel()
+    for t, shape in ((sh, (S, k)), (sc, (S,)), (sizes, (S,)), (maxh, (S,)), (stream_ids, (B,))):
+        if t is not None and (not t.is_cuda or t.dtype != torch.int64 or t.device != dev or tuple(t.shape) != shape
+                              or not t.is_contiguous()):
+            raise N.IllegalArgumentException("state and stream_ids must be contiguous int64 tensors on the hashes' "
+                                             "device, shaped (S, k), (S,), (S,), (S,) and (B,)")
+    if cap is None:
+        cap = segmented_candidate_cap(k, int((offsets[1:] - offsets[:-1]).max()) if B else 1)
+    cap = int(cap)
+    pos = torch.empty((B, max(cap, 0)), dtype=torch.int64, device=dev)
+    hs = torch.empty((B, max(cap, 0)), dtype=torch.int64, device=dev)
+    counts = torch.empty(B, dtype=torch.int64, device=dev)
+    N.check(L.rsv_distinct_segmented_candidates(
+        _ptr(hashes), _ptr(offsets), _ptr(stream_ids), B, S, k, seed & (2**64 - 1), stream_base & (2**64 - 1),
+        _ptr(sh) if S else None, _ptr(sc) if S else None, _ptr(sizes), _ptr(maxh), _ptr(pos), _ptr(hs), cap,
+        _ptr(counts), _stream_ptr(torch, dev)))
+    return pos, hs, counts
+
+
+class SegmentedObjectDistinct:
+    """S long-lived Sampler.distinct streams over any hashable B (str, tuple, dataclass), one launch per batch.
+
+    The engine reads hash(map(x)) only and returns per stream the positions the reference could still admit
+    (distinct_segmented_candidates); one exact replica per row (values.RandomValues: heap, set, maxHash) is
+    replayed over those elements alone.  Row r equals a single Sampler.distinct(k, key_type="object",
+    seed=seed + stream_base + r) handle fed the same elements.  State: shadow_hashes (S, k), shadow_counts (S,),
+    set_sizes (S,), max_hashes (S,) on the device, and the replicas on the host, created when a row is first named.
+    map_fn: applied to the candidates only (None: the elements are the B's).  cap: candidates stored per segment
+    (None: segmented_candidate_cap per batch).
+    """
+
+    def __init__(self, num_streams: int, k: int, seed: int, stream_base: int = 0, map_fn=None, cap=None, device=None):
+        import torch
+
+        from .values import LONG_MIN
+
+        N.load()
+        if num_streams < 0:
+            raise N.IllegalArgumentException("negative stream count")
+        if k <= 0:
+            raise N.IllegalArgumentException("k out of range")
+        if k > _SEG_DISTINCT_MAX_K:
+            raise N.ReservoirError(
+                f"SegmentedObjectDistinct holds k <= {_SEG_DISTINCT_MAX_K} per stream; use separate handles beyond")
+        if cap is not None and cap < 1:
+            raise N.IllegalArgumentException("cap must be at least 1")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise N.IllegalArgumentException("the state lives on the device")
+        self.num_streams, self.k = int(num_streams), int(k)
+        self.seed, self.stream_base = seed & (2**64 - 1), stream_base & (2**64 - 1)
+        self._map, self._cap = map_fn, cap
+        self.shadow_hashes = torch.empty((self.num_streams, self.k), dtype=torch.int64, device=dev)
+        self.shadow_counts = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
+        self.set_sizes = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
+        self.max_hashes = torch.full((self.num_streams,), LONG_MIN, dtype=torch.int64, device=dev)
+        self._values: dict = {}
+        self._candidates = self._launches = self._reruns = 0
+
+    def _state(self):
+        return self.shadow_hashes, self.shadow_counts, self.set_sizes, self.max_hashes
+
+    def _launch(self, torch, hashes, offsets, ids, cap):
+        """One launch; returns per segment (positions, hashes) as host lists, None where the segment overflowed,
+        and the counts."""
+        pos, hs, counts = distinct_segmented_candidates(hashes, offsets, self.k, self.seed, self.stream_base, cap=cap,
+                                                        stream_ids=ids, state=self._state())
+        self._launches += 1
+        cnt = counts.cpu()  # the first read-back
+        fits = counts <= cap
+        keep = (torch.arange(cap, device=pos.device)[None, :] < counts[:, None]) & fits[:, None]
+        p, h = pos[keep].cpu().tolist(), hs[keep].cpu().tolist()  # the second
+        out, a = [], 0
+        for c in cnt.tolist():
+            if c > cap:
+                out.append(None)
+            else:
+                out.append((p[a:a + c], h[a:a + c]))
+                a += c
+        return out, cnt
+
+    def update(self, elements, hashes, offsets, stream_ids=None, check_ids: bool = True):
+        """Segment b = elements[offsets[b]:offsets[b+1]] into row stream_ids[b] (None: row b).
+
+        elements: indexable; hashes: one int64 per element, hash(map(x)), a numpy array or a CUDA tensor; offsets
+        and stream_ids: int64, numpy or tensors.  One launch over the batch, one read-back of the counts and one of
+        the candidates; segments that overflowed cap are rerun once with the count they reported.  Every candidate
+        is mapped before any replica changes; if that throws, the shadow rows the batch named are put back from a
+        copy taken before the launch, the replicas are left as they were and the exception propagates: the batch
+        never came.  ids as SegmentedDistinct.update.  Returns self.
+        """
+        import numpy as np
+        import torch
+
+        from .values import RandomValues
+
+        dev = self.shadow_counts.device
+
+        def on_device(t, what):
+            if isinstance(t, np.ndarray):
+                t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.int64))
+            if t.dtype != torch.int64 or t.dim() != 1:
+                raise N.IllegalArgumentException(f"{what} must be 1-d int64")
+            return t.to(dev).contiguous()
+
+        hashes, offsets = on_device(hashes, "hashes"), on_device(offsets, "offsets")
+        B = offsets.numel() - 1
+        if hashes.numel() != len(elements):
+            raise N.IllegalArgumentException("one hash per element")
+        if B <= 0 or self.num_streams == 0:
+            return self
+        if stream_ids is None:
+            if B > self.num_streams:
+                raise N.IllegalArgumentException("more segments than streams without stream_ids")
+            ids = None
+            rows = torch.arange(B, dtype=torch.int64)
+        else:
+            ids = on_device(stream_ids, "stream_ids")
+            if ids.numel() != B:
+                raise N.IllegalArgumentException("stream_ids must be an int64 tensor, one per segment")
+            if check_ids:
+                _check_stream_ids(torch, ids, self.num_streams)
+            rows = ids.cpu()
+        offs = offsets.cpu()
+        lens = offs[1:] - offs[:-1]
+        named = rows[(rows >= 0) & (rows < self.num_streams) & (lens > 0)]
+        if named.numel() == 0:
+            return self
+        named_dev = named.to(dev)
+        saved = self.shadow_hashes[named_dev], self.shadow_counts[named_dev]  # (indexing copies)
+        cap = self._cap if self._cap is not None else segmented_candidate_cap(self.k, int(lens.max()))
+        try:
+            got, cnt = self._launch(torch, hashes, offsets, ids, cap)
+            over = [b for b, g in enumerate(got) if g is None]
+            if over:
+                # the overflowed segments alone, each followed by the gap up to the next one under an id no
+                # row has (the kernel skips it before it addresses anything)
+                self._reruns += len(over)
+                ob = torch.tensor(over, dtype=torch.int64)
+                o2 = torch.stack([offs[ob], offs[ob + 1]], dim=1).reshape(-1)
+                i2 = torch.stack([rows[ob], torch.full_like(ob, -1)], dim=1).reshape(-1)[:-1]
+                again, _ = self._launch(torch, hashes, o2.to(dev), i2.to(dev), int(cnt[ob].max()))
+                for j, b in enumerate(over):
+                    got[b] = again[2 * j]
+                    if got[b] is None:
+                        raise N.ReservoirError("a rerun with the reported count overflowed: the state rows changed "
+                                               "between the two launches")
+            mp = self._map
+            mapped = [[elements[i] if mp is None else mp(elements[i]) for i in g[0]] for g in got]
+        except BaseException:
+            self.shadow_hashes[named_dev] = saved[0]
+            self.shadow_counts[named_dev] = saved[1]
+            raise
+        touched, sizes, maxh = [], [], []
+        for b, (g, es) in enumerate(zip(got, mapped)):
+            if not es:
+                continue
+            r = int(rows[b])
+            v = self._values.get(r)
+            if v is None:
+                v = self._values[r] = RandomValues(self.k)
+            for e, h in zip(es, g[1]):
+                v.sample(e, h)
+            self._candidates += len(es)
+            touched.append(r)
+            sizes.append(v.size)
+            maxh.append(v.max_hash)
+        if touched:
+            t = torch.tensor(touched, dtype=torch.int64).to(dev)
+            self.set_sizes[t] = torch.tensor(sizes, dtype=torch.int64).to(dev)
+            self.max_hashes[t] = torch.tensor(maxh, dtype=torch.int64).to(dev)
+        return self
+
+    def result(self, r: int) -> list:
+        """Row r's distinct elements, ascending by scrambled hash (RandomValues.result())."""
+        if r < 0 or r >= self.num_streams:
+            raise N.IllegalArgumentException(f"row outside [0, {self.num_streams})")
+        v = self._values.get(int(r))
+        return v.result() if v is not None else []
+
+    def results(self) -> list:
+        return [self.result(r) for r in range(self.num_streams)]
+
+    def replica(self, r: int):
+        """Row r's RandomValues, or None while no candidate of the row has been replayed."""
+        return self._values.get(int(r))
+
+    def info(self) -> dict:
+        """What the engine returned so far: candidates replayed, launches made, segments rerun after an overflow."""
+        return {"candidates": self._candidates, "launches": self._launches, "reruns": self._reruns}
 
 
 _SEG_SAMPLE_STATE_MAX_K = 15104  # rsv_internal.h kSegSampleStateMaxK

@@ -235,6 +235,16 @@ hipError_t launch_segdistinct_rows_ordered_update(const void* rows, int key_widt
                                                   int64_t num_states, uint32_t k, uint64_t seed0, void* state_rows,
                                                   int64_t* state_hashes, int32_t* state_slots, int64_t* state_counts,
                                                   hipStream_t st);
+// Candidates by hash for S object-key streams (rsv_segdistinct.hip, K5's forms and merge): segment b into the hash
+// shadow of row stream_ids[b] (null: row b; shadow_hashes[num_states*k] ascending, shadow_counts), seeded seed0 + row;
+// the positions with h below min(the shadow's k-th value, max_hashes[row] when set_sizes[row] >= k) -- every
+// position while neither is known -- as (index into hashes, h) at out[b*cap + j], j < cap, the number found in
+// out_counts[b].  A row whose segment overflowed cap is not written.  set_sizes and max_hashes: both or null.
+hipError_t launch_segdistinct_candidates(const int64_t* hashes, const int64_t* offsets, const int64_t* stream_ids,
+                                         int64_t num_segments, int64_t num_states, uint32_t k, uint64_t seed0,
+                                         int64_t* shadow_hashes, int64_t* shadow_counts, const int64_t* set_sizes,
+                                         const int64_t* max_hashes, int64_t* out_pos, int64_t* out_hashes, int64_t cap,
+                                         int64_t* out_counts, hipStream_t st);
 // K5 resumed over byte keys (rsv_segdistinct.hip): the state is rows[num_states*k] of key_width bytes, hashes,
 // counts, as launch_segdistinct_rows writes them, moved in place.  rows / part_rows ([parts][num_states][k] rows)
 // and state_rows 8-byte aligned, and no input may alias the state.  hashes as for launch_segdistinct_rows.

@@ -2002,6 +2002,33 @@ rsv_status rsv_distinct_segmented_rows_merge(const void* part_rows_dev, const in
     return RSV_OK;
 }
 
+// The eleventh: candidates by hash for object keys.  No key width and no hash kind; K5's checks in K5's order
+// otherwise (hashes_dev is not among the required buffers: a launch whose segments are all empty has none).
+rsv_status rsv_distinct_segmented_candidates(const int64_t* hashes_dev, const int64_t* offsets_dev,
+                                             const int64_t* stream_ids_dev, int64_t num_segments, int64_t num_states,
+                                             int32_t k, uint64_t seed, uint64_t stream_base, int64_t* shadow_hashes_dev,
+                                             int64_t* shadow_counts_dev, const int64_t* set_sizes_dev,
+                                             const int64_t* max_hashes_dev, int64_t* out_pos_dev, int64_t* out_hashes_dev,
+                                             int64_t cap, int64_t* out_counts_dev, void* hip_stream) {
+    const SegDistinctCall c{"rsv_distinct_segmented_candidates"};
+    if (rsv_status st = check_segdistinct_shape(c, k, 8)) return st;
+    if (num_segments < 0 || num_states < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative segment or state count");
+    if (cap < 1) return fail(RSV_E_ILLEGAL_ARGUMENT, "cap must be at least 1");
+    if (!stream_ids_dev && num_segments > num_states)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "more segments than state rows without stream_ids_dev");
+    if (num_segments == 0) return RSV_OK;
+    if (!offsets_dev || !out_pos_dev || !out_hashes_dev || !out_counts_dev ||
+        (num_states > 0 && (!shadow_hashes_dev || !shadow_counts_dev)))
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (!set_sizes_dev != !max_hashes_dev)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, std::string(c.fn) + " takes set_sizes_dev and max_hashes_dev together or neither");
+    RSV_HIP_TRY(launch_segdistinct_candidates(hashes_dev, offsets_dev, stream_ids_dev, num_segments, num_states,
+                                              (uint32_t)k, seed + stream_base, shadow_hashes_dev, shadow_counts_dev,
+                                              set_sizes_dev, max_hashes_dev, out_pos_dev, out_hashes_dev, cap,
+                                              out_counts_dev, (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
 rsv_status rsv_replay_events(const void* keys_dev, int64_t n, int32_t key_width, int64_t base_index,
                              const int64_t* ev_pos_dev, const int32_t* ev_slot_dev, int64_t n_events, int32_t k,
                              void* reservoir_dev, void* hip_stream) {

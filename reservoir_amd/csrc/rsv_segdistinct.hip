@@ -8,6 +8,8 @@
 //                                   members chosen by arrival order and the heap's tie behaviour: stateless, _update
 //                                   (DESIGN.md 5c.3 - 5c.6).  Not provided: merge (two heaps over parts of a stream
 //                                   do not determine the heap over the whole), k > 4096.
+// An eleventh, rsv_distinct_segmented_candidates, is the third key kind, any B: the kernel reads hashes only and
+// returns candidate positions (segcand_kernel, behind the resumed set frames; the forms and merge_set are shared).
 // The pieces, in the file's order:
 //
 // Entry.  16 bytes (h, second word) in LDS, for every key kind and width, so every form keeps its LDS budget.
@@ -786,6 +788,127 @@ __global__ __launch_bounds__(NT) void segrowstate_kernel(const uint64_t* in_rows
     });
 }
 
+// ---- Candidates by hash (rsv_distinct_segmented_candidates) ----
+// Sampler.distinct for any B, S streams per launch: the kernel reads hash(map(x)) alone, 8 bytes per element, and
+// emits per segment, in arrival order, the positions RandomValues could still admit; the caller's replica decides
+// them.  The row's state is the hash shadow: the <= k smallest distinct scrambled hashes among the candidates the
+// row has emitted, ascending, as entries (h, 0) -- so merge_set, the forms and the lazy scheme are the set loop's
+// own, and equal hashes are one entry whatever elements carry them.  k distinct hash values seen mean the
+// reference's set is full and its maxHash is at most the k-th of them, whichever k seen values
+// they are: a full shadow's k-th value T bounds maxHash.
+//   bound      min(T when the shadow is full, max_hashes[r] when set_sizes[r] >= k: the caller's replica as of its
+//              last replay).  Neither known: the row is open and every element is a candidate, INT64_MAX included.
+//              Otherwise a candidate has h < bound, strictly: the reference admits below maxHash only, so a repeat
+//              of T itself is none (the set loop's `admits` lets it through; this loop has its own test).
+//   lazy T     candidates are appended behind the shadow and merged when the buffer cannot take another step (or
+//              4k wait below a full shadow), as in take_piece.  Between two merges T is the last merge's, which is
+//              above the exact one: more candidates, never fewer, and at most one buffer of them (P entries: 256 /
+//              512 / 2048 / 8192 by form) behind the exact running T.
+//   emission   a step's candidates in lane order, the waves' counts summed in wave order through s_wave (two
+//              buffers, taken in turn: one barrier per step).  The LDS append uses the same offsets, so the launch
+//              is deterministic and takes no atomic.  Entry j of segment b goes to out[b * cap + j] while j < cap;
+//              out_counts[b] is the number found, stored or not.
+//   epilogue   found > cap: nothing of the row is written, and a rerun with cap >= found starts from the same row
+//              and, the merges depending on counts alone, finds the same candidates.  Nothing found: nothing
+//              written.  Otherwise the last merge, the shadow and zeros up to k, the count.
+// A skipped segment (an id outside [0, num_states), or no elements) gets out_counts[b] = 0 before any row is
+// addressed; the count read from the state is clamped, and nothing else read from it indexes memory.
+template <int NT>
+__global__ __launch_bounds__(NT) void segcand_kernel(const int64_t* __restrict__ hashes, const int64_t* __restrict__ offsets,
+                                                     const int64_t* __restrict__ ids, int64_t num_segments,
+                                                     int64_t num_states, uint32_t k, uint32_t P, uint64_t seed0,
+                                                     int64_t* shadow_hashes, int64_t* shadow_counts,
+                                                     const int64_t* __restrict__ set_sizes,
+                                                     const int64_t* __restrict__ max_hashes, int64_t* __restrict__ out_pos,
+                                                     int64_t* __restrict__ out_hashes, int64_t cap,
+                                                     int64_t* __restrict__ out_counts) {
+    extern __shared__ __align__(16) unsigned char seg_lds[];
+    Ent* const se = (Ent*)seg_lds;
+    constexpr uint32_t kWavesT = NT / 64;
+    __shared__ uint32_t s_scan[kWavesT > 1 ? kWavesT : 1];
+    __shared__ uint32_t s_wave[2][kWavesT > 1 ? kWavesT : 1];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t turn = 0;  // which s_wave buffer the next step writes
+
+    for (int64_t b = blockIdx.x; b < num_segments; b += gridDim.x) {
+        const int64_t r = ids ? ids[b] : b;
+        const int64_t lo = offsets[b], hi = offsets[b + 1];
+        if (r < 0 || r >= num_states || hi <= lo) {
+            if (tid == 0) out_counts[b] = 0;
+            continue;
+        }
+        const int64_t ob = r * (int64_t)k, eb = b * cap;
+        const uint32_t m0 = clamp_count(shadow_counts[r], k);
+        __syncthreads();  // the previous row's output reads are done
+        for (uint32_t i = tid; i < m0; i += NT) se[i] = Ent{shadow_hashes[ob + i], 0};
+        __syncthreads();
+        const bool caller_full = set_sizes && set_sizes[r] >= (int64_t)k;
+        const int64_t caller_bound = caller_full ? max_hashes[r] : kMaxI64;
+        uint32_t m = m0, n = m0;  // the shadow's size; the shadow and the candidates behind it
+        int64_t bound = caller_bound;
+        if (m == k) bound = std::min(bound, se[k - 1].h);
+        bool open = !caller_full && m < k;
+        int64_t r0, r1;
+        java_r0r1(seed0 + (uint64_t)r, r0, r1);
+        int64_t found = 0;
+
+        constexpr int64_t kChunk = (int64_t)NT * kU;
+        for (int64_t base = lo; base < hi; base += kChunk) {
+            int64_t hv[kU];
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                const int64_t i = base + (int64_t)u * NT + tid;
+                hv[u] = i < hi ? hashes[i] : 0;
+            }
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                const int64_t i = base + (int64_t)u * NT + tid;
+                if (base + (int64_t)u * NT >= hi) break;  // uniform: the tail chunk's empty steps
+                if (n + NT > P || (m < k && n >= 4 * k)) {
+                    m = merge_set<NT>(se, n, k, s_scan, KeyOrd{});
+                    n = m;
+                    if (m == k) {  // (the appends land behind se[k - 1])
+                        bound = std::min(caller_bound, se[k - 1].h);
+                        open = false;
+                    }
+                }
+                const int64_t h = scramble(r0, r1, hv[u]);
+                const bool pass = i < hi && (open || h < bound);
+                const uint64_t mask = __ballot(pass);
+                uint32_t pre = (uint32_t)__popcll(mask & ((1ULL << lane) - 1));
+                uint32_t total = (uint32_t)__popcll(mask);
+                if constexpr (kWavesT > 1) {
+                    if (lane == 0) s_wave[turn][wave] = total;
+                    __syncthreads();
+                    total = 0;
+                    for (uint32_t w = 0; w < kWavesT; ++w) {
+                        const uint32_t c = s_wave[turn][w];
+                        if (w < wave) pre += c;
+                        total += c;
+                    }
+                    turn ^= 1;
+                }
+                if (pass) {  // n + NT <= P
+                    se[n + pre] = Ent{h, 0};
+                    const int64_t j = found + pre;
+                    if (j < cap) {
+                        out_pos[eb + j] = i;
+                        out_hashes[eb + j] = h;
+                    }
+                }
+                n += total;
+                found += total;
+            }
+        }
+        if (tid == 0) out_counts[b] = found;
+        if (found == 0 || found > cap) continue;
+        if (n != m) m = merge_set<NT>(se, n, k, s_scan, KeyOrd{});
+        __syncthreads();
+        for (uint32_t i = tid; i < k; i += NT) shadow_hashes[ob + i] = i < m ? se[i].h : 0;
+        if (tid == 0) shadow_counts[r] = m;
+    }
+}
+
 // ---- Ordered (rsv_distinct_segmented_ordered, _rows_ordered) ----
 // "Key" below reads "row" over byte keys.  Once RandomValues' heap is full its maximum M is the k-th smallest hash
 // over the distinct keys seen and it holds every key with h < M, so its set is the bottom-k by (h, key) unless more
@@ -1291,6 +1414,21 @@ hipError_t launch_segdistinct_rows_update(const void* rows, int key_width, const
         return launch_teams(segrowstate_kernel<NT, false>, NT, num_segments, P, st, (const uint64_t*)rows, hashes,
                             offsets, stream_ids, (const int64_t*)nullptr, num_segments, num_states, (int32_t)0,
                             (uint32_t)key_width / 8, k, P, seed0, (uint64_t*)state_rows, state_hashes, state_counts);
+    };
+    return with_form_of<int64_t>(k, f);
+}
+
+hipError_t launch_segdistinct_candidates(const int64_t* hashes, const int64_t* offsets, const int64_t* stream_ids,
+                                         int64_t num_segments, int64_t num_states, uint32_t k, uint64_t seed0,
+                                         int64_t* shadow_hashes, int64_t* shadow_counts, const int64_t* set_sizes,
+                                         const int64_t* max_hashes, int64_t* out_pos, int64_t* out_hashes, int64_t cap,
+                                         int64_t* out_counts, hipStream_t st) {
+    if (num_segments <= 0) return hipSuccess;
+    auto f = [&](int64_t, auto nt, uint32_t P) {
+        constexpr int NT = decltype(nt)::value;
+        return launch_teams(segcand_kernel<NT>, NT, num_segments, P, st, hashes, offsets, stream_ids, num_segments,
+                            num_states, k, P, seed0, shadow_hashes, shadow_counts, set_sizes, max_hashes, out_pos,
+                            out_hashes, cap, out_counts);
     };
     return with_form_of<int64_t>(k, f);
 }
