@@ -13,6 +13,14 @@
 // a strided sample of the batch; a threshold that proves too tight (fewer than k distinct
 // candidates) or too loose (candidate buffer overflow) is corrected and the pass re-run, so the
 // result is exact regardless of the estimate.
+//
+// Host state: NarrowDistinct holds its device and pinned memory by role, each role a
+// member struct of owning buffers (rsv_buffers.h) -- set (the set arrays), cand (the filter's queue),
+// mrg (the radix-sort merge and rocPRIM's scratch), bkt (the bucketed merge, its control block and the
+// coherent host copy), olog (the ordered candidate log), rpl (one segment's replay: device arrays and two
+// pinned staging sets), fst (the first-occurrence sort), sch (the scheduled pass and the rows merge's
+// area), pend (a pending rows merge).  A role's capacity is cap(), the minimum over its members; the
+// ensure_* functions hold the sizing rules only and the destructor frees nothing by name.
 #include <cstdio>
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -1631,7 +1639,9 @@ struct LogSeg {
 };
 
 // The Long (KeyT = int64_t) and Int (int32_t) engine behind DistinctEngine (rsv_internal.h).  Every
-// entry point settles a pending rows merge first (settle).
+// entry point settles a pending rows merge first (settle).  The device and pinned memory is held by
+// role, each role a member struct of owning buffers (rsv_buffers.h); a role's capacity is the minimum
+// over its members (cap()), so there is no capacity to keep in step with the pointers.
 template <typename KeyT>
 struct NarrowDistinct final : DistinctEngine {
     static constexpr int kw = (int)sizeof(KeyT);
@@ -1641,34 +1651,39 @@ struct NarrowDistinct final : DistinctEngine {
     int64_t m = 0;                // current set size
     int64_t max_h = INT64_MIN;    // valid when m == k
     int64_t set_top = INT64_MIN;  // the set's largest hash, valid when m > 0
-    int64_t* set_h = nullptr;     // [set_cap <= k], ascending (h, key)
-    KeyT* set_k = nullptr;
-    int64_t set_cap = 0;
+    struct SetArrays {            // [cap() <= k], ascending (h, key); grown with their contents kept
+        DevBuf<int64_t> h;
+        DevBuf<KeyT> k;
+        int64_t cap() const { return group_cap(h, k); }
+    } set;
     // speculative set publication (the base's `spec`; set mode, batches >= spec_min_batch): when armed,
     // read_ctl enqueues publish_set_kernel behind ctl_publish
     int64_t spec_min_batch = 1ll << 27;  // smallest batch that publishes speculatively (~180 us of filter)
-    int64_t cand_limit = 0;       // 4k + 4096: the most candidates one filter pass may keep
-    int64_t cand_cap = 0;         // allocated (grows on demand up to cand_limit)
-    int64_t* cand_h = nullptr;
-    KeyT* cand_k = nullptr;
-    unsigned long long* counter = nullptr;
-    int64_t merge_cap = 0;        // set + candidates of one merge (grows on demand)
-    int64_t *mh0 = nullptr, *mh1 = nullptr;
-    KeyT *mk0 = nullptr, *mk1 = nullptr;
-    uint32_t *flags = nullptr, *pos = nullptr;
-    int64_t* d_count = nullptr;
-    // bucketed merge (bucket_scatter/sort/emit); log_bmax < 0: radix-sort merge only
-    int32_t log_bmax = -1;
-    int64_t* ctl = nullptr;       // control block (see bucket_scatter); `counter` points at ctl[0]
-    int64_t* hc = nullptr;        // coherent host: ctl[0..3] copies + flag at hc[8]
-    int64_t* hc_dev = nullptr;
-    uint32_t hc_gen = 0;
-    int64_t* bh = nullptr;        // [bmax * kBucketCap] bucket entries
-    KeyT* bk = nullptr;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
-    int64_t* samp = nullptr;      // [2 * kSample]
-    int64_t* h_pinned = nullptr;  // host scalars
+    struct Candidates {           // one filter pass's candidates
+        int64_t limit = 0;        // 4k + 4096: the most candidates one filter pass may keep
+        DevBuf<int64_t> h;        // cap() grows on demand up to limit
+        DevBuf<KeyT> k;
+        int64_t cap() const { return group_cap(h, k); }
+    } cand;
+    struct MergeArea {            // set + candidates of one radix-sort merge (grows on demand)
+        DevBuf<int64_t> h0, h1;
+        DevBuf<KeyT> k0, k1;
+        DevBuf<uint32_t> flags, pos;
+        DevBuf<int64_t> count;    // [4] distinct count, largest kept h, tie
+        Scratch temp;             // rocPRIM's scratch, shared by every sort and scan of the engine
+        int64_t cap() const { return group_cap(h0, h1, k0, k1, flags, pos); }
+    } mrg;
+    struct Buckets {              // bucketed merge (bucket_scatter/sort/emit); log_bmax < 0: radix-sort merge only
+        int32_t log_bmax = -1;
+        DevBuf<int64_t> ctl;      // control block (see bucket_scatter)
+        unsigned long long* counter = nullptr;  // the candidate counter: ctl[0]
+        MappedBuf<int64_t> hc;    // coherent host: ctl[0..3] copies + flag at hc[8]
+        uint32_t gen = 0;
+        DevBuf<int64_t> h;        // [bmax * kBucketCap] bucket entries
+        DevBuf<KeyT> k;
+    } bkt;
+    DevBuf<int64_t> samp;         // [2 * kSample] the threshold sample and its sorted copy
+    HostBuf<int64_t> h_pinned;    // host scalars
     std::vector<int64_t> samp_host;
     KernelTimer* timer = nullptr;
     bool last_tie = false;        // merge_into_set: rank k tied with rank k - 1 on h
@@ -1681,51 +1696,61 @@ struct NarrowDistinct final : DistinctEngine {
     int64_t rate_c = 0, rate_m = 0; // the last full-heap chunk: candidates, length,
     double rate_span = 0;           // and its threshold's distance above Long.MinValue
     std::vector<LogSeg> segs;
-    int64_t* log_h = nullptr;       // [log_cap] candidates of every chunk since the last replay
-    KeyT* log_k = nullptr;
-    uint32_t* log_i = nullptr;      // chunk-relative arrival index
-    int64_t log_n = 0, log_cap = 0, log_limit = 0;
-    // the scheduled pass (sched_sample): range bounds, its own merge area, the set's backup
-    SchedDev* sdev = nullptr;
-    int64_t* sctl = nullptr;        // ctl words + bucket counts of the scheduled merge
-    int32_t log_bmax_s = -1;
-    int64_t* sbh = nullptr;
-    KeyT* sbk = nullptr;
-    uint32_t* sbi = nullptr;
-    int* vacc = nullptr;            // [kVerifyCopies][kMaxRanges + 1]
-    int64_t* bak_h = nullptr;       // [k] the set before the pass
-    KeyT* bak_k = nullptr;
-    int64_t* shc = nullptr;         // coherent host: published words + flag at [12]
-    int64_t* shc_dev = nullptr;
-    uint32_t sgen = 0;
-    bool sdirty = false;            // sctl / vacc allocated, not yet zeroed (the fused pass zeroes them)
+    struct OrderedLog {             // [cap()] candidates of every chunk since the last replay, grown with contents kept
+        DevBuf<int64_t> h;
+        DevBuf<KeyT> k;
+        DevBuf<uint32_t> i;         // chunk-relative arrival index
+        int64_t n = 0, limit = 0;
+        int64_t cap() const { return group_cap(h, k, i); }
+    } olog;
+    // the scheduled pass (sched_sample) and the device rows merge: range bounds, their own merge area
+    // of 2^log_bmax buckets, the set's backup, the published verdict
+    struct Sched {
+        DevBuf<SchedDev> dev;
+        int32_t log_bmax = -1;      // the area below holds 2^log_bmax buckets (-1: none)
+        DevBuf<int64_t> ctl;        // ctl words + bucket counts of the scheduled merge
+        DevBuf<int64_t> bh;
+        DevBuf<KeyT> bk;
+        DevBuf<uint32_t> bi;
+        DevBuf<int> vacc;           // [kVerifyCopies][kMaxRanges + 1]
+        DevBuf<int64_t> bak_h;      // [k] the set before the pass
+        DevBuf<KeyT> bak_k;
+        MappedBuf<int64_t> hc;      // coherent host: published words + flag at [12]
+        uint32_t gen = 0;
+        bool dirty = false;         // ctl / vacc allocated, not yet zeroed (the fused pass zeroes them)
+    } sch;
     bool sched = true;              // RSV_ORDERED_SCHED=0: the chunk loop only
     double sched_beta = 1.6;        // RSV_SCHED_BETA (test hook: a small beta forces the fallback)
-    uint32_t* perm = nullptr;       // [ord_cap] one segment's candidates in arrival order
-    uint32_t* sorted_i = nullptr;   // [ord_cap] radix-sort key output
-    int64_t* ord_h = nullptr;       // [ord_cap] one segment's hashes and keys permuted into arrival order
-    KeyT* ord_k = nullptr;
-    int64_t ord_cap = 0;            // capacity of the two buffers above and of the pinned copies
-    int64_t* ph = nullptr;          // pinned: hashes, keys (as KeyT) of one segment in arrival order
-    KeyT* pk = nullptr;
-    // first-occurrence flags (segment_to_host with `first`): members + segment keys, sorted copies,
-    // their positions, the flags on the device and pinned, the members' pinned staging
-    KeyT* fk_in = nullptr;
-    KeyT* fk_out = nullptr;
-    uint32_t* fv = nullptr;
-    uint8_t* fflag = nullptr;
-    uint8_t* pflag = nullptr;
-    KeyT* pmem = nullptr;
-    int64_t fcap = 0;               // capacity (entries) of fk_in / fk_out / fv; fflag / pflag hold ord_cap
-    int64_t pmem_cap = 0;
+    // the pinned copies of one segment in arrival order: hashes, keys, first-occurrence flags
+    struct Staging {
+        HostBuf<int64_t> h;
+        HostBuf<KeyT> k;
+        HostBuf<uint8_t> flag;
+        int64_t cap() const { return group_cap(h, k, flag); }
+    };
+    // the replay of one logged segment (segment_in_arrival_order, segment_to_host): the permutation and
+    // its sort output, the segment's hashes and keys in arrival order, its first-occurrence flags, and
+    // two pinned sets -- the host replays out of one while the next segment is staged into the other
+    struct Replay {
+        DevBuf<uint32_t> perm, sorted_i;
+        DevBuf<int64_t> ord_h;
+        DevBuf<KeyT> ord_k;
+        DevBuf<uint8_t> fflag;
+        Staging pin[2];             // pin[0] is sized with the device arrays; pin[1] by replay_log when it overlaps
+        hipEvent_t ev = nullptr;    // a segment's own copies done (the next one's staging may still run);
+                                    // created at first use, destroyed with the engine
+        int64_t cap() const { return std::min(group_cap(perm, sorted_i, ord_h, ord_k, fflag), pin[0].cap()); }
+    } rpl;
+    // first-occurrence flags: members + segment keys, their sorted copies and positions, the members'
+    // pinned staging
+    struct FirstOccurrence {
+        DevBuf<KeyT> in, out;
+        DevBuf<uint32_t> v;
+        HostBuf<KeyT> pmem;
+        int64_t cap() const { return group_cap(in, out, v); }
+    } fst;
     int64_t first_min = 4096;       // segments at least this long replay through the flags (no host set)
-    // the next segment staged while the host runs this one (replay_log): its pinned copies
-    int64_t* ph2 = nullptr;
-    KeyT* pk2 = nullptr;
-    uint8_t* pflag2 = nullptr;
-    int64_t ord2_cap = 0;
     bool overlap = true;            // RSV_REPLAY_OVERLAP=0 (test hook): stage no segment ahead
-    hipEvent_t seg_ev = nullptr;    // a segment's own copies done (the next one's staging may still run)
     // Exact multi-rank merge of ordered samplers (rsv_export_log / rsv_merge_log): the candidates
     // the replica consumed (arrival order, host) + the segments still in the log, and the segments
     // logged before the last merge -- together every candidate logged since creation (the base's
@@ -1741,16 +1766,16 @@ struct NarrowDistinct final : DistinctEngine {
     bool rep_stale = false;
     // device combine of packed rows (merge_rows): enqueued without a host wait; the host
     // fields (m, max_h, set_top, over) are settled from its published words at the next call
-    bool pend = false;
-    uint32_t pend_gen = 0;
-    uint32_t pend_lb = 0;
-    const int64_t* pend_rows = nullptr;  // the rows' snapshot (rows_copy) a bucket overflow redoes the merge from
-    int64_t* rows_copy = nullptr;        // engine-owned copy of the last merged rows (the caller may reuse theirs)
-    int64_t rows_copy_cap = 0;           // words
-    int32_t pend_parts = 0;
-    int64_t pend_stride = 0;
-    uint32_t* mstart = nullptr;  // [(parts + 1) x (B + 1)] bucket starts of every run
-    int64_t mstart_cap = 0;
+    struct PendingRows {
+        bool on = false;
+        uint32_t gen = 0;
+        uint32_t lb = 0;
+        const int64_t* rows = nullptr;  // the rows' snapshot (copy) a bucket overflow redoes the merge from
+        DevBuf<int64_t> copy;           // engine-owned copy of the last merged rows (the caller may reuse theirs)
+        int32_t parts = 0;
+        int64_t stride = 0;
+        DevBuf<uint32_t> mstart;        // [(parts + 1) x (B + 1)] bucket starts of every run
+    } pend;
 
     hipError_t init(int32_t k, int hash_kind, int64_t r0, int64_t r1, bool ordered);  // distinct_create's allocations
     ~NarrowDistinct() override;
@@ -1758,11 +1783,11 @@ struct NarrowDistinct final : DistinctEngine {
     int sample_device(const void* keys, const int64_t* hashes, int64_t n, hipStream_t st) override;
     int64_t size() const override { return m; }
     int finalize(hipStream_t st) override;
-    const void* keys_dev() const override { return set_k; }
+    const void* keys_dev() const override { return set.k; }
     int publish(void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st) override;
     void spec_target(void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter) override {
         // the bucketed merge only: set mode behind ctl_publish, ordered mode behind the scheduled pass
-        if (log_bmax >= 0) spec.target(dst_host_dev, flag_dev, gen_counter);
+        if (bkt.log_bmax >= 0) spec.target(dst_host_dev, flag_dev, gen_counter);
     }
     int64_t spec_min() const override { return spec_min_batch; }
     int export_set(void* keys_dev, int64_t* hash_dev, hipStream_t st) override;
@@ -1806,103 +1831,81 @@ static hipError_t temp_bytes_for(int64_t cap, size_t* bytes) {
     return hipSuccess;
 }
 
+// Room for a filter pass of cand_need candidates and a merge of merge_need entries (set + candidates); the
+// set arrays grow with the merge, their contents kept.
 template <typename KeyT>
 static hipError_t ensure_caps(NarrowDistinct<KeyT>* d, int64_t cand_need, int64_t merge_need, hipStream_t st) {
-    const size_t kw = (size_t)d->kw;
     hipError_t e = hipSuccess;
-    cand_need = std::min(cand_need, d->cand_limit);
-    if (cand_need > d->cand_cap) {
-        const int64_t c = grown_capacity(d->cand_cap, cand_need, d->cand_limit);
-        if ((e = pool_device_grow((void**)&d->cand_h, 0, (size_t)c * 8, false, st))) return e;
-        if ((e = pool_device_grow((void**)&d->cand_k, 0, (size_t)c * kw, false, st))) return e;
-        d->cand_cap = c;
+    cand_need = std::min(cand_need, d->cand.limit);
+    if (cand_need > d->cand.cap()) {
+        const int64_t c = grown_capacity(d->cand.cap(), cand_need, d->cand.limit);
+        if ((e = reserve_all(c, st, d->cand.h, d->cand.k))) return e;
     }
     const int64_t set_need = std::min<int64_t>(merge_need, d->k);
-    if (set_need > d->set_cap) {
-        const int64_t c = grown_capacity(d->set_cap, set_need, d->k);
-        if ((e = pool_device_grow((void**)&d->set_h, (size_t)d->m * 8, (size_t)c * 8, true, st))) return e;
-        if ((e = pool_device_grow((void**)&d->set_k, (size_t)d->m * kw, (size_t)c * kw, true, st))) return e;
-        d->set_cap = c;
+    if (set_need > d->set.cap()) {
+        const int64_t c = grown_capacity(d->set.cap(), set_need, d->k);
+        if ((e = d->set.h.reserve_keep(c, d->m, st))) return e;
+        if ((e = d->set.k.reserve_keep(c, d->m, st))) return e;
     }
-    if (merge_need > d->merge_cap) {
-        const int64_t c = grown_capacity(d->merge_cap, merge_need, (int64_t)d->k + d->cand_limit);
-        if ((e = pool_device_grow((void**)&d->mh0, 0, (size_t)c * 8, false, st))) return e;
-        if ((e = pool_device_grow((void**)&d->mh1, 0, (size_t)c * 8, false, st))) return e;
-        if ((e = pool_device_grow((void**)&d->mk0, 0, (size_t)c * kw, false, st))) return e;
-        if ((e = pool_device_grow((void**)&d->mk1, 0, (size_t)c * kw, false, st))) return e;
-        if ((e = pool_device_grow((void**)&d->flags, 0, (size_t)c * 4, false, st))) return e;
-        if ((e = pool_device_grow((void**)&d->pos, 0, (size_t)c * 4, false, st))) return e;
-        size_t tb = 0;
-        e = temp_bytes_for<KeyT>(c, &tb);
-        if (e != hipSuccess) return e;
-        if (tb > d->temp_bytes) {
-            if ((e = pool_device_grow(&d->temp, 0, tb, false, st))) return e;
-            d->temp_bytes = tb;
-        }
-        d->merge_cap = c;
+    if (merge_need > d->mrg.cap()) {
+        const int64_t c = grown_capacity(d->mrg.cap(), merge_need, (int64_t)d->k + d->cand.limit);
+        auto& g = d->mrg;
+        size_t tb = 0;  // the scratch first: the arrays' capacity says that a merge of c entries can run
+        if ((e = temp_bytes_for<KeyT>(c, &tb))) return e;
+        if ((e = g.temp.reserve(tb, st))) return e;
+        if ((e = reserve_all(c, st, g.h0, g.h1, g.k0, g.k1, g.flags, g.pos))) return e;
     }
     return hipSuccess;
 }
 
 template <typename KeyT>
 hipError_t NarrowDistinct<KeyT>::init(int32_t k, int hash_kind, int64_t r0, int64_t r1, bool ordered) {
-    NarrowDistinct* const d = this;
-    const int key_width = kw;
-    d->ordered = ordered;
-    if (ordered) d->rep.reset(k);
-    d->k = k;
-    d->hash_kind = hash_kind;
-    d->r0 = r0;
-    d->r1 = r1;
-    d->cand_limit = 4 * (int64_t)k + 4096;
-    d->log_limit = std::max<int64_t>(d->cand_limit, std::min<int64_t>(std::max<int64_t>(32 * d->cand_limit, 1 << 22), 1 << 27));
+    this->ordered = ordered;
+    if (ordered) rep.reset(k);
+    this->k = k;
+    this->hash_kind = hash_kind;
+    this->r0 = r0;
+    this->r1 = r1;
+    cand.limit = 4 * (int64_t)k + 4096;
+    olog.limit = std::max<int64_t>(cand.limit, std::min<int64_t>(std::max<int64_t>(32 * cand.limit, 1 << 22), 1 << 27));
     if (const char* v = std::getenv("RSV_ORDERED_LOG_LIMIT"))  // test hook: force eager replays
-        d->log_limit = std::max<int64_t>(d->cand_limit, std::atoll(v));
-    if (const char* v = std::getenv("RSV_ORDERED_SCHED")) d->sched = v[0] != '0';
-    if (const char* v = std::getenv("RSV_SCHED_BETA")) d->sched_beta = std::atof(v);
+        olog.limit = std::max<int64_t>(cand.limit, std::atoll(v));
+    if (const char* v = std::getenv("RSV_ORDERED_SCHED")) sched = v[0] != '0';
+    if (const char* v = std::getenv("RSV_SCHED_BETA")) sched_beta = std::atof(v);
     if (const char* v = std::getenv("RSV_FIRST_MIN"))  // test hook: which replay form serves small segments
-        d->first_min = std::max<int64_t>(1, std::atoll(v));
-    if (const char* v = std::getenv("RSV_REPLAY_OVERLAP")) d->overlap = v[0] != '0';  // test hook
+        first_min = std::max<int64_t>(1, std::atoll(v));
+    if (const char* v = std::getenv("RSV_REPLAY_OVERLAP")) overlap = v[0] != '0';  // test hook
     if (const char* v = std::getenv("RSV_SPEC_MIN_BATCH"))  // test hook: speculative publication
-        d->spec_min_batch = std::max<int64_t>(1, std::atoll(v));
+        spec_min_batch = std::max<int64_t>(1, std::atoll(v));
     hipError_t e = hipSuccess;
-    auto A = [&](void** p, size_t bytes) {
-        if (e == hipSuccess) e = pool_device_alloc(p, bytes ? bytes : 16);
-    };
     // bucketed merge for typical k: bmax buckets of kBucketCap entries, mean occupancy <= 128 at
-    // the largest merge (k + cand_limit entries)
+    // the largest merge (k + cand.limit entries)
     int32_t log_bmax = 0;
-    while (((int64_t)1 << (log_bmax + kBucketAvgLog)) < (int64_t)k + d->cand_limit) ++log_bmax;
-    const double bucket_bytes = (double)((int64_t)1 << log_bmax) * kBucketCap * (8 + key_width);
+    while (((int64_t)1 << (log_bmax + kBucketAvgLog)) < (int64_t)k + cand.limit) ++log_bmax;
+    const double bucket_bytes = (double)((int64_t)1 << log_bmax) * kBucketCap * (8 + kw);
     const bool bucketed = bucket_bytes <= 256.0 * 1024 * 1024;
     const size_t ctl_bytes =
         kCtlWords * 8 + (bucketed ? ((size_t)(kCountStride + 1) * 4 << log_bmax) + 4 * (((size_t)1 << log_bmax >> 4) + 1) : 0);
-    A((void**)&d->ctl, ctl_bytes);
-    if (e == hipSuccess) e = hipMemset(d->ctl, 0, ctl_bytes);  // once: bucket_sort keeps the counts zeroed
-    d->counter = (unsigned long long*)d->ctl;
-    if (e == hipSuccess) e = pool_host_alloc((void**)&d->hc, 128, hipHostMallocCoherent | hipHostMallocMapped);
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&d->hc_dev, d->hc, 0);
-    if (e == hipSuccess) ((uint32_t*)(d->hc + 8))[0] = 0;
+    if ((e = bkt.ctl.reserve((int64_t)((ctl_bytes + 7) / 8), 0))) return e;
+    if ((e = hipMemset(bkt.ctl, 0, ctl_bytes))) return e;  // once: bucket_sort keeps the counts zeroed
+    bkt.counter = (unsigned long long*)bkt.ctl.p;
+    if ((e = bkt.hc.reserve(16))) return e;
+    ((uint32_t*)(bkt.hc + 8))[0] = 0;
     if (bucketed) {
-        A((void**)&d->bh, ((size_t)1 << log_bmax) * kBucketCap * 8);
-        A((void**)&d->bk, ((size_t)1 << log_bmax) * kBucketCap * key_width);
-        if (e == hipSuccess) d->log_bmax = log_bmax;
+        if ((e = reserve_all(((int64_t)1 << log_bmax) * kBucketCap, 0, bkt.h, bkt.k))) return e;
+        bkt.log_bmax = log_bmax;
     }
-    A((void**)&d->d_count, 32);
-
-    A((void**)&d->samp, 2 * kSample * 8);
-    if (e == hipSuccess) {
-        size_t tb = 0;  // the threshold sample's sort
-        e = rocprim::radix_sort_keys(nullptr, tb, (int64_t*)nullptr, (int64_t*)nullptr, (size_t)kSample);
-        d->temp_bytes = tb;
-    }
-    A(&d->temp, d->temp_bytes);
-    if (e == hipSuccess) e = pool_host_alloc((void**)&d->h_pinned, 128, hipHostMallocDefault);
+    if ((e = mrg.count.reserve(4, 0))) return e;
+    if ((e = samp.reserve(2 * kSample, 0))) return e;
+    size_t tb = 0;  // the threshold sample's sort
+    if ((e = rocprim::radix_sort_keys(nullptr, tb, (int64_t*)nullptr, (int64_t*)nullptr, (size_t)kSample))) return e;
+    if ((e = mrg.temp.reserve(tb, 0))) return e;
+    if ((e = h_pinned.reserve(16))) return e;
     // Typical k: allocate the whole working set now (nothing is allocated on the sampling path).
     // Huge k (up to Int.MaxValue - 2): grow with what the sampler holds.
-    const int64_t full_merge = (int64_t)k + d->cand_limit;
-    const double eager_bytes = (double)full_merge * (2 * 8 + 2 * key_width + 8) + (double)d->cand_limit * (8 + key_width);
-    if (e == hipSuccess && eager_bytes < 512.0 * 1024 * 1024) e = ensure_caps(d, d->cand_limit, full_merge, 0);
+    const int64_t full_merge = (int64_t)k + cand.limit;
+    const double eager_bytes = (double)full_merge * (2 * 8 + 2 * kw + 8) + (double)cand.limit * (8 + kw);
+    if (eager_bytes < 512.0 * 1024 * 1024) e = ensure_caps(this, cand.limit, full_merge, 0);
     return e;
 }
 
@@ -1928,41 +1931,25 @@ DistinctEngine* distinct_create(int32_t k, int key_width, int hash_kind, int64_t
 }
 
 template <typename KeyT>
-NarrowDistinct<KeyT>::~NarrowDistinct() {
-    NarrowDistinct* const d = this;
-    void* ps[] = {d->set_h, d->set_k, d->cand_h, d->cand_k, d->ctl, d->bh, d->bk, d->mh0, d->mh1, d->mk0,
-                  d->mk1, d->flags, d->pos, d->d_count, d->samp, d->temp, d->log_h, d->log_k, d->log_i,
-                  d->perm, d->sorted_i, d->ord_h, d->ord_k, d->sdev, d->sctl, d->sbh, d->sbk, d->sbi, d->vacc,
-                  d->bak_h, d->bak_k, d->mstart, d->fk_in, d->fk_out, d->fv, d->fflag, d->rows_copy};
-    for (void* p : ps) pool_device_free(p);  // the owner's stream is idle (rsv_destroy)
-    pool_host_free(d->h_pinned);
-    pool_host_free(d->hc);
-    pool_host_free(d->ph);
-    pool_host_free(d->pk);
-    pool_host_free(d->pflag);
-    pool_host_free(d->ph2);
-    pool_host_free(d->pk2);
-    pool_host_free(d->pflag2);
-    if (d->seg_ev) (void)hipEventDestroy(d->seg_ev);
-    pool_host_free(d->pmem);
-    pool_host_free(d->shc);
+NarrowDistinct<KeyT>::~NarrowDistinct() {  // the buffers return their blocks: the owner's stream is idle (rsv_destroy)
+    if (rpl.ev) (void)hipEventDestroy(rpl.ev);
 }
 
 template <typename KeyT>
 int NarrowDistinct<KeyT>::publish(void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st) {
-    RSV_HIP_TRY(launch_publish_multi(set_k, m * kw, dst_host_dev, flag_dev, gen, (uint32_t*)(ctl + 4), st));
+    RSV_HIP_TRY(launch_publish_multi(set.k, m * kw, dst_host_dev, flag_dev, gen, (uint32_t*)(bkt.ctl + 4), st));
     return RSV_OK;
 }
 
 template <typename KeyT>
 static hipError_t launch_filter(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t* hashes, int64_t n,
                                 int64_t tinc, hipStream_t st) {
-    KeyT* ck = d->cand_k;
-    if (tinc == INT64_MAX && n <= d->cand_cap) {  // no bound: every element a candidate, in place
+    KeyT* ck = d->cand.k;
+    if (tinc == INT64_MAX && n <= d->cand.cap()) {  // no bound: every element a candidate, in place
         const unsigned g = (unsigned)std::min<int64_t>(std::max<int64_t>(grid_1d(n), 1), 4096);
 #define RSV_HASH_ALL(H)                                                                                       \
     hipLaunchKernelGGL((hash_all<KeyT, H, false>), dim3(g), dim3(kBlock), 0, st, keys, hashes, n, d->r0, d->r1, \
-                       d->cand_h, ck, (uint32_t*)nullptr, d->counter)
+                       d->cand.h, ck, (uint32_t*)nullptr, d->bkt.counter)
         switch (d->hash_kind) {
         case kHashJavaLong: RSV_HASH_ALL(kHashJavaLong); break;
         case kHashJavaInt: RSV_HASH_ALL(kHashJavaInt); break;
@@ -1977,19 +1964,19 @@ static hipError_t launch_filter(NarrowDistinct<KeyT>* d, const KeyT* keys, const
     switch (d->hash_kind) {
     case kHashJavaLong:
         hipLaunchKernelGGL((k3_filter<KeyT, kHashJavaLong>), dim3(grid), dim3(kBlock), 0, st, keys, hashes,
-                           n, d->r0, d->r1, tinc, d->cand_h, ck, d->counter, d->cand_cap);
+                           n, d->r0, d->r1, tinc, d->cand.h, ck, d->bkt.counter, d->cand.cap());
         break;
     case kHashJavaInt:
         hipLaunchKernelGGL((k3_filter<KeyT, kHashJavaInt>), dim3(grid), dim3(kBlock), 0, st, keys, hashes,
-                           n, d->r0, d->r1, tinc, d->cand_h, ck, d->counter, d->cand_cap);
+                           n, d->r0, d->r1, tinc, d->cand.h, ck, d->bkt.counter, d->cand.cap());
         break;
     case kHashPrecomputed:
         hipLaunchKernelGGL((k3_filter<KeyT, kHashPrecomputed>), dim3(grid), dim3(kBlock), 0, st, keys,
-                           hashes, n, d->r0, d->r1, tinc, d->cand_h, ck, d->counter, d->cand_cap);
+                           hashes, n, d->r0, d->r1, tinc, d->cand.h, ck, d->bkt.counter, d->cand.cap());
         break;
     default:
         hipLaunchKernelGGL((k3_filter<KeyT, kHashIdentity>), dim3(grid), dim3(kBlock), 0, st, keys, hashes,
-                           n, d->r0, d->r1, tinc, d->cand_h, ck, d->counter, d->cand_cap);
+                           n, d->r0, d->r1, tinc, d->cand.h, ck, d->bkt.counter, d->cand.cap());
     }
     return hipGetLastError();
 }
@@ -2017,8 +2004,8 @@ static hipError_t launch_sample(NarrowDistinct<KeyT>* d, const KeyT* keys, const
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    size_t tb = d->temp_bytes;
-    return rocprim::radix_sort_keys(d->temp, tb, d->samp, d->samp + kSample, (size_t)ns, 0, 64, st);
+    size_t tb = d->mrg.temp.bytes();
+    return rocprim::radix_sort_keys(d->mrg.temp.p(), tb, d->samp.p, d->samp + kSample, (size_t)ns, 0, 64, st);
 }
 
 // span bits of every hash in a merge whose entries are all <= top (rocPRIM and the buckets both
@@ -2032,10 +2019,10 @@ static unsigned span_bits(int64_t top) {
 // synchronize costs ~15-20 us more); falls back to a blocking synchronize after ~2 ms
 template <typename KeyT>
 static hipError_t read_ctl(NarrowDistinct<KeyT>* d, int64_t* out, hipStream_t st) {
-    const uint32_t gen = ++d->hc_gen;
-    uint32_t* flag = (uint32_t*)(d->hc + 8);
-    hipLaunchKernelGGL(ctl_publish, dim3(1), dim3(64), 0, st, d->ctl, d->hc_dev,
-                       (uint32_t*)(d->hc_dev + 8), gen);
+    const uint32_t gen = ++d->bkt.gen;
+    uint32_t* flag = (uint32_t*)(d->bkt.hc + 8);
+    hipLaunchKernelGGL(ctl_publish, dim3(1), dim3(64), 0, st, d->bkt.ctl, d->bkt.hc.dev,
+                       (uint32_t*)(d->bkt.hc.dev + 8), gen);
     if (hipError_t e = hipGetLastError()) return e;
     if (d->spec.arm) {  // behind ctl_publish (which re-arms ctl[0..1]; the kernel reads ctl[2])
         d->spec.arm = false;
@@ -2043,9 +2030,9 @@ static hipError_t read_ctl(NarrowDistinct<KeyT>* d, int64_t* out, hipStream_t st
         const int64_t per = 32 * 1024;  // bytes per workgroup, as launch_publish_multi
         const unsigned grid =
             (unsigned)std::min<int64_t>(32, std::max<int64_t>(1, ((int64_t)d->k * d->kw + per - 1) / per));
-        hipLaunchKernelGGL(publish_set_kernel, dim3(grid), dim3(1024), 0, st, (const uint32_t*)d->set_k,
-                           (uint32_t*)d->spec.dst, (const int64_t*)d->ctl, (int64_t)d->k, d->kw / 4, d->spec.flag,
-                           g, (uint32_t*)(d->ctl + 4));
+        hipLaunchKernelGGL(publish_set_kernel, dim3(grid), dim3(1024), 0, st, (const uint32_t*)d->set.k.p,
+                           (uint32_t*)d->spec.dst, (const int64_t*)d->bkt.ctl, (int64_t)d->k, d->kw / 4, d->spec.flag,
+                           g, (uint32_t*)(d->bkt.ctl + 4));
         if (hipError_t e = hipGetLastError()) return e;
         d->spec.gen = g;
     }
@@ -2063,7 +2050,7 @@ static hipError_t read_ctl(NarrowDistinct<KeyT>* d, int64_t* out, hipStream_t st
         if (hipError_t e = hipStreamSynchronize(st)) return e;
         if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != gen) return hipErrorUnknown;
     }
-    for (int i = 0; i < 6; ++i) out[i] = __atomic_load_n(d->hc + i, __ATOMIC_RELAXED);
+    for (int i = 0; i < 6; ++i) out[i] = __atomic_load_n(d->bkt.hc + i, __ATOMIC_RELAXED);
     return hipSuccess;
 }
 
@@ -2073,24 +2060,24 @@ template <typename KeyT>
 static hipError_t launch_bucket_merge(NarrowDistinct<KeyT>* d, int64_t tinc, hipStream_t st, const int64_t* cand_h = nullptr,
                                       const KeyT* cand_k = nullptr, int64_t cand_cap = 0) {
     if (!cand_h) {  // the set-mode filter's buffer
-        cand_h = d->cand_h;
-        cand_k = d->cand_k;
-        cand_cap = d->cand_cap;
+        cand_h = d->cand.h;
+        cand_k = d->cand.k;
+        cand_cap = d->cand.cap();
     }
     const int64_t top = d->m ? std::max(tinc, d->set_top) : tinc;
     const uint64_t span = (uint64_t)top - (uint64_t)INT64_MIN;
     const uint64_t q = span == UINT64_MAX ? 1ull : UINT64_MAX / (span + 1);
-    const unsigned waves = 1u << d->log_bmax;  // one per bucket
+    const unsigned waves = 1u << d->bkt.log_bmax;  // one per bucket
     const unsigned wgrid = (waves + kBlock / 64 - 1) / (kBlock / 64);
     const unsigned sgrid = (unsigned)std::min<int64_t>(std::max<int64_t>(grid_1d(d->m + cand_cap), 1), 1024);
-    KeyT* bk = d->bk;
-    hipLaunchKernelGGL(bucket_scatter<KeyT>, dim3(sgrid), dim3(kBlock), 0, st, d->set_h, (const KeyT*)d->set_k, d->m,
-                       cand_h, cand_k, cand_cap, d->ctl, q, d->log_bmax, d->bh, bk);
-    hipLaunchKernelGGL(bucket_sort<KeyT>, dim3(wgrid), dim3(kBlock), 0, st, d->m, cand_cap, d->ctl, d->log_bmax,
-                       d->bh, bk);
+    KeyT* bk = d->bkt.k;
+    hipLaunchKernelGGL(bucket_scatter<KeyT>, dim3(sgrid), dim3(kBlock), 0, st, d->set.h, (const KeyT*)d->set.k, d->m,
+                       cand_h, cand_k, cand_cap, d->bkt.ctl, q, d->bkt.log_bmax, d->bkt.h, bk);
+    hipLaunchKernelGGL(bucket_sort<KeyT>, dim3(wgrid), dim3(kBlock), 0, st, d->m, cand_cap, d->bkt.ctl, d->bkt.log_bmax,
+                       d->bkt.h, bk);
     const unsigned egrid = (waves + kEmitBuckets - 1) / kEmitBuckets;
-    hipLaunchKernelGGL(bucket_emit<KeyT>, dim3(egrid), dim3(kBlock), 0, st, d->m, cand_cap, d->ctl, d->log_bmax,
-                       (const int64_t*)d->bh, (const KeyT*)bk, (int64_t)d->k, d->set_h, (KeyT*)d->set_k);
+    hipLaunchKernelGGL(bucket_emit<KeyT>, dim3(egrid), dim3(kBlock), 0, st, d->m, cand_cap, d->bkt.ctl, d->bkt.log_bmax,
+                       (const int64_t*)d->bkt.h, (const KeyT*)bk, (int64_t)d->k, d->set.h, (KeyT*)d->set.k);
     return hipGetLastError();
 }
 
@@ -2113,47 +2100,47 @@ static hipError_t merge_into_set(NarrowDistinct<KeyT>* d, const int64_t* src_h, 
         return hipSuccess;
     }
     if (hipError_t e0 = ensure_caps(d, 0, total, st)) return e0;
-    KeyT* mk0 = d->mk0;
-    KeyT* mk1 = d->mk1;
+    int64_t *mh0 = d->mrg.h0, *mh1 = d->mrg.h1;
+    KeyT *mk0 = d->mrg.k0, *mk1 = d->mrg.k1;
     hipError_t e;
     if (d->m) {
-        if ((e = hipMemcpyAsync(d->mh0, d->set_h, d->m * 8, hipMemcpyDeviceToDevice, st))) return e;
-        if ((e = hipMemcpyAsync(mk0, d->set_k, d->m * sizeof(KeyT), hipMemcpyDeviceToDevice, st))) return e;
+        if ((e = hipMemcpyAsync(mh0, d->set.h, d->m * 8, hipMemcpyDeviceToDevice, st))) return e;
+        if ((e = hipMemcpyAsync(mk0, d->set.k, d->m * sizeof(KeyT), hipMemcpyDeviceToDevice, st))) return e;
     }
     if (c) {
-        if ((e = hipMemcpyAsync(d->mh0 + d->m, src_h, c * 8, hipMemcpyDeviceToDevice, st))) return e;
+        if ((e = hipMemcpyAsync(mh0 + d->m, src_h, c * 8, hipMemcpyDeviceToDevice, st))) return e;
         if ((e = hipMemcpyAsync(mk0 + d->m, src_k, c * sizeof(KeyT), hipMemcpyDeviceToDevice, st))) return e;
     }
-    size_t tb = d->temp_bytes;
+    size_t tb = d->mrg.temp.bytes();
     if (d->hash_kind == kHashIdentity || d->hash_kind == kHashJavaInt) {
         // injective hash: equal h <=> equal element, so one sort by h orders (h, key)
-        if ((e = rocprim::radix_sort_pairs(d->temp, tb, d->mh0, d->mh1, mk0, mk1, (size_t)total, 0, hbits, st)))
+        if ((e = rocprim::radix_sort_pairs(d->mrg.temp.p(), tb, mh0, mh1, mk0, mk1, (size_t)total, 0, hbits, st)))
             return e;
-        std::swap(d->mh0, d->mh1);
-        std::swap(d->mk0, d->mk1);
-        mk0 = d->mk0;
-        mk1 = d->mk1;
+        d->mrg.h0.swap(d->mrg.h1);  // the sorted entries are in h0 / k0 either way
+        d->mrg.k0.swap(d->mrg.k1);
+        std::swap(mh0, mh1);
+        std::swap(mk0, mk1);
     } else {
         // stable LSD order: by key, then by h  ->  sorted by (h, key)
-        if ((e = rocprim::radix_sort_pairs(d->temp, tb, mk0, mk1, d->mh0, d->mh1, (size_t)total, 0,
+        if ((e = rocprim::radix_sort_pairs(d->mrg.temp.p(), tb, mk0, mk1, mh0, mh1, (size_t)total, 0,
                                            8 * (unsigned)sizeof(KeyT), st)))
             return e;
-        tb = d->temp_bytes;
-        if ((e = rocprim::radix_sort_pairs(d->temp, tb, d->mh1, d->mh0, mk1, mk0, (size_t)total, 0, hbits, st)))
+        tb = d->mrg.temp.bytes();
+        if ((e = rocprim::radix_sort_pairs(d->mrg.temp.p(), tb, mh1, mh0, mk1, mk0, (size_t)total, 0, hbits, st)))
             return e;
     }
-    hipLaunchKernelGGL(dedup_flags<KeyT>, dim3(grid_1d(total)), dim3(kBlock), 0, st, d->mh0, mk0, total,
-                       d->flags);
+    hipLaunchKernelGGL(dedup_flags<KeyT>, dim3(grid_1d(total)), dim3(kBlock), 0, st, mh0, mk0, total,
+                       d->mrg.flags);
     if ((e = hipGetLastError())) return e;
-    if ((e = hipMemsetAsync(d->d_count + 2, 0, 8, st))) return e;
-    tb = d->temp_bytes;
-    if ((e = rocprim::exclusive_scan(d->temp, tb, d->flags, d->pos, 0u, (size_t)total,
+    if ((e = hipMemsetAsync(d->mrg.count + 2, 0, 8, st))) return e;
+    tb = d->mrg.temp.bytes();
+    if ((e = rocprim::exclusive_scan(d->mrg.temp.p(), tb, d->mrg.flags.p, d->mrg.pos.p, 0u, (size_t)total,
                                      rocprim::plus<uint32_t>(), st)))
         return e;
-    hipLaunchKernelGGL(compact_first_k<KeyT>, dim3(grid_1d(total)), dim3(kBlock), 0, st, d->mh0, mk0,
-                       d->flags, d->pos, total, (int64_t)d->k, d->set_h, (KeyT*)d->set_k, d->d_count);
+    hipLaunchKernelGGL(compact_first_k<KeyT>, dim3(grid_1d(total)), dim3(kBlock), 0, st, mh0, mk0,
+                       d->mrg.flags, d->mrg.pos, total, (int64_t)d->k, d->set.h, (KeyT*)d->set.k, d->mrg.count);
     if ((e = hipGetLastError())) return e;
-    if ((e = hipMemcpyAsync(d->h_pinned, d->d_count, 24, hipMemcpyDeviceToHost, st))) return e;
+    if ((e = hipMemcpyAsync(d->h_pinned, d->mrg.count, 24, hipMemcpyDeviceToHost, st))) return e;
     if ((e = hipStreamSynchronize(st))) return e;
     *n_distinct = d->h_pinned[0];
     d->last_tie = d->h_pinned[2] != 0;
@@ -2191,8 +2178,8 @@ static int sample_impl(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t*
         return qq >= ns ? t_allowed : std::min(d->samp_host[(size_t)std::max<int64_t>(qq, 0)], t_allowed);
     };
     int64_t tinc = t_allowed;
-    const bool estimate = !full && n > d->cand_limit / 2;
-    DTRY(ensure_caps(d, estimate ? d->cand_limit : n, 0, st));
+    const bool estimate = !full && n > d->cand.limit / 2;
+    DTRY(ensure_caps(d, estimate ? d->cand.limit : n, 0, st));
     if (estimate) {
         // The scrambled hash of distinct elements is uniform on int64 (double byteswap64 keyed
         // by the random r0, r1), so ~2k + 1024 elements fall below INT64_MIN + f 2^64 with
@@ -2203,19 +2190,19 @@ static int sample_impl(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t*
         tinc = f >= 1.0L ? t_allowed : (int64_t)((long double)INT64_MIN + f * 18446744073709551616.0L);
     }
     for (int attempt = 0; attempt < 128; ++attempt) {
-        if (attempt == 8 && n > d->cand_limit / 2) {
+        if (attempt == 8 && n > d->cand.limit / 2) {
             // A hash with few distinct values near the boundary (e.g. a constant precomputed hash)
             // defeats the threshold search: no threshold keeps between k and cand_cap candidates.
             // Take the batch in slices whose every element fits the candidate buffer (each slice
             // merges in one pass); what the attempts above merged is a subset of the batch.
-            const int64_t step = d->cand_limit / 2;
+            const int64_t step = d->cand.limit / 2;
             for (int64_t off = 0; off < n; off += step)
                 if (int rc = sample_impl<KeyT>(d, keys + off, hashes ? hashes + off : nullptr, std::min(step, n - off), st))
                     return rc;
             return RSV_OK;
         }
         // the merge needs the set arrays at their full size (set_h/set_k are written by rank)
-        const bool bucketed = d->log_bmax >= 0 && d->set_cap >= d->k;
+        const bool bucketed = d->bkt.log_bmax >= 0 && d->set.cap() >= d->k;
         // candidate counter and overflow word: zeroed at creation and re-armed by every read_ctl
         // (ctl_publish), so no memset dispatch ahead of the filter
         if (d->timer) d->timer->mark(st);
@@ -2229,11 +2216,11 @@ static int sample_impl(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t*
         d->spec.arm = spec;
         DTRY(read_ctl(d, d->h_pinned + 4, st));
         const int64_t c = d->h_pinned[4];
-        if (c > d->cand_cap) {  // threshold too loose for the candidate buffer: tighten
+        if (c > d->cand.cap()) {  // threshold too loose for the candidate buffer: tighten
             if (ns == 0) {
                 if (int rc = take_sample()) return rc;
-                q = (int64_t)((__int128)(d->cand_limit / 4) * ns / n);
-                DTRY(ensure_caps(d, d->cand_limit, 0, st));
+                q = (int64_t)((__int128)(d->cand.limit / 4) * ns / n);
+                DTRY(ensure_caps(d, d->cand.limit, 0, st));
             } else {
                 q /= 2;
             }
@@ -2250,8 +2237,8 @@ static int sample_impl(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t*
             if (d->m == d->k) d->max_h = d->set_top;
         } else {
             if (bucketed)  // bucket overflow: the scatter's counts were not consumed
-                DTRY(hipMemsetAsync(d->ctl + kCtlWords, 0, (size_t)kCountStride * 4 << d->log_bmax, st));
-            DTRY(merge_into_set<KeyT>(d, d->cand_h, d->cand_k, c, &nd, st, tinc));
+                DTRY(hipMemsetAsync(d->bkt.ctl + kCtlWords, 0, (size_t)kCountStride * 4 << d->bkt.log_bmax, st));
+            DTRY(merge_into_set<KeyT>(d, d->cand.h, d->cand.k, c, &nd, st, tinc));
         }
         // exact once every batch element below the new k-th hash was a candidate
         if (tinc >= t_allowed || (d->m == d->k && d->max_h <= tinc)) {
@@ -2285,7 +2272,7 @@ static hipError_t launch_filter_idx(NarrowDistinct<KeyT>* d, const KeyT* keys, c
         const unsigned g = (unsigned)std::min<int64_t>(std::max<int64_t>(grid_1d(n), 1), 4096);
 #define RSV_HASH_ALL(H)                                                                                        \
     hipLaunchKernelGGL((hash_all<KeyT, H, true>), dim3(g), dim3(kBlock), 0, st, keys, hashes, n, d->r0, d->r1, out_h, \
-                       out_k, out_i, d->counter)
+                       out_k, out_i, d->bkt.counter)
         switch (d->hash_kind) {
         case kHashJavaLong: RSV_HASH_ALL(kHashJavaLong); break;
         case kHashJavaInt: RSV_HASH_ALL(kHashJavaInt); break;
@@ -2301,7 +2288,7 @@ static hipError_t launch_filter_idx(NarrowDistinct<KeyT>* d, const KeyT* keys, c
     const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(grid_1d(n / 8 + 1), 1), 256 * 32);
 #define RSV_FILTER_IDX(H)                                                                                       \
     hipLaunchKernelGGL((k3_filter<KeyT, H, true>), dim3(grid), dim3(kBlock), 0, st, keys, hashes, n, d->r0,     \
-                       d->r1, tinc, out_h, out_k, d->counter, cap, out_i)
+                       d->r1, tinc, out_h, out_k, d->bkt.counter, cap, out_i)
     switch (d->hash_kind) {
     case kHashJavaLong: RSV_FILTER_IDX(kHashJavaLong); break;
     case kHashJavaInt: RSV_FILTER_IDX(kHashJavaInt); break;
@@ -2312,52 +2299,42 @@ static hipError_t launch_filter_idx(NarrowDistinct<KeyT>* d, const KeyT* keys, c
     return hipGetLastError();
 }
 
-// ordered-mode replay buffers: device permutation / sort output and pinned host copies of one
-// logged segment
+// the shared rocPRIM scratch for a sort of n (key, arrival index) pairs
+template <typename SortKey>
+static hipError_t reserve_index_sort(Scratch& temp, int64_t n, hipStream_t st) {
+    size_t tb = 0;
+    if (hipError_t e = rocprim::radix_sort_pairs(nullptr, tb, (SortKey*)nullptr, (SortKey*)nullptr,
+                                                 rocprim::counting_iterator<uint32_t>(0), (uint32_t*)nullptr, (size_t)n))
+        return e;
+    return temp.reserve(tb, st);
+}
+
+// ordered-mode replay buffers: device permutation / sort output and the pinned host copies (set 0) of
+// one logged segment of up to `cap` candidates
 template <typename KeyT>
 static hipError_t ensure_ordered(NarrowDistinct<KeyT>* d, int64_t cap, hipStream_t st) {
-    if (cap <= d->ord_cap) return hipSuccess;
+    auto& r = d->rpl;
+    if (cap <= r.cap()) return hipSuccess;
     hipError_t e;
-    if ((e = pool_device_grow((void**)&d->perm, 0, (size_t)cap * 4, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->sorted_i, 0, (size_t)cap * 4, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->ord_h, 0, (size_t)cap * 8, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->ord_k, 0, (size_t)cap * d->kw, false, st))) return e;
-    pool_host_free(d->ph);
-    pool_host_free(d->pk);
-    d->ph = nullptr;
-    d->pk = nullptr;
-    if ((e = pool_host_alloc((void**)&d->ph, (size_t)cap * 8, hipHostMallocDefault))) return e;
-    if ((e = pool_host_alloc((void**)&d->pk, (size_t)cap * d->kw, hipHostMallocDefault))) return e;
-    if ((e = pool_device_grow((void**)&d->fflag, 0, (size_t)cap, false, st))) return e;
-    pool_host_free(d->pflag);
-    d->pflag = nullptr;
-    if ((e = pool_host_alloc((void**)&d->pflag, (size_t)cap, hipHostMallocDefault))) return e;
-    size_t tb = 0;
-    if ((e = rocprim::radix_sort_pairs(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                       rocprim::counting_iterator<uint32_t>(0), (uint32_t*)nullptr, (size_t)cap)))
-        return e;
-    if (tb > d->temp_bytes) {
-        if ((e = pool_device_grow(&d->temp, 0, tb, false, st))) return e;
-        d->temp_bytes = tb;
-    }
-    d->ord_cap = cap;
-    return hipSuccess;
+    if ((e = reserve_index_sort<uint32_t>(d->mrg.temp, cap, st))) return e;
+    if ((e = reserve_all(cap, st, r.perm, r.sorted_i, r.ord_h, r.ord_k, r.fflag))) return e;
+    return reserve_all(cap, st, r.pin[0].h, r.pin[0].k, r.pin[0].flag);
 }
 
 // room for `need` log entries (kept contents).  The first allocation takes ~8 full chunks (at most
 // 256 MB): a growth copies the log and waits for the stream (~100 us each, measured).
 template <typename KeyT>
 static hipError_t ensure_log(NarrowDistinct<KeyT>* d, int64_t need, hipStream_t st) {
-    if (need <= d->log_cap) return hipSuccess;
-    const int64_t first = std::min<int64_t>(8 * d->cand_limit, (256ll << 20) / (12 + d->kw));
-    const int64_t want = std::max(need, std::min(d->log_limit, d->log_cap ? need : first));
-    const int64_t c = grown_capacity(d->log_cap, want, std::max(want, d->log_limit));
+    auto& l = d->olog;
+    const int64_t cur = l.cap();
+    if (need <= cur) return hipSuccess;
+    const int64_t first = std::min<int64_t>(8 * d->cand.limit, (256ll << 20) / (12 + d->kw));
+    const int64_t want = std::max(need, std::min(l.limit, cur ? need : first));
+    const int64_t c = grown_capacity(cur, want, std::max(want, l.limit));
     hipError_t e;
-    if ((e = pool_device_grow((void**)&d->log_h, (size_t)d->log_n * 8, (size_t)c * 8, true, st))) return e;
-    if ((e = pool_device_grow((void**)&d->log_k, (size_t)d->log_n * d->kw, (size_t)c * d->kw, true, st))) return e;
-    if ((e = pool_device_grow((void**)&d->log_i, (size_t)d->log_n * 4, (size_t)c * 4, true, st))) return e;
-    d->log_cap = c;
-    return hipSuccess;
+    if ((e = l.h.reserve_keep(c, l.n, st))) return e;
+    if ((e = l.k.reserve_keep(c, l.n, st))) return e;
+    return l.i.reserve_keep(c, l.n, st);
 }
 
 // The replica's set -> the device set arrays (ascending (h, key), as the SET mode keeps them), so
@@ -2374,14 +2351,14 @@ static hipError_t upload_replica(NarrowDistinct<KeyT>* d, hipStream_t st) {
     }
     std::vector<KeyT> kk((size_t)m);
     for (int64_t i = 0; i < m; ++i) kk[(size_t)i] = (KeyT)d->rep.he[(size_t)i + 1];
-    if ((e = hipMemcpyAsync(d->mh0, d->rep.hh.data() + 1, (size_t)m * 8, hipMemcpyHostToDevice, st))) return e;
-    if ((e = hipMemcpyAsync(d->mk0, kk.data(), (size_t)m * sizeof(KeyT), hipMemcpyHostToDevice, st))) return e;
-    size_t tb = d->temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(d->temp, tb, d->mk0, d->mk1, d->mh0, d->mh1, (size_t)m, 0,
+    if ((e = hipMemcpyAsync(d->mrg.h0, d->rep.hh.data() + 1, (size_t)m * 8, hipMemcpyHostToDevice, st))) return e;
+    if ((e = hipMemcpyAsync(d->mrg.k0, kk.data(), (size_t)m * sizeof(KeyT), hipMemcpyHostToDevice, st))) return e;
+    size_t tb = d->mrg.temp.bytes();
+    if ((e = rocprim::radix_sort_pairs(d->mrg.temp.p(), tb, d->mrg.k0.p, d->mrg.k1.p, d->mrg.h0.p, d->mrg.h1.p, (size_t)m, 0,
                                        8 * (unsigned)sizeof(KeyT), st)))
         return e;
-    tb = d->temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(d->temp, tb, d->mh1, d->set_h, d->mk1, d->set_k, (size_t)m, 0,
+    tb = d->mrg.temp.bytes();
+    if ((e = rocprim::radix_sort_pairs(d->mrg.temp.p(), tb, d->mrg.h1.p, d->set.h.p, d->mrg.k1.p, d->set.k.p, (size_t)m, 0,
                                        64, st)))
         return e;
     if ((e = hipStreamSynchronize(st))) return e;  // kk goes out of scope
@@ -2391,78 +2368,91 @@ static hipError_t upload_replica(NarrowDistinct<KeyT>* d, hipStream_t st) {
     return hipSuccess;
 }
 
-// the first-occurrence sort's buffers for `total` entries (members + one segment)
+// the first-occurrence sort's buffers for `total` entries (nm members + segments)
 template <typename KeyT>
 static hipError_t ensure_first(NarrowDistinct<KeyT>* d, int64_t nm, int64_t total, hipStream_t st) {
+    auto& f = d->fst;
     hipError_t e;
-    if (nm > d->pmem_cap) {
-        const int64_t c = std::min<int64_t>(d->k, std::max<int64_t>(nm, 2 * d->pmem_cap));
-        pool_host_free(d->pmem);
-        d->pmem = nullptr;
-        d->pmem_cap = 0;
-        if ((e = pool_host_alloc((void**)&d->pmem, (size_t)c * sizeof(KeyT), hipHostMallocDefault))) return e;
-        d->pmem_cap = c;
-    }
-    if (total <= d->fcap) return hipSuccess;
-    if ((e = pool_device_grow((void**)&d->fk_in, 0, (size_t)total * sizeof(KeyT), false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->fk_out, 0, (size_t)total * sizeof(KeyT), false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->fv, 0, (size_t)total * 4, false, st))) return e;
-    size_t tb = 0;
-    if ((e = rocprim::radix_sort_pairs(nullptr, tb, (KeyT*)nullptr, (KeyT*)nullptr,
-                                       rocprim::counting_iterator<uint32_t>(0), (uint32_t*)nullptr, (size_t)total)))
-        return e;
-    if (tb > d->temp_bytes) {
-        if ((e = pool_device_grow(&d->temp, 0, tb, false, st))) return e;
-        d->temp_bytes = tb;
-    }
-    d->fcap = total;
-    return hipSuccess;
+    if (nm > f.pmem.cap && (e = f.pmem.reserve(std::min<int64_t>(d->k, std::max<int64_t>(nm, 2 * f.pmem.cap))))) return e;
+    if (total <= f.cap()) return hipSuccess;
+    if ((e = reserve_index_sort<KeyT>(d->mrg.temp, total, st))) return e;
+    return reserve_all(total, st, f.in, f.out, f.v);
 }
 
-// One logged segment in arrival order into the pinned host copies d->ph / d->pk: a radix sort by
-// the chunk-relative index restores the order, and the permutation is applied on the device, so
-// the host reads the segment sequentially (two random reads per element from a ~20 MB log cost
-// more than the replica's heap).  With `first`, also its first-occurrence flags into d->pflag.
+// Segment g -> arrival order in rpl.ord_h / ord_k: a radix sort by the chunk-relative index restores
+// the order, and the permutation is applied on the device, so the host reads the segment sequentially
+// (two random reads per element from a ~20 MB log cost more than the replica's heap).
+template <typename KeyT>
+static hipError_t segment_in_arrival_order(NarrowDistinct<KeyT>* d, const LogSeg& g, hipStream_t st) {
+    auto& r = d->rpl;
+    unsigned bits = 1;
+    while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)g.m) ++bits;
+    size_t tb = d->mrg.temp.bytes();
+    if (hipError_t e = rocprim::radix_sort_pairs(d->mrg.temp.p(), tb, d->olog.i + g.off, r.sorted_i.p,
+                                                 rocprim::counting_iterator<uint32_t>(0), r.perm.p, (size_t)g.c, 0, bits, st))
+        return e;
+    hipLaunchKernelGGL(permute_log<KeyT>, dim3((unsigned)std::min<int64_t>((g.c + kBlock - 1) / kBlock, 8192)),
+                       dim3(kBlock), 0, st, r.perm, d->olog.h + g.off, (const KeyT*)d->olog.k + g.off, g.c, r.ord_h,
+                       (KeyT*)r.ord_k);
+    return hipGetLastError();
+}
+
+// the replica's nm members into fst.in[0, nm), through the pinned staging (free: the stream was
+// synchronized since its last upload)
+template <typename KeyT>
+static hipError_t upload_members(NarrowDistinct<KeyT>* d, int64_t nm, hipStream_t st) {
+    KeyT* pm = d->fst.pmem;
+    for (int64_t i = 0; i < nm; ++i) pm[i] = (KeyT)d->rep.he[(size_t)i + 1];
+    return nm ? hipMemcpyAsync(d->fst.in, pm, (size_t)nm * sizeof(KeyT), hipMemcpyHostToDevice, st) : hipSuccess;
+}
+
+// Flags of [prefix | segment] -> rpl.fflag: the c keys in rpl.ord_k go behind the `prefix` keys already in
+// fst.in, and fflag[t] says whether segment key t occurs nowhere before it (mark_first over the sorted keys).
+template <typename KeyT>
+static hipError_t flags_behind_prefix(NarrowDistinct<KeyT>* d, int64_t prefix, int64_t c, hipStream_t st) {
+    auto& f = d->fst;
+    const int64_t total = prefix + c;
+    hipError_t e;
+    if ((e = hipMemcpyAsync(f.in + prefix, d->rpl.ord_k, (size_t)c * sizeof(KeyT), hipMemcpyDeviceToDevice, st))) return e;
+    size_t tb = d->mrg.temp.bytes();
+    if ((e = rocprim::radix_sort_pairs(d->mrg.temp.p(), tb, f.in.p, f.out.p, rocprim::counting_iterator<uint32_t>(0), f.v.p,
+                                       (size_t)total, 0, 8 * (unsigned)sizeof(KeyT), st)))
+        return e;
+    hipLaunchKernelGGL(mark_first<KeyT>, dim3((unsigned)std::min<int64_t>((total + kBlock - 1) / kBlock, 8192)),
+                       dim3(kBlock), 0, st, (const KeyT*)f.out, (const uint32_t*)f.v, total, (uint32_t)prefix,
+                       d->rpl.fflag);
+    return hipGetLastError();
+}
+
+// the c entries of rpl.ord_h / ord_k (and their flags) into one pinned set
+template <typename KeyT>
+static hipError_t segment_copy_out(NarrowDistinct<KeyT>* d, typename NarrowDistinct<KeyT>::Staging& pin, int64_t c,
+                                   bool flags, hipStream_t st) {
+    hipError_t e;
+    if (flags && (e = hipMemcpyAsync(pin.flag, d->rpl.fflag, (size_t)c, hipMemcpyDeviceToHost, st))) return e;
+    if ((e = hipMemcpyAsync(pin.h, d->rpl.ord_h, (size_t)c * 8, hipMemcpyDeviceToHost, st))) return e;
+    return hipMemcpyAsync(pin.k, d->rpl.ord_k, (size_t)c * sizeof(KeyT), hipMemcpyDeviceToHost, st);
+}
+
+// One logged segment in arrival order into the pinned set 0 (grown as needed).  With `first`, also its
+// first-occurrence flags against the replica's members.  Waits for the stream, or (!sync) records rpl.ev
+// behind the copies: the caller enqueues more (the next segment's staging), then waits for the event only.
 template <typename KeyT>
 static hipError_t segment_to_host(NarrowDistinct<KeyT>* d, const LogSeg& g, hipStream_t st, bool first,
                                   bool sync = true) {
     hipError_t e;
     if ((e = ensure_ordered(d, g.c, st))) return e;
-    unsigned bits = 1;
-    while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)g.m) ++bits;
-    size_t tb = d->temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(d->temp, tb, d->log_i + g.off, d->sorted_i,
-                                       rocprim::counting_iterator<uint32_t>(0), d->perm, (size_t)g.c, 0, bits, st)))
-        return e;
-    hipLaunchKernelGGL(permute_log<KeyT>, dim3((unsigned)std::min<int64_t>((g.c + kBlock - 1) / kBlock, 8192)),
-                       dim3(kBlock), 0, st, d->perm, d->log_h + g.off, (const KeyT*)d->log_k + g.off, g.c, d->ord_h,
-                       (KeyT*)d->ord_k);
-    if ((e = hipGetLastError())) return e;
+    if ((e = segment_in_arrival_order(d, g, st))) return e;
     if (first) {
-        const int64_t nm = d->rep.size(), total = nm + g.c;
-        if ((e = ensure_first<KeyT>(d, nm, total, st))) return e;
-        KeyT* pm = d->pmem;
-        for (int64_t i = 0; i < nm; ++i) pm[i] = (KeyT)d->rep.he[(size_t)i + 1];
-        if (nm && (e = hipMemcpyAsync(d->fk_in, pm, (size_t)nm * sizeof(KeyT), hipMemcpyHostToDevice, st))) return e;
-        if ((e = hipMemcpyAsync(d->fk_in + nm, d->ord_k, (size_t)g.c * sizeof(KeyT), hipMemcpyDeviceToDevice, st)))
-            return e;
-        size_t fb = d->temp_bytes;
-        if ((e = rocprim::radix_sort_pairs(d->temp, fb, d->fk_in, d->fk_out,
-                                           rocprim::counting_iterator<uint32_t>(0), d->fv, (size_t)total, 0,
-                                           8 * (unsigned)sizeof(KeyT), st)))
-            return e;
-        hipLaunchKernelGGL(mark_first<KeyT>, dim3((unsigned)std::min<int64_t>((total + kBlock - 1) / kBlock, 8192)),
-                           dim3(kBlock), 0, st, (const KeyT*)d->fk_out, (const uint32_t*)d->fv, total, (uint32_t)nm,
-                           d->fflag);
-        if ((e = hipGetLastError())) return e;
-        if ((e = hipMemcpyAsync(d->pflag, d->fflag, (size_t)g.c, hipMemcpyDeviceToHost, st))) return e;
+        const int64_t nm = d->rep.size();
+        if ((e = ensure_first<KeyT>(d, nm, nm + g.c, st))) return e;
+        if ((e = upload_members(d, nm, st))) return e;
+        if ((e = flags_behind_prefix(d, nm, g.c, st))) return e;
     }
-    if ((e = hipMemcpyAsync(d->ph, d->ord_h, (size_t)g.c * 8, hipMemcpyDeviceToHost, st))) return e;
-    if ((e = hipMemcpyAsync(d->pk, d->ord_k, (size_t)g.c * sizeof(KeyT), hipMemcpyDeviceToHost, st))) return e;
+    if ((e = segment_copy_out(d, d->rpl.pin[0], g.c, first, st))) return e;
     if (sync) return hipStreamSynchronize(st);
-    // the caller enqueues more (the next segment's staging), then waits for this event only
-    if (!d->seg_ev && (e = hipEventCreateWithFlags(&d->seg_ev, hipEventDisableTiming))) return e;
-    return hipEventRecord(d->seg_ev, st);
+    if (!d->rpl.ev && (e = hipEventCreateWithFlags(&d->rpl.ev, hipEventDisableTiming))) return e;
+    return hipEventRecord(d->rpl.ev, st);
 }
 
 // The replica from the set arrays, in (h, key) order, after a merge replaced the set (a merged set
@@ -2473,8 +2463,8 @@ static hipError_t rebuild_replica(NarrowDistinct<KeyT>* d, hipStream_t st) {
     std::vector<KeyT> kk((size_t)d->m);
     hipError_t e = hipSuccess;
     if (d->m) {
-        if ((e = hipMemcpyAsync(hh.data(), d->set_h, (size_t)d->m * 8, hipMemcpyDeviceToHost, st))) return e;
-        if ((e = hipMemcpyAsync(kk.data(), d->set_k, (size_t)d->m * sizeof(KeyT), hipMemcpyDeviceToHost, st))) return e;
+        if ((e = hipMemcpyAsync(hh.data(), d->set.h, (size_t)d->m * 8, hipMemcpyDeviceToHost, st))) return e;
+        if ((e = hipMemcpyAsync(kk.data(), d->set.k, (size_t)d->m * sizeof(KeyT), hipMemcpyDeviceToHost, st))) return e;
         if ((e = hipStreamSynchronize(st))) return e;
     }
     d->rep.reset(d->k);
@@ -2485,69 +2475,24 @@ static hipError_t rebuild_replica(NarrowDistinct<KeyT>* d, hipStream_t st) {
 }
 
 // The next segment's host copies staged while the host replays this one (replay_log): segment gn in
-// arrival order into the pinned buffers the current run does not read, with first-occurrence flags
+// arrival order into the pinned set the current run does not read, with first-occurrence flags
 // taken against the members at the START of the current segment gs plus all of gs's keys -- the
 // replica's members at gn's start are a subset of those, and a key of gs that is no member there
 // cannot be admitted at gn either (rejected at its first arrival, or evicted as the heap's maximum:
 // maxHash has not risen since, Sampler.scala:403), so the flags are exactly as exact as gn's own
 // would be.  gs's keys are still in ord_k (put there in arrival order for gs's own copies).  Enqueued
-// only: the caller synchronizes the stream before it reads the copies.
+// only: the caller synchronizes the stream before it reads the copies.  No buffer grows here.
 template <typename KeyT>
 static hipError_t segment_stage_next(NarrowDistinct<KeyT>* d, const LogSeg& gs, const LogSeg& gn,
-                                     int64_t* dph, KeyT* dpk, uint8_t* dpflag, hipStream_t st) {
+                                     typename NarrowDistinct<KeyT>::Staging& pin, hipStream_t st) {
     hipError_t e;
     const int64_t nm = d->rep.size();  // the members at gs's start (gs has not been replayed yet)
-    const int64_t total = nm + gs.c + gn.c;
-    KeyT* pm = d->pmem;  // free: the stream was synchronized since its last upload
-    for (int64_t i = 0; i < nm; ++i) pm[i] = (KeyT)d->rep.he[(size_t)i + 1];
-    if (nm && (e = hipMemcpyAsync(d->fk_in, pm, (size_t)nm * sizeof(KeyT), hipMemcpyHostToDevice, st))) return e;
-    if ((e = hipMemcpyAsync(d->fk_in + nm, d->ord_k, (size_t)gs.c * sizeof(KeyT), hipMemcpyDeviceToDevice, st)))
+    if ((e = upload_members(d, nm, st))) return e;
+    if ((e = hipMemcpyAsync(d->fst.in + nm, d->rpl.ord_k, (size_t)gs.c * sizeof(KeyT), hipMemcpyDeviceToDevice, st)))
         return e;
-    unsigned bits = 1;
-    while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)gn.m) ++bits;
-    size_t tb = d->temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(d->temp, tb, d->log_i + gn.off, d->sorted_i,
-                                       rocprim::counting_iterator<uint32_t>(0), d->perm, (size_t)gn.c, 0, bits, st)))
-        return e;
-    hipLaunchKernelGGL(permute_log<KeyT>, dim3((unsigned)std::min<int64_t>((gn.c + kBlock - 1) / kBlock, 8192)),
-                       dim3(kBlock), 0, st, d->perm, d->log_h + gn.off, (const KeyT*)d->log_k + gn.off, gn.c, d->ord_h,
-                       (KeyT*)d->ord_k);
-    if ((e = hipGetLastError())) return e;
-    if ((e = hipMemcpyAsync(d->fk_in + nm + gs.c, d->ord_k, (size_t)gn.c * sizeof(KeyT), hipMemcpyDeviceToDevice,
-                            st)))
-        return e;
-    size_t fb = d->temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(d->temp, fb, d->fk_in, d->fk_out,
-                                       rocprim::counting_iterator<uint32_t>(0), d->fv, (size_t)total, 0,
-                                       8 * (unsigned)sizeof(KeyT), st)))
-        return e;
-    hipLaunchKernelGGL(mark_first<KeyT>, dim3((unsigned)std::min<int64_t>((total + kBlock - 1) / kBlock, 8192)),
-                       dim3(kBlock), 0, st, (const KeyT*)d->fk_out, (const uint32_t*)d->fv, total,
-                       (uint32_t)(nm + gs.c), d->fflag);
-    if ((e = hipGetLastError())) return e;
-    if ((e = hipMemcpyAsync(dpflag, d->fflag, (size_t)gn.c, hipMemcpyDeviceToHost, st))) return e;
-    if ((e = hipMemcpyAsync(dph, d->ord_h, (size_t)gn.c * 8, hipMemcpyDeviceToHost, st))) return e;
-    return hipMemcpyAsync(dpk, d->ord_k, (size_t)gn.c * sizeof(KeyT), hipMemcpyDeviceToHost, st);
-}
-
-// the alternate pinned copies for segments of up to `cap` candidates
-template <typename KeyT>
-static hipError_t ensure_ordered2(NarrowDistinct<KeyT>* d, int64_t cap) {
-    if (cap <= d->ord2_cap) return hipSuccess;
-    hipError_t e;
-    pool_host_free(d->ph2);
-    pool_host_free(d->pk2);
-    pool_host_free(d->pflag2);
-    if (d->seg_ev) (void)hipEventDestroy(d->seg_ev);
-    d->ph2 = nullptr;
-    d->pk2 = nullptr;
-    d->pflag2 = nullptr;
-    d->ord2_cap = 0;
-    if ((e = pool_host_alloc((void**)&d->ph2, (size_t)cap * 8, hipHostMallocDefault))) return e;
-    if ((e = pool_host_alloc((void**)&d->pk2, (size_t)cap * d->kw, hipHostMallocDefault))) return e;
-    if ((e = pool_host_alloc((void**)&d->pflag2, (size_t)cap, hipHostMallocDefault))) return e;
-    d->ord2_cap = cap;
-    return hipSuccess;
+    if ((e = segment_in_arrival_order(d, gn, st))) return e;
+    if ((e = flags_behind_prefix(d, nm + gs.c, gn.c, st))) return e;
+    return segment_copy_out(d, pin, gn.c, true, st);
 }
 
 // Every logged segment, in order, through the host replica (RandomValues.sample on each candidate,
@@ -2574,15 +2519,11 @@ static hipError_t replay_log(NarrowDistinct<KeyT>* d, hipStream_t st) {
         }
         if ((e = ensure_ordered(d, cmax, st))) return e;
         if ((e = ensure_first<KeyT>(d, d->k, d->k + pair, st))) return e;
-        if ((e = ensure_ordered2(d, cmax))) return e;
+        auto& alt = d->rpl.pin[1];  // the alternate pinned set
+        if ((e = reserve_all(cmax, st, alt.h, alt.k, alt.flag))) return e;
     }
-    // the pinned copies of a segment: set 0 (ph / pk / pflag, segment_to_host's, which may grow them)
-    // or set 1 (ph2 / pk2 / pflag2)
-    auto set_h = [&](int c) { return c ? d->ph2 : d->ph; };
-    auto set_k = [&](int c) { return c ? d->pk2 : d->pk; };
-    auto set_f = [&](int c) { return c ? d->pflag2 : d->pflag; };
     bool staged = false;  // segment s's copies (and flags) were staged behind the previous run
-    int cur = 0;          // the set segment s's copies are in
+    int cur = 0;          // the pinned set segment s's copies are in (segment_to_host's is set 0)
     for (size_t s = 0; s < ns; ++s) {
         const LogSeg& g = d->segs[s];
         if (g.c == 0) {
@@ -2599,9 +2540,9 @@ static hipError_t replay_log(NarrowDistinct<KeyT>* d, hipStream_t st) {
         // the next segment is staged behind this one when both replay through the flags
         const LogSeg* gn = s + 1 < ns ? &d->segs[s + 1] : nullptr;
         const int64_t nm = d->rep.size();
-        const bool stage_next = d->overlap && d->ph2 && gn && gn->c > 0 && first_ok(gn->c, g.c) &&
-                                nm + g.c + gn->c <= d->fcap && gn->c <= d->ord2_cap && gn->c <= d->ord_cap &&
-                                d->pmem_cap >= nm;
+        const bool stage_next = d->overlap && gn && gn->c > 0 && first_ok(gn->c, g.c) &&
+                                nm + g.c + gn->c <= d->fst.cap() && gn->c <= d->rpl.pin[1].cap() &&
+                                gn->c <= d->rpl.cap() && d->fst.pmem.cap >= nm;
         if (!staged) {
             first = first_ok(g.c, 0);
             // (when staging follows, wait only for this segment's own copies, after enqueueing it)
@@ -2611,14 +2552,14 @@ static hipError_t replay_log(NarrowDistinct<KeyT>* d, hipStream_t st) {
         const bool was_staged = staged;
         staged = false;
         if (stage_next && first) {
-            if ((e = segment_stage_next<KeyT>(d, g, *gn, set_h(cur ^ 1), set_k(cur ^ 1), set_f(cur ^ 1), st))) return e;
+            if ((e = segment_stage_next<KeyT>(d, g, *gn, d->rpl.pin[cur ^ 1], st))) return e;
             staged = true;
-            if (!was_staged && (e = hipEventSynchronize(d->seg_ev))) return e;
+            if (!was_staged && (e = hipEventSynchronize(d->rpl.ev))) return e;
         }
         const auto t1 = std::chrono::steady_clock::now();
-        const KeyT* pk = set_k(cur);
-        const int64_t* ph = set_h(cur);
-        const uint8_t* pflag = set_f(cur);
+        const KeyT* pk = d->rpl.pin[cur].k;
+        const int64_t* ph = d->rpl.pin[cur].h;
+        const uint8_t* pflag = d->rpl.pin[cur].flag;
         if (d->retain && d->arch_ok) {
             if ((int64_t)d->arch_h.size() + g.c > kArchMax) {
                 d->drop_archive();
@@ -2645,50 +2586,46 @@ static hipError_t replay_log(NarrowDistinct<KeyT>* d, hipStream_t st) {
     }
     if (staged && (e = hipStreamSynchronize(st))) return e;  // (never: the last segment stages nothing)
     d->segs.clear();
-    if (d->pre_segs.empty()) d->log_n = 0;  // else the log still holds the pre-merge segments
+    if (d->pre_segs.empty()) d->olog.n = 0;  // else the log still holds the pre-merge segments
     return hipSuccess;
 }
 
-// the scheduled pass's buffers for merges of up to `entries` (set + candidates); allocated on first use
+// the scheduled pass's buffers for merges over 2^lb buckets; allocated on first use
 template <typename KeyT>
 static hipError_t sched_ensure(NarrowDistinct<KeyT>* d, int32_t lb, hipStream_t st, bool defer_zero = false) {
+    auto& s = d->sch;
     hipError_t e = hipSuccess;
-    if (!d->sdev) {
-        if ((e = pool_device_alloc((void**)&d->sdev, sizeof(SchedDev)))) return e;
-        if ((e = pool_host_alloc((void**)&d->shc, 128, hipHostMallocCoherent | hipHostMallocMapped))) return e;
-        if ((e = hipHostGetDevicePointer((void**)&d->shc_dev, d->shc, 0))) return e;
-        ((uint32_t*)(d->shc + 12))[0] = 0;
-        if ((e = pool_device_alloc((void**)&d->vacc, (size_t)kVerifyCopies * (kMaxRanges + 1) * 4))) return e;
-        d->sdirty = true;  // re-armed by sched_publish after every pass
-        if ((e = pool_device_alloc((void**)&d->bak_h, (size_t)d->k * 8))) return e;
-        if ((e = pool_device_alloc((void**)&d->bak_k, (size_t)d->k * d->kw))) return e;
+    if ((e = s.dev.reserve(1, st))) return e;
+    if (!s.hc) {
+        if ((e = s.hc.reserve(16))) return e;
+        ((uint32_t*)(s.hc + 12))[0] = 0;
     }
-    if (lb > d->log_bmax_s) {
+    if (!s.vacc) {
+        if ((e = s.vacc.reserve((int64_t)kVerifyCopies * (kMaxRanges + 1), st))) return e;
+        s.dirty = true;  // re-armed by sched_publish after every pass
+    }
+    if ((e = s.bak_h.reserve(d->k, st))) return e;
+    if ((e = s.bak_k.reserve(d->k, st))) return e;
+    if (lb > s.log_bmax) {
         // the old area may still be read by queued work: wait before it goes back to the pool
-        if (d->sctl && (e = hipStreamSynchronize(st))) return e;
-        for (void* p : {(void*)d->sctl, (void*)d->sbh, (void*)d->sbk, (void*)d->sbi}) pool_device_free(p);
-        d->sctl = nullptr;
-        d->sbh = nullptr;
-        d->sbk = nullptr;
-        d->sbi = nullptr;
-        d->log_bmax_s = -1;
+        if (s.ctl && (e = hipStreamSynchronize(st))) return e;
+        s.ctl.release(), s.bh.release(), s.bk.release(), s.bi.release();
+        s.log_bmax = -1;
         const size_t B = (size_t)1 << lb;
         // rounded to 256 B: one aligned fill dispatch (an unaligned tail costs a second one)
         const size_t ctl_bytes = (kCtlWords * 8 + (kCountStride + 1) * 4 * B + 4 * ((B >> 4) + 1) + 255) & ~(size_t)255;
-        if ((e = pool_device_alloc((void**)&d->sctl, ctl_bytes))) return e;
-        d->sdirty = true;  // counts, counter: re-armed after each pass
-        if ((e = pool_device_alloc((void**)&d->sbh, B * kBucketCap * 8))) return e;
-        if ((e = pool_device_alloc((void**)&d->sbk, B * kBucketCap * sizeof(KeyT)))) return e;
-        if ((e = pool_device_alloc((void**)&d->sbi, B * kBucketCap * 4))) return e;
-        d->log_bmax_s = lb;
+        if ((e = s.ctl.reserve((int64_t)(ctl_bytes / 8), st))) return e;
+        s.dirty = true;  // counts, counter: re-armed after each pass
+        if ((e = reserve_all((int64_t)(B * kBucketCap), st, s.bh, s.bk, s.bi))) return e;
+        s.log_bmax = lb;  // only now: every member holds the area
     }
     // zeroed here unless the caller's next pass is the fused one (ctl_plan + sched_filter zero
     // them: two fills and their host calls fewer ahead of a fresh sampler's first kernel)
-    if (d->sdirty && !defer_zero) {
-        const size_t B = (size_t)1 << d->log_bmax_s;
-        if ((e = hipMemsetAsync(d->vacc, 0, (size_t)kVerifyCopies * (kMaxRanges + 1) * 4, st))) return e;
-        if ((e = hipMemsetAsync(d->sctl, 0, kCtlWords * 8 + kCountStride * 4 * B, st))) return e;
-        d->sdirty = false;
+    if (s.dirty && !defer_zero) {
+        const size_t B = (size_t)1 << s.log_bmax;
+        if ((e = hipMemsetAsync(s.vacc, 0, (size_t)kVerifyCopies * (kMaxRanges + 1) * 4, st))) return e;
+        if ((e = hipMemsetAsync(s.ctl, 0, kCtlWords * 8 + kCountStride * 4 * B, st))) return e;
+        s.dirty = false;
     }
     return hipSuccess;
 }
@@ -2728,24 +2665,24 @@ static hipError_t sched_prepare(NarrowDistinct<KeyT>* d, int64_t n, hipStream_t 
         if (hipError_t _e = (x)) return hip_status(_e, "distinct (scheduled pass): " #x); \
     } while (0)
 
-// The pass's kernels over keys[0, n), the plan already in d->sdev (or being written there by a
+// The pass's kernels over keys[0, n), the plan already in d->sch.dev (or being written there by a
 // kernel ahead of them): candidates into the log from lbase (+ the plan's `off`), the set's
-// backup, the bucket merge, the verdict to d->shc; then the speculative publication of the set.
+// backup, the bucket merge, the verdict to d->sch.hc; then the speculative publication of the set.
 template <typename KeyT>
 static int sched_launch(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t* hashes, int64_t n, int64_t lbase,
                         int64_t cap, uint32_t B, int32_t lb, hipStream_t st, uint32_t* gen, bool* spec,
                         bool zero = false) {
     const int64_t k = d->k;
     const size_t kw = sizeof(KeyT);
-    KeyT* bk = d->sbk;
+    KeyT* bk = d->sch.bk;
     if (d->timer) d->timer->mark(st);
     {
         const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(grid_1d(n / 32 + 1), 1), kK3Grid);
-        KeyT* lk = d->log_k + lbase;
+        KeyT* lk = d->olog.k + lbase;
 #define RSV_SCHED_FILTER(H)                                                                                        \
     hipLaunchKernelGGL((sched_filter<KeyT, H>), dim3(grid), dim3(kBlock), 0, st, keys, hashes, n, d->r0, d->r1,      \
-                       (const SchedDev*)d->sdev, d->log_h + lbase, lk, d->log_i + lbase, d->sctl, cap, d->log_bmax_s,     \
-                       zero ? d->vacc : nullptr)
+                       (const SchedDev*)d->sch.dev, d->olog.h + lbase, lk, d->olog.i + lbase, d->sch.ctl, cap, d->sch.log_bmax,     \
+                       zero ? d->sch.vacc : nullptr)
         switch (d->hash_kind) {
         case kHashJavaLong: RSV_SCHED_FILTER(kHashJavaLong); break;
         case kHashJavaInt: RSV_SCHED_FILTER(kHashJavaInt); break;
@@ -2759,18 +2696,18 @@ static int sched_launch(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t
         // ~1.1 M entries waited on ~4 atomics per thread in sequence (61 us)
         const uint32_t C = 1u << bin_log((uint32_t)lb);
         const unsigned fgrid = (unsigned)((k + cap + kBinFileThreads * kBinTile - 1) / (kBinFileThreads * kBinTile));
-        hipLaunchKernelGGL(sched_bin_file<KeyT>, dim3(fgrid), dim3(kBinFileThreads), C * 4, st, (const SchedDev*)d->sdev,
-                           (const int64_t*)(d->log_h + lbase), (const KeyT*)lk, (const uint32_t*)(d->log_i + lbase),
-                           d->sctl, cap, (const int64_t*)d->set_h, (const KeyT*)d->set_k, k, d->sbh, bk, d->sbi,
-                           d->bak_h, (KeyT*)d->bak_k);
+        hipLaunchKernelGGL(sched_bin_file<KeyT>, dim3(fgrid), dim3(kBinFileThreads), C * 4, st, (const SchedDev*)d->sch.dev,
+                           (const int64_t*)(d->olog.h + lbase), (const KeyT*)lk, (const uint32_t*)(d->olog.i + lbase),
+                           d->sch.ctl, cap, (const int64_t*)d->set.h, (const KeyT*)d->set.k, k, d->sch.bh, bk, d->sch.bi,
+                           d->sch.bak_h, (KeyT*)d->sch.bak_k);
         STRY(hipGetLastError());
     }
     if (d->timer) d->timer->mark(st);
-    hipLaunchKernelGGL(sched_bin_sort<KeyT>, dim3(1u << bin_log((uint32_t)lb)), dim3(kBinSortThreads), 0, st, cap, d->sctl, d->log_bmax_s,
-                       d->sbh, bk, d->sbi, (const SchedDev*)d->sdev, d->vacc);
+    hipLaunchKernelGGL(sched_bin_sort<KeyT>, dim3(1u << bin_log((uint32_t)lb)), dim3(kBinSortThreads), 0, st, cap, d->sch.ctl, d->sch.log_bmax,
+                       d->sch.bh, bk, d->sch.bi, (const SchedDev*)d->sch.dev, d->sch.vacc);
     hipLaunchKernelGGL(bucket_emit<KeyT>, dim3((B + kEmitBuckets - 1) / kEmitBuckets), dim3(kBlock), 0, st, k, cap,
-                       d->sctl, d->log_bmax_s, (const int64_t*)d->sbh, (const KeyT*)bk, k, d->set_h, (KeyT*)d->set_k, lb);
-    *gen = ++d->sgen;
+                       d->sch.ctl, d->sch.log_bmax, (const int64_t*)d->sch.bh, (const KeyT*)bk, k, d->set.h, (KeyT*)d->set.k, lb);
+    *gen = ++d->sch.gen;
     // the merged set published speculatively with the verdict (size from sctl[2] on the device):
     // result() takes it if the pass verified and left no tie for the replica to settle
     *spec = d->spec.dst && n >= d->spec_min_batch;
@@ -2778,10 +2715,10 @@ static int sched_launch(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t
     const unsigned pgrid =
         *spec ? (unsigned)std::min<int64_t>(32, std::max<int64_t>(1, (k * (int64_t)kw + per - 1) / per)) : 1u;
     const uint32_t g = *spec ? ++*d->spec.gen_ctr : 0u;
-    hipLaunchKernelGGL(sched_publish, dim3(pgrid), dim3(1024), 0, st, d->sctl, d->vacc, (const SchedDev*)d->sdev, k,
-                       d->shc_dev, (uint32_t*)(d->shc_dev + 12), *gen, (const uint32_t*)d->set_k,
+    hipLaunchKernelGGL(sched_publish, dim3(pgrid), dim3(1024), 0, st, d->sch.ctl, d->sch.vacc, (const SchedDev*)d->sch.dev, k,
+                       d->sch.hc.dev, (uint32_t*)(d->sch.hc.dev + 12), *gen, (const uint32_t*)d->set.k.p,
                        *spec ? (uint32_t*)d->spec.dst : nullptr, (int32_t)(kw / 4), d->spec.flag, g,
-                       (uint32_t*)(d->ctl + 4));
+                       (uint32_t*)(d->bkt.ctl + 4));
     STRY(hipGetLastError());
     if (*spec) d->spec.gen = g;
     return RSV_OK;
@@ -2790,7 +2727,7 @@ static int sched_launch(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t
 // the host side of a pass's verdict: spin on the flag (a stream synchronize after 50 ms)
 template <typename KeyT>
 static int sched_wait(NarrowDistinct<KeyT>* d, uint32_t gen, hipStream_t st, int64_t* hv) {
-    uint32_t* flag = (uint32_t*)(d->shc + 12);
+    uint32_t* flag = (uint32_t*)(d->sch.hc + 12);
     const auto t0w = std::chrono::steady_clock::now();
     bool seen = false;
     for (uint32_t spin = 1;; ++spin) {
@@ -2805,7 +2742,7 @@ static int sched_wait(NarrowDistinct<KeyT>* d, uint32_t gen, hipStream_t st, int
         STRY(hipStreamSynchronize(st));
         if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != gen) STRY(hipErrorUnknown);
     }
-    for (int i = 0; i < 9; ++i) hv[i] = __atomic_load_n(d->shc + i, __ATOMIC_RELAXED);
+    for (int i = 0; i < 9; ++i) hv[i] = __atomic_load_n(d->sch.hc + i, __ATOMIC_RELAXED);
     return RSV_OK;
 }
 
@@ -2824,13 +2761,13 @@ static int sched_finish(NarrowDistinct<KeyT>* d, const int64_t* hv, int64_t n, i
                      (long long)n, (long long)hv[8], (long long)c, (long long)cap, (long long)hv[1], (long long)hv[6],
                      (long long)hv[7], (long long)k);
     if (c > cap || hv[1]) {  // buffer or bucket overflow: nothing was merged; the counts were not consumed
-        STRY(hipMemsetAsync(d->sctl + kCtlWords, 0, (size_t)kCountStride * 4 * B, st));
+        STRY(hipMemsetAsync(d->sch.ctl + kCtlWords, 0, (size_t)kCountStride * 4 * B, st));
         ++d->sched_fallbacks;
         return RSV_OK;
     }
     if (hv[6] >= 0) {  // a predicted bound was too tight: put the set back, the chunk loop redoes the batch
-        STRY(hipMemcpyAsync(d->set_h, d->bak_h, (size_t)k * 8, hipMemcpyDeviceToDevice, st));
-        STRY(hipMemcpyAsync(d->set_k, d->bak_k, (size_t)k * sizeof(KeyT), hipMemcpyDeviceToDevice, st));
+        STRY(hipMemcpyAsync(d->set.h, d->sch.bak_h, (size_t)k * 8, hipMemcpyDeviceToDevice, st));
+        STRY(hipMemcpyAsync(d->set.k, d->sch.bak_k, (size_t)k * sizeof(KeyT), hipMemcpyDeviceToDevice, st));
         ++d->sched_fallbacks;
         return RSV_OK;
     }
@@ -2843,8 +2780,8 @@ static int sched_finish(NarrowDistinct<KeyT>* d, const int64_t* hv, int64_t n, i
     d->rate_c = c;
     d->rate_m = n;
     d->rate_span = (double)((uint64_t)t0 - (uint64_t)INT64_MIN) + 1.0;
-    d->segs.push_back(LogSeg{d->log_n, c, n});
-    d->log_n += c;
+    d->segs.push_back(LogSeg{d->olog.n, c, n});
+    d->olog.n += c;
     d->seen += n;
     d->spec.ok = spec && d->m == k && !d->over;  // verified, and no replay will change the set
     *done = true;
@@ -2862,7 +2799,7 @@ static int sched_sample(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t
                         bool* done) {
     *done = false;
     const int64_t k = d->k;
-    if (d->m != k || d->max_h == INT64_MIN || n >= ((int64_t)1 << 31) || d->set_cap < k) return RSV_OK;
+    if (d->m != k || d->max_h == INT64_MIN || n >= ((int64_t)1 << 31) || d->set.cap() < k) return RSV_OK;
     SchedDev plan;
     const int64_t t0 = d->max_h - 1;
     const double c_pred = sched_plan_ranges(&plan, (double)d->seen, t0, n, k, d->sched_beta);
@@ -2873,17 +2810,17 @@ static int sched_sample(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t
     sched_plan_map(&plan, k, lb);
     plan.off = 0;
     // the log holds this batch's candidates as one segment
-    if (d->log_n + cap > d->log_limit) {
-        if (cap > d->log_limit) return RSV_OK;
+    if (d->olog.n + cap > d->olog.limit) {
+        if (cap > d->olog.limit) return RSV_OK;
         if (!d->segs.empty()) STRY(replay_log<KeyT>(d, st));
-        if (d->log_n + cap > d->log_limit) return RSV_OK;
+        if (d->olog.n + cap > d->olog.limit) return RSV_OK;
     }
-    STRY(ensure_log(d, d->log_n + cap, st));
+    STRY(ensure_log(d, d->olog.n + cap, st));
     STRY(sched_ensure<KeyT>(d, lb, st));
-    hipLaunchKernelGGL(sched_plan_store, dim3(1), dim3(256), 0, st, plan, d->sdev);
+    hipLaunchKernelGGL(sched_plan_store, dim3(1), dim3(256), 0, st, plan, d->sch.dev);
     uint32_t gen;
     bool spec;
-    if (int rc = sched_launch<KeyT>(d, keys, hashes, n, d->log_n, cap, plan.B, lb, st, &gen, &spec)) return rc;
+    if (int rc = sched_launch<KeyT>(d, keys, hashes, n, d->olog.n, cap, plan.B, lb, st, &gen, &spec)) return rc;
     int64_t hv[9];
     if (int rc = sched_wait(d, gen, st, hv)) return rc;
     return sched_finish<KeyT>(d, hv, n, t0, cap, plan.B, spec, st, done);
@@ -2898,26 +2835,26 @@ template <typename KeyT>
 static int fused_fill_and_pass(NarrowDistinct<KeyT>* d, const KeyT* keys, const int64_t* hashes, int64_t m, int64_t n,
                                int64_t ccap, int64_t cap, int32_t lb, hipStream_t st, int64_t* hp, int64_t* hv,
                                bool* pass, bool* spec) {
-    int64_t* lh = d->log_h + d->log_n;
-    KeyT* lk = d->log_k + d->log_n;
+    int64_t* lh = d->olog.h + d->olog.n;
+    KeyT* lk = d->olog.k + d->olog.n;
     if (d->timer) d->timer->mark(st);
-    STRY(launch_filter_idx<KeyT>(d, keys, hashes, m, INT64_MAX, lh, lk, d->log_i + d->log_n, ccap, st));
+    STRY(launch_filter_idx<KeyT>(d, keys, hashes, m, INT64_MAX, lh, lk, d->olog.i + d->olog.n, ccap, st));
     if (d->timer) d->timer->mark(st);
     STRY(launch_bucket_merge<KeyT>(d, INT64_MAX, st, lh, lk, ccap));
-    const uint32_t cgen = ++d->hc_gen;
-    const bool zero = d->sdirty;
-    hipLaunchKernelGGL(ctl_plan, dim3(1), dim3(64), 0, st, d->ctl, d->hc_dev, (uint32_t*)(d->hc_dev + 8), cgen, ccap,
-                       (int64_t)d->k, std::max(1.0, (double)(d->seen + m)), n - m, d->sched_beta, cap, lb, d->sdev,
-                       d->sctl, (int)zero);
+    const uint32_t cgen = ++d->bkt.gen;
+    const bool zero = d->sch.dirty;
+    hipLaunchKernelGGL(ctl_plan, dim3(1), dim3(64), 0, st, d->bkt.ctl, d->bkt.hc.dev, (uint32_t*)(d->bkt.hc.dev + 8), cgen, ccap,
+                       (int64_t)d->k, std::max(1.0, (double)(d->seen + m)), n - m, d->sched_beta, cap, lb, d->sch.dev,
+                       d->sch.ctl, (int)zero);
     STRY(hipGetLastError());
     uint32_t gen;
-    if (int rc = sched_launch<KeyT>(d, keys + m, hashes ? hashes + m : nullptr, n - m, d->log_n, cap, 1u << lb, lb, st,
+    if (int rc = sched_launch<KeyT>(d, keys + m, hashes ? hashes + m : nullptr, n - m, d->olog.n, cap, 1u << lb, lb, st,
                                     &gen, spec, zero))
         return rc;
-    d->sdirty = false;
+    d->sch.dirty = false;
     if (int rc = sched_wait(d, gen, st, hv)) return rc;
-    if (__atomic_load_n((uint32_t*)(d->hc + 8), __ATOMIC_ACQUIRE) != cgen) STRY(hipErrorUnknown);  // stream order
-    for (int i = 0; i < 6; ++i) hp[i] = __atomic_load_n(d->hc + i, __ATOMIC_RELAXED);
+    if (__atomic_load_n((uint32_t*)(d->bkt.hc + 8), __ATOMIC_ACQUIRE) != cgen) STRY(hipErrorUnknown);  // stream order
+    for (int i = 0; i < 6; ++i) hp[i] = __atomic_load_n(d->bkt.hc + i, __ATOMIC_RELAXED);
     *pass = hv[8] >= 2;
     return RSV_OK;
 }
@@ -2947,11 +2884,11 @@ static int ordered_sample_impl(NarrowDistinct<KeyT>* d, const KeyT* keys, const 
     } while (0)
     if (n <= 0) return RSV_OK;
     const int64_t k = d->k;
-    const int64_t ccap = std::min<int64_t>(d->cand_limit, std::max<int64_t>(4096, 2 * std::min<int64_t>(n, d->cand_limit)));
+    const int64_t ccap = std::min<int64_t>(d->cand.limit, std::max<int64_t>(4096, 2 * std::min<int64_t>(n, d->cand.limit)));
     OTRY(ensure_caps(d, 0, std::min<int64_t>(k, ccap + d->m), st));
     int64_t pos = 0;
     int64_t m_next = 0;  // chunk length after an overflow retry
-    bool sched_tried = !d->sched || d->log_bmax < 0;
+    bool sched_tried = !d->sched || d->bkt.log_bmax < 0;
     // the heap-filling chunk and the pass behind it in one enqueue (fused_fill_and_pass): its sizes
     int64_t fcap = 0;
     int32_t flb = 0;
@@ -2994,11 +2931,11 @@ static int ordered_sample_impl(NarrowDistinct<KeyT>* d, const KeyT* keys, const 
                                           (double)(1ll << 31));
         }
         m = std::min(std::min(m, n - pos), std::min<int64_t>(full ? ((int64_t)1 << 31) : ccap, (int64_t)1 << 31));
-        if (d->log_n + ccap > d->log_limit && !d->segs.empty()) OTRY(replay_log<KeyT>(d, st));
-        OTRY(ensure_log(d, d->log_n + ccap, st));
-        int64_t* lh = d->log_h + d->log_n;
-        KeyT* lk = d->log_k + d->log_n;
-        const bool bucketed = d->log_bmax >= 0 && d->set_cap >= k;
+        if (d->olog.n + ccap > d->olog.limit && !d->segs.empty()) OTRY(replay_log<KeyT>(d, st));
+        OTRY(ensure_log(d, d->olog.n + ccap, st));
+        int64_t* lh = d->olog.h + d->olog.n;
+        KeyT* lk = d->olog.k + d->olog.n;
+        const bool bucketed = d->bkt.log_bmax >= 0 && d->set.cap() >= k;
         int64_t* hp = d->h_pinned + 4;
         // the chunk that may fill the heap, with the pass over the rest planned on the device behind
         // it when the plan's buffers are in place (sched_sample plans on the host: ~18 us of idle GPU
@@ -3006,9 +2943,9 @@ static int ordered_sample_impl(NarrowDistinct<KeyT>* d, const KeyT* keys, const 
         bool pass = false, spec = false;
         int64_t hv[9];
         if (fuse_ok && !sched_tried && !full && bucketed && !m_next && d->m + m >= k && n - pos - m >= 8 * ccap &&
-            d->log_n + ccap + fcap <= d->log_limit) {
+            d->olog.n + ccap + fcap <= d->olog.limit) {
             sched_tried = true;
-            OTRY(ensure_log(d, d->log_n + ccap + fcap, st));
+            OTRY(ensure_log(d, d->olog.n + ccap + fcap, st));
             OTRY(sched_ensure<KeyT>(d, flb, st, true));
             if (int rc = fused_fill_and_pass<KeyT>(d, keys + pos, hashes ? hashes + pos : nullptr, m, n - pos, ccap,
                                                    fcap, flb, st, hp, hv, &pass, &spec))
@@ -3018,7 +2955,7 @@ static int ordered_sample_impl(NarrowDistinct<KeyT>* d, const KeyT* keys, const 
             // candidate counter and overflow word: zeroed at creation and re-armed by every read_ctl
             if (d->timer) d->timer->mark(st);
             OTRY(launch_filter_idx<KeyT>(d, keys + pos, hashes ? hashes + pos : nullptr, m, tinc, lh, lk,
-                                         d->log_i + d->log_n, ccap, st));
+                                         d->olog.i + d->olog.n, ccap, st));
             if (d->timer) d->timer->mark(st);
             if (bucketed) OTRY(launch_bucket_merge<KeyT>(d, tinc, st, lh, lk, ccap));
             OTRY(read_ctl(d, hp, st));
@@ -3038,7 +2975,7 @@ static int ordered_sample_impl(NarrowDistinct<KeyT>* d, const KeyT* keys, const 
             tie = hp[5] != 0;
         } else {
             if (bucketed)  // bucket overflow: the scatter's counts were not consumed
-                OTRY(hipMemsetAsync(d->ctl + kCtlWords, 0, (size_t)kCountStride * 4 << d->log_bmax, st));
+                OTRY(hipMemsetAsync(d->bkt.ctl + kCtlWords, 0, (size_t)kCountStride * 4 << d->bkt.log_bmax, st));
             int64_t nd = 0;
             OTRY(merge_into_set<KeyT>(d, lh, lk, c, &nd, st, tinc));
             tie = d->last_tie;
@@ -3049,8 +2986,8 @@ static int ordered_sample_impl(NarrowDistinct<KeyT>* d, const KeyT* keys, const 
             d->rate_m = m;
             d->rate_span = (double)((uint64_t)tinc - (uint64_t)INT64_MIN) + 1.0;
         }
-        d->segs.push_back(LogSeg{d->log_n, c, m});
-        d->log_n += c;
+        d->segs.push_back(LogSeg{d->olog.n, c, m});
+        d->olog.n += c;
         pos += m;
         d->seen += m;
         if (pass) {  // the pass's verdict, after the chunk's (its log right behind the chunk's)
@@ -3074,7 +3011,7 @@ int NarrowDistinct<KeyT>::sample_device(const void* keys, const int64_t* hashes,
     if (merged && n > 0) {  // sampling on after a merge: the pre-merge candidates are history
         merged = false;
         pre_segs.clear();
-        if (segs.empty()) log_n = 0;
+        if (segs.empty()) olog.n = 0;
         drop_archive();
     }
     return ordered ? ordered_sample_impl<KeyT>(this, (const KeyT*)keys, hashes, n, st)
@@ -3102,8 +3039,8 @@ int NarrowDistinct<KeyT>::finalize(hipStream_t st) {
 template <typename KeyT>
 int NarrowDistinct<KeyT>::export_set(void* keys_dev, int64_t* hash_dev, hipStream_t st) {
     if (m == 0) return RSV_OK;
-    if (keys_dev) RSV_HIP_TRY(hipMemcpyAsync(keys_dev, set_k, m * kw, hipMemcpyDeviceToDevice, st));
-    if (hash_dev) RSV_HIP_TRY(hipMemcpyAsync(hash_dev, set_h, m * 8, hipMemcpyDeviceToDevice, st));
+    if (keys_dev) RSV_HIP_TRY(hipMemcpyAsync(keys_dev, set.k, m * kw, hipMemcpyDeviceToDevice, st));
+    if (hash_dev) RSV_HIP_TRY(hipMemcpyAsync(hash_dev, set.h, m * 8, hipMemcpyDeviceToDevice, st));
     return RSV_OK;
 }
 
@@ -3146,34 +3083,33 @@ static void merged_bookkeeping(NarrowDistinct<KeyT>* d) {
 template <typename KeyT>
 int NarrowDistinct<KeyT>::merge_parts(const void* keys_dev, const int64_t* hash_dev, const int64_t* part_n,
                                       int32_t parts, int64_t part_len, hipStream_t st) {
-    NarrowDistinct* const d = this;
     int64_t total = 0;
     for (int32_t p = 0; p < parts; ++p) total += std::max<int64_t>(0, std::min(part_n[p], part_len));
     if (int rc = settle(st)) return rc;
     if (total == 0) return RSV_OK;
     if (int rc = finalize(st)) return rc;
-    bool tie = d->m == d->k && d->over;
+    bool tie = m == k && over;
     for (int32_t p = 0; p < parts; ++p) {
         const int64_t n = std::max<int64_t>(0, std::min(part_n[p], part_len));
         const KeyT* kp = (const KeyT*)keys_dev + (size_t)p * part_len;
         const int64_t* hp = hash_dev + (size_t)p * part_len;
         for (int64_t off = 0; off < n;) {  // chunks that fit the merge buffer
-            const int64_t c = std::min<int64_t>(n - off, d->cand_limit);
-            const int64_t old_max = d->max_h;
-            const bool was_full = d->m == d->k;
+            const int64_t c = std::min<int64_t>(n - off, cand.limit);
+            const int64_t old_max = max_h;
+            const bool was_full = m == this->k;
             int64_t nd = 0;
-            if (hipError_t e = merge_into_set<KeyT>(d, hp + off, kp + off, c, &nd, st)) {
+            if (hipError_t e = merge_into_set<KeyT>(this, hp + off, kp + off, c, &nd, st)) {
                 // (RSV_E_DEVICE here even for hipErrorOutOfMemory, unlike every other entry point:
                 // hip_status supplies the message only)
                 hip_status(e, "distinct_merge");
                 return RSV_E_DEVICE;
             }
-            tie = d->m == d->k && (d->last_tie || (tie && was_full && d->max_h == old_max));
+            tie = m == k && (last_tie || (tie && was_full && max_h == old_max));
             off += c;
         }
     }
-    d->over = tie;
-    merged_bookkeeping(d);
+    over = tie;
+    merged_bookkeeping(this);
     return RSV_OK;
 }
 
@@ -3181,15 +3117,14 @@ int NarrowDistinct<KeyT>::merge_parts(const void* keys_dev, const int64_t* hash_
 
 template <typename KeyT>
 int NarrowDistinct<KeyT>::export_row(int64_t* row, int64_t count, hipStream_t st) {
-    NarrowDistinct* const d = this;
     if (int rc = settle(st)) return rc;
     if (int rc = finalize(st)) return rc;
-    const int64_t k = d->k;
+    const int64_t k = this->k;
     const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(grid_1d(k), 1), 2048);
-    const int64_t tied = d->m == k && d->over, mx = d->m ? d->set_top : INT64_MIN;
+    const int64_t tied = m == k && over, mx = m ? set_top : INT64_MIN;
     const int64_t ret = retained();
-    hipLaunchKernelGGL(export_row_kernel<KeyT>, dim3(grid), dim3(kBlock), 0, st, (const int64_t*)d->set_h,
-                       (const KeyT*)d->set_k, d->m, k, row, count, tied, mx, ret, (int64_t)d->ordered);
+    hipLaunchKernelGGL(export_row_kernel<KeyT>, dim3(grid), dim3(kBlock), 0, st, (const int64_t*)set.h,
+                       (const KeyT*)set.k, m, k, row, count, tied, mx, ret, (int64_t)ordered);
     RSV_HIP_TRY(hipGetLastError());
     return RSV_OK;
 }
@@ -3224,14 +3159,14 @@ static int merge_rows_radix(NarrowDistinct<KeyT>* d, const int64_t* rows, int32_
         const int64_t* rk = rows + (size_t)p * stride;
         const KeyT* keys = (const KeyT*)rk;
         if constexpr (sizeof(KeyT) == 4) {  // row keys are int64-widened
-            RSV_HIP_TRY(ensure_caps(d, std::min<int64_t>(n, d->cand_limit), 0, st));
-            keys = d->cand_k;
+            RSV_HIP_TRY(ensure_caps(d, std::min<int64_t>(n, d->cand.limit), 0, st));
+            keys = d->cand.k;
         }
         for (int64_t off = 0; off < n;) {  // chunks that fit the merge buffer
-            const int64_t c = std::min<int64_t>(n - off, d->cand_limit);
+            const int64_t c = std::min<int64_t>(n - off, d->cand.limit);
             if constexpr (sizeof(KeyT) == 4) {
                 hipLaunchKernelGGL(narrow_keys<KeyT>, dim3((unsigned)std::min<int64_t>(grid_1d(c), 1024)), dim3(kBlock),
-                                   0, st, rk + off, c, (KeyT*)d->cand_k);
+                                   0, st, rk + off, c, (KeyT*)d->cand.k);
                 RSV_HIP_TRY(hipGetLastError());
             }
             const int64_t old_max = d->max_h;
@@ -3250,14 +3185,13 @@ static int merge_rows_radix(NarrowDistinct<KeyT>* d, const int64_t* rows, int32_
 // the new set's size, maximum and tie state; a bucket overflow redoes the merge on the radix path.
 template <typename KeyT>
 int NarrowDistinct<KeyT>::settle(hipStream_t st) {
-    NarrowDistinct* const d = this;
-    if (!d->pend) return RSV_OK;
-    d->pend = false;
-    uint32_t* flag = (uint32_t*)(d->shc + 12);
+    if (!pend.on) return RSV_OK;
+    pend.on = false;
+    uint32_t* flag = (uint32_t*)(sch.hc + 12);
     const auto t0 = std::chrono::steady_clock::now();
     bool seen = false;
     for (uint32_t spin = 1;; ++spin) {
-        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == d->pend_gen) {
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == pend.gen) {
             seen = true;
             break;
         }
@@ -3266,77 +3200,70 @@ int NarrowDistinct<KeyT>::settle(hipStream_t st) {
     }
     if (!seen) {
         RSV_HIP_TRY(hipStreamSynchronize(st));
-        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != d->pend_gen) RSV_HIP_TRY(hipErrorUnknown);
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != pend.gen) RSV_HIP_TRY(hipErrorUnknown);
     }
     int64_t hv[8];
-    for (int i = 0; i < 8; ++i) hv[i] = __atomic_load_n(d->shc + i, __ATOMIC_RELAXED);
-    const int64_t k = d->k;
+    for (int i = 0; i < 8; ++i) hv[i] = __atomic_load_n(sch.hc + i, __ATOMIC_RELAXED);
+    const int64_t k = this->k;
     if (hv[1])  // a bucket overflowed (rows_sort): nothing was merged
-        return merge_rows_radix<KeyT>(d, d->pend_rows, d->pend_parts, d->pend_stride, st);
-    d->m = std::min<int64_t>(hv[2], k);
-    if (d->m) d->set_top = hv[3];
-    if (d->m == k) d->max_h = d->set_top;
-    d->over = d->m == k && (hv[5] != 0 || ((hv[6] & 2) && d->set_top == hv[7]));
+        return merge_rows_radix<KeyT>(this, pend.rows, pend.parts, pend.stride, st);
+    m = std::min<int64_t>(hv[2], k);
+    if (m) set_top = hv[3];
+    if (m == k) max_h = set_top;
+    over = m == k && (hv[5] != 0 || ((hv[6] & 2) && set_top == hv[7]));
     return RSV_OK;
 }
 
 template <typename KeyT>
 int NarrowDistinct<KeyT>::merge_rows(const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st) {
-    NarrowDistinct* const d = this;
     if (int rc = settle(st)) return rc;
     if (parts <= 0) return RSV_OK;  // (settled all the same, unlike a byte-key engine's empty merge)
     if (int rc = finalize(st)) return rc;  // an ordered set must be exact before it merges
-    const int64_t k = d->k;
-    const int64_t total = d->m + (int64_t)parts * k;
+    const int64_t k = this->k;
+    const int64_t total = m + (int64_t)parts * k;
     int32_t lb = 1;  // <= 64 entries per bucket on average: most sort in one 64-lane pass
     while (((int64_t)1 << (lb + 6)) < total) ++lb;
     const bool device = parts <= 64 && (((int64_t)kBucketCap * (8 + (int64_t)sizeof(KeyT)) + 20) << lb) <= ((int64_t)1 << 30);
     if (!device) {
-        if (int rc = merge_rows_radix<KeyT>(d, rows, parts, stride, st)) return rc;
-        merged_bookkeeping(d);
+        if (int rc = merge_rows_radix<KeyT>(this, rows, parts, stride, st)) return rc;
+        merged_bookkeeping(this);
         return RSV_OK;
     }
-    RSV_HIP_TRY(ensure_caps(d, 0, k, st));  // bucket_emit writes the set by rank: full-size arrays
-    RSV_HIP_TRY(sched_ensure<KeyT>(d, lb, st));
+    RSV_HIP_TRY(ensure_caps(this, 0, k, st));  // bucket_emit writes the set by rank: full-size arrays
+    RSV_HIP_TRY(sched_ensure<KeyT>(this, lb, st));
     const uint32_t B = 1u << lb;
     const int64_t need = (int64_t)(parts + 1) * (B + 1);
-    if (need > d->mstart_cap) {
-        RSV_HIP_TRY(pool_device_grow((void**)&d->mstart, 0, (size_t)need * 4, false, st));
-        d->mstart_cap = need;
-    }
-    const Runs<KeyT> R{rows, stride, k, d->set_h, d->set_k, d->m};
-    RSV_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d->mstart, 0xFFFFFFFFu, (size_t)need, st));
-    const int64_t longest = std::max<int64_t>(d->m, k) + 1;
+    RSV_HIP_TRY(pend.mstart.reserve(need, st));
+    const Runs<KeyT> R{rows, stride, k, set.h, set.k, m};
+    RSV_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)pend.mstart, 0xFFFFFFFFu, (size_t)need, st));
+    const int64_t longest = std::max<int64_t>(m, k) + 1;
     const dim3 bgrid((unsigned)std::min<int64_t>((longest + kBlock - 1) / kBlock, 1024), (unsigned)(parts + 1));
-    hipLaunchKernelGGL(rows_bounds<KeyT>, bgrid, dim3(kBlock), 0, st, R, parts, d->m ? d->set_top : INT64_MIN,
-                       (int32_t)(d->m == k && d->over), (uint32_t)lb, d->sctl, d->log_bmax_s, d->mstart);
-    hipLaunchKernelGGL(rows_fill, dim3((unsigned)(parts + 1)), dim3(1024), 0, st, (uint32_t)lb, d->mstart);
-    KeyT* bk = d->sbk;
+    hipLaunchKernelGGL(rows_bounds<KeyT>, bgrid, dim3(kBlock), 0, st, R, parts, m ? set_top : INT64_MIN,
+                       (int32_t)(m == k && over), (uint32_t)lb, sch.ctl, sch.log_bmax, pend.mstart);
+    hipLaunchKernelGGL(rows_fill, dim3((unsigned)(parts + 1)), dim3(1024), 0, st, (uint32_t)lb, pend.mstart);
+    KeyT* bk = sch.bk;
     hipLaunchKernelGGL(rows_sort<KeyT>, dim3((B + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, st, R, parts,
-                       (uint32_t)lb, (const uint32_t*)d->mstart, d->sctl, d->log_bmax_s, d->sbh, bk);
-    hipLaunchKernelGGL(bucket_emit<KeyT>, dim3((B + kEmitBuckets - 1) / kEmitBuckets), dim3(kBlock), 0, st, d->m,
-                       INT64_MAX, d->sctl, d->log_bmax_s, (const int64_t*)d->sbh, (const KeyT*)bk, k, d->set_h,
-                       (KeyT*)d->set_k, lb);
-    const uint32_t gen = ++d->sgen;
-    hipLaunchKernelGGL(merge_publish, dim3(1), dim3(64), 0, st, d->sctl, d->shc_dev, (uint32_t*)(d->shc_dev + 12), gen);
+                       (uint32_t)lb, (const uint32_t*)pend.mstart, sch.ctl, sch.log_bmax, sch.bh, bk);
+    hipLaunchKernelGGL(bucket_emit<KeyT>, dim3((B + kEmitBuckets - 1) / kEmitBuckets), dim3(kBlock), 0, st, m,
+                       INT64_MAX, sch.ctl, sch.log_bmax, (const int64_t*)sch.bh, (const KeyT*)bk, k, set.h,
+                       (KeyT*)set.k, lb);
+    const uint32_t gen = ++sch.gen;
+    hipLaunchKernelGGL(merge_publish, dim3(1), dim3(64), 0, st, sch.ctl, sch.hc.dev, (uint32_t*)(sch.hc.dev + 12), gen);
     RSV_HIP_TRY(hipGetLastError());
     // the rows as merged, in engine memory: a degenerate hash that overflows a bucket is redone from
     // them at the settle, while the caller may already be reusing its gather buffer (stream-ordered
     // behind the merge kernels: parts x (2k + 6) words, ~8 MB at 8 x 65536)
     const int64_t rw = 2 * k + kRowMeta;
-    if ((int64_t)parts * rw > d->rows_copy_cap) {
-        RSV_HIP_TRY(pool_device_grow((void**)&d->rows_copy, 0, (size_t)parts * rw * 8, false, st));
-        d->rows_copy_cap = (int64_t)parts * rw;
-    }
-    RSV_HIP_TRY(hipMemcpy2DAsync(d->rows_copy, (size_t)rw * 8, rows, (size_t)stride * 8, (size_t)rw * 8, (size_t)parts,
+    RSV_HIP_TRY(pend.copy.reserve((int64_t)parts * rw, st));
+    RSV_HIP_TRY(hipMemcpy2DAsync(pend.copy, (size_t)rw * 8, rows, (size_t)stride * 8, (size_t)rw * 8, (size_t)parts,
                                  hipMemcpyDeviceToDevice, st));
-    d->pend = true;
-    d->pend_gen = gen;
-    d->pend_lb = (uint32_t)lb;
-    d->pend_rows = d->rows_copy;
-    d->pend_parts = parts;
-    d->pend_stride = rw;
-    merged_bookkeeping(d);
+    pend.on = true;
+    pend.gen = gen;
+    pend.lb = (uint32_t)lb;
+    pend.rows = pend.copy;
+    pend.parts = parts;
+    pend.stride = rw;
+    merged_bookkeeping(this);
     return RSV_OK;
 }
 
@@ -3358,7 +3285,7 @@ int NarrowDistinct<KeyT>::log_export(int64_t bound, int64_t* out_h, void* out_k,
         for (const LogSeg& g : *v) {
             if (g.c == 0) continue;
             if (hipError_t e = segment_to_host<KeyT>(this, g, st, false)) return hip_status(e, "rsv_export_log");
-            for (int64_t t = 0; t < g.c; ++t) one(ph[t], pk[t]);
+            for (int64_t t = 0; t < g.c; ++t) one(rpl.pin[0].h[t], rpl.pin[0].k[t]);
         }
     return emit.finish(out_n);
 }
@@ -3368,26 +3295,25 @@ int NarrowDistinct<KeyT>::log_export(int64_t bound, int64_t* out_h, void* out_k,
 // the sampler's state, as if it had seen the whole stream.
 template <typename KeyT>
 int NarrowDistinct<KeyT>::log_merge(const int64_t* h, const void* keys, int64_t n, int64_t seen, hipStream_t st) {
-    NarrowDistinct* const d = this;
-    if (!d->ordered) {
+    if (!ordered) {
         set_error("rsv_merge_log needs an RSV_DISTINCT_ORDERED sampler");
         return RSV_E_UNSUPPORTED;
     }
     if (int rc = settle(st)) return rc;
-    d->rep.reset(d->k);
-    d->rep_stale = false;
+    rep.reset(k);
+    rep_stale = false;
     const KeyT* kk = (const KeyT*)keys;
-    d->rep.sample_run(n, [&](int64_t t) { return (int64_t)kk[t]; }, [&](int64_t t) { return h[t]; });
-    d->segs.clear();
-    d->pre_segs.clear();
-    d->log_n = 0;
+    rep.sample_run(n, [&](int64_t t) { return (int64_t)kk[t]; }, [&](int64_t t) { return h[t]; });
+    segs.clear();
+    pre_segs.clear();
+    olog.n = 0;
     drop_archive();
-    if (hipError_t e = upload_replica<KeyT>(d, st)) return hip_status(e, "rsv_merge_log");
-    d->over = false;
-    d->exact = true;
-    d->merged = true;
-    d->spec.ok = false;
-    d->seen = std::max(d->seen, seen);
+    if (hipError_t e = upload_replica<KeyT>(this, st)) return hip_status(e, "rsv_merge_log");
+    over = false;
+    exact = true;
+    merged = true;
+    spec.ok = false;
+    this->seen = std::max(this->seen, seen);
     return RSV_OK;
 }
 

@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "rsv_buffers.h"  // the resource pool (rsv_pool.h) and the owning buffers over it
+
 namespace rsv {
 
 // thread-local last error (rsv_last_error)
@@ -23,24 +25,6 @@ int hip_status(hipError_t e, const char* what);
             return _e == hipErrorOutOfMemory ? RSV_E_OUT_OF_MEMORY : RSV_E_DEVICE;            \
         }                                                                                     \
     } while (0)
-
-// ---- resource pool (rsv_pool.hip): device / pinned host buffers, streams, events ------------
-// Allocation is on the current device.  A buffer may only be released once no queued work can
-// touch it (synchronize its stream first).
-hipError_t pool_device_alloc(void** p, size_t bytes);
-void pool_device_free(void* p);
-// Replace *p (old_bytes in use) by a block of new_bytes, its contents kept when `keep`; the stream is
-// synchronized before the old block goes back to the pool.
-hipError_t pool_device_grow(void** p, size_t old_bytes, size_t new_bytes, bool keep, hipStream_t st);
-// Capacity for `need` entries: `cur` (at least 1024) doubled until it holds them, at most `cap`.
-int64_t grown_capacity(int64_t cur, int64_t need, int64_t cap);
-hipError_t pool_host_alloc(void** p, size_t bytes, unsigned flags);
-void pool_host_free(void* p);
-void pool_trim();  // free every idle cached buffer
-hipError_t pool_stream(hipStream_t* out);  // non-blocking stream of the current device
-void pool_release_stream(int device, hipStream_t st);
-hipError_t pool_event(hipEvent_t* out, unsigned flags);
-void pool_release_event(int device, hipEvent_t e, unsigned flags);
 
 // HIP-event timing of a handle's hot kernel (rsv_profile_enable / rsv_profile_read)
 struct KernelTimer {

@@ -299,7 +299,7 @@ struct ObjDistinct {
     int64_t r0 = 0, r1 = 0;
     KernelTimer* timer = nullptr;
     // the shadow: sh[cur] is the committed one (c_m values, bound c_T when c_m == k)
-    int64_t* sh[2] = {nullptr, nullptr};
+    DevBuf<int64_t> sh[2];
     int cur = 0;
     int64_t c_m = 0, c_T = 0;
     // the caller's replica after the last committed batch
@@ -309,31 +309,23 @@ struct ObjDistinct {
     bool ran = false;  // it ran chunks: sh[cur ^ 1] and p_m / p_T hold its shadow
     int64_t p_m = 0, p_T = 0;
     int64_t n_cand = 0;
-    // device buffers
-    int64_t* ctl = nullptr;
-    int64_t* ctl_h = nullptr;  // pinned copy of ctl
-    int64_t* cand_h = nullptr;  // the room: (h, offset) in the atomics' order
-    int64_t* cand_i = nullptr;
-    int64_t* out_h = nullptr;   // the same in offset order
-    int64_t* out_i = nullptr;
-    int64_t room = 0;
-    int64_t* area = nullptr;    // sort area
-    int64_t S = 0;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
-    int64_t* hash_d = nullptr;  // a host batch's hashes
-    int64_t hash_cap = 0;
-    int64_t* pin[2] = {nullptr, nullptr};
+    // the buffers (rsv_buffers.h)
+    DevBuf<int64_t> ctl;
+    HostBuf<int64_t> ctl_h;     // pinned copy of ctl
+    DevBuf<int64_t> cand_h;     // the room: (h, offset) in the atomics' order
+    DevBuf<int64_t> cand_i;
+    DevBuf<int64_t> out_h;      // the same in offset order
+    DevBuf<int64_t> out_i;
+    int64_t room() const { return group_cap(cand_h, cand_i, out_h, out_i); }
+    DevBuf<int64_t> area;       // sort area, area.cap entries
+    Scratch temp;
+    DevBuf<int64_t> hash_d;     // a host batch's hashes
+    HostBuf<int64_t> pin[2];
     hipEvent_t pin_free[2] = {nullptr, nullptr};
     int64_t room_first = 0;  // RSV_OBJ_ROOM: the first batch's room (tests force an overflow with it)
 };
 
 namespace {
-
-void free_dev(ObjDistinct* d, int64_t** p) {
-    pool_device_free(*p);
-    *p = nullptr;
-}
 
 // The sort area holds the shadow (<= k) and one chunk's candidates: ~kGrow k expected (each seen
 // length contributes ~k), room for >= 7k; the fill chunk (every element while no bound is known)
@@ -349,23 +341,21 @@ int64_t chunk_len(const ObjDistinct* d, bool open, int64_t seen, int64_t left) {
     return std::min<int64_t>(open ? first_chunk(d) : std::max<int64_t>(first_chunk(d), kGrow * seen), left);
 }
 
+// The old blocks go back to the pool before the new ones are taken (after one wait for the stream), so
+// a retry with twice the room does not hold both.
 int ensure_room(ObjDistinct* d, int64_t room, hipStream_t st) {
-    if (room <= d->room) return RSV_OK;
+    if (room <= d->room()) return RSV_OK;
     OBJ_TRY(hipStreamSynchronize(st));
-    for (int64_t** p : {&d->cand_h, &d->cand_i, &d->out_h, &d->out_i}) {
-        free_dev(d, p);
-        OBJ_TRY(pool_device_alloc((void**)p, (size_t)room * 8));
-    }
-    d->room = room;
+    d->cand_h.release(), d->cand_i.release(), d->out_h.release(), d->out_i.release();
+    OBJ_TRY(reserve_all(room, st, d->cand_h, d->cand_i, d->out_h, d->out_i));
     return RSV_OK;
 }
 
 int ensure_area(ObjDistinct* d, int64_t S, hipStream_t st) {
-    if (S <= d->S) return RSV_OK;
+    if (S <= d->area.cap) return RSV_OK;
     OBJ_TRY(hipStreamSynchronize(st));
-    free_dev(d, &d->area);
-    OBJ_TRY(pool_device_alloc((void**)&d->area, (size_t)S * 8));
-    d->S = S;
+    d->area.release();
+    OBJ_TRY(d->area.reserve(S, st));
     return RSV_OK;
 }
 
@@ -377,7 +367,7 @@ int run_chunks(ObjDistinct* d, const int64_t* hashes, int64_t n, int64_t seen, h
                                   : d->caller_open ? d->c_T : std::min(d->c_T, d->caller_bound);
     hipLaunchKernelGGL(obj_begin, dim3(1), dim3(64), 0, st, d->ctl, d->c_m, (int64_t)open, bound,
                        (int64_t)d->caller_open, d->caller_bound);
-    const int64_t S = d->S;
+    const int64_t S = d->area.cap;
     bool first = true;
     for (int64_t off = 0; off < n;) {
         const int64_t len = chunk_len(d, open, seen, n - off);
@@ -385,13 +375,13 @@ int run_chunks(ObjDistinct* d, const int64_t* hashes, int64_t n, int64_t seen, h
             std::min<int64_t>(std::max<int64_t>((len / 2 + kOBlock * kOU - 1) / (kOBlock * kOU), 1), kOGrid);
         if (d->timer) d->timer->mark(st);
         hipLaunchKernelGGL(obj_filter, dim3((unsigned)blocks), dim3(kOBlock), 0, st, hashes + off, len, off, d->r0, d->r1,
-                           d->ctl, d->cand_h, d->cand_i, d->room);
+                           d->ctl, d->cand_h, d->cand_i, d->room());
         if (d->timer) d->timer->mark(st);
         // shadow update: the committed shadow is read by the first chunk only
         const int64_t* src = first ? d->sh[d->cur] : d->sh[d->cur ^ 1];
         first = false;
         hipLaunchKernelGGL(obj_gather, dim3((unsigned)std::min<int64_t>((S + kOBlock - 1) / kOBlock, 4096)), dim3(kOBlock), 0,
-                           st, d->ctl, src, d->cand_h, d->room, d->area, S);
+                           st, d->ctl, src, d->cand_h, d->room(), d->area, S);
         hipLaunchKernelGGL(obj_sort_tile, dim3((unsigned)(S / kSortTile)), dim3(kSortTile / 2), 0, st, d->area,
                            (int64_t)kSortTile, 1);
         for (int64_t size = 2 * kSortTile; size <= S; size <<= 1) {
@@ -401,7 +391,7 @@ int run_chunks(ObjDistinct* d, const int64_t* hashes, int64_t n, int64_t seen, h
             hipLaunchKernelGGL(obj_sort_tile, dim3((unsigned)(S / kSortTile)), dim3(kSortTile / 2), 0, st, d->area,
                                size, 0);
         }
-        hipLaunchKernelGGL(obj_compact, dim3(1), dim3(kCompactBlock), 0, st, d->ctl, d->area, d->room, S,
+        hipLaunchKernelGGL(obj_compact, dim3(1), dim3(kCompactBlock), 0, st, d->ctl, d->area, d->room(), S,
                            d->sh[d->cur ^ 1], d->k);
         OBJ_TRY(hipGetLastError());
         off += len;
@@ -410,7 +400,7 @@ int run_chunks(ObjDistinct* d, const int64_t* hashes, int64_t n, int64_t seen, h
             OBJ_TRY(hipMemcpyAsync(d->ctl_h, d->ctl, kCtlWords * 8, hipMemcpyDeviceToHost, st));
             OBJ_TRY(hipStreamSynchronize(st));
             open = d->ctl_h[kCtlOpen] != 0;
-            if (d->ctl_h[kCtlCount] > d->room) return RSV_OK;
+            if (d->ctl_h[kCtlCount] > d->room()) return RSV_OK;
         }
     }
     OBJ_TRY(hipMemcpyAsync(d->ctl_h, d->ctl, kCtlWords * 8, hipMemcpyDeviceToHost, st));
@@ -426,9 +416,9 @@ ObjDistinct* obj_create(int32_t k, int64_t r0, int64_t r1, int* status) {
     d->r0 = r0;
     d->r1 = r1;
     if (const char* e = std::getenv("RSV_OBJ_ROOM")) d->room_first = std::max<int64_t>(std::atoll(e), 0);
-    hipError_t e = pool_device_alloc((void**)&d->ctl, kCtlWords * 8);
-    if (e == hipSuccess) e = pool_host_alloc((void**)&d->ctl_h, kCtlWords * 8, hipHostMallocDefault);
-    for (int b = 0; b < 2 && e == hipSuccess; ++b) e = pool_device_alloc((void**)&d->sh[b], (size_t)k * 8);
+    hipError_t e = d->ctl.reserve(kCtlWords, 0);
+    if (e == hipSuccess) e = d->ctl_h.reserve(kCtlWords);
+    for (int b = 0; b < 2 && e == hipSuccess; ++b) e = d->sh[b].reserve(k, 0);
     if (e != hipSuccess) {
         *status = hip_status(e, "allocating the hash shadow");
         obj_destroy(d);
@@ -440,14 +430,9 @@ ObjDistinct* obj_create(int32_t k, int64_t r0, int64_t r1, int* status) {
 
 void obj_destroy(ObjDistinct* d) {
     if (!d) return;
-    // the caller has synchronized the stream
-    void* ds[] = {d->ctl, d->sh[0], d->sh[1], d->cand_h, d->cand_i, d->out_h, d->out_i, d->area, d->temp, d->hash_d};
-    for (void* p : ds) pool_device_free(p);
-    pool_host_free(d->ctl_h);
-    for (int b = 0; b < 2; ++b) {
-        pool_host_free(d->pin[b]);
-        if (d->pin_free[b]) (void)hipEventDestroy(d->pin_free[b]);
-    }
+    // the caller has synchronized the stream: the buffers return their blocks
+    for (hipEvent_t e : d->pin_free)
+        if (e) (void)hipEventDestroy(e);
     delete d;
 }
 
@@ -460,16 +445,14 @@ int obj_candidates(ObjDistinct* d, const int64_t* hashes, int64_t n, bool on_dev
     *n_cand = 0;
     if (n == 0) return RSV_OK;
     if (!on_device) {  // through the pinned staging pair into a device copy of the batch's hashes
-        if (n > d->hash_cap) {
+        if (n > d->hash_d.cap) {
             OBJ_TRY(hipStreamSynchronize(st));
-            free_dev(d, &d->hash_d);
-            d->hash_cap = 0;
-            OBJ_TRY(pool_device_alloc((void**)&d->hash_d, (size_t)n * 8));
-            d->hash_cap = n;
+            d->hash_d.release();
+            OBJ_TRY(d->hash_d.reserve(n, st));
         }
         for (int b = 0; b < 2; ++b)
             if (!d->pin[b]) {
-                OBJ_TRY(pool_host_alloc((void**)&d->pin[b], (size_t)kPinned * 8, hipHostMallocDefault));
+                OBJ_TRY(d->pin[b].reserve(kPinned));
                 OBJ_TRY(hipEventCreateWithFlags(&d->pin_free[b], hipEventDisableTiming));
             }
         int b = 0;
@@ -501,12 +484,12 @@ int obj_candidates(ObjDistinct* d, const int64_t* hashes, int64_t n, bool on_dev
         if (int rc = ensure_area(d, S, st)) return rc;
         if (int rc = run_chunks(d, hashes, n, seen, st)) return rc;
         const int64_t got = d->ctl_h[kCtlCount];
-        if (got <= d->room && !d->ctl_h[kCtlSpill]) break;
+        if (got <= d->room() && !d->ctl_h[kCtlSpill]) break;
         // candidates were dropped (and counted): a larger room / sort area, and the batch again from
         // the committed shadow.  Still no bound at the end: every element is a candidate.
-        if (d->ctl_h[kCtlSpill]) S = 2 * d->S;
-        if (got > d->room)
-            room = d->ctl_h[kCtlOpen] ? n : std::min<int64_t>(n, std::max<int64_t>(2 * d->room, chunks * chunk_room(d)));
+        if (d->ctl_h[kCtlSpill]) S = 2 * d->area.cap;
+        if (got > d->room())
+            room = d->ctl_h[kCtlOpen] ? n : std::min<int64_t>(n, std::max<int64_t>(2 * d->room(), chunks * chunk_room(d)));
     }
     d->ran = true;
     d->p_m = d->ctl_h[kCtlM];
@@ -522,17 +505,11 @@ int obj_candidates(ObjDistinct* d, const int64_t* hashes, int64_t n, bool on_dev
         int bits = 1;
         while (bits < 63 && (n >> bits) != 0) ++bits;
         size_t need = 0;
-        OBJ_TRY(rocprim::radix_sort_pairs(nullptr, need, d->cand_i, d->out_i, d->cand_h, d->out_h, (size_t)d->n_cand, 0,
-                                          (unsigned)bits, st));
-        if (need > d->temp_bytes) {
-            pool_device_free(d->temp);
-            d->temp = nullptr;
-            d->temp_bytes = 0;
-            OBJ_TRY(pool_device_alloc(&d->temp, need));
-            d->temp_bytes = need;
-        }
-        OBJ_TRY(rocprim::radix_sort_pairs(d->temp, need, d->cand_i, d->out_i, d->cand_h, d->out_h, (size_t)d->n_cand, 0,
-                                          (unsigned)bits, st));
+        OBJ_TRY(rocprim::radix_sort_pairs(nullptr, need, d->cand_i.p, d->out_i.p, d->cand_h.p, d->out_h.p,
+                                          (size_t)d->n_cand, 0, (unsigned)bits, st));
+        OBJ_TRY(d->temp.reserve(need, st));  // (a growth waits for the stream, idle here since run_chunks)
+        OBJ_TRY(rocprim::radix_sort_pairs(d->temp.p(), need, d->cand_i.p, d->out_i.p, d->cand_h.p, d->out_h.p,
+                                          (size_t)d->n_cand, 0, (unsigned)bits, st));
         OBJ_TRY(hipStreamSynchronize(st));
     }
     *n_cand = d->n_cand;

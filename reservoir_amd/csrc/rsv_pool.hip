@@ -164,6 +164,17 @@ int64_t grown_capacity(int64_t cur, int64_t need, int64_t cap) {
 }
 
 hipError_t pool_host_alloc(void** p, size_t bytes, unsigned flags) { return alloc(kHost, flags, bytes, p); }
+hipError_t pool_host_alloc_mapped(void** p, void** dev_alias, size_t bytes) {
+    void* q = nullptr;
+    hipError_t e = pool_host_alloc(&q, bytes, hipHostMallocCoherent | hipHostMallocMapped);
+    if (e != hipSuccess) return e;
+    if ((e = hipHostGetDevicePointer(dev_alias, q, 0)) != hipSuccess) {
+        release(q);
+        return e;
+    }
+    *p = q;
+    return hipSuccess;
+}
 void pool_host_free(void* p) { release(p); }
 
 void pool_trim() {

@@ -159,27 +159,27 @@ struct rsv_sampler {
     AlgoLState algo_l;
     std::vector<int64_t> ev_pos_h;
     std::vector<int32_t> ev_slot_h;
-    int64_t* ev_pos_d = nullptr;
-    int32_t* ev_slot_d = nullptr;
-    int64_t ev_cap = 0;
+    DevBuf<int64_t> ev_pos_d;
+    DevBuf<int32_t> ev_slot_d;
     // index-only batches (rsv_sample_indexed): per slot the batch offset of its new element
-    int64_t* idx_offs_d = nullptr;
+    DevBuf<int64_t> idx_offs_d;
     // rsv_abort_indexed: the slot indices before the pending index-only batch, and its start
-    int64_t* idx_bak_d = nullptr;
+    DevBuf<int64_t> idx_bak_d;
     bool idx_fresh = false;
     int64_t idx_base = 0;
     AlgoLState idx_algo_l;  // JAVA_L: java.util.Random and W before the batch's events
     // the index-only batch's offsets in host memory: k <= 8192 coherent + mapped, published by the
     // resolve kernel with flag offs_flag = offs_gen; larger k a pinned D2H target
-    int64_t* offs_h = nullptr;
+    MappedBuf<uint8_t> offs_pub;  // the owner of the published form (offsets + flag line)
+    HostBuf<int64_t> offs_pin;    // the owner of the pinned form
+    int64_t* offs_h = nullptr;    // the offsets in whichever of the two
     int64_t* offs_dev = nullptr;
     uint32_t* offs_flag = nullptr;
     uint32_t* offs_flag_dev = nullptr;
     uint32_t offs_gen = 0;
     // the winners' keys in slot order (host gather of a winners-only batch, rsv_fill_slots): pinned,
     // coherent and mapped, read by the fill kernel across PCIe (no H2D copy, no host wait)
-    uint8_t* gath_h = nullptr;
-    void* gath_dev = nullptr;
+    MappedBuf<uint8_t> gath_h;
     // DISTINCT
     DistinctEngine* distinct = nullptr;
     int hash_kind = kHashIdentity;
@@ -190,23 +190,22 @@ struct rsv_sampler {
     // host staging: per-element calls and host batches
     // per-element sample(): two pinned staging buffers; a full one is flushed asynchronously
     // (H2D + kernels, no host wait) while the other fills; an event says when it is free again
-    uint8_t* stage_h[2] = {nullptr, nullptr};
-    void* stage_dev[2] = {nullptr, nullptr};  // device aliases (winners-only flushes read them in place)
-    int64_t* stage_hash_h[2] = {nullptr, nullptr};
+    MappedBuf<uint8_t> stage_h[2];  // (winners-only flushes read them in place through the device alias)
+    HostBuf<int64_t> stage_hash_h[2];
     hipEvent_t stage_free[2] = {nullptr, nullptr};
     // java_l staged flushes: the batch's Algorithm-L events in pinned memory owned by the staging
     // buffer (free again with stage_free[b]), so their H2D copies need no host wait
-    int64_t* stage_ev_pos[2] = {nullptr, nullptr};
-    int32_t* stage_ev_slot[2] = {nullptr, nullptr};
-    int64_t stage_ev_cap[2] = {0, 0};
+    HostBuf<int64_t> stage_ev_pos[2];
+    HostBuf<int32_t> stage_ev_slot[2];
     bool stage_pending[2] = {false, false};
     int stage_cur = 0;
     int64_t stage_n = 0;
     int64_t stage_cap = 0;
-    void* chunk_d = nullptr;     // device chunk for host batches
-    int64_t* chunk_hash_d = nullptr;
-    int64_t chunk_cap = 0;
-    void* result_h = nullptr;  // pinned staging for result() (k keys)
+    DevBuf<uint8_t> chunk_d;     // device chunk for host batches (kChunkKeys keys)
+    DevBuf<int64_t> chunk_hash_d;
+    MappedBuf<uint8_t> result_pub;  // the owner of result_h's published form (keys + flag line)
+    HostBuf<uint8_t> result_pin;    // the owner of its pinned form
+    void* result_h = nullptr;  // pinned staging for result() (k keys) in whichever of the two
     // small reservoirs: result_h is coherent + mapped and publish_kernel writes it directly,
     // followed by result_gen in result_flag (same allocation); the host spins on the flag
     bool result_publish = false;
@@ -338,17 +337,11 @@ rsv_status check_keyed(const rsv_sampler* s) {
 }
 
 rsv_status ensure_events(rsv_sampler* s, int64_t n) {
-    if (n <= s->ev_cap) return RSV_OK;
-    int64_t cap = std::max<int64_t>(n, 2 * s->ev_cap);
+    const int64_t cur = group_cap(s->ev_pos_d, s->ev_slot_d);
+    if (n <= cur) return RSV_OK;
     if (s->ev_pos_d || s->ev_slot_d) RSV_HIP_TRY(sync_stream(s));  // before reuse elsewhere
-    pool_device_free(s->ev_pos_d);
-    pool_device_free(s->ev_slot_d);
-    s->ev_pos_d = nullptr;
-    s->ev_slot_d = nullptr;
-    s->ev_cap = 0;
-    RSV_HIP_TRY(pool_device_alloc((void**)&s->ev_pos_d, cap * 8));
-    RSV_HIP_TRY(pool_device_alloc((void**)&s->ev_slot_d, cap * 4));
-    s->ev_cap = cap;
+    s->ev_pos_d.release(), s->ev_slot_d.release();
+    RSV_HIP_TRY(reserve_all(std::max<int64_t>(n, 2 * cur), s->stream, s->ev_pos_d, s->ev_slot_d));
     return RSV_OK;
 }
 
@@ -407,12 +400,14 @@ constexpr int64_t kPublishMaxBytes = 1 << 20;
 
 // A publication target: `bytes` of coherent, mapped host memory and one 64-byte flag line behind it,
 // with their device aliases; the flag starts at the generation `gen` (nothing published yet).
-rsv_status alloc_flagged(size_t bytes, uint32_t gen, void** host, void** dev, uint32_t** flag, uint32_t** flag_dev) {
+rsv_status alloc_flagged(size_t bytes, uint32_t gen, MappedBuf<uint8_t>& blk, void** host, void** dev, uint32_t** flag,
+                         uint32_t** flag_dev) {
     const size_t flag_off = (bytes + 63) & ~(size_t)63;
-    RSV_HIP_TRY(pool_host_alloc(host, flag_off + 64, hipHostMallocCoherent | hipHostMallocMapped));
-    RSV_HIP_TRY(hipHostGetDevicePointer(dev, *host, 0));
-    *flag = (uint32_t*)((uint8_t*)*host + flag_off);
-    *flag_dev = (uint32_t*)((uint8_t*)*dev + flag_off);
+    RSV_HIP_TRY(blk.reserve((int64_t)flag_off + 64));
+    *host = blk.p;
+    *dev = blk.dev;
+    *flag = (uint32_t*)(blk.p + flag_off);
+    *flag_dev = (uint32_t*)(blk.dev + flag_off);
     **flag = gen;
     return RSV_OK;
 }
@@ -421,12 +416,13 @@ rsv_status ensure_result_buffer(rsv_sampler* s) {
     if (s->result_h) return RSV_OK;
     const size_t bytes = (size_t)s->k * s->kw;
     if ((int64_t)bytes <= kPublishMaxBytes) {
-        if (rsv_status st = alloc_flagged(bytes, s->result_gen, &s->result_h, &s->result_dev, &s->result_flag,
-                                          &s->result_flag_dev))
+        if (rsv_status st = alloc_flagged(bytes, s->result_gen, s->result_pub, &s->result_h, &s->result_dev,
+                                          &s->result_flag, &s->result_flag_dev))
             return st;
         s->result_publish = true;
     } else {
-        RSV_HIP_TRY(pool_host_alloc(&s->result_h, bytes, hipHostMallocDefault));
+        RSV_HIP_TRY(s->result_pin.reserve((int64_t)bytes));
+        s->result_h = s->result_pin.p;
     }
     return RSV_OK;
 }
@@ -512,17 +508,10 @@ rsv_status replay_java_l(rsv_sampler* s, int64_t base, int64_t n, int stage_b, i
     const void* pos_src = s->ev_pos_h.data();
     const void* slot_src = s->ev_slot_h.data();
     if (stage_b >= 0) {
-        if (s->stage_ev_cap[stage_b] < ne) {
-            const int64_t cap = std::max<int64_t>(ne, 2 * s->stage_ev_cap[stage_b]);
-            pool_host_free(s->stage_ev_pos[stage_b]);
-            pool_host_free(s->stage_ev_slot[stage_b]);
-            s->stage_ev_pos[stage_b] = nullptr;
-            s->stage_ev_slot[stage_b] = nullptr;
-            s->stage_ev_cap[stage_b] = 0;
-            RSV_HIP_TRY(pool_host_alloc((void**)&s->stage_ev_pos[stage_b], cap * 8, hipHostMallocDefault));
-            RSV_HIP_TRY(pool_host_alloc((void**)&s->stage_ev_slot[stage_b], cap * 4, hipHostMallocDefault));
-            s->stage_ev_cap[stage_b] = cap;
-        }
+        const int64_t cur = group_cap(s->stage_ev_pos[stage_b], s->stage_ev_slot[stage_b]);
+        if (cur < ne)
+            RSV_HIP_TRY(reserve_all(std::max<int64_t>(ne, 2 * cur), nullptr, s->stage_ev_pos[stage_b],
+                                    s->stage_ev_slot[stage_b]));
         memcpy(s->stage_ev_pos[stage_b], pos_src, ne * 8);
         memcpy(s->stage_ev_slot[stage_b], slot_src, ne * 4);
         pos_src = s->stage_ev_pos[stage_b];
@@ -621,11 +610,9 @@ rsv_status process_device_batch(rsv_sampler* s, const void* keys, const int64_t*
 }
 
 rsv_status ensure_chunk(rsv_sampler* s) {
-    if (s->chunk_d) return RSV_OK;
-    RSV_HIP_TRY(pool_device_alloc(&s->chunk_d, kChunkKeys * s->kw));
+    RSV_HIP_TRY(s->chunk_d.reserve(kChunkKeys * s->kw, s->stream));
     if (s->cfg.kind == RSV_KIND_DISTINCT && s->hash_kind == kHashPrecomputed)
-        RSV_HIP_TRY(pool_device_alloc((void**)&s->chunk_hash_d, kChunkKeys * 8));
-    s->chunk_cap = kChunkKeys;
+        RSV_HIP_TRY(s->chunk_hash_d.reserve(kChunkKeys, s->stream));
     return RSV_OK;
 }
 
@@ -652,16 +639,16 @@ rsv_status spin_flag(rsv_sampler* s, const uint32_t* flag, uint32_t gen, const c
 // valid until the handle's next index-only batch).  No key is read.  The caller then supplies the
 // winners' keys (fill_gathered) or undoes the batch (rsv_abort_indexed).
 rsv_status index_batch(rsv_sampler* s, int64_t n, const int64_t** offs_out) {
-    if (!s->idx_offs_d) RSV_HIP_TRY(pool_device_alloc((void**)&s->idx_offs_d, (size_t)s->k * 8));
-    if (!s->idx_bak_d) RSV_HIP_TRY(pool_device_alloc((void**)&s->idx_bak_d, (size_t)s->k * 8));
+    RSV_HIP_TRY(reserve_all(s->k, s->stream, s->idx_offs_d, s->idx_bak_d));
     const bool publish = resolve_indices_publish_ok(s->k);
     if (!s->offs_h) {
         if (publish) {
-            if (rsv_status st = alloc_flagged((size_t)s->k * 8, s->offs_gen, (void**)&s->offs_h, (void**)&s->offs_dev,
-                                              &s->offs_flag, &s->offs_flag_dev))
+            if (rsv_status st = alloc_flagged((size_t)s->k * 8, s->offs_gen, s->offs_pub, (void**)&s->offs_h,
+                                              (void**)&s->offs_dev, &s->offs_flag, &s->offs_flag_dev))
                 return st;
         } else {
-            RSV_HIP_TRY(pool_host_alloc((void**)&s->offs_h, (size_t)s->k * 8, hipHostMallocDefault));
+            RSV_HIP_TRY(s->offs_pin.reserve(s->k));
+            s->offs_h = s->offs_pin.p;
         }
     }
     const int64_t base = s->count;
@@ -702,9 +689,7 @@ rsv_status index_batch(rsv_sampler* s, int64_t n, const int64_t** offs_out) {
 }
 
 rsv_status ensure_gather(rsv_sampler* s) {
-    if (s->gath_h) return RSV_OK;
-    RSV_HIP_TRY(pool_host_alloc((void**)&s->gath_h, (size_t)s->k * s->kw, hipHostMallocCoherent | hipHostMallocMapped));
-    RSV_HIP_TRY(hipHostGetDevicePointer(&s->gath_dev, s->gath_h, 0));
+    RSV_HIP_TRY(s->gath_h.reserve((int64_t)s->k * s->kw));
     return RSV_OK;
 }
 
@@ -717,7 +702,7 @@ rsv_status fill_gathered(rsv_sampler* s) {
     touch(s);
     Publication pub;
     if (rsv_status st = begin_publish(s, fill_slots_publish_ok(s->k, s->kw), s->count, &pub)) return st;
-    RSV_HIP_TRY(launch_fill_slots(s->idx_offs_d, s->gath_dev, slot_block(s), pub, s->stream));
+    RSV_HIP_TRY(launch_fill_slots(s->idx_offs_d, s->gath_h.dev, slot_block(s), pub, s->stream));
     record_publish(s, pub);
     s->keys_owed = false;
     return RSV_OK;
@@ -747,8 +732,8 @@ rsv_status process_host_batch(rsv_sampler* s, const void* keys, const int64_t* h
     if (s->cfg.kind == RSV_KIND_ELEMENTS) return host_batch_elements(s, keys, n);
     if (rsv_status st = ensure_chunk(s)) return st;
     join_side(s);  // (a forked resolve reads its batch's keys; none for DISTINCT, kept for symmetry)
-    for (int64_t off = 0; off < n; off += s->chunk_cap) {
-        const int64_t c = std::min(s->chunk_cap, n - off);
+    for (int64_t off = 0; off < n; off += (int64_t)kChunkKeys) {
+        const int64_t c = std::min((int64_t)kChunkKeys, n - off);
         RSV_HIP_TRY(hipMemcpyAsync(s->chunk_d, (const uint8_t*)keys + off * s->kw, c * s->kw,
                                    hipMemcpyHostToDevice, s->stream));
         if (s->chunk_hash_d && hashes)
@@ -794,7 +779,7 @@ rsv_status flush_stage(rsv_sampler* s) {
     if (stage_in_place(s, n)) {
         s->stage_pending[b] = true;
         s->stage_cur = b ^ 1;
-        if (rsv_status st = process_device_batch(s, s->stage_dev[b], nullptr, n, b)) return st;
+        if (rsv_status st = process_device_batch(s, s->stage_h[b].dev, nullptr, n, b)) return st;
         // the buffer is free once the resolve that reads it has run (on the resolve stream if forked)
         RSV_HIP_TRY(hipEventRecord(s->stage_free[b], s->side_pending ? s->rstream : s->stream));
         return RSV_OK;
@@ -819,18 +804,8 @@ rsv_status flush_stage(rsv_sampler* s) {
 void free_all(rsv_sampler* s) {
     // callers have synchronized the stream: nothing queued touches these any more
     if (s->slots && s->win_zero && give_clean_slots(s->slots, s->k, s->kw, s->device)) s->slots = nullptr;
-    void* ds[] = {s->slots, s->ev_pos_d, s->ev_slot_d, s->chunk_d, s->chunk_hash_d, s->idx_offs_d, s->idx_bak_d};
-    for (void* p : ds) pool_device_free(p);
-    for (int b = 0; b < 2; ++b) {
-        pool_host_free(s->stage_h[b]);
-        pool_host_free(s->stage_hash_h[b]);
-        pool_host_free(s->stage_ev_pos[b]);
-        pool_host_free(s->stage_ev_slot[b]);
-        pool_release_event(s->device, s->stage_free[b], hipEventDisableTiming);
-    }
-    pool_host_free(s->result_h);
-    pool_host_free(s->offs_h);
-    pool_host_free(s->gath_h);
+    pool_device_free(s->slots);  // (every other block is owned by a buffer and goes back with the handle)
+    for (hipEvent_t e : s->stage_free) pool_release_event(s->device, e, hipEventDisableTiming);
     // the handover record has completed: the stream waiting on it was synchronized, or its
     // publication seen, before this
     if (s->handover) pool_release_event(s->device, s->handover, hipEventDisableTiming);
@@ -1000,10 +975,8 @@ static rsv_status stage_slow(rsv_sampler* s, bool pre) {
     if (!s->stage_h[0]) {
         for (int b = 0; b < 2; ++b) {
             // coherent + mapped: a winners-only flush's resolve reads the keys in place (flush_stage)
-            RSV_HIP_TRY(pool_host_alloc((void**)&s->stage_h[b], kStageKeys * s->kw,
-                                        hipHostMallocCoherent | hipHostMallocMapped));
-            RSV_HIP_TRY(hipHostGetDevicePointer(&s->stage_dev[b], s->stage_h[b], 0));
-            if (pre) RSV_HIP_TRY(pool_host_alloc((void**)&s->stage_hash_h[b], kStageKeys * 8, hipHostMallocDefault));
+            RSV_HIP_TRY(s->stage_h[b].reserve(kStageKeys * s->kw));
+            if (pre) RSV_HIP_TRY(s->stage_hash_h[b].reserve(kStageKeys));
             RSV_HIP_TRY(pool_event(&s->stage_free[b], hipEventDisableTiming));
         }
         s->stage_cap = kStageKeys;
@@ -1314,7 +1287,8 @@ rsv_status rsv_result_take(rsv_sampler* s, void** buf, int64_t* out_n) {
     rsv_status st = result_impl(s, nullptr, cap, out_n, false, /*take=*/true);
     if (st != RSV_OK) return st;
     *buf = h;
-    s->result_h = nullptr;  // the caller's now: a closed single-use handle publishes nothing more
+    (void)s->result_pub.detach();  // the caller's now (rsv_host_release): a closed single-use handle publishes nothing more
+    s->result_h = nullptr;
     s->result_dev = nullptr;
     s->result_flag = nullptr;
     s->result_flag_dev = nullptr;

@@ -24,6 +24,11 @@
 // distinct_create in rsv_distinct.hip picks it for key_width > 8): the runtime calls its methods
 // through the interface, and the speculative-publication target, the log-retention rules and
 // rsv_export_log's messages are the base's, shared with the Long / Int engine.
+//
+// Host state: the device and pinned memory sits in owning buffers (rsv_buffers.h) grouped by
+// role -- set (the set pair), cand (candidates), mrg (merge entries and rocPRIM's scratch), wb (the bucket
+// area), olog (the ordered log), pin (the replay's pinned copies).  Rows take `words` entries each, so the
+// capacities in rows are computed (set_cap(), cand_cap(), log_cap(), pin_cap()), not stored.
 #include <rocprim/device/device_merge_sort.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -826,45 +831,49 @@ struct WideDistinct final : DistinctEngine {
     bool tied = false;            // full, and the boundary hash bucket holds more distinct elements
     bool exact = true;            // ordered: the set arrays hold the reference's set
     KernelTimer* timer = nullptr;
-    // device
-    int64_t* set_h = nullptr;     // [set_cap] ascending (h, key words)
-    uint64_t* set_k = nullptr;
-    int64_t* set_h2 = nullptr;    // the merge's output (swapped in)
-    uint64_t* set_k2 = nullptr;
-    int64_t set_cap = 0;
-    int64_t* cand_h = nullptr;    // [cand_cap] candidates: h, batch offset, row
-    int64_t* cand_i = nullptr;
-    uint64_t* cand_k = nullptr;
-    int64_t cand_cap = 0;
-    int64_t *eh0 = nullptr, *eh1 = nullptr;  // [merge_cap] merge entries
-    uint32_t *ev0 = nullptr, *ev1 = nullptr, *flags = nullptr, *pos = nullptr;
-    int64_t merge_cap = 0;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
-    int64_t* ctl = nullptr;       // [8]: [0] candidate counter [1] long run [2] distinct [3] top [4] tie
-    int64_t* hctl = nullptr;      // pinned copy
+    // Device and pinned memory by role, in owning buffers (rsv_buffers.h).  Rows take `words` entries each,
+    // so a role's capacity in rows is computed by the *_cap() members below, never stored.
+    struct SetPair {              // ascending (h, key words), and the merge's output (swapped in)
+        DevBuf<int64_t> h, h2;
+        DevBuf<uint64_t> k, k2;
+    } set;
+    struct Candidates {           // h, batch offset, row
+        DevBuf<int64_t> h, i;
+        DevBuf<uint64_t> k;
+    } cand;
+    struct MergeArea {            // merge entries (h, index), dedup flags and positions, rocPRIM's scratch
+        DevBuf<int64_t> h0, h1;
+        DevBuf<uint32_t> v0, v1, flags, pos;
+        Scratch temp;
+        int64_t cap() const { return group_cap(h0, h1, v0, v1, flags, pos); }
+    } mrg;
+    DevBuf<int64_t> ctl;          // [8]: [0] candidate counter [1] long run [2] distinct [3] top [4] tie
+    HostBuf<int64_t> hctl;        // pinned copy
     // ordered mode: the candidate log since the replica's state (h, global index, row), device
-    int64_t* log_h = nullptr;
-    int64_t* log_g = nullptr;
-    uint64_t* log_k = nullptr;
-    int64_t log_n = 0, log_cap = 0, log_limit = 0;
+    struct OrderedLog {
+        DevBuf<int64_t> h, g;
+        DevBuf<uint64_t> k;
+        int64_t n = 0, limit = 0;
+    } olog;
+    int64_t set_cap() const { return std::min(group_cap(set.h, set.h2), group_cap(set.k, set.k2) / words); }
+    int64_t cand_cap() const { return std::min(group_cap(cand.h, cand.i), cand.k.cap / words); }
+    int64_t log_cap() const { return std::min(group_cap(olog.h, olog.g), olog.k.cap / words); }
+    int64_t pin_cap() const { return std::min(group_cap(pin.oh, pin.fl), pin.ok.cap / words); }
     HostValuesWide rep;           // the exact RandomValues state before the log's first entry
     bool rep_stale = false;       // a merge replaced the set: rebuild the replica from it first
     std::vector<int64_t> arch_h;  // consumed candidates in arrival order (the base's `retain`)
     std::vector<uint64_t> arch_k;
     // ordered mode's scheduled pass: range table + verification counts (device [0, 2 kWMaxR + 1) the
     // table, [kSchedCounts, + kWMaxR + 1) the counts; pinned staging alike)
-    int64_t* sched = nullptr;
-    int64_t* hsched = nullptr;
-    // the bucketed merge's area (wb_scatter / wb_sort / wb_emit), sized for wb_cap buckets
-    int64_t* wb_h = nullptr;
-    uint32_t* wb_e = nullptr;
-    int64_t* wb_a = nullptr;
-    uint32_t* wb_cnt = nullptr;
-    uint32_t* wb_dist = nullptr;
-    uint32_t* wb_gsum = nullptr;
-    uint32_t wb_cap = 0;
-    bool wb_cnt_dirty = false;    // a new bucket area: its counters are zeroed by the next wb_prep
+    DevBuf<int64_t> sched;
+    HostBuf<int64_t> hsched;
+    // the bucketed merge's area (wb_scatter / wb_sort / wb_emit), sized for `cap` buckets
+    struct BucketArea {
+        DevBuf<int64_t> h, a;
+        DevBuf<uint32_t> e, cnt, dist, gsum;
+        uint32_t cap = 0;         // set once every member holds that many buckets (ensure_buckets)
+        bool cnt_dirty = false;   // a new bucket area: its counters are zeroed by the next wb_prep
+    } wb;
     bool bucketed_on = true;      // RSV_WIDE_BUCKETED=0: the sort-based merge only (A/B, tests)
     bool last_bucketed = false;   // the last merge's sorted entries are in the bucket area (wb_verify)
     uint32_t last_B = 0;
@@ -879,17 +888,18 @@ struct WideDistinct final : DistinctEngine {
     // pinned host copies of the log for the replay (hashes, rows, first-occurrence flags), kept
     // between replays: a fresh pageable vector per replay paid its page faults and zero fill, and
     // pageable copies run at about half the DMA rate
-    int64_t* p_oh = nullptr;
-    uint64_t* p_ok = nullptr;
-    uint32_t* p_fl = nullptr;
-    int64_t p_cap = 0;
+    struct PinnedLog {
+        HostBuf<int64_t> oh;
+        HostBuf<uint64_t> ok;
+        HostBuf<uint32_t> fl;
+    } pin;
 
     ~WideDistinct() override;
     void set_timer(KernelTimer* t) override { timer = t; }
     int sample_device(const void* keys, const int64_t* hashes, int64_t n, hipStream_t st) override;
     int64_t size() const override { return m; }
     int finalize(hipStream_t st) override;
-    const void* keys_dev() const override { return set_k; }
+    const void* keys_dev() const override { return set.k; }
     int publish(void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, hipStream_t st) override;
     void spec_target(void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter) override;
     // the one-pass batches decide by their own shape, whatever RSV_SPEC_MIN_BATCH says
@@ -914,65 +924,40 @@ struct WideDistinct final : DistinctEngine {
 
 namespace {
 
+// room for a set of `need` rows (contents kept) and for the merge's output beside it
 hipError_t ensure_set(WideDistinct* d, int64_t need, hipStream_t st) {
     need = std::min<int64_t>(need, d->k);
-    if (need <= d->set_cap) return hipSuccess;
-    const int64_t c = grown_capacity(d->set_cap, need, d->k);
-    const size_t W = (size_t)d->words * 8;
+    if (need <= d->set_cap()) return hipSuccess;
+    const int64_t c = grown_capacity(d->set_cap(), need, d->k), w = d->words;
     hipError_t e;
-    if ((e = pool_device_grow((void**)&d->set_h, (size_t)d->m * 8, (size_t)c * 8, true, st))) return e;
-    if ((e = pool_device_grow((void**)&d->set_k, (size_t)d->m * W, (size_t)c * W, true, st))) return e;
-    if ((e = pool_device_grow((void**)&d->set_h2, 0, (size_t)c * 8, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->set_k2, 0, (size_t)c * W, false, st))) return e;
-    d->set_cap = c;
-    return hipSuccess;
+    if ((e = d->set.h.reserve_keep(c, d->m, st))) return e;
+    if ((e = d->set.k.reserve_keep(c * w, d->m * w, st))) return e;
+    if ((e = d->set.h2.reserve(c, st))) return e;
+    return d->set.k2.reserve(c * w, st);
 }
 
 hipError_t ensure_cand(WideDistinct* d, int64_t need, hipStream_t st) {
-    if (need <= d->cand_cap) return hipSuccess;
-    const int64_t c = grown_capacity(d->cand_cap, need, INT64_MAX);
+    if (need <= d->cand_cap()) return hipSuccess;
+    const int64_t c = grown_capacity(d->cand_cap(), need, INT64_MAX);
     hipError_t e;
-    if ((e = pool_device_grow((void**)&d->cand_h, 0, (size_t)c * 8, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->cand_i, 0, (size_t)c * 8, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->cand_k, 0, (size_t)c * d->words * 8, false, st))) return e;
-    d->cand_cap = c;
-    return hipSuccess;
+    if ((e = reserve_all(c, st, d->cand.h, d->cand.i))) return e;
+    return d->cand.k.reserve(c * d->words, st);
 }
 
 hipError_t ensure_merge(WideDistinct* d, int64_t N, hipStream_t st) {
-    if (N <= d->merge_cap) return hipSuccess;
-    const int64_t c = grown_capacity(d->merge_cap, N, INT64_MAX);
+    auto& g = d->mrg;
+    if (N <= g.cap()) return hipSuccess;
+    const int64_t c = grown_capacity(g.cap(), N, INT64_MAX);
     hipError_t e;
-    if ((e = pool_device_grow((void**)&d->eh0, 0, (size_t)c * 8, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->eh1, 0, (size_t)c * 8, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->ev0, 0, (size_t)c * 4, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->ev1, 0, (size_t)c * 4, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->flags, 0, (size_t)c * 4, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->pos, 0, (size_t)c * 4, false, st))) return e;
-    size_t a = 0, b = 0, g = 0;
+    size_t a = 0, b = 0;  // the scratch first: the arrays' capacity says that a merge of c entries can run
     if ((e = rocprim::radix_sort_pairs(nullptr, a, (int64_t*)nullptr, (int64_t*)nullptr, (uint32_t*)nullptr,
                                        (uint32_t*)nullptr, (size_t)c)))
         return e;
     if ((e = rocprim::exclusive_scan(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)c,
                                      rocprim::plus<uint32_t>())))
         return e;
-    if ((e = rocprim::radix_sort_pairs(nullptr, g, (int64_t*)nullptr, (int64_t*)nullptr, (uint32_t*)nullptr,
-                                       (uint32_t*)nullptr, (size_t)c)))
-        return e;
-    const size_t tb = std::max(a, std::max(b, g));
-    if (tb > d->temp_bytes) {
-        if ((e = pool_device_grow(&d->temp, 0, tb, false, st))) return e;
-        d->temp_bytes = tb;
-    }
-    d->merge_cap = c;
-    return hipSuccess;
-}
-
-hipError_t ensure_temp(WideDistinct* d, size_t bytes, hipStream_t st) {
-    if (bytes <= d->temp_bytes) return hipSuccess;
-    hipError_t e = pool_device_grow(&d->temp, 0, bytes, false, st);
-    if (e == hipSuccess) d->temp_bytes = bytes;
-    return e;
+    if ((e = g.temp.reserve(std::max(a, b), st))) return e;
+    return reserve_all(c, st, g.h0, g.h1, g.v0, g.v1, g.flags, g.pos);
 }
 
 hipError_t read_ctl(WideDistinct* d, hipStream_t st) {
@@ -983,17 +968,18 @@ hipError_t read_ctl(WideDistinct* d, hipStream_t st) {
 
 // the bucket area for B buckets (the counters zeroed: every merge leaves the ones it used zero)
 hipError_t ensure_buckets(WideDistinct* d, uint32_t B, hipStream_t st) {
-    if (B <= d->wb_cap) return hipSuccess;
-    const size_t c = std::max<uint32_t>(B, 64);
+    auto& w = d->wb;
+    if (B <= w.cap) return hipSuccess;
+    const int64_t c = std::max<uint32_t>(B, 64);
     hipError_t e;
-    if ((e = pool_device_grow((void**)&d->wb_h, 0, c * kWCap * 8, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->wb_e, 0, c * kWCap * 4, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->wb_a, 0, c * kWCap * 8, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->wb_dist, 0, c * 4, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->wb_gsum, 0, (c / 16 + 1) * 4, false, st))) return e;
-    if ((e = pool_device_grow((void**)&d->wb_cnt, 0, c * kWStride * 4, false, st))) return e;
-    d->wb_cnt_dirty = true;
-    d->wb_cap = (uint32_t)c;
+    if ((e = w.h.reserve(c * kWCap, st))) return e;
+    if ((e = w.e.reserve(c * kWCap, st))) return e;
+    if ((e = w.a.reserve(c * kWCap, st))) return e;
+    if ((e = w.dist.reserve(c, st))) return e;
+    if ((e = w.gsum.reserve(c / 16 + 1, st))) return e;
+    if ((e = w.cnt.reserve(c * kWStride, st))) return e;
+    w.cnt_dirty = true;
+    w.cap = (uint32_t)c;
     return hipSuccess;
 }
 
@@ -1046,24 +1032,24 @@ hipError_t merge_bucketed(WideDistinct* d, int64_t c, int64_t span_hi, bool arri
     lo[ns] = INT64_MAX;
     b0[ns] = B;
     if ((e = ensure_buckets(d, (uint32_t)B, st))) return e;
-    const WRows R{d->set_k, d->cand_k, d->m, d->words};
+    const WRows R{d->set.k, d->cand.k, d->m, d->words};
     // ctl[1..6]; ctl[0] is the filter's count when c_on_device, ctl[7] the publication ticket (always 0)
-    const uint32_t n_cnt = d->wb_cnt_dirty ? d->wb_cap * kWStride : 0u;
+    const uint32_t n_cnt = d->wb.cnt_dirty ? d->wb.cap * kWStride : 0u;
     hipLaunchKernelGGL(wb_prep, dim3(std::max<uint32_t>(1, std::min<uint32_t>((n_cnt + 4 * kWBlock - 1) / (4 * kWBlock), 256))),
-                       dim3(kWBlock), 0, st, d->ctl, d->wb_cnt, n_cnt);
-    d->wb_cnt_dirty = false;
-    hipLaunchKernelGGL(wb_scatter, dim3(wgrid(N, 8192)), dim3(kWBlock), 0, st, d->set_h, d->m, d->cand_h, c, d->hwb_seg,
-                       ns, (uint32_t)B, d->wb_h, d->wb_e, d->wb_cnt, d->wb_gsum, d->ctl, c_on_device);
+                       dim3(kWBlock), 0, st, d->ctl, d->wb.cnt, n_cnt);
+    d->wb.cnt_dirty = false;
+    hipLaunchKernelGGL(wb_scatter, dim3(wgrid(N, 8192)), dim3(kWBlock), 0, st, d->set.h, d->m, d->cand.h, c, d->hwb_seg,
+                       ns, (uint32_t)B, d->wb.h, d->wb.e, d->wb.cnt, d->wb.gsum, d->ctl, c_on_device);
     hipLaunchKernelGGL(wb_sort, dim3((unsigned)((B + kWBlock / 64 - 1) / (kWBlock / 64))), dim3(kWBlock), 0, st, d->m,
-                       (uint32_t)B, d->wb_h, d->wb_e, arrivals ? d->wb_a : nullptr, d->wb_cnt, d->wb_dist, d->wb_gsum, R,
-                       d->cand_i, d->ctl);
+                       (uint32_t)B, d->wb.h, d->wb.e, arrivals ? d->wb.a : nullptr, d->wb.cnt, d->wb.dist, d->wb.gsum, R,
+                       d->cand.i, d->ctl);
     hipLaunchKernelGGL(wb_emit, dim3((unsigned)((B + kWEmitBuckets - 1) / kWEmitBuckets)), dim3(kWBlock), 0, st,
-                       (uint32_t)B, d->wb_h, d->wb_e, d->wb_dist, d->wb_gsum, (int64_t)d->k, R, d->set_h2, d->set_k2,
+                       (uint32_t)B, d->wb.h, d->wb.e, d->wb.dist, d->wb.gsum, (int64_t)d->k, R, d->set.h2, d->set.k2,
                        d->ctl);
     if ((e = hipGetLastError())) return e;
     if (d->spec.arm && d->spec.dst) {  // the merged set straight to the host, before the host reads ctl
         const uint32_t gen = ++*d->spec.gen_ctr;
-        if ((e = launch_publish_multi(d->set_k2, (int64_t)d->k * d->words * 8, d->spec.dst, d->spec.flag, gen,
+        if ((e = launch_publish_multi(d->set.k2, (int64_t)d->k * d->words * 8, d->spec.dst, d->spec.flag, gen,
                                       (uint32_t*)(d->ctl + 7), st)))
             return e;
         d->spec.gen = gen;
@@ -1077,8 +1063,8 @@ hipError_t merge_bucketed(WideDistinct* d, int64_t c, int64_t span_hi, bool arri
     d->m = std::min<int64_t>(d->hctl[2], d->k);
     d->top = d->hctl[3];
     d->tied = d->m == d->k && d->hctl[4] != 0;
-    std::swap(d->set_h, d->set_h2);
-    std::swap(d->set_k, d->set_k2);
+    std::swap(d->set.h, d->set.h2);
+    std::swap(d->set.k, d->set.k2);
     d->last_bucketed = true;
     d->last_B = (uint32_t)B;
     ++d->merges;
@@ -1103,34 +1089,34 @@ hipError_t merge_cands(WideDistinct* d, int64_t c, hipStream_t st, int64_t span_
     }
     // the sort-based merge: a 64-bit radix sort by h, runs of equal h by the key words
     if ((e = ensure_merge(d, N, st))) return e;
-    const WRows R{d->set_k, d->cand_k, d->m, d->words};
+    const WRows R{d->set.k, d->cand.k, d->m, d->words};
     const unsigned g = wgrid(N, 4096);
-    hipLaunchKernelGGL(wide_merge_init, dim3(g), dim3(kWBlock), 0, st, d->set_h, d->cand_h, d->m, N, d->eh0, d->ev0);
-    size_t tb = d->temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(d->temp, tb, d->eh0, d->eh1, d->ev0, d->ev1, (size_t)N, 0, 64, st))) return e;
+    hipLaunchKernelGGL(wide_merge_init, dim3(g), dim3(kWBlock), 0, st, d->set.h, d->cand.h, d->m, N, d->mrg.h0, d->mrg.v0);
+    size_t tb = d->mrg.temp.bytes();
+    if ((e = rocprim::radix_sort_pairs(d->mrg.temp.p(), tb, d->mrg.h0.p, d->mrg.h1.p, d->mrg.v0.p, d->mrg.v1.p, (size_t)N, 0, 64, st))) return e;
     if ((e = hipMemsetAsync(d->ctl, 0, 8 * 8, st))) return e;
-    hipLaunchKernelGGL(wide_run_fix, dim3(g), dim3(kWBlock), 0, st, d->eh1, d->ev1, N, R, d->ctl);
+    hipLaunchKernelGGL(wide_run_fix, dim3(g), dim3(kWBlock), 0, st, d->mrg.h1, d->mrg.v1, N, R, d->ctl);
     auto finish = [&]() -> hipError_t {
-        hipLaunchKernelGGL(wide_flags, dim3(g), dim3(kWBlock), 0, st, d->eh1, d->ev1, N, R, d->flags);
-        size_t sb = d->temp_bytes;
-        hipError_t e2 = rocprim::exclusive_scan(d->temp, sb, d->flags, d->pos, 0u, (size_t)N, rocprim::plus<uint32_t>(),
+        hipLaunchKernelGGL(wide_flags, dim3(g), dim3(kWBlock), 0, st, d->mrg.h1, d->mrg.v1, N, R, d->mrg.flags);
+        size_t sb = d->mrg.temp.bytes();
+        hipError_t e2 = rocprim::exclusive_scan(d->mrg.temp.p(), sb, d->mrg.flags.p, d->mrg.pos.p, 0u, (size_t)N, rocprim::plus<uint32_t>(),
                                                 st);
         if (e2) return e2;
-        hipLaunchKernelGGL(wide_emit, dim3(g), dim3(kWBlock), 0, st, d->eh1, d->ev1, d->flags, d->pos, N,
-                           (int64_t)d->k, R, d->set_h2, d->set_k2, d->ctl);
+        hipLaunchKernelGGL(wide_emit, dim3(g), dim3(kWBlock), 0, st, d->mrg.h1, d->mrg.v1, d->mrg.flags, d->mrg.pos, N,
+                           (int64_t)d->k, R, d->set.h2, d->set.k2, d->ctl);
         if ((e2 = hipGetLastError())) return e2;
         return read_ctl(d, st);
     };
     if ((e = finish())) return e;
     if (d->hctl[1]) {  // a run of > kRunMax equal hashes: the comparison sort orders the whole merge
         size_t mb = 0;
-        const WLess less{d->eh0, R};
-        if ((e = rocprim::merge_sort(nullptr, mb, d->ev1, d->ev1, (size_t)N, less, st))) return e;
-        if ((e = ensure_temp(d, mb, st))) return e;
-        hipLaunchKernelGGL(wide_iota, dim3(g), dim3(kWBlock), 0, st, d->ev0, N);
-        mb = d->temp_bytes;
-        if ((e = rocprim::merge_sort(d->temp, mb, d->ev0, d->ev1, (size_t)N, less, st))) return e;
-        hipLaunchKernelGGL(wide_gather_h, dim3(g), dim3(kWBlock), 0, st, d->eh0, d->ev1, N, d->eh1);
+        const WLess less{d->mrg.h0, R};
+        if ((e = rocprim::merge_sort(nullptr, mb, d->mrg.v1.p, d->mrg.v1.p, (size_t)N, less, st))) return e;
+        if ((e = d->mrg.temp.reserve(mb, st))) return e;
+        hipLaunchKernelGGL(wide_iota, dim3(g), dim3(kWBlock), 0, st, d->mrg.v0, N);
+        mb = d->mrg.temp.bytes();
+        if ((e = rocprim::merge_sort(d->mrg.temp.p(), mb, d->mrg.v0.p, d->mrg.v1.p, (size_t)N, less, st))) return e;
+        hipLaunchKernelGGL(wide_gather_h, dim3(g), dim3(kWBlock), 0, st, d->mrg.h0, d->mrg.v1, N, d->mrg.h1);
         if ((e = hipMemsetAsync(d->ctl, 0, 8 * 8, st))) return e;
         if ((e = finish())) return e;
     }
@@ -1138,8 +1124,8 @@ hipError_t merge_cands(WideDistinct* d, int64_t c, hipStream_t st, int64_t span_
     d->m = std::min<int64_t>(nd, d->k);
     d->top = d->hctl[3];
     d->tied = d->m == d->k && d->hctl[4] != 0;
-    std::swap(d->set_h, d->set_h2);
-    std::swap(d->set_k, d->set_k2);
+    std::swap(d->set.h, d->set.h2);
+    std::swap(d->set.k, d->set.k2);
     ++d->merges;
     return hipSuccess;
 }
@@ -1156,8 +1142,8 @@ hipError_t upload_replica(WideDistinct* d, hipStream_t st) {
     d->m = 0;
     if (!nm) return hipSuccess;
     if ((e = ensure_cand(d, nm, st))) return e;
-    if ((e = hipMemcpyAsync(d->cand_h, hs.data(), (size_t)nm * 8, hipMemcpyHostToDevice, st))) return e;
-    if ((e = hipMemcpyAsync(d->cand_k, rows.data(), (size_t)nm * d->words * 8, hipMemcpyHostToDevice, st))) return e;
+    if ((e = hipMemcpyAsync(d->cand.h, hs.data(), (size_t)nm * 8, hipMemcpyHostToDevice, st))) return e;
+    if ((e = hipMemcpyAsync(d->cand.k, rows.data(), (size_t)nm * d->words * 8, hipMemcpyHostToDevice, st))) return e;
     const bool tied = d->tied;
     if ((e = merge_cands(d, nm, st))) return e;  // synchronizes (its control words): hs / rows may go
     d->tied = tied;
@@ -1171,8 +1157,8 @@ hipError_t rebuild_replica(WideDistinct* d, hipStream_t st) {
     if (!d->m) return hipSuccess;
     std::vector<int64_t> hs((size_t)d->m);
     std::vector<uint64_t> rows((size_t)(d->m * d->words));
-    hipError_t e = hipMemcpyAsync(hs.data(), d->set_h, hs.size() * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(rows.data(), d->set_k, rows.size() * 8, hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(hs.data(), d->set.h, hs.size() * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(rows.data(), d->set.k, rows.size() * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return e;
     for (int64_t i = 0; i < d->m; ++i) d->rep.sample(hs[(size_t)i], rows.data() + (size_t)i * d->words);
@@ -1182,54 +1168,44 @@ hipError_t rebuild_replica(WideDistinct* d, hipStream_t st) {
 // the log in arrival order on the host: sort by global index on the device, permute, copy back
 // into oh[n] / ok[n x words] (synchronized when `sync`)
 hipError_t log_to_host(WideDistinct* d, int64_t* oh, uint64_t* ok, hipStream_t st, bool sync = true) {
-    const int64_t n = d->log_n;
+    const int64_t n = d->olog.n;
     if (!n) return hipSuccess;
     hipError_t e;
     if ((e = ensure_merge(d, n, st))) return e;
     if ((e = ensure_cand(d, n, st))) return e;
     const unsigned g = wgrid(n, 4096);
-    hipLaunchKernelGGL(wide_iota, dim3(g), dim3(kWBlock), 0, st, d->ev0, n);
-    size_t tb = d->temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(d->temp, tb, d->log_g, d->eh1, d->ev0, d->ev1, (size_t)n, 0, 64, st)))
+    hipLaunchKernelGGL(wide_iota, dim3(g), dim3(kWBlock), 0, st, d->mrg.v0, n);
+    size_t tb = d->mrg.temp.bytes();
+    if ((e = rocprim::radix_sort_pairs(d->mrg.temp.p(), tb, d->olog.g.p, d->mrg.h1.p, d->mrg.v0.p, d->mrg.v1.p, (size_t)n, 0, 64, st)))
         return e;
-    hipLaunchKernelGGL(wide_log_permute, dim3(g), dim3(kWBlock), 0, st, d->ev1, d->log_h, d->log_k, n, d->words,
-                       d->cand_h, d->cand_k);
+    hipLaunchKernelGGL(wide_log_permute, dim3(g), dim3(kWBlock), 0, st, d->mrg.v1, d->olog.h, d->olog.k, n, d->words,
+                       d->cand.h, d->cand.k);
     if ((e = hipGetLastError())) return e;
-    if ((e = hipMemcpyAsync(oh, d->cand_h, (size_t)n * 8, hipMemcpyDeviceToHost, st))) return e;
-    if ((e = hipMemcpyAsync(ok, d->cand_k, (size_t)n * d->words * 8, hipMemcpyDeviceToHost, st))) return e;
+    if ((e = hipMemcpyAsync(oh, d->cand.h, (size_t)n * 8, hipMemcpyDeviceToHost, st))) return e;
+    if ((e = hipMemcpyAsync(ok, d->cand.k, (size_t)n * d->words * 8, hipMemcpyDeviceToHost, st))) return e;
     return sync ? hipStreamSynchronize(st) : hipSuccess;
 }
 
 hipError_t log_to_host(WideDistinct* d, std::vector<int64_t>& oh, std::vector<uint64_t>& ok, hipStream_t st) {
-    oh.resize((size_t)d->log_n);
-    ok.resize((size_t)(d->log_n * d->words));
+    oh.resize((size_t)d->olog.n);
+    ok.resize((size_t)(d->olog.n * d->words));
     return log_to_host(d, oh.data(), ok.data(), st);
 }
 
 // the replay's pinned copies for a log of n entries
 hipError_t ensure_pinned_log(WideDistinct* d, int64_t n) {
-    if (n <= d->p_cap) return hipSuccess;
-    const int64_t c = std::max<int64_t>(n, 2 * d->p_cap);
-    pool_host_free(d->p_oh);
-    pool_host_free(d->p_ok);
-    pool_host_free(d->p_fl);
-    d->p_oh = nullptr;
-    d->p_ok = nullptr;
-    d->p_fl = nullptr;
-    d->p_cap = 0;
+    if (n <= d->pin_cap()) return hipSuccess;
+    const int64_t c = std::max<int64_t>(n, 2 * d->pin_cap());
     hipError_t e;
-    if ((e = pool_host_alloc((void**)&d->p_oh, (size_t)c * 8, hipHostMallocDefault))) return e;
-    if ((e = pool_host_alloc((void**)&d->p_ok, (size_t)c * d->words * 8, hipHostMallocDefault))) return e;
-    if ((e = pool_host_alloc((void**)&d->p_fl, (size_t)c * 4, hipHostMallocDefault))) return e;
-    d->p_cap = c;
-    return hipSuccess;
+    if ((e = reserve_all(c, nullptr, d->pin.oh, d->pin.fl))) return e;
+    return d->pin.ok.reserve(c * d->words);
 }
 
 // First-occurrence flags of the log (already in arrival order in cand_h / cand_k, log_to_host):
 // entries [the replica's members | the log] through the merge's sort (stable radix by h, runs of
 // equal h stably by the key words, or the comparison sort for runs > kRunMax), then wide_mark_first.
 hipError_t first_flags(WideDistinct* d, uint32_t* flags, hipStream_t st) {
-    const int64_t n = d->log_n;
+    const int64_t n = d->olog.n;
     std::vector<int64_t> mh;
     std::vector<uint64_t> mk;
     d->rep.members_heap(mh, mk);  // (any order: the sort below groups the keys)
@@ -1238,30 +1214,30 @@ hipError_t first_flags(WideDistinct* d, uint32_t* flags, hipStream_t st) {
     if ((e = ensure_set(d, nm, st))) return e;
     if ((e = ensure_merge(d, N, st))) return e;
     if (nm) {
-        if ((e = hipMemcpyAsync(d->set_h2, mh.data(), (size_t)nm * 8, hipMemcpyHostToDevice, st))) return e;
-        if ((e = hipMemcpyAsync(d->set_k2, mk.data(), (size_t)nm * d->words * 8, hipMemcpyHostToDevice, st))) return e;
+        if ((e = hipMemcpyAsync(d->set.h2, mh.data(), (size_t)nm * 8, hipMemcpyHostToDevice, st))) return e;
+        if ((e = hipMemcpyAsync(d->set.k2, mk.data(), (size_t)nm * d->words * 8, hipMemcpyHostToDevice, st))) return e;
     }
-    const WRows R{d->set_k2, d->cand_k, nm, d->words};
+    const WRows R{d->set.k2, d->cand.k, nm, d->words};
     const unsigned g = wgrid(N, 4096);
-    hipLaunchKernelGGL(wide_merge_init, dim3(g), dim3(kWBlock), 0, st, d->set_h2, d->cand_h, nm, N, d->eh0, d->ev0);
-    size_t tb = d->temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(d->temp, tb, d->eh0, d->eh1, d->ev0, d->ev1, (size_t)N, 0, 64, st))) return e;
+    hipLaunchKernelGGL(wide_merge_init, dim3(g), dim3(kWBlock), 0, st, d->set.h2, d->cand.h, nm, N, d->mrg.h0, d->mrg.v0);
+    size_t tb = d->mrg.temp.bytes();
+    if ((e = rocprim::radix_sort_pairs(d->mrg.temp.p(), tb, d->mrg.h0.p, d->mrg.h1.p, d->mrg.v0.p, d->mrg.v1.p, (size_t)N, 0, 64, st))) return e;
     if ((e = hipMemsetAsync(d->ctl, 0, 8 * 8, st))) return e;
-    hipLaunchKernelGGL(wide_run_fix, dim3(g), dim3(kWBlock), 0, st, d->eh1, d->ev1, N, R, d->ctl);
+    hipLaunchKernelGGL(wide_run_fix, dim3(g), dim3(kWBlock), 0, st, d->mrg.h1, d->mrg.v1, N, R, d->ctl);
     if ((e = read_ctl(d, st))) return e;
     if (d->hctl[1]) {  // a run longer than kRunMax: the (stable) comparison sort over (h, key words)
         size_t mb = 0;
-        const WLess less{d->eh0, R};
-        if ((e = rocprim::merge_sort(nullptr, mb, d->ev1, d->ev1, (size_t)N, less, st))) return e;
-        if ((e = ensure_temp(d, mb, st))) return e;
-        hipLaunchKernelGGL(wide_iota, dim3(g), dim3(kWBlock), 0, st, d->ev0, N);
-        mb = d->temp_bytes;
-        if ((e = rocprim::merge_sort(d->temp, mb, d->ev0, d->ev1, (size_t)N, less, st))) return e;
-        hipLaunchKernelGGL(wide_gather_h, dim3(g), dim3(kWBlock), 0, st, d->eh0, d->ev1, N, d->eh1);
+        const WLess less{d->mrg.h0, R};
+        if ((e = rocprim::merge_sort(nullptr, mb, d->mrg.v1.p, d->mrg.v1.p, (size_t)N, less, st))) return e;
+        if ((e = d->mrg.temp.reserve(mb, st))) return e;
+        hipLaunchKernelGGL(wide_iota, dim3(g), dim3(kWBlock), 0, st, d->mrg.v0, N);
+        mb = d->mrg.temp.bytes();
+        if ((e = rocprim::merge_sort(d->mrg.temp.p(), mb, d->mrg.v0.p, d->mrg.v1.p, (size_t)N, less, st))) return e;
+        hipLaunchKernelGGL(wide_gather_h, dim3(g), dim3(kWBlock), 0, st, d->mrg.h0, d->mrg.v1, N, d->mrg.h1);
     }
-    hipLaunchKernelGGL(wide_mark_first, dim3(g), dim3(kWBlock), 0, st, d->eh1, d->ev1, N, R, d->pos);
+    hipLaunchKernelGGL(wide_mark_first, dim3(g), dim3(kWBlock), 0, st, d->mrg.h1, d->mrg.v1, N, R, d->mrg.pos);
     if ((e = hipGetLastError())) return e;
-    if ((e = hipMemcpyAsync(flags, d->pos, (size_t)n * 4, hipMemcpyDeviceToHost, st))) return e;
+    if ((e = hipMemcpyAsync(flags, d->mrg.pos, (size_t)n * 4, hipMemcpyDeviceToHost, st))) return e;
     return hipStreamSynchronize(st);
 }
 
@@ -1271,19 +1247,19 @@ hipError_t first_flags(WideDistinct* d, uint32_t* flags, hipStream_t st) {
 hipError_t replay_log(WideDistinct* d, hipStream_t st) {
     hipError_t e;
     if (d->rep_stale && (e = rebuild_replica(d, st))) return e;
-    const bool first = d->log_n > 0 && d->log_n >= d->first_min;
-    const int64_t n_log = d->log_n;
+    const bool first = d->olog.n > 0 && d->olog.n >= d->first_min;
+    const int64_t n_log = d->olog.n;
     const auto t0 = std::chrono::steady_clock::now();
     if ((e = ensure_pinned_log(d, n_log))) return e;
-    const int64_t* oh = d->p_oh;
-    const uint64_t* ok = d->p_ok;
+    const int64_t* oh = d->pin.oh;
+    const uint64_t* ok = d->pin.ok;
     // the log's copies are enqueued before the flags' sort (one wait for both when first)
-    if ((e = log_to_host(d, d->p_oh, d->p_ok, st, !first))) return e;
+    if ((e = log_to_host(d, d->pin.oh, d->pin.ok, st, !first))) return e;
     const auto t1 = std::chrono::steady_clock::now();
     auto t2 = t1;
     if (first) {
-        const uint32_t* fl = d->p_fl;
-        if ((e = first_flags(d, d->p_fl, st))) return e;
+        const uint32_t* fl = d->pin.fl;
+        if ((e = first_flags(d, d->pin.fl, st))) return e;
         t2 = std::chrono::steady_clock::now();
         // members name log entries during the run (no row moves per replacement), then take slots
         for (int64_t t = 0; t < n_log; ++t)
@@ -1304,7 +1280,7 @@ hipError_t replay_log(WideDistinct* d, hipStream_t st) {
             d->arch_k.insert(d->arch_k.end(), ok, ok + n_log * d->words);
         }
     }
-    d->log_n = 0;
+    d->olog.n = 0;
     if ((e = upload_replica(d, st))) return e;
     d->exact = true;
     if (std::getenv("RSV_REPLAY_DEBUG")) {
@@ -1316,28 +1292,22 @@ hipError_t replay_log(WideDistinct* d, hipStream_t st) {
     return hipSuccess;
 }
 
+// room for `need` log entries, the olog.n in use kept: three fresh blocks, three copies, one wait
 hipError_t ensure_log(WideDistinct* d, int64_t need, hipStream_t st) {
-    if (need <= d->log_cap) return hipSuccess;
-    const int64_t c = grown_capacity(d->log_cap, need, INT64_MAX);
-    const size_t W = (size_t)d->words * 8;
-    void* nb[3] = {nullptr, nullptr, nullptr};
-    const size_t bytes[3] = {(size_t)c * 8, (size_t)c * 8, (size_t)c * W};
-    const size_t used[3] = {(size_t)d->log_n * 8, (size_t)d->log_n * 8, (size_t)d->log_n * W};
-    void** old[3] = {(void**)&d->log_h, (void**)&d->log_g, (void**)&d->log_k};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = pool_device_alloc(&nb[i], bytes[i]);
-    for (int i = 0; i < 3 && e == hipSuccess; ++i)
-        if (*old[i] && used[i]) e = hipMemcpyAsync(nb[i], *old[i], used[i], hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && (d->log_h || d->log_g || d->log_k)) e = hipStreamSynchronize(st);  // one wait, three copies
-    if (e != hipSuccess) {
-        for (void* p : nb) pool_device_free(p);
-        return e;
-    }
-    for (int i = 0; i < 3; ++i) {
-        pool_device_free(*old[i]);
-        *old[i] = nb[i];
-    }
-    d->log_cap = c;
+    if (need <= d->log_cap()) return hipSuccess;
+    const int64_t c = grown_capacity(d->log_cap(), need, INT64_MAX), w = d->words;
+    auto& l = d->olog;
+    DevBuf<int64_t> h, g;
+    DevBuf<uint64_t> k;
+    hipError_t e;
+    if ((e = reserve_all(c, st, h, g))) return e;
+    if ((e = k.reserve(c * w, st))) return e;
+    const size_t used = (size_t)l.n * 8;
+    if (l.h && used && (e = hipMemcpyAsync(h, l.h, used, hipMemcpyDeviceToDevice, st))) return e;
+    if (l.g && used && (e = hipMemcpyAsync(g, l.g, used, hipMemcpyDeviceToDevice, st))) return e;
+    if (l.k && used && (e = hipMemcpyAsync(k, l.k, used * w, hipMemcpyDeviceToDevice, st))) return e;
+    if ((l.h || l.g || l.k) && (e = hipStreamSynchronize(st))) return e;
+    l.h.swap(h), l.g.swap(g), l.k.swap(k);  // the old blocks go back to the pool with the locals
     return hipSuccess;
 }
 
@@ -1351,16 +1321,16 @@ hipError_t sample_chunk(WideDistinct* d, const void* keys, const int64_t* hashes
     hipError_t e;
     int64_t c;
     // bounded log: replay what it holds before this chunk's candidates take the scratch buffers
-    if (d->ordered && d->log_n > 0 && d->log_n + std::min<int64_t>(L, 8 * (int64_t)d->k + 4096) > d->log_limit)
+    if (d->ordered && d->olog.n > 0 && d->olog.n + std::min<int64_t>(L, 8 * (int64_t)d->k + 4096) > d->olog.limit)
         if ((e = replay_log(d, st))) return e;
     if (d->m < d->k && !bound_in) {  // still filling, no predicted bound: every element is a candidate
         if ((e = ensure_cand(d, L, st))) return e;
         if (d->src == kWideSrcHashes)
             hipLaunchKernelGGL(wide_hash_all<kWideSrcHashes>, dim3(wgrid(L, 8192)), dim3(kWBlock), 0, st, hv, rows, L,
-                               d->r0, d->r1, d->cand_h, d->cand_i);
+                               d->r0, d->r1, d->cand.h, d->cand.i);
         else
             hipLaunchKernelGGL(wide_hash_all<kWideSrcUuid>, dim3(wgrid(L, 8192)), dim3(kWBlock), 0, st, hv, rows, L,
-                               d->r0, d->r1, d->cand_h, d->cand_i);
+                               d->r0, d->r1, d->cand.h, d->cand.i);
         if ((e = hipGetLastError())) return e;
         c = L;
     } else {
@@ -1369,7 +1339,7 @@ hipError_t sample_chunk(WideDistinct* d, const void* keys, const int64_t* hashes
         const unsigned g = (unsigned)std::min<int64_t>(
             std::max<int64_t>((L / (d->src == kWideSrcHashes ? 2 * kWideU : kWideU) + kWBlock - 1) / kWBlock, 1),
             kWideGrid);
-        if (!d->ordered && d->bucketed_on && R == 0 && d->m + d->cand_cap < ((int64_t)1 << 30)) {
+        if (!d->ordered && d->bucketed_on && R == 0 && d->m + d->cand_cap() < ((int64_t)1 << 30)) {
             // Set mode: filter, rows and the bucketed merge enqueued together -- the candidate count
             // stays on the device (the kernels read the filter's counter), one host read at the end
             for (;;) {
@@ -1377,20 +1347,20 @@ hipError_t sample_chunk(WideDistinct* d, const void* keys, const int64_t* hashes
                 if (d->timer) d->timer->mark(st);
                 if (d->src == kWideSrcHashes)
                     hipLaunchKernelGGL(wide_filter_hashes, dim3(g), dim3(kWBlock), 0, st, hv, L, d->r0, d->r1, bound,
-                                       d->cand_h, d->cand_i, (unsigned long long*)d->ctl, d->cand_cap, d->sched, 0);
+                                       d->cand.h, d->cand.i, (unsigned long long*)d->ctl.p, d->cand_cap(), d->sched, 0);
                 else
                     hipLaunchKernelGGL(wide_filter_uuid, dim3(g), dim3(kWBlock), 0, st, rows, L, d->r0, d->r1, bound,
-                                       d->cand_h, d->cand_i, (unsigned long long*)d->ctl, d->cand_cap, d->sched, 0);
+                                       d->cand.h, d->cand.i, (unsigned long long*)d->ctl.p, d->cand_cap(), d->sched, 0);
                 if (d->timer) d->timer->mark(st);
-                hipLaunchKernelGGL(wide_gather_rows, dim3(wgrid(d->cand_cap * d->words, 8192)), dim3(kWBlock), 0, st,
-                                   rows, d->cand_i, d->cand_cap, d->words, d->cand_k, (const int64_t*)d->ctl);
+                hipLaunchKernelGGL(wide_gather_rows, dim3(wgrid(d->cand_cap() * d->words, 8192)), dim3(kWBlock), 0, st,
+                                   rows, d->cand.i, d->cand_cap(), d->words, d->cand.k, (const int64_t*)d->ctl);
                 if ((e = hipGetLastError())) return e;
-                if ((e = ensure_set(d, std::min<int64_t>(d->m + d->cand_cap, d->k), st))) return e;
+                if ((e = ensure_set(d, std::min<int64_t>(d->m + d->cand_cap(), d->k), st))) return e;
                 d->last_bucketed = false;
                 bool done = false;
-                if ((e = merge_bucketed(d, d->cand_cap, bound, false, nullptr, st, &done, true))) return e;
+                if ((e = merge_bucketed(d, d->cand_cap(), bound, false, nullptr, st, &done, true))) return e;
                 c = d->hctl[0];
-                if (c > d->cand_cap) {  // more candidates than room (nothing merged): again, with room
+                if (c > d->cand_cap()) {  // more candidates than room (nothing merged): again, with room
                     if ((e = ensure_cand(d, c, st))) return e;
                     continue;
                 }
@@ -1405,30 +1375,30 @@ hipError_t sample_chunk(WideDistinct* d, const void* keys, const int64_t* hashes
             if (d->timer) d->timer->mark(st);
             if (d->src == kWideSrcHashes)
                 hipLaunchKernelGGL(wide_filter_hashes, dim3(g), dim3(kWBlock), 0, st, hv, L, d->r0, d->r1, bound,
-                                   d->cand_h, d->cand_i, (unsigned long long*)d->ctl, d->cand_cap, d->sched, R);
+                                   d->cand.h, d->cand.i, (unsigned long long*)d->ctl.p, d->cand_cap(), d->sched, R);
             else
                 hipLaunchKernelGGL(wide_filter_uuid, dim3(g), dim3(kWBlock), 0, st, rows, L, d->r0, d->r1, bound,
-                                   d->cand_h, d->cand_i, (unsigned long long*)d->ctl, d->cand_cap, d->sched, R);
+                                   d->cand.h, d->cand.i, (unsigned long long*)d->ctl.p, d->cand_cap(), d->sched, R);
             if (d->timer) d->timer->mark(st);
             if ((e = hipGetLastError())) return e;
             if ((e = read_ctl(d, st))) return e;
             c = d->hctl[0];
-            if (c <= d->cand_cap) break;
+            if (c <= d->cand_cap()) break;
             if ((e = ensure_cand(d, c, st))) return e;  // more candidates than room: again, with room
         }
     }
     if (c_out) *c_out = c;
     if (c == 0) return hipSuccess;
     hipLaunchKernelGGL(wide_gather_rows, dim3(wgrid(c * d->words, 8192)), dim3(kWBlock), 0, st, (const uint64_t*)keys +
-                       (size_t)off * d->words, d->cand_i, c, d->words, d->cand_k);
+                       (size_t)off * d->words, d->cand.i, c, d->words, d->cand.k);
     if ((e = hipGetLastError())) return e;
     if (d->ordered) {
-        if ((e = ensure_log(d, d->log_n + c, st))) return e;
-        hipLaunchKernelGGL(wide_log_append, dim3(wgrid(c * d->words, 8192)), dim3(kWBlock), 0, st, d->cand_h,
-                           d->cand_i, d->cand_k, c, d->words, gbase + off, d->log_h + d->log_n, d->log_g + d->log_n,
-                           d->log_k + (size_t)d->log_n * d->words);
+        if ((e = ensure_log(d, d->olog.n + c, st))) return e;
+        hipLaunchKernelGGL(wide_log_append, dim3(wgrid(c * d->words, 8192)), dim3(kWBlock), 0, st, d->cand.h,
+                           d->cand.i, d->cand.k, c, d->words, gbase + off, d->olog.h + d->olog.n, d->olog.g + d->olog.n,
+                           d->olog.k + (size_t)d->olog.n * d->words);
         if ((e = hipGetLastError())) return e;
-        d->log_n += c;
+        d->olog.n += c;
     }
     // no candidate's h exceeds the filter's bound (hash_all: any h)
     const int64_t span_hi = (d->m < d->k && !bound_in) ? INT64_MAX : (bound_in ? *bound_in : d->top);
@@ -1450,13 +1420,11 @@ hipError_t sample_sched(WideDistinct* d, const void* keys, const int64_t* hashes
                         int64_t gbase, hipStream_t st, bool* ok) {
     *ok = false;
     hipError_t e;
-    if (!d->sched) {
-        if ((e = pool_device_alloc((void**)&d->sched, kSchedWords * 8))) return e;
-        if ((e = pool_host_alloc((void**)&d->hsched, kSchedWords * 8, hipHostMallocDefault))) return e;
-    }
+    if ((e = d->sched.reserve(kSchedWords, st))) return e;
+    if ((e = d->hsched.reserve(kSchedWords))) return e;
     // a bounded log is replayed first (as sample_chunk would), so the state saved below is the one
     // the pass starts from
-    if (d->log_n > 0 && d->log_n + std::min<int64_t>(rest, 8 * (int64_t)d->k + 4096) > d->log_limit)
+    if (d->olog.n > 0 && d->olog.n + std::min<int64_t>(rest, 8 * (int64_t)d->k + 4096) > d->olog.limit)
         if ((e = replay_log(d, st))) return e;
     // the ranges (host; the pinned table's previous contents were consumed by a synchronized pass)
     const int64_t seen = std::max<int64_t>(d->seen, 1);
@@ -1485,12 +1453,12 @@ hipError_t sample_sched(WideDistinct* d, const void* keys, const int64_t* hashes
     if (expect > 32.0 * (double)d->k + (double)(1 << 22)) return hipSuccess;
     const int64_t room = (int64_t)(1.25 * expect) + 65536;
     if ((e = ensure_cand(d, room, st))) return e;
-    if (d->ordered && (e = ensure_log(d, d->log_n + room, st))) return e;  // no log growth after the filter
+    if (d->ordered && (e = ensure_log(d, d->olog.n + room, st))) return e;  // no log growth after the filter
     if ((e = hipMemcpyAsync(d->sched, rs, (size_t)(2 * R + 1) * 8, hipMemcpyHostToDevice, st))) return e;
     if ((e = hipMemsetAsync(d->sched + kSchedCounts, 0, (kWMaxR + 1) * 8, st))) return e;
     // the set and the scalars before the pass: the pass's one merge writes the other set buffers, so
     // a failed proof swaps back instead of restoring a copy
-    const int64_t m0 = d->m, top0 = d->top, log0 = d->log_n, merges0 = d->merges;
+    const int64_t m0 = d->m, top0 = d->top, log0 = d->olog.n, merges0 = d->merges;
     const bool tied0 = d->tied, exact0 = d->exact;
     // how the pass's merge entries spread along h (the bucket map, merge_bucketed): range r adds its
     // candidates uniformly below its bound B_r, so band (B_(j+1), B_j] holds ranges 0..j's; the set's
@@ -1523,11 +1491,11 @@ hipError_t sample_sched(WideDistinct* d, const void* keys, const int64_t* hashes
         const int64_t N = m0 + c;
         if (d->last_bucketed)
             hipLaunchKernelGGL(wb_verify, dim3(std::min<uint32_t>((d->last_B + 3) / 4, 4096)), dim3(kWBlock), 0,
-                               st, d->last_B, d->wb_h, d->wb_a, d->wb_dist, d->sched, R,
+                               st, d->last_B, d->wb.h, d->wb.a, d->wb.dist, d->sched, R,
                                (unsigned long long*)(d->sched + kSchedCounts));
         else
-            hipLaunchKernelGGL(wide_verify, dim3(wgrid(N, 4096)), dim3(kWBlock), 0, st, d->eh1, d->ev1, d->flags, N, m0,
-                               d->cand_i, d->sched, R, (unsigned long long*)(d->sched + kSchedCounts));
+            hipLaunchKernelGGL(wide_verify, dim3(wgrid(N, 4096)), dim3(kWBlock), 0, st, d->mrg.h1, d->mrg.v1, d->mrg.flags, N, m0,
+                               d->cand.i, d->sched, R, (unsigned long long*)(d->sched + kSchedCounts));
         if ((e = hipGetLastError())) return e;
         if ((e = hipMemcpyAsync(d->hsched + kSchedCounts, d->sched + kSchedCounts, (size_t)(R + 1) * 8, hipMemcpyDeviceToHost, st)))
             return e;
@@ -1549,15 +1517,15 @@ hipError_t sample_sched(WideDistinct* d, const void* keys, const int64_t* hashes
     }
     // the proof failed: the set (the merge's input, intact in the other buffers) and the log as before
     if (d->merges != merges0) {
-        std::swap(d->set_h, d->set_h2);
-        std::swap(d->set_k, d->set_k2);
+        std::swap(d->set.h, d->set.h2);
+        std::swap(d->set.k, d->set.k2);
         d->merges = merges0;
     }
     d->m = m0;
     d->top = top0;
     d->tied = tied0;
     d->exact = exact0;
-    d->log_n = log0;
+    d->olog.n = log0;
     return hipStreamSynchronize(st);
 }
 
@@ -1586,9 +1554,9 @@ int merge_external(WideDistinct* d, const std::vector<std::pair<const int64_t*, 
             const int64_t c = std::min<int64_t>(n - off, 8 * (int64_t)d->k + 4096);
             hipError_t e;
             if ((e = ensure_cand(d, c, st))) return hip_status(e, "distinct merge");
-            if ((e = hipMemcpyAsync(d->cand_h, src[p].first + off, (size_t)c * 8, hipMemcpyDeviceToDevice, st)))
+            if ((e = hipMemcpyAsync(d->cand.h, src[p].first + off, (size_t)c * 8, hipMemcpyDeviceToDevice, st)))
                 return hip_status(e, "distinct merge");
-            if ((e = hipMemcpyAsync(d->cand_k, src[p].second + (size_t)off * d->words, (size_t)c * d->words * 8,
+            if ((e = hipMemcpyAsync(d->cand.k, src[p].second + (size_t)off * d->words, (size_t)c * d->words * 8,
                                     hipMemcpyDeviceToDevice, st)))
                 return hip_status(e, "distinct merge");
             const int64_t old_top = d->top;
@@ -1620,9 +1588,9 @@ DistinctEngine* new_wide_distinct(int32_t k, int key_width, int src, int64_t r0,
     d->r0 = r0;
     d->r1 = r1;
     d->ordered = ordered;
-    d->log_limit = std::min<int64_t>(std::max<int64_t>(32 * (int64_t)k + 65536, (int64_t)1 << 22), (int64_t)1 << 27);
+    d->olog.limit = std::min<int64_t>(std::max<int64_t>(32 * (int64_t)k + 65536, (int64_t)1 << 22), (int64_t)1 << 27);
     if (const char* v = std::getenv("RSV_ORDERED_LOG_LIMIT"))  // test hook: force eager replays
-        d->log_limit = std::max<int64_t>(1, std::atoll(v));
+        d->olog.limit = std::max<int64_t>(1, std::atoll(v));
     if (ordered) d->rep.reset(k, d->words);
     if (const char* v = std::getenv("RSV_WIDE_SCHED")) d->sched_on = std::atoi(v) != 0;  // test hook: the chunk loop only
     if (const char* v = std::getenv("RSV_WIDE_SCHED_BETA"))  // test hook: tight bounds, failed proofs
@@ -1630,9 +1598,9 @@ DistinctEngine* new_wide_distinct(int32_t k, int key_width, int src, int64_t r0,
     if (const char* v = std::getenv("RSV_FIRST_MIN"))  // test hook: which replay form serves a log
         d->first_min = std::max<int64_t>(0, std::atoll(v));
     if (const char* v = std::getenv("RSV_WIDE_BUCKETED")) d->bucketed_on = std::atoi(v) != 0;  // A/B hook
-    hipError_t e = pool_device_alloc((void**)&d->ctl, 8 * 8);
+    hipError_t e = d->ctl.reserve(8, 0);
     if (e == hipSuccess) e = hipMemset(d->ctl, 0, 8 * 8);  // ctl[7]: the publication ticket
-    if (e == hipSuccess) e = pool_host_alloc((void**)&d->hctl, 8 * 8, hipHostMallocDefault);
+    if (e == hipSuccess) e = d->hctl.reserve(8);
     if (e != hipSuccess) {
         *status = hip_status(e, "distinct_create (wide keys)");
         delete d;
@@ -1642,67 +1610,53 @@ DistinctEngine* new_wide_distinct(int32_t k, int key_width, int src, int64_t r0,
     return d;
 }
 
-WideDistinct::~WideDistinct() {
-    WideDistinct* const d = this;
-    void* ps[] = {d->set_h, d->set_k, d->set_h2, d->set_k2, d->cand_h, d->cand_i, d->cand_k, d->eh0, d->eh1,
-                  d->ev0, d->ev1, d->flags, d->pos, d->temp, d->ctl, d->log_h, d->log_g, d->log_k};
-    for (void* p : ps) pool_device_free(p);  // the owner's stream is idle (rsv_destroy)
-    pool_device_free(d->sched);
-    void* wb[] = {d->wb_h, d->wb_e, d->wb_a, d->wb_cnt, d->wb_dist, d->wb_gsum};
-    for (void* p : wb) pool_device_free(p);
-    pool_host_free(d->hsched);
-    pool_host_free(d->hctl);
-    pool_host_free(d->p_oh);
-    pool_host_free(d->p_ok);
-    pool_host_free(d->p_fl);
-}
+WideDistinct::~WideDistinct() = default;  // the buffers return their blocks: the owner's stream is idle (rsv_destroy)
 
 int WideDistinct::sample_device(const void* keys, const int64_t* hashes, int64_t n, hipStream_t st) {
-    WideDistinct* const d = this;
     if (n <= 0) return RSV_OK;
-    if (d->merged) {  // sampling on after a merge: the pre-merge candidates are history
-        d->merged = false;
-        d->log_n = 0;
-        d->arch_h.clear();
-        d->arch_k.clear();
-        d->arch_ok = false;
+    if (merged) {  // sampling on after a merge: the pre-merge candidates are history
+        merged = false;
+        olog.n = 0;
+        arch_h.clear();
+        arch_k.clear();
+        arch_ok = false;
     }
-    const int64_t seen0 = d->seen;
+    const int64_t seen0 = seen;
     bool predicted = false;
     for (int64_t off = 0; off < n;) {
         const int64_t rest = n - off;
-        if (d->ordered && d->sched_on && d->k >= kSchedMinK && d->m == d->k && !predicted && rest > 4 * d->seen) {
+        if (ordered && sched_on && k >= kSchedMinK && m == k && !predicted && rest > 4 * seen) {
             predicted = true;
             bool ok = false;
-            if (hipError_t e = sample_sched(d, keys, hashes, off, rest, seen0, st, &ok))
+            if (hipError_t e = sample_sched(this, keys, hashes, off, rest, seen0, st, &ok))
                 return hip_status(e, "distinct sample");
             if (ok) {
-                d->seen += rest;
+                seen += rest;
                 break;
             }
             continue;  // a range's bound was short: the chunk loop below covers the same rest
         }
-        if (!d->ordered && d->m == 0 && d->seen == 0 && !predicted && rest >= 64 * (int64_t)d->k) {
+        if (!ordered && m == 0 && seen == 0 && !predicted && rest >= 64 * (int64_t)k) {
             // Set mode, a fresh sampler and a long batch: no filling chunk -- ONE pass under the bound
             // the batch's k-th smallest hash is predicted under if at least 1 / 2.5 of it is distinct
             // (uniform scrambled hashes: k / D of the range).  Proved like the pass below: a full
             // set whose maximum is <= B saw every element under it; else the chunk loop redoes the
             // batch (what the pass merged is seen again: duplicates merge away).
             predicted = true;
-            const double frac = 2.5 * (double)d->k / (double)rest;
+            const double frac = 2.5 * (double)k / (double)rest;
             const int64_t B = (int64_t)((uint64_t)INT64_MIN + (uint64_t)(18446744073709551616.0 * frac));
-            d->spec.arm = true;
-            hipError_t e = sample_chunk(d, keys, hashes, off, rest, seen0, st, &B);
-            d->spec.arm = false;
+            spec.arm = true;
+            hipError_t e = sample_chunk(this, keys, hashes, off, rest, seen0, st, &B);
+            spec.arm = false;
             if (e) return hip_status(e, "distinct sample");
-            if (d->m == d->k && d->top <= B) {
-                d->spec.ok = d->spec.dst && d->merges == d->spec_merges;  // the published set is the final one
-                d->seen += rest;
+            if (m == k && top <= B) {
+                spec.ok = spec.dst && merges == spec_merges;  // the published set is the final one
+                seen += rest;
                 break;
             }
             continue;
         }
-        if (!d->ordered && d->m == d->k && !predicted && rest > 4 * d->seen) {
+        if (!ordered && m == k && !predicted && rest > 4 * seen) {
             // Set mode, a long rest: ONE pass with the bound the rest's bottom-k is predicted under.
             // The scrambled hash is uniform, so the k-th smallest of D distinct values sits near
             // k / D of the range; with the rest's distinct share like the seen part's, the final
@@ -1710,23 +1664,23 @@ int WideDistinct::sample_device(const void* keys, const int64_t* hashes, int64_t
             // merge proves it: a full set whose maximum is <= B saw every element under it; else the
             // rest is filtered again by the chunk loop (duplicate candidates are merged away).
             predicted = true;
-            const double frac = 2.0 * (double)d->seen / (double)(d->seen + rest);
-            const uint64_t span = (uint64_t)d->top - (uint64_t)INT64_MIN;
-            const int64_t B = frac >= 1.0 ? d->top : (int64_t)((uint64_t)INT64_MIN + (uint64_t)((double)span * frac));
-            if (hipError_t e = sample_chunk(d, keys, hashes, off, rest, seen0, st, &B))
+            const double frac = 2.0 * (double)seen / (double)(seen + rest);
+            const uint64_t span = (uint64_t)top - (uint64_t)INT64_MIN;
+            const int64_t B = frac >= 1.0 ? top : (int64_t)((uint64_t)INT64_MIN + (uint64_t)((double)span * frac));
+            if (hipError_t e = sample_chunk(this, keys, hashes, off, rest, seen0, st, &B))
                 return hip_status(e, "distinct sample");
-            if (d->m == d->k && d->top <= B) {
-                d->seen += rest;
+            if (m == k && top <= B) {
+                seen += rest;
                 break;
             }
             continue;  // the prediction was short: the chunk loop below covers the same rest
         }
         // filling: enough for the set plus slack; full: ~4 seen lengths (~4k candidates a chunk)
-        const int64_t L = d->m < d->k ? std::min<int64_t>(rest, 4 * ((int64_t)d->k - d->m) + 4096)
-                                      : std::min<int64_t>(rest, std::max<int64_t>(4 * d->seen, 1 << 16));
-        if (hipError_t e = sample_chunk(d, keys, hashes, off, L, seen0, st)) return hip_status(e, "distinct sample");
+        const int64_t L = m < k ? std::min<int64_t>(rest, 4 * ((int64_t)k - m) + 4096)
+                                      : std::min<int64_t>(rest, std::max<int64_t>(4 * seen, 1 << 16));
+        if (hipError_t e = sample_chunk(this, keys, hashes, off, L, seen0, st)) return hip_status(e, "distinct sample");
         off += L;
-        d->seen += L;
+        seen += L;
     }
     return RSV_OK;
 }
@@ -1742,16 +1696,16 @@ int WideDistinct::publish(void* dst_host_dev, uint32_t* flag_dev, uint32_t gen, 
     // one workgroup's posted PCIe writes run at ~20 GB/s (a 1 MB UUID set: 45 us): large sets from
     // several workgroups (ctl[7] is the ticket: zero at creation, re-armed by every publication)
     if (bytes >= (64 << 10))
-        RSV_HIP_TRY(launch_publish_multi(set_k, bytes, dst_host_dev, flag_dev, gen, (uint32_t*)(ctl + 7), st));
+        RSV_HIP_TRY(launch_publish_multi(set.k, bytes, dst_host_dev, flag_dev, gen, (uint32_t*)(ctl + 7), st));
     else
-        RSV_HIP_TRY(launch_publish(set_k, bytes, dst_host_dev, flag_dev, gen, st));
+        RSV_HIP_TRY(launch_publish(set.k, bytes, dst_host_dev, flag_dev, gen, st));
     return RSV_OK;
 }
 
 int WideDistinct::export_set(void* keys_dev, int64_t* hash_dev, hipStream_t st) {
     if (m == 0) return RSV_OK;
-    if (keys_dev) RSV_HIP_TRY(hipMemcpyAsync(keys_dev, set_k, (size_t)m * words * 8, hipMemcpyDeviceToDevice, st));
-    if (hash_dev) RSV_HIP_TRY(hipMemcpyAsync(hash_dev, set_h, (size_t)m * 8, hipMemcpyDeviceToDevice, st));
+    if (keys_dev) RSV_HIP_TRY(hipMemcpyAsync(keys_dev, set.k, (size_t)m * words * 8, hipMemcpyDeviceToDevice, st));
+    if (hash_dev) RSV_HIP_TRY(hipMemcpyAsync(hash_dev, set.h, (size_t)m * 8, hipMemcpyDeviceToDevice, st));
     return RSV_OK;
 }
 
@@ -1763,43 +1717,40 @@ void WideDistinct::info(int32_t* o_ordered, int32_t* o_tied, int32_t* o_retained
     *o_retained = retained();
     *o_size = m;
     *o_max_hash = m ? top : INT64_MIN;
-    *o_log_entries = ordered ? (int64_t)arch_h.size() + log_n : 0;
+    *o_log_entries = ordered ? (int64_t)arch_h.size() + olog.n : 0;
 }
 
 int WideDistinct::merge_parts(const void* keys_dev, const int64_t* hash_dev, const int64_t* part_n, int32_t parts,
                               int64_t part_len, hipStream_t st) {
-    WideDistinct* const d = this;
     if (int rc = finalize(st)) return rc;
     std::vector<std::pair<const int64_t*, const uint64_t*>> src;
     std::vector<int64_t> counts, tops;
     std::vector<int32_t> ties;
     for (int32_t p = 0; p < parts; ++p) {
         const int64_t n = std::max<int64_t>(0, std::min(part_n[p], part_len));
-        src.emplace_back(hash_dev + (size_t)p * part_len, (const uint64_t*)keys_dev + (size_t)p * part_len * d->words);
+        src.emplace_back(hash_dev + (size_t)p * part_len, (const uint64_t*)keys_dev + (size_t)p * part_len * words);
         counts.push_back(n);
         tops.push_back(INT64_MAX);  // no per-part tie information in this form
         ties.push_back(0);
     }
-    return merge_external(d, src, counts, tops, ties, st);
+    return merge_external(this, src, counts, tops, ties, st);
 }
 
 int WideDistinct::export_row(int64_t* row, int64_t count, hipStream_t st) {
-    WideDistinct* const d = this;
     if (int rc = finalize(st)) return rc;
-    const int64_t k = d->k;
-    const int64_t tied = d->m == k && d->tied, mx = d->m ? d->top : INT64_MIN;
+    const int64_t k = this->k;
+    const int64_t tied = m == k && this->tied, mx = m ? top : INT64_MIN;
     const int64_t ret = retained();
-    hipLaunchKernelGGL(wide_export_row, dim3(wgrid(k * (d->words + 1), 4096)), dim3(kWBlock), 0, st, d->set_h,
-                       d->set_k, d->m, k, d->words, row, count, tied, mx, ret, (int64_t)d->ordered);
+    hipLaunchKernelGGL(wide_export_row, dim3(wgrid(k * (words + 1), 4096)), dim3(kWBlock), 0, st, set.h,
+                       set.k, m, k, words, row, count, tied, mx, ret, (int64_t)ordered);
     RSV_HIP_TRY(hipGetLastError());
     return RSV_OK;
 }
 
 int WideDistinct::merge_rows(const int64_t* rows, int32_t parts, int64_t stride, hipStream_t st) {
-    WideDistinct* const d = this;
     if (parts <= 0) return RSV_OK;  // (no finalize either: an empty merge leaves the engine as it was)
     if (int rc = finalize(st)) return rc;
-    const int64_t k = d->k, kw = k * d->words;
+    const int64_t k = this->k, kw = k * words;
     std::vector<int64_t> meta((size_t)parts * 6);
     for (int32_t p = 0; p < parts; ++p)
         RSV_HIP_TRY(hipMemcpyAsync(meta.data() + (size_t)p * 6, rows + (size_t)p * stride + kw + k, 6 * 8,
@@ -1816,7 +1767,7 @@ int WideDistinct::merge_rows(const int64_t* rows, int32_t parts, int64_t stride,
         tops.push_back(mt[3]);
         ties.push_back(mt[2] != 0);
     }
-    return merge_external(d, src, counts, tops, ties, st);
+    return merge_external(this, src, counts, tops, ties, st);
 }
 
 void WideDistinct::spec_target(void* dst_host_dev, uint32_t* flag_dev, uint32_t* gen_counter) {
@@ -1825,12 +1776,11 @@ void WideDistinct::spec_target(void* dst_host_dev, uint32_t* flag_dev, uint32_t*
 }
 
 int WideDistinct::log_export(int64_t bound, int64_t* out_h, void* out_k, int64_t cap, int64_t* out_n, hipStream_t st) {
-    WideDistinct* const d = this;
     if (int rc = log_export_check()) return rc;
     std::vector<int64_t> lh;
     std::vector<uint64_t> lk;
-    if (hipError_t e = log_to_host(d, lh, lk, st)) return hip_status(e, "rsv_export_log");
-    const int64_t W = d->words;
+    if (hipError_t e = log_to_host(this, lh, lk, st)) return hip_status(e, "rsv_export_log");
+    const int64_t W = words;
     uint64_t* ok = (uint64_t*)out_k;
     LogEmit emit{bound, cap};
     auto one = [&](int64_t h, const uint64_t* r) {
@@ -1839,29 +1789,28 @@ int WideDistinct::log_export(int64_t bound, int64_t* out_h, void* out_k, int64_t
             std::memcpy(ok + i * W, r, (size_t)W * 8);
         });
     };
-    for (size_t i = 0; i < d->arch_h.size(); ++i) one(d->arch_h[i], d->arch_k.data() + i * W);
+    for (size_t i = 0; i < arch_h.size(); ++i) one(arch_h[i], arch_k.data() + i * W);
     for (size_t i = 0; i < lh.size(); ++i) one(lh[i], lk.data() + i * W);
     return emit.finish(out_n);
 }
 
 int WideDistinct::log_merge(const int64_t* h, const void* keys, int64_t n, int64_t seen, hipStream_t st) {
-    WideDistinct* const d = this;
-    if (!d->ordered) {
+    if (!ordered) {
         set_error("rsv_merge_log needs an RSV_DISTINCT_ORDERED sampler");
         return RSV_E_UNSUPPORTED;
     }
-    d->rep.reset(d->k, d->words);
-    d->rep_stale = false;
+    rep.reset(k, words);
+    rep_stale = false;
     const uint64_t* kk = (const uint64_t*)keys;
-    for (int64_t t = 0; t < n; ++t) d->rep.sample(h[t], kk + (size_t)t * d->words);
-    d->log_n = 0;
-    d->arch_h.clear();
-    d->arch_k.clear();
-    if (hipError_t e = upload_replica(d, st)) return hip_status(e, "rsv_merge_log");
-    d->tied = false;
-    d->exact = true;
-    d->merged = true;
-    d->seen = std::max(d->seen, seen);
+    for (int64_t t = 0; t < n; ++t) rep.sample(h[t], kk + (size_t)t * words);
+    olog.n = 0;
+    arch_h.clear();
+    arch_k.clear();
+    if (hipError_t e = upload_replica(this, st)) return hip_status(e, "rsv_merge_log");
+    tied = false;
+    exact = true;
+    merged = true;
+    this->seen = std::max(this->seen, seen);
     return RSV_OK;
 }
 

@@ -462,6 +462,87 @@ def test_maximum_sample_size(cuda, oracle):
     assert np.array_equal(d.result(), ref.result()[0])
 
 
+def _growth_batches(fresh, rng):
+    """Three batches of 1 500, 6 000 and 40 000 fresh keys (rows of `fresh`), each with 300 repeats of keys seen by
+    then: the set grows three times (to 2048, 8192 and 65536 entries), each time with its contents kept."""
+    out, lo = [], 0
+    for n in (1_500, 6_000, 40_000):
+        part = np.concatenate([fresh[lo:lo + n], fresh[rng.integers(0, lo + n, size=300)]])
+        rng.shuffle(part)
+        out.append(part)
+        lo += n
+    return out
+
+
+@pytest.mark.parametrize("key_type,order", [("long", "set"), ("int", "set"), ("long", "ordered"), ("bytes16", "auto")])
+def test_state_grows_with_kept_contents(cuda, oracle, key_type, order):
+    """k = Int.MaxValue - 2 allocates nothing for k: the set arrays (and, in ordered mode, the candidate log)
+    grow batch by batch and keep what they hold.  result() after every batch equals the oracle's, for Long and
+    Int keys, for the ordered log, and for 16-byte rows under UUID.hashCode (the byte-key engine)."""
+    import torch
+
+    from reservoir_amd import Sampler
+
+    k, k_ref = 2**31 - 1 - 2, 1 << 17  # the oracle keeps everything too: 47 500 distinct keys
+    rng = np.random.default_rng(31)
+    if key_type == "bytes16":
+        fresh = rng.integers(0, 256, size=(47_500, 16), dtype=np.uint8)
+        ref = oracle.DistinctRows(k_ref, 7, 16, "uuid")
+        d = Sampler.distinct(k, key_type="bytes16", seed=7, reusable=True)()
+        assert d.is_ordered
+    elif key_type == "int":
+        fresh = rng.permutation(np.unique(rng.integers(-2**31, 2**31 - 1, size=60_000)))[:47_500].astype(np.int32)
+        ref = oracle.Distinct(k_ref, 7, oracle.HASH_JAVA_INT)
+        d = Sampler.distinct(k, seed=7, key_type="int", order=order, reusable=True)()
+    else:
+        fresh = rng.permutation(np.unique(rng.integers(-2**63, 2**63 - 1, size=48_000, dtype=np.int64)))[:47_500]
+        ref = oracle.Distinct(k_ref, 7, oracle.HASH_IDENTITY)
+        d = Sampler.distinct(k, seed=7, order=order, reusable=True)(hash="identity")
+    assert fresh.shape[0] == 47_500
+    size = 0
+    for part in _growth_batches(fresh, rng):
+        d.sample_all(torch.from_numpy(part).to(cuda))
+        size += part.shape[0] - 300
+        if key_type == "bytes16":
+            ref.sample_all(part, None)
+            got, want = d.result(), ref.result()[0]
+            assert got.shape[0] == size
+            assert sorted(bytes(r) for r in np.ascontiguousarray(got)) == sorted(bytes(r) for r in want)
+        else:
+            ref.sample_all(part.astype(np.int64))
+            got = d.result()
+            assert got.size == size
+            assert got.astype(np.int64).tolist() == ref.result()[0].tolist()  # ascending (hash, key) on both sides
+
+
+def test_ordered_replay_staging_grows(cuda, oracle, monkeypatch):
+    """Two replays of a reusable ordered sampler, each over several logged segments with the next segment staged
+    behind the current one (RSV_FIRST_MIN=1, RSV_REPLAY_OVERLAP=1: test hooks), the second replay's segments
+    larger than any of the first: both pinned staging sets grow between the replays, and the event that says a
+    segment's own copies are done is the one created at the first replay.  Round two's batches repeat the current
+    members (every repeat below the maximum is a candidate), so its segments hold several thousand candidates
+    against the two thousand of the first round (the chunk that fills the heap and the one after it)."""
+    import torch
+
+    from reservoir_amd import Sampler
+
+    monkeypatch.setenv("RSV_FIRST_MIN", "1")
+    monkeypatch.setenv("RSV_REPLAY_OVERLAP", "1")
+    rng = np.random.default_rng(77)
+    ref = oracle.Distinct(500, 9, oracle.HASH_JAVA_LONG)
+    r = Sampler.distinct(500, seed=9, reusable=True)()
+    for fresh, repeats in ((10_000, 300), (6_000, 4_000)):
+        for _ in range(4):
+            part = _colliding(rng, fresh, 2000)
+            members = ref.result()[0]
+            if members.size:
+                part = np.concatenate([part, members[rng.integers(0, members.size, size=repeats)]])
+                rng.shuffle(part)
+            r.sample_all(torch.from_numpy(part).to(cuda))
+            ref.sample_all(part)
+        assert r.result().tolist() == ref.result()[0].tolist()
+
+
 @pytest.mark.parametrize("key_type", ["long", "int"])
 def test_set_mode_speculative_publication(cuda, oracle, monkeypatch, key_type):
     """Set-mode batches of at least RSV_SPEC_MIN_BATCH keys (test hook, read at creation; the
