@@ -446,6 +446,46 @@ rsv_status rsv_sample_segmented_rows_merge(const void* part_rows_dev, const int6
                                            int32_t key_width, int32_t k, void* state_rows_dev,
                                            int64_t* state_idx_dev, int64_t* state_next_dev, void* hip_stream);
 
+/* Segmented sampling without keys (Sampler.apply for any B over S streams): the elements stay with the
+ * caller, only the streams' lengths reach the device.  Stream s has len = offsets[s+1] - offsets[s]
+ * elements (offsets_dev is read for its differences alone) and Philox stream id stream_base + s;
+ * out_idx_dev[s*k + j] is the stream-relative index of the element slot j holds -- the slot's last
+ * writer, else j where j < len, else -1 -- and counts_dev[s] = min(len, k): stream s holds what a single
+ * ELEMENTS handle on RSV_ENGINE_PHILOX_R fed len elements through rsv_sample_indexed holds.  Every slot
+ * and every count is written.  k as rsv_sample_segmented.  A stream longer than the split length (a
+ * multiple of 1024 indices; RSV_K2_SPLIT_LEN, read once per process, overrides it, 0 disables it) is
+ * taken in pieces spread over the whole device and combined per slot by the largest index; the result
+ * does not depend on the split.  Stream-ordered on hip_stream; the split form takes its work list from
+ * the stream-ordered allocator and adds no host wait.  All pointers are device pointers. */
+rsv_status rsv_sample_segmented_indexed(const int64_t* offsets_dev, int64_t num_streams, int32_t k, uint64_t seed,
+                                        uint64_t stream_base, int64_t* out_idx_dev, int64_t* counts_dev,
+                                        void* hip_stream);
+
+/* rsv_sample_segmented_update without keys: the state is state_idx_dev[num_states*k] and
+ * state_next_dev[num_states] as there (a fresh state is idx = -1, next = 0).  Segments (offsets_dev: their
+ * lengths), stream_ids_dev, bases_dev and the skipped segments as rsv_sample_segmented_update; the
+ * stream_ids of one call must be distinct (the caller's contract).  A slot's idx is replaced only where the
+ * segment's last writer or fill index is later.  hits_dev[b*k + j] (int64) is, for each slot j that segment b
+ * replaced, the position inside the segment of the element the slot now holds (its global index minus the
+ * segment's base), and -1 for every other slot; hit_counts_dev[b] is the number of replaced slots.  Both are
+ * written for every segment, skipped ones included (a row of -1, a count of 0): the caller keeps its elements
+ * in step by storing segment b's element hits[b*k + j] into slot j of row stream_ids[b].  1 <= k <= 15104
+ * (larger: RSV_E_UNSUPPORTED).  Stateless and stream-ordered on hip_stream: no host wait, no allocation. */
+rsv_status rsv_sample_segmented_indexed_update(const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                               const int64_t* bases_dev, int64_t num_segments, int64_t num_states,
+                                               int32_t k, uint64_t seed, uint64_t stream_base, int64_t* state_idx_dev,
+                                               int64_t* state_next_dev, int64_t* hits_dev, int64_t* hit_counts_dev,
+                                               void* hip_stream);
+
+/* rsv_sample_segmented_merge without keys: part_idx_dev is [parts][num_states][k], part_next_dev
+ * [parts][num_states].  Per slot the part with the largest idx wins if it beats the state's; next becomes the
+ * max over the row and the parts.  src_dev[r*k + j] (int32) is the part slot j of row r was taken from -- the
+ * lowest of the parts that hold the largest idx -- or -1 where the row's own entry stood: the caller copies its
+ * element from slot j of row r of that part.  k as rsv_sample_segmented_indexed_update. */
+rsv_status rsv_sample_segmented_indexed_merge(const int64_t* part_idx_dev, const int64_t* part_next_dev, int32_t parts,
+                                              int64_t num_states, int32_t k, int64_t* state_idx_dev,
+                                              int64_t* state_next_dev, int32_t* src_dev, void* hip_stream);
+
 /* Segmented distinct: S independent Sampler.distinct samplers (no reference counterpart; = S separate
  * RandomValues instances, S:383-412).  Stream s covers keys_dev[offsets[s] .. offsets[s+1]) and is
  * seeded like a single DISTINCT handle with java.util.Random(seed + stream_base + s) (wrapping to a

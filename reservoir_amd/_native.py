@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "rsv_distinct_segmented_ordered", "rsv_distinct_segmented_rows_ordered",
     "rsv_distinct_segmented_ordered_update", "rsv_distinct_segmented_rows_ordered_update",
     "rsv_distinct_segmented_candidates",
+    "rsv_sample_segmented_indexed", "rsv_sample_segmented_indexed_update", "rsv_sample_segmented_indexed_merge",
 )
 
 
@@ -141,6 +142,9 @@ def load():
     L.rsv_sample_segmented_rows.argtypes = [vp, vp, i64, i32, i32, u64, u64, vp, vp, vp]
     L.rsv_sample_segmented_rows_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_sample_segmented_rows_merge.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
+    L.rsv_sample_segmented_indexed.argtypes = [vp, i64, i32, u64, u64, vp, vp, vp]
+    L.rsv_sample_segmented_indexed_update.argtypes = [vp, vp, vp, i64, i64, i32, u64, u64, vp, vp, vp, vp, vp]
+    L.rsv_sample_segmented_indexed_merge.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp, vp]
     L.rsv_distinct_segmented.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_distinct_segmented_ordered.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp, vp]
     L.rsv_distinct_segmented_rows.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
@@ -189,7 +193,9 @@ def load():
                  "rsv_sample_segmented_rows", "rsv_sample_segmented_rows_update",
                  "rsv_sample_segmented_rows_merge", "rsv_distinct_segmented_ordered",
                  "rsv_distinct_segmented_rows_ordered", "rsv_distinct_segmented_ordered_update",
-                 "rsv_distinct_segmented_rows_ordered_update", "rsv_distinct_segmented_candidates"):
+                 "rsv_distinct_segmented_rows_ordered_update", "rsv_distinct_segmented_candidates",
+                 "rsv_sample_segmented_indexed", "rsv_sample_segmented_indexed_update",
+                 "rsv_sample_segmented_indexed_merge"):
         getattr(L, name).restype = i32
     if L.rsv_abi_version() != 1:
         raise ImportError("libreservoir_hip.so ABI version mismatch")

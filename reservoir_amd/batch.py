@@ -20,6 +20,11 @@ libreservoir_hip.so.  Every function raises if the engine is unavailable.
                          pieces from any start index (update) and combined per slot by largest index (merge)
     sample_segmented_rows -- K2 over fixed-width byte keys (UUIDs): rows in, each slot's winning row out
     SegmentedSamplerRows -- K2 resumed over byte keys: state (rows, idx, next), update and merge as SegmentedSampler
+    sample_segmented_indexed -- K2 without keys: the streams' lengths in, each slot's winning index out; streams
+                         longer than the split length are taken in pieces over the whole device
+    sample_segmented_objects -- Sampler.apply for any B over S streams: the same launch, the elements picked on the host
+    SegmentedObjectSampler -- the same as live state: (idx, next) on the device, a slot list per row on the host,
+                         one launch per batch that reports the replaced slots (update), and merge by source part
     replay_events     -- K1': apply the reference's Algorithm-L eviction events on the GPU
     export_draws      -- the per-element draw sequence j_i of draw format R2
 """
@@ -800,11 +805,7 @@ class SegmentedObjectDistinct:
         dev = self.shadow_counts.device
 
         def on_device(t, what):
-            if isinstance(t, np.ndarray):
-                t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.int64))
-            if t.dtype != torch.int64 or t.dim() != 1:
-                raise N.IllegalArgumentException(f"{what} must be 1-d int64")
-            return t.to(dev).contiguous()
+            return _host_or_device_i64(torch, t, what, dev)
 
         hashes, offsets = on_device(hashes, "hashes"), on_device(offsets, "offsets")
         B = offsets.numel() - 1
@@ -975,6 +976,195 @@ class SegmentedSampler(_SegmentedState):
 
         L = N.load()
         return self._merge(torch, L.rsv_sample_segmented_merge, SegmentedSampler, (part_keys, part_idx, part_next))
+
+
+SPLIT_LEN_DEFAULT = 1 << 18  # rsv_segmented.hip kSplitLenDefault (RSV_K2_SPLIT_LEN overrides it; 0: no split)
+
+
+def sample_segmented_indexed(offsets, k: int, seed: int, stream_base: int = 0):
+    """Sampler.apply over S streams whose elements stay with the caller: only their lengths reach the device.
+
+    offsets: int64 device tensor (S + 1,); stream s has offsets[s+1] - offsets[s] elements.  Returns
+    (idx[S, k], counts[S]) device tensors: idx[s, j] is the stream-relative index of the element slot j holds
+    (-1: the slot is empty), counts[s] = min(len, k).  Stream s draws like a single "philox_r" Sampler with
+    stream_id = stream_base + s.  Streams longer than the split length (RSV_K2_SPLIT_LEN) are taken in pieces
+    over the whole device; the result does not depend on it.
+    """
+    import torch
+
+    L = N.load()
+    if not offsets.is_cuda or offsets.dtype != torch.int64:
+        raise N.IllegalArgumentException("offsets must be an int64 device tensor")
+    offsets = offsets.contiguous()
+    S = offsets.numel() - 1
+    idx = torch.empty((max(S, 0), k), dtype=torch.int64, device=offsets.device)  # (every slot is written)
+    counts = torch.empty(max(S, 0), dtype=torch.int64, device=offsets.device)
+    if S <= 0:
+        return idx, counts
+    N.check(L.rsv_sample_segmented_indexed(
+        _ptr(offsets), S, k, seed & (2**64 - 1), stream_base & (2**64 - 1), _ptr(idx), _ptr(counts),
+        _stream_ptr(torch, offsets.device)))
+    return idx, counts
+
+
+def _host_or_device_i64(torch, t, what, dev):
+    """A 1-d int64 numpy array or tensor as a contiguous tensor on dev."""
+    import numpy as np
+
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.int64))
+    if t.dtype != torch.int64 or t.dim() != 1:
+        raise N.IllegalArgumentException(f"{what} must be 1-d int64")
+    return t.to(dev).contiguous()
+
+
+def sample_segmented_objects(elements, offsets, k: int, seed: int, stream_base: int = 0, map_fn=None):
+    """Sampler.apply for any B over S streams in one launch: stream s = elements[offsets[s]:offsets[s+1]].
+
+    elements: indexable; offsets: int64, a numpy array or a tensor.  Returns a list of S lists, each stream's
+    filled slots in slot order; map_fn runs on those elements only.  Stream s equals a single
+    Sampler(k, seed=seed, stream_id=stream_base + s, key_type="object")(map_fn) fed the same elements.
+    """
+    import torch
+
+    dev = offsets.device if hasattr(offsets, "is_cuda") and offsets.is_cuda else torch.device(
+        "cuda", torch.cuda.current_device())
+    offsets = _host_or_device_i64(torch, offsets, "offsets", dev)
+    idx, _ = sample_segmented_indexed(offsets, k, seed, stream_base)
+    starts = offsets.cpu().tolist()
+    out = []
+    for s, row in enumerate(idx.cpu().tolist()):
+        picked = [elements[starts[s] + i] for i in row if i >= 0]
+        out.append(picked if map_fn is None else [map_fn(e) for e in picked])
+    return out
+
+
+class SegmentedObjectSampler(_SegmentedState):
+    """S long-lived Sampler.apply streams over any B (str, tuple, dataclass), one launch per batch.
+
+    The engine sees the segments' lengths only.  The state is idx (S, k) and next (S,) on the device --
+    SegmentedSampler's state without keys -- and one Python slot list per row on the host, created when a row
+    is first named.  update() reads back, for each slot a segment replaced, the position of its new element
+    inside the segment (hits) and stores map_fn(element) there; merge() reads back the part each slot came
+    from (src).  Row r equals a single Sampler(k, seed=seed, stream_id=stream_base + r,
+    key_type="object")(map_fn) fed the same elements.  Everything runs on torch's current stream.
+    """
+
+    _NAME, _TENSORS, _MAX_K = "SegmentedObjectSampler", ("idx", "next"), _SEG_SAMPLE_STATE_MAX_K
+    _SAME = "seed and stream_base"
+    _EMPTY = object()  # a slot no element has reached (map_fn may return None)
+
+    def _identity(self):
+        return self.num_streams, self.k, self.seed, self.stream_base
+
+    def __init__(self, num_streams: int, k: int, seed: int, stream_base: int = 0, map_fn=None, device=None):
+        import torch
+
+        N.load()
+        dev = self._init_state(torch, num_streams, k, seed, stream_base, device)
+        self._map = map_fn
+        self.idx = torch.full((self.num_streams, self.k), -1, dtype=torch.int64, device=dev)
+        self.next = torch.zeros(self.num_streams, dtype=torch.int64, device=dev)
+        self._slots: dict = {}
+
+    @property
+    def counts(self):
+        """Filled slots per row (a device tensor)."""
+        return (self.idx >= 0).sum(1)
+
+    def update(self, elements, offsets, stream_ids=None, bases=None, check_ids: bool = True):
+        """Segment b = elements[offsets[b]:offsets[b+1]] into row stream_ids[b] (None: row b).
+
+        elements: indexable; offsets, stream_ids and bases: int64, numpy arrays or tensors.  bases, ids and the
+        skipped segments as SegmentedSampler.update.  One launch; the hits are compacted on the device and read
+        back once as (segment, slot, position).  Every hit element is mapped before any slot list changes: if
+        the launch, the read-back or map_fn raises, the named rows' idx and next are put back from a copy taken
+        before the launch, the slot lists are left as they were and the exception propagates: the batch never
+        came.  last_hit_counts keeps the launch's hit_counts (B,) on the device.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        dev = self.idx.device
+        offsets = _host_or_device_i64(torch, offsets, "offsets", dev)
+        if stream_ids is not None:
+            stream_ids = _host_or_device_i64(torch, stream_ids, "stream_ids", dev)
+        if bases is not None:
+            bases = _host_or_device_i64(torch, bases, "bases", dev)
+        if stream_ids is None and offsets.numel() - 1 > self.num_streams:
+            raise N.IllegalArgumentException("more segments than streams without stream_ids")
+        seg = self._segments(torch, offsets, check_ids, stream_ids, bases=bases)
+        if seg is None or self.num_streams == 0:
+            return self
+        B, stream_ids, bases = seg
+        rows = stream_ids if stream_ids is not None else torch.arange(B, dtype=torch.int64, device=dev)
+        # (ids the kernel skips fall on a row that then keeps what it has)
+        named = rows.clamp(0, self.num_streams - 1)
+        saved = self.idx[named], self.next[named]  # (indexing copies)
+        hits = torch.empty((B, self.k), dtype=torch.int64, device=dev)
+        hit_counts = torch.empty(B, dtype=torch.int64, device=dev)
+        try:
+            N.check(L.rsv_sample_segmented_indexed_update(
+                _ptr(offsets), _ptr(stream_ids), _ptr(bases), B, self.num_streams, self.k, self.seed,
+                self.stream_base, _ptr(self.idx), _ptr(self.next), _ptr(hits), _ptr(hit_counts),
+                _stream_ptr(torch, dev)))
+            at = (hits >= 0).nonzero()
+            b, j = at[:, 0], at[:, 1]
+            pos = hits[b, j]
+            # the one read-back: (segment, slot, position), with the row and the element they name
+            got = torch.stack([b, j, pos, rows[b], offsets[b] + pos]).cpu().tolist()
+            mp = self._map
+            mapped = [elements[e] if mp is None else mp(elements[e]) for e in got[4]]
+        except BaseException:
+            self.idx[named] = saved[0]
+            self.next[named] = saved[1]
+            raise
+        self.last_hit_counts = hit_counts
+        for r, j, v in zip(got[3], got[1], mapped):
+            self._row(r)[j] = v
+        return self
+
+    def _row(self, r: int) -> list:
+        lst = self._slots.get(r)
+        if lst is None:
+            lst = self._slots[r] = [self._EMPTY] * self.k
+        return lst
+
+    def result(self, r: int) -> list:
+        """Row r's filled slots in slot order."""
+        if r < 0 or r >= self.num_streams:
+            raise N.IllegalArgumentException(f"row outside [0, {self.num_streams})")
+        return [v for v in self._slots.get(int(r), ()) if v is not self._EMPTY]
+
+    def results(self) -> list:
+        return [self.result(r) for r in range(self.num_streams)]
+
+    def merge(self, *others):
+        """Per slot the largest idx among row r and row r of every other state wins, and the slot takes that
+        state's element; next takes the max.  others: SegmentedObjectSampler objects of this state's shape, seed
+        and stream_base.  One launch, one read-back of the part each slot came from.  Returns self."""
+        import torch
+
+        L = N.load()
+        for o in others:
+            if not isinstance(o, SegmentedObjectSampler) or o._identity() != self._identity():
+                raise N.IllegalArgumentException(f"merge needs states of the same shape, {self._SAME}")
+        dev = self.idx.device
+        if any(o.idx.device != dev for o in others):
+            raise N.IllegalArgumentException("parts must live on the state's device")
+        if not others or self.num_streams == 0:
+            return self
+        part_idx = torch.stack([o.idx for o in others]).contiguous()
+        part_next = torch.stack([o.next for o in others]).contiguous()
+        src = torch.empty((self.num_streams, self.k), dtype=torch.int32, device=dev)
+        N.check(L.rsv_sample_segmented_indexed_merge(
+            _ptr(part_idx), _ptr(part_next), len(others), self.num_streams, self.k, _ptr(self.idx), _ptr(self.next),
+            _ptr(src), _stream_ptr(torch, dev)))
+        at = (src >= 0).nonzero()
+        got = torch.stack([at[:, 0], at[:, 1], src[at[:, 0], at[:, 1]].to(torch.int64)]).cpu().tolist()
+        for r, j, p in zip(*got):
+            self._row(r)[j] = others[p]._slots[r][j]
+        return self
 
 
 def _seg_rows_inputs(torch, rows, offsets):

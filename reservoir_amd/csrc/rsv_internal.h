@@ -164,6 +164,21 @@ hipError_t launch_segmented_rows_update(const void* rows, int key_width, const i
 hipError_t launch_segmented_rows_merge(const void* part_rows, int key_width, const int64_t* part_idx,
                                        const int64_t* part_next, int32_t parts, int64_t num_states, uint32_t k,
                                        void* state_rows, int64_t* state_idx, int64_t* state_next, hipStream_t st);
+// K2 keyless (rsv_segmented.hip, the same element loops and forms): no element reaches the device.  Stateless:
+// out_idx[S*k] takes each slot's stream-relative source index (-1: empty), streams longer than the split length
+// (RSV_K2_SPLIT_LEN) in pieces over the whole device.  The resumed state is (idx, next) as above; update also
+// writes hits[num_segments*k] (the position inside the segment of each slot it replaced, else -1) and
+// hit_counts[num_segments], for skipped segments too; merge writes src[num_states*k], the part each slot was
+// taken from (-1: the row's own entry stood).
+hipError_t launch_segmented_indexed(const int64_t* offsets, int64_t S, uint32_t k, const DrawParams& dp,
+                                    int64_t* out_idx, int64_t* counts, hipStream_t st);
+hipError_t launch_segmented_indexed_update(const int64_t* offsets, const int64_t* stream_ids, const int64_t* bases,
+                                           int64_t num_segments, int64_t num_states, uint32_t k, const DrawParams& dp,
+                                           int64_t* state_idx, int64_t* state_next, int64_t* hits, int64_t* hit_counts,
+                                           hipStream_t st);
+hipError_t launch_segmented_indexed_merge(const int64_t* part_idx, const int64_t* part_next, int32_t parts,
+                                          int64_t num_states, uint32_t k, int64_t* state_idx, int64_t* state_next,
+                                          int32_t* src, hipStream_t st);
 // K5: segmented distinct (rsv_segdistinct.hip): per stream the bottom-k by (scrambled hash, key),
 // (r0, r1) from java.util.Random(seed0 + s); hashes only for kHashPrecomputed, out_hashes may be null.
 // k <= kSegDistinctMaxK; one wave per stream up to kSegDistinctWaveMaxK, one workgroup above.

@@ -1716,6 +1716,48 @@ rsv_status rsv_sample_segmented_rows_merge(const void* part_rows_dev, const int6
     return RSV_OK;
 }
 
+// the three keyless entry points: the checks of their keyed siblings, in their order, without a key width
+rsv_status rsv_sample_segmented_indexed(const int64_t* offsets_dev, int64_t num_streams, int32_t k, uint64_t seed,
+                                        uint64_t stream_base, int64_t* out_idx_dev, int64_t* counts_dev,
+                                        void* hip_stream) {
+    if (rsv_status st = check_segsample_shape("rsv_sample_segmented_indexed", nullptr, k, 8, false)) return st;
+    if (num_streams < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative stream count");
+    if (num_streams == 0) return RSV_OK;
+    if (!offsets_dev || !out_idx_dev || !counts_dev) return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    const DrawParams dp{seed, stream_base};
+    RSV_HIP_TRY(launch_segmented_indexed(offsets_dev, num_streams, (uint32_t)k, dp, out_idx_dev, counts_dev,
+                                         (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
+rsv_status rsv_sample_segmented_indexed_update(const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                               const int64_t* bases_dev, int64_t num_segments, int64_t num_states,
+                                               int32_t k, uint64_t seed, uint64_t stream_base, int64_t* state_idx_dev,
+                                               int64_t* state_next_dev, int64_t* hits_dev, int64_t* hit_counts_dev,
+                                               void* hip_stream) {
+    rsv_status st = check_segsample_shape("rsv_sample_segmented_indexed_update", nullptr, k, 8, true);
+    if (st || segsample_update_done(num_segments, num_states, stream_ids_dev, st)) return st;
+    if (!offsets_dev || !state_idx_dev || !state_next_dev || !hits_dev || !hit_counts_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    const DrawParams dp{seed, stream_base};
+    RSV_HIP_TRY(launch_segmented_indexed_update(offsets_dev, stream_ids_dev, bases_dev, num_segments, num_states,
+                                                (uint32_t)k, dp, state_idx_dev, state_next_dev, hits_dev,
+                                                hit_counts_dev, (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
+rsv_status rsv_sample_segmented_indexed_merge(const int64_t* part_idx_dev, const int64_t* part_next_dev, int32_t parts,
+                                              int64_t num_states, int32_t k, int64_t* state_idx_dev,
+                                              int64_t* state_next_dev, int32_t* src_dev, void* hip_stream) {
+    rsv_status st = check_segsample_shape("rsv_sample_segmented_indexed_merge", nullptr, k, 8, true);
+    if (st || segsample_merge_done(parts, num_states, st)) return st;
+    if (!part_idx_dev || !part_next_dev || !state_idx_dev || !state_next_dev || !src_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    RSV_HIP_TRY(launch_segmented_indexed_merge(part_idx_dev, part_next_dev, parts, num_states, (uint32_t)k,
+                                               state_idx_dev, state_next_dev, src_dev, (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
 // ---- K5: the ten rsv_distinct_segmented* entry points ----
 // What an entry point tells its checker about itself, and what the checker tells it (hk, st).  There are three
 // checkers, one per kind of call (stateless, update, merge); each holds that kind's checks once, in the one order they

@@ -35,7 +35,11 @@
 // kernels (k2_segmented_rows*, rsv_k2.h) then gather whole rows, lanes side by side on a row's 16- or
 // 8-byte granules, with 64-bit byte offsets.  The key-typed kernels above are not instantiated for rows.
 //
-// What the nine kernels and six launchers share exists once.  Device (rsv_k2.h): build_lut, the frames
+// Keyless (rsv_sample_segmented_indexed / _update / _merge): only the streams' lengths reach the
+// device and indices come back.  The kernels (rsv_indexed.hip, declared in rsv_k2_indexed.h) run the same element
+// loops and forms; the launchers are at the end of this file, with the split form of the stateless launch.
+//
+// What the nine keyed kernels and six launchers share exists once.  Device (rsv_k2.h): build_lut, the frames
 // wave_frame / wg_frame (the Wave over the workgroup's LDS and its winner table), read_segment (an update's
 // segment header and its skip rules), slot_source (the stateless slot rule) and merge_pick.  Host (below):
 // SeedWords, wave_grid / wg_grid, tables_fit_u32, with_global_table (gt_acquire .. gt_release around a
@@ -47,6 +51,7 @@
 
 #include "rsv_internal.h"
 #include "rsv_k2.h"
+#include "rsv_k2_indexed.h"
 
 namespace rsv {
 
@@ -355,6 +360,100 @@ hipError_t launch_segmented_rows_merge(const void* part_rows, int key_width, con
                            (unsigned char*)state_rows, state_idx, state_next);
         return hipGetLastError();
     });
+}
+
+// ---- keyless: lengths in, indices out ------------------------------------------------------------
+namespace {
+// The split length of the stateless keyless launch (rsv_indexed.hip), in indices.  RSV_K2_SPLIT_LEN (read once per
+// process) overrides it, rounded down to a multiple of 1024; 0 disables the split.  2^18 was the fastest of 2^18,
+// 2^20 and 2^22 on 2^16 streams x 4096 beside one stream of 2^32 indices (k = 64: 1.19 / 1.82 / 5.37 ms, unsplit
+// 2630 ms; k = 1024: 1.68 / 1.69 / 1.74 ms, unsplit 426 ms), and at C3's shape, where no stream is split, the
+// launch stays inside the run-to-run spread of the launch without it (profiles/segmented_indexed/bench.json).
+constexpr int64_t kSplitLenDefault = 1ll << 18;
+constexpr uint32_t kSplitListCap = 1024;  // streams whose pieces a launch records; the others stay whole
+int64_t env_split_len() {
+    static const int64_t split_len = [] {
+        const char* e = std::getenv("RSV_K2_SPLIT_LEN");
+        const long long v = e ? std::atoll(e) : (long long)kSplitLenDefault;
+        return v < 1024 ? (int64_t)0 : (int64_t)(v & ~1023ll);
+    }();
+    return split_len;
+}
+
+// the second kernel's grid: what the device holds at once (8 waves a SIMD, one workgroup's LDS), whatever S is
+unsigned resident_grid(size_t lds, int waves) {
+    const uint64_t by_waves = 8 * 4 / (uint64_t)waves;
+    return (unsigned)(256 * std::max<uint64_t>(1, std::min<uint64_t>(by_waves, k2::kLdsMax / lds)));
+}
+}  // namespace
+
+hipError_t launch_segmented_indexed(const int64_t* offsets, int64_t S, uint32_t k, const DrawParams& dp,
+                                    int64_t* out_idx, int64_t* counts, hipStream_t st) {
+    if (S <= 0) return hipSuccess;
+    const uint32_t fifo_cap = env_fifo_cap();
+    const SeedWords sw(dp);
+    const bool wg = k >= k2::kWGMinK;
+    // the list of the split form: stream-ordered memory, its count zeroed ahead of the first kernel; the
+    // global-table form (no u32 table of k entries fits LDS) stays unsplit
+    SplitList sl{nullptr, nullptr, 0, 0};
+    void* list = nullptr;
+    if (env_split_len() > 0 && (!wg || k2::lds_bytes_wg(k, 4, false) <= k2::kLdsMax)) {
+        RSV_HIP_RET(hipMallocAsync(&list, 16 + (size_t)kSplitListCap * 16, st));
+        sl = SplitList{(unsigned long long*)list, (int64_t*)((unsigned char*)list + 16), kSplitListCap, env_split_len()};
+    }
+    hipError_t e = list ? hipMemsetAsync(list, 0, 16, st) : hipSuccess;
+    if (e == hipSuccess && wg) {  // one workgroup per stream, and per piece
+        e = launch_wg(offsets, S, k, st, [&](auto gt, unsigned grid, size_t lds, auto* tab) {
+            using TabT = std::remove_pointer_t<decltype(tab)>;
+            hipLaunchKernelGGL((k2_indexed_wg<TabT, decltype(gt)::value>), dim3(grid), dim3(64 * kWavesWG), lds, st,
+                               offsets, S, k, sw.k0, sw.k1, dp.stream, out_idx, counts, fifo_cap, tab, sl);
+            if constexpr (!decltype(gt)::value)
+                if (sl.C > 0)
+                    hipLaunchKernelGGL(k2_indexed_pieces_wg<TabT>, dim3(resident_grid(lds, kWavesWG)),
+                                       dim3(64 * kWavesWG), lds, st, k, sw.k0, sw.k1, dp.stream, out_idx, fifo_cap, sl);
+        });
+    } else if (e == hipSuccess) {
+        const size_t lds = k2::lds_bytes(k);
+        hipLaunchKernelGGL(k2_indexed, dim3(wave_grid(S)), dim3(64 * kWaves), lds, st, offsets, S, k, sw.k0, sw.k1,
+                           dp.stream, out_idx, counts, fifo_cap, sl);
+        if (sl.C > 0)
+            hipLaunchKernelGGL(k2_indexed_pieces, dim3(resident_grid(lds, kWaves)), dim3(64 * kWaves), lds, st, k, sw.k0,
+                               sw.k1, dp.stream, out_idx, fifo_cap, sl);
+        e = hipGetLastError();
+    }
+    if (list) {
+        const hipError_t f = hipFreeAsync(list, st);
+        if (e == hipSuccess) e = f;
+    }
+    return e;
+}
+
+hipError_t launch_segmented_indexed_update(const int64_t* offsets, const int64_t* stream_ids, const int64_t* bases,
+                                           int64_t num_segments, int64_t num_states, uint32_t k, const DrawParams& dp,
+                                           int64_t* state_idx, int64_t* state_next, int64_t* hits, int64_t* hit_counts,
+                                           hipStream_t st) {
+    if (num_segments <= 0 || num_states <= 0) return hipSuccess;
+    if (k > kSegSampleStateMaxK) return hipErrorInvalidValue;
+    const SeedWords sw(dp);
+    const uint32_t fifo_cap = env_fifo_cap();
+    auto launch = [&](auto kernel, int waves) {
+        return [&, kernel, waves](unsigned grid, size_t lds) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, st, offsets, stream_ids, bases, num_segments,
+                               num_states, k, sw.k0, sw.k1, dp.stream, state_idx, state_next, hits, hit_counts, fifo_cap);
+        };
+    };
+    return launch_update(num_segments, k, launch(k2_indexed_update_wg, kWavesWG), launch(k2_indexed_update, kWaves));
+}
+
+hipError_t launch_segmented_indexed_merge(const int64_t* part_idx, const int64_t* part_next, int32_t parts,
+                                          int64_t num_states, uint32_t k, int64_t* state_idx, int64_t* state_next,
+                                          int32_t* src, hipStream_t st) {
+    if (parts <= 0 || num_states <= 0) return hipSuccess;
+    unsigned grid = 0;
+    RSV_HIP_RET(merge_grid(num_states, k, &grid));
+    hipLaunchKernelGGL(k2_indexed_merge, dim3(grid), dim3(256), 0, st, part_idx, part_next, parts, num_states, k,
+                       state_idx, state_next, src);
+    return hipGetLastError();
 }
 
 }  // namespace rsv
