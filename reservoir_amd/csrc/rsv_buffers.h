@@ -5,7 +5,9 @@
 // pointer.  A group of buffers that must all hold n entries has no capacity of its own: it is
 // group_cap(members), the minimum, so a growth that failed half way is simply seen as too small by the
 // next call.  The buffers choose no sizes: the growth policy (grown_capacity and each site's limit) stays
-// with the caller.  Uses nothing of HIP but its types: a host program links it against stub pool functions.
+// with the caller.  Behind the buffers, three types of the sampler handle (rsv_runtime.hip): its host landing
+// zones, its pool events and its work clock.  Uses nothing of HIP but its types: a host program links it
+// against stub pool functions.
 #pragma once
 #include <string.h>
 
@@ -114,6 +116,83 @@ struct MappedBuf {
         T* q = p;
         p = dev = nullptr, cap = 0;
         return q;
+    }
+};
+
+// A host landing zone: entries of host memory a kernel delivers into.  Published form: a coherent, mapped
+// block with a 64-byte flag line behind the entries, into which the kernel stores the generation after
+// them (the host spins on it); pinned form: the target of a D2H copy and a stream synchronize.  The first
+// ensure chooses the form; afterwards the form is which of the two owners holds a block.
+struct Landing {
+    MappedBuf<uint8_t> pub;
+    HostBuf<uint8_t> pin;
+    uint32_t gen = 0;  // the newest generation issued (the flag starts there: nothing published yet)
+
+    bool published() const { return pub.p != nullptr; }
+    void* host() const { return pub.p ? (void*)pub.p : (void*)pin.p; }
+    void* dev() const { return pub.dev; }
+    uint32_t* flag() const { return (uint32_t*)(pub.p + pub.cap - 64); }
+    uint32_t* flag_dev() const { return (uint32_t*)(pub.dev + pub.cap - 64); }
+    uint32_t next_gen() { return ++gen; }
+    hipError_t ensure(size_t bytes, bool may_publish) {
+        if (host()) return hipSuccess;
+        if (!may_publish) return pin.reserve((int64_t)bytes);
+        if (hipError_t e = pub.reserve((int64_t)((bytes + 63) & ~(size_t)63) + 64)) return e;
+        *flag() = gen;
+        return hipSuccess;
+    }
+    void* give() { return pub.detach(); }  // the published block leaves (pool_host_free is the taker's to call)
+};
+
+// A pool event with its device and flags: taken at first use, returned with its owner -- whose queued work
+// has completed by then.
+struct PoolEvent {
+    hipEvent_t e = nullptr;
+    int device = 0;
+    unsigned flags = 0;
+
+    PoolEvent() = default;
+    PoolEvent(PoolEvent&& o) noexcept : e(o.e), device(o.device), flags(o.flags) { o.e = nullptr; }
+    PoolEvent& operator=(PoolEvent&& o) noexcept {
+        if (this != &o) release(), std::swap(e, o.e), device = o.device, flags = o.flags;
+        return *this;
+    }
+    ~PoolEvent() { release(); }
+    operator hipEvent_t() const { return e; }
+    hipError_t ensure(int dev, unsigned fl) {  // on the current device, which is `dev`
+        if (e) return hipSuccess;
+        device = dev, flags = fl;
+        return pool_event(&e, fl);
+    }
+    void release() {
+        if (e) pool_release_event(device, e, flags);
+        e = nullptr;
+    }
+};
+
+// A handle's work clock.  Device work is enqueued on the handle's stream in groups (`ops`); `ops_done` are the
+// groups known complete.  A launch may publish the reservoir into the result's landing zone: pub_ops / pub_gen
+// are that launch's group and generation, and pub_valid says that nothing has changed the slots since.
+struct WorkClock {
+    uint64_t ops = 0, ops_done = 0, pub_ops = 0;
+    uint32_t pub_gen = 0;
+    bool pub_valid = false;
+
+    void group() { ++ops; }             // a new group of device work
+    void drained() { ops_done = ops; }  // a stream synchronize returned: everything enqueued is complete
+    bool idle() const { return ops == ops_done; }
+    // a launch of the current group changed the slots and published them as generation g, or (!did) not at all
+    void published(bool did, uint32_t g) {
+        pub_valid = did;
+        if (did) pub_ops = ops, pub_gen = g;
+    }
+    void invalidate() { pub_valid = false; }  // the slots changed behind the publication
+    bool holds() const { return pub_valid; }  // the publication has the current slots
+    bool current() const { return pub_valid && pub_ops == ops; }  // ... and no group of work came after it
+    // the host has seen generation g of a landing zone whose newest is `newest`, stored as the last memory
+    // operation of group `at`: where that is the last group, everything is complete
+    void seen(uint64_t at, uint32_t g, uint32_t newest) {
+        if (at == ops && g == newest) ops_done = ops;
     }
 };
 

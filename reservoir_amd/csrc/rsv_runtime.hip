@@ -125,6 +125,30 @@ using namespace rsv;
 static_assert(__BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__ && sizeof(bool) == 1, "rsv_sampler::gate reads four bools as a word");
 constexpr uint32_t kGateReady = 1;  // bytes {open = 1, keys_owed = 0, keys_external = 0, cand_pending = 0}
 
+// One pinned staging buffer of per-element calls (rsv_sample, rsv_stage_acquire); a full one is flushed
+// asynchronously (H2D + kernels, no host wait) while the other fills.
+struct alignas(64) Stage {
+    MappedBuf<uint8_t> keys;  // coherent + mapped: a winners-only flush reads them in place through the alias
+    HostBuf<int64_t> hashes;
+    // java_l flushes: the batch's Algorithm-L events in pinned memory (free again with `free`), so their
+    // H2D copies need no host wait
+    HostBuf<int64_t> ev_pos;
+    HostBuf<int32_t> ev_slot;
+    PoolEvent free;        // recorded behind the flush's last read of the buffer
+    bool pending = false;  // a flush is queued: wait for `free` before the buffer fills again
+};
+
+// The ELEMENTS slot block, one raw pool block (kernels take its views by value, and the clean-slot cache
+// outlives handles): batch_win[k] | slot_idx[k] | slot_key[k] | k1_ticket.
+struct Slots {
+    void* block = nullptr;
+    SlotBlock sb{};              // win, slot_idx, slot_key, k, key width
+    uint32_t* ticket = nullptr;  // fused K1 + resolve_publish: zero between launches
+    // device-state knowledge, in stream order: batch_win all zero (resolve leaves it so) / slot arrays
+    // initialised.  Creation enqueues no device work; the first batch initialises.
+    bool win_zero = false, init = false;
+};
+
 struct rsv_sampler {
     rsv_config cfg{};
     int device = 0;
@@ -146,88 +170,54 @@ struct rsv_sampler {
     int64_t count = 0;
     int kw = 8;
     uint32_t k = 0;
-    // ELEMENTS
-    void* slots = nullptr;  // one pooled block: batch_win[k] | slot_idx[k] | slot_key[k] | k1_ticket
-    // device-state knowledge, in stream order: batch_win all zero (resolve leaves it so) / slot
-    // arrays initialised.  Creation enqueues no device work; the first batch initialises.
-    bool win_zero = false;
-    bool slots_init = false;
-    void* slot_key = nullptr;
-    int64_t* slot_idx = nullptr;
-    unsigned long long* batch_win = nullptr;
-    uint32_t* k1_ticket = nullptr;  // fused K1 + resolve_publish: zero between launches
-    AlgoLState algo_l;
-    std::vector<int64_t> ev_pos_h;
-    std::vector<int32_t> ev_slot_h;
-    DevBuf<int64_t> ev_pos_d;
-    DevBuf<int32_t> ev_slot_d;
-    // index-only batches (rsv_sample_indexed): per slot the batch offset of its new element
-    DevBuf<int64_t> idx_offs_d;
-    // rsv_abort_indexed: the slot indices before the pending index-only batch, and its start
-    DevBuf<int64_t> idx_bak_d;
-    bool idx_fresh = false;
-    int64_t idx_base = 0;
-    AlgoLState idx_algo_l;  // JAVA_L: java.util.Random and W before the batch's events
-    // the index-only batch's offsets in host memory: k <= 8192 coherent + mapped, published by the
-    // resolve kernel with flag offs_flag = offs_gen; larger k a pinned D2H target
-    MappedBuf<uint8_t> offs_pub;  // the owner of the published form (offsets + flag line)
-    HostBuf<int64_t> offs_pin;    // the owner of the pinned form
-    int64_t* offs_h = nullptr;    // the offsets in whichever of the two
-    int64_t* offs_dev = nullptr;
-    uint32_t* offs_flag = nullptr;
-    uint32_t* offs_flag_dev = nullptr;
-    uint32_t offs_gen = 0;
-    // the winners' keys in slot order (host gather of a winners-only batch, rsv_fill_slots): pinned,
-    // coherent and mapped, read by the fill kernel across PCIe (no H2D copy, no host wait)
-    MappedBuf<uint8_t> gath_h;
-    // DISTINCT
-    DistinctEngine* distinct = nullptr;
     int hash_kind = kHashIdentity;
+    // host staging of per-element calls: stage[stage_cur] fills, stage_n of stage_cap keys so far
+    int stage_cur = 0;
+    int64_t stage_n = 0;
+    int64_t stage_cap = 0;
+    Stage stage[2];
+    Slots slots;  // ELEMENTS
+    struct {      // java_l: the reference's Algorithm-L state, and a batch's events on the host and the device
+        AlgoLState algo;
+        std::vector<int64_t> pos_h;
+        std::vector<int32_t> slot_h;
+        DevBuf<int64_t> pos_d;
+        DevBuf<int32_t> slot_d;
+    } jl;
+    struct {  // the index-only batch (rsv_sample_indexed) and what rsv_abort_indexed restores
+        DevBuf<int64_t> offs_d;  // per slot the batch offset of its new element
+        DevBuf<int64_t> bak_d;   // the slot indices before the pending batch
+        bool fresh = false;
+        int64_t base = 0;    // the pending batch's start
+        AlgoLState algo;     // JAVA_L: java.util.Random and W before the batch's events
+        // the offsets in host memory: published by the resolve kernel where resolve_indices_publish_ok(k)
+        Landing offs;
+        // the winners' keys in slot order (host gather of a winners-only batch, rsv_fill_slots): read by the
+        // fill kernel across PCIe (no H2D copy, no host wait)
+        MappedBuf<uint8_t> gath;
+    } idx;
+    DistinctEngine* distinct = nullptr;  // DISTINCT
     // distinct for any B (rsv_distinct_candidates): the hash-only candidate pass; the caller keeps the
     // elements (keys_external) and owes a commit or abort while cand_pending
     ObjDistinct* obj = nullptr;
     int64_t cand_batch = 0;  // the pending batch's element count
-    // host staging: per-element calls and host batches
-    // per-element sample(): two pinned staging buffers; a full one is flushed asynchronously
-    // (H2D + kernels, no host wait) while the other fills; an event says when it is free again
-    MappedBuf<uint8_t> stage_h[2];  // (winners-only flushes read them in place through the device alias)
-    HostBuf<int64_t> stage_hash_h[2];
-    hipEvent_t stage_free[2] = {nullptr, nullptr};
-    // java_l staged flushes: the batch's Algorithm-L events in pinned memory owned by the staging
-    // buffer (free again with stage_free[b]), so their H2D copies need no host wait
-    HostBuf<int64_t> stage_ev_pos[2];
-    HostBuf<int32_t> stage_ev_slot[2];
-    bool stage_pending[2] = {false, false};
-    int stage_cur = 0;
-    int64_t stage_n = 0;
-    int64_t stage_cap = 0;
-    DevBuf<uint8_t> chunk_d;     // device chunk for host batches (kChunkKeys keys)
-    DevBuf<int64_t> chunk_hash_d;
-    MappedBuf<uint8_t> result_pub;  // the owner of result_h's published form (keys + flag line)
-    HostBuf<uint8_t> result_pin;    // the owner of its pinned form
-    void* result_h = nullptr;  // pinned staging for result() (k keys) in whichever of the two
-    // small reservoirs: result_h is coherent + mapped and publish_kernel writes it directly,
-    // followed by result_gen in result_flag (same allocation); the host spins on the flag
-    bool result_publish = false;
-    void* result_dev = nullptr;  // device alias of result_h
-    uint32_t* result_flag = nullptr;
-    uint32_t* result_flag_dev = nullptr;
-    uint32_t result_gen = 0;
-    // small reservoirs: every batch's resolve also publishes the reservoir (resolve_publish
-    // kernel), so result() only waits for generation pub_gen -- while pub_valid says no other
-    // kernel (merge, init) has changed the slots since
-    uint32_t pub_gen = 0;
-    bool pub_valid = false;
+    struct {                 // the device chunk of host batches and copied flushes (kChunkKeys keys)
+        DevBuf<uint8_t> keys;
+        DevBuf<int64_t> hashes;
+    } chunk;
+    // result(): k keys; up to kPublishMaxBytes published -- by publish_kernel, or by a batch's own resolve
+    // (small reservoirs), so that result() only waits for generation clock.pub_gen while clock.holds()
+    Landing result;
+    WorkClock clock;
     KernelTimer timer;
-    hipEvent_t handover = nullptr;  // rsv_set_stream's event (kept until destroy: see there)
+    PoolEvent handover;  // rsv_set_stream's event (kept until destroy: see there)
     // rsv_set_resolve_stream: each batch's resolve + publication on this caller stream, forked from
-    // `stream` after K1 (side_fork) and joined back (side_join) before the handle's next device work
-    hipStream_t rstream = nullptr;
-    hipEvent_t side_fork = nullptr, side_join = nullptr;
-    bool side_pending = false;
-    // device work enqueued on `stream` by this handle, in groups, vs the groups known complete
-    // (a stream synchronize, or the host flag of a publication that was the last group)
-    uint64_t ops = 0, ops_done = 0, pub_ops = 0;
+    // `stream` after K1 (fork) and joined back (join) before the handle's next device work
+    struct {
+        hipStream_t rstream = nullptr;
+        PoolEvent fork, join;
+        bool pending = false;
+    } side;
 };
 
 namespace {
@@ -240,21 +230,21 @@ KernelTimer& global_timer() {
     return *t;
 }
 
-// a new group of device work on the handle's stream / everything enqueued so far is complete
 // the forked resolve (rsv_set_resolve_stream) ordered before the handle's next work on its stream
 inline void join_side(rsv_sampler* s) {
-    if (!s->side_pending) return;
-    (void)hipStreamWaitEvent(s->stream, s->side_join, 0);
-    s->side_pending = false;
+    if (!s->side.pending) return;
+    (void)hipStreamWaitEvent(s->stream, s->side.join, 0);
+    s->side.pending = false;
 }
+// a new group of device work on the handle's stream / everything enqueued so far is complete
 inline void touch(rsv_sampler* s) {
     join_side(s);
-    ++s->ops;
+    s->clock.group();
 }
 inline hipError_t sync_stream(rsv_sampler* s) {
     join_side(s);
     hipError_t e = hipStreamSynchronize(s->stream);
-    if (e == hipSuccess) s->ops_done = s->ops;
+    if (e == hipSuccess) s->clock.drained();
     return e;
 }
 
@@ -337,26 +327,24 @@ rsv_status check_keyed(const rsv_sampler* s) {
 }
 
 rsv_status ensure_events(rsv_sampler* s, int64_t n) {
-    const int64_t cur = group_cap(s->ev_pos_d, s->ev_slot_d);
+    const int64_t cur = group_cap(s->jl.pos_d, s->jl.slot_d);
     if (n <= cur) return RSV_OK;
-    if (s->ev_pos_d || s->ev_slot_d) RSV_HIP_TRY(sync_stream(s));  // before reuse elsewhere
-    s->ev_pos_d.release(), s->ev_slot_d.release();
-    RSV_HIP_TRY(reserve_all(std::max<int64_t>(n, 2 * cur), s->stream, s->ev_pos_d, s->ev_slot_d));
+    if (s->jl.pos_d || s->jl.slot_d) RSV_HIP_TRY(sync_stream(s));  // before reuse elsewhere
+    s->jl.pos_d.release(), s->jl.slot_d.release();
+    RSV_HIP_TRY(reserve_all(std::max<int64_t>(n, 2 * cur), s->stream, s->jl.pos_d, s->jl.slot_d));
     return RSV_OK;
 }
 
-inline SlotBlock slot_block(const rsv_sampler* s) {
-    return SlotBlock{s->batch_win, s->slot_idx, s->slot_key, s->k, s->kw};
-}
+inline const SlotBlock& slot_block(const rsv_sampler* s) { return s->slots.sb; }
 
 // slot arrays of a fresh handle: slot_key = 0, slot_idx = -1 (empty), batch_win = 0, on the
 // handle's current stream before its first use (creation itself enqueues no device work)
 rsv_status ensure_slots(rsv_sampler* s) {
-    if (s->slots_init || s->cfg.kind != RSV_KIND_ELEMENTS) return RSV_OK;
+    if (s->slots.init || s->cfg.kind != RSV_KIND_ELEMENTS) return RSV_OK;
     touch(s);
-    RSV_HIP_TRY(launch_init_slots(slot_block(s), s->stream, s->k1_ticket));
-    s->slots_init = s->win_zero = true;
-    s->pub_valid = false;
+    RSV_HIP_TRY(launch_init_slots(slot_block(s), s->stream, s->slots.ticket));
+    s->slots.init = s->slots.win_zero = true;
+    s->clock.invalidate();
     return RSV_OK;
 }
 
@@ -396,34 +384,33 @@ bool give_clean_slots(void* p, uint32_t k, int kw, int device) {
     return true;
 }
 
-constexpr int64_t kPublishMaxBytes = 1 << 20;
-
-// A publication target: `bytes` of coherent, mapped host memory and one 64-byte flag line behind it,
-// with their device aliases; the flag starts at the generation `gen` (nothing published yet).
-rsv_status alloc_flagged(size_t bytes, uint32_t gen, MappedBuf<uint8_t>& blk, void** host, void** dev, uint32_t** flag,
-                         uint32_t** flag_dev) {
-    const size_t flag_off = (bytes + 63) & ~(size_t)63;
-    RSV_HIP_TRY(blk.reserve((int64_t)flag_off + 64));
-    *host = blk.p;
-    *dev = blk.dev;
-    *flag = (uint32_t*)(blk.p + flag_off);
-    *flag_dev = (uint32_t*)(blk.dev + flag_off);
-    **flag = gen;
-    return RSV_OK;
+// a handle's slot block and its views: a clean one of the same shape (batch_win known zero), else a new one
+hipError_t acquire_slots(Slots& sl, uint32_t k32, int kw, int device) {
+    const size_t k = k32, keys = (k * kw + 7) & ~(size_t)7;
+    sl.block = take_clean_slots(k32, kw, device);
+    sl.win_zero = sl.block != nullptr;
+    if (!sl.block)
+        if (hipError_t e = pool_device_alloc(&sl.block, k * 16 + keys + 8)) return e;
+    uint8_t* b = (uint8_t*)sl.block;
+    sl.sb = SlotBlock{(unsigned long long*)b, (int64_t*)(b + k * 8), b + k * 16, k32, kw};
+    sl.ticket = (uint32_t*)(b + k * 16 + keys);
+    return hipSuccess;
 }
 
+// the block back to the clean-slot cache when batch_win is known zero, else to the pool; the caller has
+// synchronized the stream
+void recycle_slots(Slots& sl, int device) {
+    if (!(sl.block && sl.win_zero && give_clean_slots(sl.block, sl.sb.k, sl.sb.key_width, device)))
+        pool_device_free(sl.block);
+    sl = Slots{};
+}
+
+constexpr int64_t kPublishMaxBytes = 1 << 20;
+
+// the result's landing zone: published up to kPublishMaxBytes
 rsv_status ensure_result_buffer(rsv_sampler* s) {
-    if (s->result_h) return RSV_OK;
     const size_t bytes = (size_t)s->k * s->kw;
-    if ((int64_t)bytes <= kPublishMaxBytes) {
-        if (rsv_status st = alloc_flagged(bytes, s->result_gen, s->result_pub, &s->result_h, &s->result_dev,
-                                          &s->result_flag, &s->result_flag_dev))
-            return st;
-        s->result_publish = true;
-    } else {
-        RSV_HIP_TRY(s->result_pin.reserve((int64_t)bytes));
-        s->result_h = s->result_pin.p;
-    }
+    RSV_HIP_TRY(s->result.ensure(bytes, (int64_t)bytes <= kPublishMaxBytes));
     return RSV_OK;
 }
 
@@ -435,17 +422,13 @@ rsv_status begin_publish(rsv_sampler* s, bool allowed, int64_t count, Publicatio
     *pub = Publication{};
     if (!allowed) return RSV_OK;
     if (rsv_status st = ensure_result_buffer(s)) return st;
-    if (s->result_publish)
-        *pub = Publication{std::min<int64_t>(count, (int64_t)s->k), s->result_dev, s->result_flag_dev, ++s->result_gen};
+    Landing& r = s->result;
+    if (r.published()) *pub = Publication{std::min<int64_t>(count, (int64_t)s->k), r.dev(), r.flag_dev(), r.next_gen()};
     return RSV_OK;
 }
 
-void record_publish(rsv_sampler* s, const Publication& pub) {
-    s->pub_valid = pub.dst != nullptr;
-    if (!pub.dst) return;
-    s->pub_ops = s->ops;  // the last work of this group
-    s->pub_gen = pub.gen;
-}
+// (the publication is the last work of the current group)
+void record_publish(rsv_sampler* s, const Publication& pub) { s->clock.published(pub.dst != nullptr, pub.gen); }
 
 constexpr uint32_t kFusedPublishMaxK = 8192;  // resolve_publish: one workgroup, <= 8 slots per lane
 
@@ -461,7 +444,7 @@ bool resolve_small() {
 
 // The batch's resolve: fill phase + winners into the slots; for reservoirs of <= 8192 keys it
 // also writes the first min(count, k) keys into the coherent result buffer and publishes
-// generation ++result_gen there (one dispatch instead of resolve now + publish at result()).
+// generation result.next_gen() there (one dispatch instead of resolve now + publish at result()).
 rsv_status resolve_batch(rsv_sampler* s, const void* keys, int64_t base, int64_t n, bool fresh,
                          hipStream_t rst = nullptr) {
     if (!rst) rst = s->stream;
@@ -479,56 +462,55 @@ rsv_status resolve_batch(rsv_sampler* s, const void* keys, int64_t base, int64_t
 // zero until the batch's resolve is enqueued, which is where end stands.
 rsv_status begin_element_batch(rsv_sampler* s, bool* fresh) {
     touch(s);
-    if (!s->win_zero) {  // never-used block: full init
-        RSV_HIP_TRY(launch_init_slots(slot_block(s), s->stream, s->k1_ticket));
-        s->slots_init = s->win_zero = true;
+    if (!s->slots.win_zero) {  // never-used block: full init
+        RSV_HIP_TRY(launch_init_slots(slot_block(s), s->stream, s->slots.ticket));
+        s->slots.init = s->slots.win_zero = true;
     }
-    *fresh = !s->slots_init;
-    s->win_zero = false;
+    *fresh = !s->slots.init;
+    s->slots.win_zero = false;
     return RSV_OK;
 }
 
 void end_element_batch(rsv_sampler* s, int64_t n) {
-    s->slots_init = s->win_zero = true;
+    s->slots.init = s->slots.win_zero = true;
     s->count += n;
 }
 
 // java_l: the reference's own Algorithm-L events of the batch [base, base + n) (S:261-273 skips by
-// them), computed on the host, uploaded and replayed into batch_win; *n_events of them.  stage_b >= 0:
-// the batch is staging buffer stage_b, and the uploads read that buffer's pinned event buffers -- its
-// previous flush has completed (stage_slow waited for it), and its stage_free event releases them.
-// Else they read the handle's pageable event vectors, which the next batch reuses.
-rsv_status replay_java_l(rsv_sampler* s, int64_t base, int64_t n, int stage_b, int64_t* n_events) {
-    s->ev_pos_h.clear();
-    s->ev_slot_h.clear();
-    s->algo_l.events(base, n, s->ev_pos_h, s->ev_slot_h);
-    const int64_t ne = *n_events = (int64_t)s->ev_pos_h.size();
+// them), computed on the host, uploaded and replayed into batch_win; *n_events of them.  stage: the batch
+// is that staging buffer, and the uploads read its pinned event buffers -- its previous flush has
+// completed (stage_slow waited for it), and its `free` event releases them.  Null: they read the handle's
+// pageable event vectors, which the next batch reuses.
+rsv_status replay_java_l(rsv_sampler* s, int64_t base, int64_t n, Stage* stage, int64_t* n_events) {
+    auto& jl = s->jl;
+    jl.pos_h.clear();
+    jl.slot_h.clear();
+    jl.algo.events(base, n, jl.pos_h, jl.slot_h);
+    const int64_t ne = *n_events = (int64_t)jl.pos_h.size();
     if (!ne) return RSV_OK;
     if (rsv_status st = ensure_events(s, ne)) return st;
-    const void* pos_src = s->ev_pos_h.data();
-    const void* slot_src = s->ev_slot_h.data();
-    if (stage_b >= 0) {
-        const int64_t cur = group_cap(s->stage_ev_pos[stage_b], s->stage_ev_slot[stage_b]);
-        if (cur < ne)
-            RSV_HIP_TRY(reserve_all(std::max<int64_t>(ne, 2 * cur), nullptr, s->stage_ev_pos[stage_b],
-                                    s->stage_ev_slot[stage_b]));
-        memcpy(s->stage_ev_pos[stage_b], pos_src, ne * 8);
-        memcpy(s->stage_ev_slot[stage_b], slot_src, ne * 4);
-        pos_src = s->stage_ev_pos[stage_b];
-        slot_src = s->stage_ev_slot[stage_b];
+    const void* pos_src = jl.pos_h.data();
+    const void* slot_src = jl.slot_h.data();
+    if (stage) {
+        const int64_t cur = group_cap(stage->ev_pos, stage->ev_slot);
+        if (cur < ne) RSV_HIP_TRY(reserve_all(std::max<int64_t>(ne, 2 * cur), nullptr, stage->ev_pos, stage->ev_slot));
+        memcpy(stage->ev_pos, pos_src, ne * 8);
+        memcpy(stage->ev_slot, slot_src, ne * 4);
+        pos_src = stage->ev_pos;
+        slot_src = stage->ev_slot;
     }
-    RSV_HIP_TRY(hipMemcpyAsync(s->ev_pos_d, pos_src, ne * 8, hipMemcpyHostToDevice, s->stream));
-    RSV_HIP_TRY(hipMemcpyAsync(s->ev_slot_d, slot_src, ne * 4, hipMemcpyHostToDevice, s->stream));
+    RSV_HIP_TRY(hipMemcpyAsync(jl.pos_d, pos_src, ne * 8, hipMemcpyHostToDevice, s->stream));
+    RSV_HIP_TRY(hipMemcpyAsync(jl.slot_d, slot_src, ne * 4, hipMemcpyHostToDevice, s->stream));
     const bool pm = prof_begin(s, s->stream);
-    RSV_HIP_TRY(launch_replay_events(s->ev_pos_d, s->ev_slot_d, ne, s->k, s->batch_win, s->stream));
+    RSV_HIP_TRY(launch_replay_events(jl.pos_d, jl.slot_d, ne, s->k, s->slots.sb.win, s->stream));
     prof_end(s, s->stream, pm);
     return RSV_OK;
 }
 
-// one batch of n keys already in device memory, at global indices [count, count+n); stage_b >= 0:
-// the batch is staging buffer stage_b, whose pinned event buffers carry java_l's events
+// one batch of n keys already in device memory, at global indices [count, count+n); stage: the batch
+// is that staging buffer, whose pinned event buffers carry java_l's events
 rsv_status process_device_batch(rsv_sampler* s, const void* keys, const int64_t* hashes, int64_t n,
-                                int stage_b = -1) {
+                                Stage* stage = nullptr) {
     if (n <= 0) return RSV_OK;
     if (s->cfg.kind == RSV_KIND_DISTINCT) {
         touch(s);
@@ -538,17 +520,14 @@ rsv_status process_device_batch(rsv_sampler* s, const void* keys, const int64_t*
         // consumers) keep the result buffer lazy
         if ((int64_t)s->k * s->kw <= kPublishMaxBytes && n >= s->distinct->spec_min()) {
             if (rsv_status st = ensure_result_buffer(s)) return st;
-            if (s->result_publish) s->distinct->spec_target(s->result_dev, s->result_flag_dev, &s->result_gen);
+            Landing& r = s->result;
+            if (r.published()) s->distinct->spec_target(r.dev(), r.flag_dev(), &r.gen);
         }
         int rc = s->distinct->sample_device(keys, hashes, n, s->stream);
         uint32_t gen = 0;
         const bool published = s->distinct->spec_take(&gen);
         if (rc != RSV_OK) return (rsv_status)rc;
-        s->pub_valid = published;  // result() waits for it instead of publishing
-        if (published) {
-            s->pub_ops = s->ops;
-            s->pub_gen = gen;
-        }
+        s->clock.published(published, gen);  // result() waits for it instead of publishing
         s->count += n;
         return RSV_OK;
     }
@@ -557,11 +536,11 @@ rsv_status process_device_batch(rsv_sampler* s, const void* keys, const int64_t*
     if (rsv_status st = begin_element_batch(s, &fresh)) return st;
     if (s->cfg.engine == RSV_ENGINE_JAVA_L) {
         int64_t ne = 0;
-        if (rsv_status st = replay_java_l(s, base, n, stage_b, &ne)) return st;
+        if (rsv_status st = replay_java_l(s, base, n, stage, &ne)) return st;
         if (rsv_status st = resolve_batch(s, keys, base, n, fresh)) return st;
         // pageable host event vectors are reused by the next batch (a staged batch's pinned copies
-        // are released by its stage_free event instead)
-        if (ne && stage_b < 0) RSV_HIP_TRY(sync_stream(s));
+        // are released by its `free` event instead)
+        if (ne && !stage) RSV_HIP_TRY(sync_stream(s));
     } else {
         const DrawParams dp{s->cfg.seed, s->cfg.stream_id};
         const uint64_t lo = std::max<uint64_t>((uint64_t)base, s->k), hi = (uint64_t)(base + n);
@@ -584,22 +563,22 @@ rsv_status process_device_batch(rsv_sampler* s, const void* keys, const int64_t*
         if (pub.dst) {
             // one dispatch: K1, then the last workgroup resolves and publishes (resolve_batch's form)
             const bool pm = prof_begin(s, s->stream);
-            RSV_HIP_TRY(launch_k1_resolve_publish(dp, lo, hi, slot_block(s), s->k1_ticket, Batch{keys, base, n, fresh},
+            RSV_HIP_TRY(launch_k1_resolve_publish(dp, lo, hi, slot_block(s), s->slots.ticket, Batch{keys, base, n, fresh},
                                                   pub, s->stream));
             prof_end(s, s->stream, pm);
             record_publish(s, pub);
         } else {
             const bool pm = prof_begin(s, s->stream);
-            RSV_HIP_TRY(launch_k1_last_writer(dp, s->k, lo, hi, s->batch_win, s->stream));
+            RSV_HIP_TRY(launch_k1_last_writer(dp, s->k, lo, hi, s->slots.sb.win, s->stream));
             prof_end(s, s->stream, pm);
-            if (s->rstream) {  // the resolve + publication forked onto the resolve stream (see there)
-                if (!s->side_fork) RSV_HIP_TRY(pool_event(&s->side_fork, hipEventDisableTiming));
-                if (!s->side_join) RSV_HIP_TRY(pool_event(&s->side_join, hipEventDisableTiming));
-                RSV_HIP_TRY(hipEventRecord(s->side_fork, s->stream));
-                RSV_HIP_TRY(hipStreamWaitEvent(s->rstream, s->side_fork, 0));
-                if (rsv_status st = resolve_batch(s, keys, base, n, fresh, s->rstream)) return st;
-                RSV_HIP_TRY(hipEventRecord(s->side_join, s->rstream));
-                s->side_pending = true;
+            if (auto& sd = s->side; sd.rstream) {  // the resolve + publication forked onto the resolve stream (see there)
+                RSV_HIP_TRY(sd.fork.ensure(s->device, hipEventDisableTiming));
+                RSV_HIP_TRY(sd.join.ensure(s->device, hipEventDisableTiming));
+                RSV_HIP_TRY(hipEventRecord(sd.fork, s->stream));
+                RSV_HIP_TRY(hipStreamWaitEvent(sd.rstream, sd.fork, 0));
+                if (rsv_status st = resolve_batch(s, keys, base, n, fresh, sd.rstream)) return st;
+                RSV_HIP_TRY(hipEventRecord(sd.join, sd.rstream));
+                sd.pending = true;
             } else if (rsv_status st = resolve_batch(s, keys, base, n, fresh)) {
                 return st;
             }
@@ -610,9 +589,9 @@ rsv_status process_device_batch(rsv_sampler* s, const void* keys, const int64_t*
 }
 
 rsv_status ensure_chunk(rsv_sampler* s) {
-    RSV_HIP_TRY(s->chunk_d.reserve(kChunkKeys * s->kw, s->stream));
+    RSV_HIP_TRY(s->chunk.keys.reserve(kChunkKeys * s->kw, s->stream));
     if (s->cfg.kind == RSV_KIND_DISTINCT && s->hash_kind == kHashPrecomputed)
-        RSV_HIP_TRY(s->chunk_hash_d.reserve(kChunkKeys, s->stream));
+        RSV_HIP_TRY(s->chunk.hashes.reserve(kChunkKeys, s->stream));
     return RSV_OK;
 }
 
@@ -639,61 +618,52 @@ rsv_status spin_flag(rsv_sampler* s, const uint32_t* flag, uint32_t gen, const c
 // valid until the handle's next index-only batch).  No key is read.  The caller then supplies the
 // winners' keys (fill_gathered) or undoes the batch (rsv_abort_indexed).
 rsv_status index_batch(rsv_sampler* s, int64_t n, const int64_t** offs_out) {
-    RSV_HIP_TRY(reserve_all(s->k, s->stream, s->idx_offs_d, s->idx_bak_d));
-    const bool publish = resolve_indices_publish_ok(s->k);
-    if (!s->offs_h) {
-        if (publish) {
-            if (rsv_status st = alloc_flagged((size_t)s->k * 8, s->offs_gen, s->offs_pub, (void**)&s->offs_h,
-                                              (void**)&s->offs_dev, &s->offs_flag, &s->offs_flag_dev))
-                return st;
-        } else {
-            RSV_HIP_TRY(s->offs_pin.reserve(s->k));
-            s->offs_h = s->offs_pin.p;
-        }
-    }
+    auto& ix = s->idx;
+    RSV_HIP_TRY(reserve_all(s->k, s->stream, ix.offs_d, ix.bak_d));
+    RSV_HIP_TRY(ix.offs.ensure((size_t)s->k * 8, resolve_indices_publish_ok(s->k)));
     const int64_t base = s->count;
     bool fresh;
     if (rsv_status st = begin_element_batch(s, &fresh)) return st;
     // the state rsv_abort_indexed restores (a throwing `map` leaves the slots consistent)
-    s->idx_fresh = fresh;
-    s->idx_base = base;
-    s->idx_algo_l = s->algo_l;
+    ix.fresh = fresh;
+    ix.base = base;
+    ix.algo = s->jl.algo;
     if (!fresh)
-        RSV_HIP_TRY(hipMemcpyAsync(s->idx_bak_d, s->slot_idx, (size_t)s->k * 8, hipMemcpyDeviceToDevice, s->stream));
+        RSV_HIP_TRY(hipMemcpyAsync(ix.bak_d, s->slots.sb.slot_idx, (size_t)s->k * 8, hipMemcpyDeviceToDevice, s->stream));
     if (s->cfg.engine == RSV_ENGINE_JAVA_L) {
         int64_t ne = 0;  // the event vectors are read by copies that precede the waits below in stream order
-        if (rsv_status st = replay_java_l(s, base, n, -1, &ne)) return st;
+        if (rsv_status st = replay_java_l(s, base, n, nullptr, &ne)) return st;
     } else {
         const DrawParams dp{s->cfg.seed, s->cfg.stream_id};
         const uint64_t lo = std::max<uint64_t>((uint64_t)base, s->k), hi = (uint64_t)(base + n);
         const bool pm = prof_begin(s, s->stream);
-        RSV_HIP_TRY(launch_k1_last_writer(dp, s->k, lo, hi, s->batch_win, s->stream));
+        RSV_HIP_TRY(launch_k1_last_writer(dp, s->k, lo, hi, s->slots.sb.win, s->stream));
         prof_end(s, s->stream, pm);
     }
     const Batch batch{nullptr, base, n, fresh};
-    if (publish) {  // the offsets straight into coherent host memory + flag: no copy, no stream sync
-        const uint32_t gen = ++s->offs_gen;
-        RSV_HIP_TRY(launch_resolve_indices(slot_block(s), batch, s->idx_offs_d,
-                                           Publication{0, s->offs_dev, s->offs_flag_dev, gen}, s->stream));
-        if (rsv_status st = spin_flag(s, s->offs_flag, gen, "index batch")) return st;
-        if (s->offs_gen == gen) s->ops_done = s->ops;  // the publication was this handle's last work
+    if (ix.offs.published()) {  // the offsets straight into coherent host memory + flag: no copy, no stream sync
+        const uint32_t gen = ix.offs.next_gen();
+        RSV_HIP_TRY(launch_resolve_indices(slot_block(s), batch, ix.offs_d,
+                                           Publication{0, ix.offs.dev(), ix.offs.flag_dev(), gen}, s->stream));
+        if (rsv_status st = spin_flag(s, ix.offs.flag(), gen, "index batch")) return st;
+        s->clock.seen(s->clock.ops, gen, ix.offs.gen);  // the publication was this handle's last work
     } else {
-        RSV_HIP_TRY(launch_resolve_indices(slot_block(s), batch, s->idx_offs_d, Publication{}, s->stream));
-        RSV_HIP_TRY(hipMemcpyAsync(s->offs_h, s->idx_offs_d, (size_t)s->k * 8, hipMemcpyDeviceToHost, s->stream));
+        RSV_HIP_TRY(launch_resolve_indices(slot_block(s), batch, ix.offs_d, Publication{}, s->stream));
+        RSV_HIP_TRY(hipMemcpyAsync(ix.offs.host(), ix.offs_d, (size_t)s->k * 8, hipMemcpyDeviceToHost, s->stream));
         RSV_HIP_TRY(sync_stream(s));
     }
     end_element_batch(s, n);
-    s->pub_valid = false;
-    *offs_out = s->offs_h;
+    s->clock.invalidate();
+    *offs_out = (const int64_t*)ix.offs.host();
     return RSV_OK;
 }
 
 rsv_status ensure_gather(rsv_sampler* s) {
-    RSV_HIP_TRY(s->gath_h.reserve((int64_t)s->k * s->kw));
+    RSV_HIP_TRY(s->idx.gath.reserve((int64_t)s->k * s->kw));
     return RSV_OK;
 }
 
-// The winners' keys, gathered by the host into gath_h (slot order; only the slots index_batch
+// The winners' keys, gathered by the host into idx.gath (slot order; only the slots index_batch
 // changed are read), into the reservoir: one kernel reading them across PCIe, which for small
 // reservoirs also publishes the result -- enqueued, no host wait.  The gather buffer is rewritten
 // only after the handle's next index_batch has waited for its own publication, which follows this
@@ -702,7 +672,7 @@ rsv_status fill_gathered(rsv_sampler* s) {
     touch(s);
     Publication pub;
     if (rsv_status st = begin_publish(s, fill_slots_publish_ok(s->k, s->kw), s->count, &pub)) return st;
-    RSV_HIP_TRY(launch_fill_slots(s->idx_offs_d, s->gath_h.dev, slot_block(s), pub, s->stream));
+    RSV_HIP_TRY(launch_fill_slots(s->idx.offs_d, s->idx.gath.dev, slot_block(s), pub, s->stream));
     record_publish(s, pub);
     s->keys_owed = false;
     return RSV_OK;
@@ -716,13 +686,14 @@ rsv_status host_batch_elements(rsv_sampler* s, const void* keys, int64_t n) {
     if (rsv_status st = index_batch(s, n, &offs)) return st;
     if (rsv_status st = ensure_gather(s)) return st;
     const uint8_t* src = (const uint8_t*)keys;
+    uint8_t* gath = s->idx.gath;
     const size_t kw = (size_t)s->kw;
     if (kw == 8) {
         for (uint32_t j = 0; j < s->k; ++j)
-            if (offs[j] >= 0) memcpy(s->gath_h + (size_t)j * 8, src + (size_t)offs[j] * 8, 8);
+            if (offs[j] >= 0) memcpy(gath + (size_t)j * 8, src + (size_t)offs[j] * 8, 8);
     } else {
         for (uint32_t j = 0; j < s->k; ++j)
-            if (offs[j] >= 0) memcpy(s->gath_h + (size_t)j * kw, src + (size_t)offs[j] * kw, kw);
+            if (offs[j] >= 0) memcpy(gath + (size_t)j * kw, src + (size_t)offs[j] * kw, kw);
     }
     return fill_gathered(s);
 }
@@ -734,11 +705,11 @@ rsv_status process_host_batch(rsv_sampler* s, const void* keys, const int64_t* h
     join_side(s);  // (a forked resolve reads its batch's keys; none for DISTINCT, kept for symmetry)
     for (int64_t off = 0; off < n; off += (int64_t)kChunkKeys) {
         const int64_t c = std::min((int64_t)kChunkKeys, n - off);
-        RSV_HIP_TRY(hipMemcpyAsync(s->chunk_d, (const uint8_t*)keys + off * s->kw, c * s->kw,
+        RSV_HIP_TRY(hipMemcpyAsync(s->chunk.keys, (const uint8_t*)keys + off * s->kw, c * s->kw,
                                    hipMemcpyHostToDevice, s->stream));
-        if (s->chunk_hash_d && hashes)
-            RSV_HIP_TRY(hipMemcpyAsync(s->chunk_hash_d, hashes + off, c * 8, hipMemcpyHostToDevice, s->stream));
-        if (rsv_status st = process_device_batch(s, s->chunk_d, s->chunk_hash_d, c)) return st;
+        if (s->chunk.hashes && hashes)
+            RSV_HIP_TRY(hipMemcpyAsync(s->chunk.hashes, hashes + off, c * 8, hipMemcpyHostToDevice, s->stream));
+        if (rsv_status st = process_device_batch(s, s->chunk.keys, s->chunk.hashes, c)) return st;
     }
     // the caller may reuse its buffer after return (ownership stays with the caller)
     RSV_HIP_TRY(sync_stream(s));
@@ -774,43 +745,37 @@ bool stage_in_place(const rsv_sampler* s, int64_t n) {
 rsv_status flush_stage(rsv_sampler* s) {
     if (s->stage_n == 0) return RSV_OK;
     const int64_t n = s->stage_n;
-    const int b = s->stage_cur;
+    Stage& sg = s->stage[s->stage_cur];
     s->stage_n = 0;
     if (stage_in_place(s, n)) {
-        s->stage_pending[b] = true;
-        s->stage_cur = b ^ 1;
-        if (rsv_status st = process_device_batch(s, s->stage_h[b].dev, nullptr, n, b)) return st;
+        sg.pending = true;
+        s->stage_cur ^= 1;
+        if (rsv_status st = process_device_batch(s, sg.keys.dev, nullptr, n, &sg)) return st;
         // the buffer is free once the resolve that reads it has run (on the resolve stream if forked)
-        RSV_HIP_TRY(hipEventRecord(s->stage_free[b], s->side_pending ? s->rstream : s->stream));
+        RSV_HIP_TRY(hipEventRecord(sg.free, s->side.pending ? s->side.rstream : s->stream));
         return RSV_OK;
     }
     if (rsv_status st = ensure_chunk(s)) return st;
     join_side(s);  // a forked resolve may still read the chunk's previous batch
-    RSV_HIP_TRY(hipMemcpyAsync(s->chunk_d, s->stage_h[b], n * s->kw, hipMemcpyHostToDevice, s->stream));
-    if (s->chunk_hash_d && s->stage_hash_h[b])
-        RSV_HIP_TRY(hipMemcpyAsync(s->chunk_hash_d, s->stage_hash_h[b], n * 8, hipMemcpyHostToDevice, s->stream));
-    s->stage_pending[b] = true;
-    s->stage_cur = b ^ 1;
+    RSV_HIP_TRY(hipMemcpyAsync(s->chunk.keys, sg.keys, n * s->kw, hipMemcpyHostToDevice, s->stream));
+    if (s->chunk.hashes && sg.hashes)
+        RSV_HIP_TRY(hipMemcpyAsync(s->chunk.hashes, sg.hashes, n * 8, hipMemcpyHostToDevice, s->stream));
+    sg.pending = true;
+    s->stage_cur ^= 1;
     if (s->cfg.kind == RSV_KIND_ELEMENTS && s->cfg.engine == RSV_ENGINE_JAVA_L) {
-        // the batch's events travel from stage b's pinned event buffers: free after their copies
-        if (rsv_status st = process_device_batch(s, s->chunk_d, nullptr, n, b)) return st;
-        RSV_HIP_TRY(hipEventRecord(s->stage_free[b], s->stream));
+        // the batch's events travel from the stage's pinned event buffers: free after their copies
+        if (rsv_status st = process_device_batch(s, s->chunk.keys, nullptr, n, &sg)) return st;
+        RSV_HIP_TRY(hipEventRecord(sg.free, s->stream));
         return RSV_OK;
     }
-    RSV_HIP_TRY(hipEventRecord(s->stage_free[b], s->stream));
-    return process_device_batch(s, s->chunk_d, s->chunk_hash_d, n);
+    RSV_HIP_TRY(hipEventRecord(sg.free, s->stream));
+    return process_device_batch(s, s->chunk.keys, s->chunk.hashes, n);
 }
 
+// what the handle's members do not own (they go back with the handle itself); callers have synchronized
+// the stream, or seen the handle's last publication: nothing queued touches any of it any more
 void free_all(rsv_sampler* s) {
-    // callers have synchronized the stream: nothing queued touches these any more
-    if (s->slots && s->win_zero && give_clean_slots(s->slots, s->k, s->kw, s->device)) s->slots = nullptr;
-    pool_device_free(s->slots);  // (every other block is owned by a buffer and goes back with the handle)
-    for (hipEvent_t e : s->stage_free) pool_release_event(s->device, e, hipEventDisableTiming);
-    // the handover record has completed: the stream waiting on it was synchronized, or its
-    // publication seen, before this
-    if (s->handover) pool_release_event(s->device, s->handover, hipEventDisableTiming);
-    if (s->side_fork) pool_release_event(s->device, s->side_fork, hipEventDisableTiming);
-    if (s->side_join) pool_release_event(s->device, s->side_join, hipEventDisableTiming);
+    recycle_slots(s->slots, s->device);
     delete s->distinct;
     if (s->obj) obj_destroy(s->obj);
     if (s->stream && s->own_stream) pool_release_stream(s->device, s->stream);
@@ -907,22 +872,11 @@ rsv_status rsv_create(const rsv_config* cfg, rsv_sampler** out) {
     if (e != hipSuccess) return bail(RSV_E_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(e));
     s->own_stream = true;
     if (cfg->kind == RSV_KIND_ELEMENTS) {
-        const size_t k = s->k;
-        s->slots = take_clean_slots(s->k, s->kw, dev);
-        if (s->slots)
-            s->win_zero = true;
-        else
-            e = pool_device_alloc(&s->slots, k * 16 + ((k * s->kw + 7) & ~(size_t)7) + 8);
-        if (e == hipSuccess) {
-            s->batch_win = (unsigned long long*)s->slots;
-            s->slot_idx = (int64_t*)((uint8_t*)s->slots + k * 8);
-            s->slot_key = (uint8_t*)s->slots + k * 16;
-            s->k1_ticket = (uint32_t*)((uint8_t*)s->slots + k * 16 + ((k * s->kw + 7) & ~(size_t)7));
-        }
+        e = acquire_slots(s->slots, s->k, s->kw, dev);
         if (e != hipSuccess)
             return bail(e == hipErrorOutOfMemory ? RSV_E_OUT_OF_MEMORY : RSV_E_DEVICE,
                         std::string("allocating reservoir: ") + hipGetErrorString(e));
-        if (cfg->engine == RSV_ENGINE_JAVA_L) s->algo_l.init((int32_t)s->k, (int64_t)cfg->seed);
+        if (cfg->engine == RSV_ENGINE_JAVA_L) s->jl.algo.init((int32_t)s->k, (int64_t)cfg->seed);
     } else {
         // RandomValues r0, r1 (Sampler.scala:385-388) from java.util.Random(seed)
         JavaRandom r;
@@ -954,16 +908,16 @@ void rsv_destroy(rsv_sampler* s) {
     // the buffers go back to the pool: nothing this handle enqueued may still touch them.  On a
     // caller stream whose last group of work was a publication the host has seen, that holds
     // already (the flag store is the last memory operation of that group).
-    if (s->stream && (s->own_stream || s->ops != s->ops_done)) {
+    if (s->stream && (s->own_stream || !s->clock.idle())) {
         join_side(s);
         (void)hipStreamSynchronize(s->stream);
-    } else if (s->side_pending && s->rstream) {
+    } else if (s->side.pending && s->side.rstream) {
         // the publication was seen (its flag store is the resolve's last memory operation): only the
         // events and buffers remain, and they outlive the queued work by the join below
-        (void)hipEventSynchronize(s->side_join);
+        (void)hipEventSynchronize(s->side.join);
     }
     free_all(s);
-    delete s;
+    delete s;  // the members' buffers and events (the hand-over event too: see rsv_set_stream) go back now
 }
 
 // Slow part of rsv_sample: (re)arm a staging buffer, or flush a full one.  Runs once per batch.
@@ -972,19 +926,18 @@ static rsv_status stage_slow(rsv_sampler* s, bool pre) {
     if (s->stage_n == s->stage_cap && s->stage_cap) {
         if (rsv_status st = flush_stage(s)) return st;
     }
-    if (!s->stage_h[0]) {
-        for (int b = 0; b < 2; ++b) {
-            // coherent + mapped: a winners-only flush's resolve reads the keys in place (flush_stage)
-            RSV_HIP_TRY(s->stage_h[b].reserve(kStageKeys * s->kw));
-            if (pre) RSV_HIP_TRY(s->stage_hash_h[b].reserve(kStageKeys));
-            RSV_HIP_TRY(pool_event(&s->stage_free[b], hipEventDisableTiming));
+    if (!s->stage_cap) {  // (every step a no-op where an earlier, failed call got that far)
+        for (Stage& sg : s->stage) {
+            RSV_HIP_TRY(sg.keys.reserve(kStageKeys * s->kw));
+            if (pre) RSV_HIP_TRY(sg.hashes.reserve(kStageKeys));
+            RSV_HIP_TRY(sg.free.ensure(s->device, hipEventDisableTiming));
         }
         s->stage_cap = kStageKeys;
     }
-    const int b = s->stage_cur;
-    if (s->stage_n == 0 && s->stage_pending[b]) {  // its previous batch's H2D must have read it
-        RSV_HIP_TRY(hipEventSynchronize(s->stage_free[b]));
-        s->stage_pending[b] = false;
+    Stage& sg = s->stage[s->stage_cur];
+    if (s->stage_n == 0 && sg.pending) {  // its previous batch's H2D must have read it
+        RSV_HIP_TRY(hipEventSynchronize(sg.free));
+        sg.pending = false;
     }
     return RSV_OK;
 }
@@ -998,11 +951,11 @@ rsv_status rsv_sample(rsv_sampler* s, const void* key, const int64_t* hash) {
     if (s->stage_n == 0 || s->stage_n == s->stage_cap) {
         if (rsv_status st = stage_slow(s, pre)) return st;
     }
-    const int b = s->stage_cur;
-    if (s->kw == 8) memcpy(s->stage_h[b] + s->stage_n * 8, key, 8);
-    else if (s->kw == 4) memcpy(s->stage_h[b] + s->stage_n * 4, key, 4);
-    else memcpy(s->stage_h[b] + s->stage_n * s->kw, key, (size_t)s->kw);
-    if (pre) s->stage_hash_h[b][s->stage_n] = *hash;
+    Stage& sg = s->stage[s->stage_cur];
+    if (s->kw == 8) memcpy(sg.keys + s->stage_n * 8, key, 8);
+    else if (s->kw == 4) memcpy(sg.keys + s->stage_n * 4, key, 4);
+    else memcpy(sg.keys + s->stage_n * s->kw, key, (size_t)s->kw);
+    if (pre) sg.hashes[s->stage_n] = *hash;
     ++s->stage_n;
     return RSV_OK;
 }
@@ -1014,9 +967,9 @@ rsv_status rsv_stage_acquire(rsv_sampler* s, void** keys_out, int64_t** hashes_o
     if (s->stage_n == 0 || s->stage_n == s->stage_cap) {
         if (rsv_status st = stage_slow(s, pre)) return st;
     }
-    const int b = s->stage_cur;
-    *keys_out = s->stage_h[b] + s->stage_n * s->kw;
-    if (hashes_out) *hashes_out = pre ? s->stage_hash_h[b] + s->stage_n : nullptr;
+    Stage& sg = s->stage[s->stage_cur];
+    *keys_out = sg.keys + s->stage_n * s->kw;
+    if (hashes_out) *hashes_out = pre ? sg.hashes + s->stage_n : nullptr;
     *capacity = s->stage_cap - s->stage_n;
     return RSV_OK;
 }
@@ -1076,11 +1029,11 @@ rsv_status rsv_fill_slots(rsv_sampler* s, const void* keys_host) {
     if (rsv_status st = ensure_gather(s)) return st;
     // the changed slots' keys into the pinned gather buffer: the caller's buffer is theirs again on
     // return, and no copy or host wait follows
-    const int64_t* offs = s->offs_h;
+    const int64_t* offs = (const int64_t*)s->idx.offs.host();
     const size_t kw = (size_t)s->kw;
     const uint8_t* src = (const uint8_t*)keys_host;
     for (uint32_t j = 0; j < s->k; ++j)
-        if (offs[j] >= 0) memcpy(s->gath_h + (size_t)j * kw, src + (size_t)j * kw, kw);
+        if (offs[j] >= 0) memcpy(s->idx.gath + (size_t)j * kw, src + (size_t)j * kw, kw);
     return fill_gathered(s);
 }
 
@@ -1089,15 +1042,15 @@ rsv_status rsv_abort_indexed(rsv_sampler* s) {
     if (!s->keys_owed) return fail(RSV_E_ILLEGAL_STATE, "rsv_abort_indexed without a pending rsv_sample_indexed");
     DeviceGuard g(s->device);
     touch(s);
-    if (s->idx_fresh)  // the slots were never initialised before the batch: empty them again
-        RSV_HIP_TRY(launch_init_slots(slot_block(s), s->stream, s->k1_ticket));
+    if (s->idx.fresh)  // the slots were never initialised before the batch: empty them again
+        RSV_HIP_TRY(launch_init_slots(slot_block(s), s->stream, s->slots.ticket));
     else  // the changed slots still hold their old keys: their old indices make them whole again
-        RSV_HIP_TRY(hipMemcpyAsync(s->slot_idx, s->idx_bak_d, (size_t)s->k * 8, hipMemcpyDeviceToDevice, s->stream));
+        RSV_HIP_TRY(hipMemcpyAsync(s->slots.sb.slot_idx, s->idx.bak_d, (size_t)s->k * 8, hipMemcpyDeviceToDevice, s->stream));
     RSV_HIP_TRY(sync_stream(s));
-    s->slots_init = s->win_zero = true;
-    s->pub_valid = false;
-    s->count = s->idx_base;
-    s->algo_l = s->idx_algo_l;
+    s->slots.init = s->slots.win_zero = true;
+    s->clock.invalidate();
+    s->count = s->idx.base;
+    s->jl.algo = s->idx.algo;
     s->keys_owed = false;
     return RSV_OK;
 }
@@ -1108,7 +1061,7 @@ rsv_status rsv_commit_indexed(rsv_sampler* s) {
     // the slot indices are final (index_batch); the keys stay with the caller
     s->keys_owed = false;
     s->keys_external = true;
-    s->pub_valid = false;
+    s->clock.invalidate();
     return RSV_OK;
 }
 
@@ -1139,7 +1092,7 @@ rsv_status rsv_distinct_candidates(rsv_sampler* s, const int64_t* hashes, int64_
     }
     touch(s);
     if (int rc = obj_candidates(s->obj, hashes, n, mem == RSV_MEM_DEVICE, s->count, s->stream, n_cand)) return (rsv_status)rc;
-    s->ops_done = s->ops;  // obj_candidates returns with the stream drained
+    s->clock.drained();  // obj_candidates returns with the stream drained
     s->cand_pending = true;
     s->cand_batch = n;
     return RSV_OK;
@@ -1173,92 +1126,68 @@ rsv_status rsv_candidates_abort(rsv_sampler* s) {
     return RSV_OK;
 }
 
-// Wait until a publication kernel has stored `gen` in the result flag (spin_flag)
-static rsv_status wait_flag(rsv_sampler* s, uint32_t gen) { return spin_flag(s, s->result_flag, gen, "result publish"); }
-
+// result() / resultDevice() / the taken result: the first m keys of the set (DISTINCT) or of the slots
+// (ELEMENTS; resultImpl, Sampler.scala:318-331) to the caller.  To the host they travel through the
+// result's landing zone: published (flag wait, no copy, no stream synchronize) or pinned (D2H copy + stream
+// synchronize).  The two kinds differ in their source, in how they publish when no recorded publication can
+// be served, and in two rules of serving one:
+//   need_last   DISTINCT serves a recorded (speculative) publication only while no group of work came after
+//               it -- not every call that changes the set invalidates; ELEMENTS invalidates at each change of
+//               the slots, so its publications outlive read-only groups (exports, a moved stream)
+//   serve_once  DISTINCT serves a publication once: the next result() publishes again
 static rsv_status result_impl(rsv_sampler* s, void* out, int64_t cap, int64_t* out_n, bool device_out,
                               bool take = false) {
     if (rsv_status st = check_keyed(s)) return st;
     if (!out_n) return fail(RSV_E_NULL_POINTER, "out_n is NULL");
     DeviceGuard g(s->device);
     if (rsv_status st = flush_stage(s)) return st;
-    int64_t m;
-    const void* src;
-    if (s->cfg.kind == RSV_KIND_DISTINCT) {
+    const bool distinct = s->cfg.kind == RSV_KIND_DISTINCT, need_last = distinct, serve_once = distinct;
+    if (distinct)
         if (int rc = s->distinct->finalize(s->stream)) return (rsv_status)rc;
-        m = s->distinct->size();
-        if (m > cap) return fail(RSV_E_ILLEGAL_ARGUMENT, "result buffer too small");
-        if (m && !out && !take) return fail(RSV_E_NULL_POINTER, "out is NULL");
-        if (m) {
-            if (device_out) {
-                if (int rc = s->distinct->export_set(out, nullptr, s->stream)) return (rsv_status)rc;
-            } else {
-                if (rsv_status st = ensure_result_buffer(s)) return st;
-                const void* set_k = s->distinct->keys_dev();
-                if (s->result_publish) {  // the set straight into coherent host memory + flag spin
-                    uint32_t gen = s->pub_gen;
-                    if (!(s->pub_valid && s->pub_ops == s->ops)) {  // no speculative publication of it
-                        touch(s);
-                        gen = ++s->result_gen;
-                        if (int rc = s->distinct->publish(s->result_dev, s->result_flag_dev, gen, s->stream))
-                            return (rsv_status)rc;
-                    }
-                    s->pub_valid = false;
-                    if (rsv_status st = wait_flag(s, gen)) return st;
-                    // the publication was the handle's last work: no stream synchronize
-                    if (s->result_gen == gen) s->ops_done = s->ops;
-                    if (!take) memcpy(out, s->result_h, (size_t)m * s->kw);
-                    *out_n = m;
-                    if (!s->cfg.reusable) s->open = false;
-                    return RSV_OK;
-                } else {
-                    touch(s);
-                    RSV_HIP_TRY(hipMemcpyAsync(s->result_h, set_k, m * s->kw, hipMemcpyDeviceToHost, s->stream));
-                    RSV_HIP_TRY(sync_stream(s));
-                }
-                memcpy(out, s->result_h, (size_t)m * s->kw);
-            }
+    const int64_t m = distinct ? s->distinct->size() : std::min<int64_t>(s->count, (int64_t)s->k);
+    if (m > cap) return fail(RSV_E_ILLEGAL_ARGUMENT, "result buffer too small");
+    if (m && !out && !take) return fail(RSV_E_NULL_POINTER, "out is NULL");
+    // ELEMENTS with a count that came from rsv_seek alone: the slots were never written, and a recycled
+    // block still holds its last sampler's keys -- the result is m empty (zero) slots
+    if (m && !distinct)
+        if (rsv_status st = ensure_slots(s)) return st;
+    Landing& r = s->result;
+    bool waited = false;
+    if (m && device_out) {
+        if (distinct) {
+            if (int rc = s->distinct->export_set(out, nullptr, s->stream)) return (rsv_status)rc;
+        } else {
+            touch(s);
+            RSV_HIP_TRY(hipMemcpyAsync(out, s->slots.sb.slot_key, m * s->kw, hipMemcpyDeviceToDevice, s->stream));
         }
-        src = nullptr;
-    } else {
-        m = std::min<int64_t>(s->count, (int64_t)s->k);  // resultImpl, Sampler.scala:318-331
-        if (m > cap) return fail(RSV_E_ILLEGAL_ARGUMENT, "result buffer too small");
-        if (m && !out && !take) return fail(RSV_E_NULL_POINTER, "out is NULL");
-        // a count that came from rsv_seek alone: the slots were never written, and a recycled block
-        // still holds its last sampler's keys -- the result is m empty (zero) slots
-        if (m)
-            if (rsv_status st = ensure_slots(s)) return st;
-        src = s->slot_key;
-        if (m && !out && take) out = s->result_h;  // checked: a published result (see rsv_result_take)
-        if (m && device_out) {
-            touch(s);
-            RSV_HIP_TRY(hipMemcpyAsync(out, src, m * s->kw, hipMemcpyDeviceToDevice, s->stream));
-        } else if (m) {
-            if (rsv_status st = ensure_result_buffer(s)) return st;
-            if (s->result_publish) {  // publish kernel + flag spin (no D2H copy, no stream sync)
-                uint32_t gen = s->pub_gen;
-                if (!s->pub_valid) {  // the last batch's resolve did not publish the current slots
-                    touch(s);
-                    Publication pub;
-                    if (rsv_status st = begin_publish(s, true, m, &pub)) return st;
-                    gen = pub.gen;
+    } else if (m) {
+        if (rsv_status st = ensure_result_buffer(s)) return st;
+        const void* src = distinct ? s->distinct->keys_dev() : s->slots.sb.slot_key;
+        if (r.published()) {
+            uint32_t gen = s->clock.pub_gen;
+            if (!(need_last ? s->clock.current() : s->clock.holds())) {  // no publication of it: the publish launch
+                touch(s);
+                Publication pub;
+                if (rsv_status st = begin_publish(s, true, m, &pub)) return st;
+                gen = pub.gen;
+                if (distinct) {
+                    if (int rc = s->distinct->publish(pub.dst, pub.flag, gen, s->stream)) return (rsv_status)rc;
+                } else {
                     RSV_HIP_TRY(launch_publish(src, m * s->kw, pub.dst, pub.flag, gen, s->stream));
-                    record_publish(s, pub);
                 }
-                if (rsv_status st = wait_flag(s, gen)) return st;
-                if (s->pub_valid && s->pub_ops == s->ops && s->result_gen == gen) s->ops_done = s->ops;
-                if (!take) memcpy(out, s->result_h, (size_t)m * s->kw);
-                *out_n = m;
-                if (!s->cfg.reusable) s->open = false;
-                return RSV_OK;
+                record_publish(s, pub);
             }
-            // large reservoirs through a pinned buffer: a pageable D2H costs a staged copy
+            if (serve_once) s->clock.invalidate();
+            if (rsv_status st = spin_flag(s, r.flag(), gen, "result publish")) return st;
+            s->clock.seen(s->clock.pub_ops, gen, r.gen);  // the handle's last work: no stream synchronize
+            waited = true;
+        } else {  // large reservoirs through a pinned buffer: a pageable D2H costs a staged copy
             touch(s);
-            RSV_HIP_TRY(hipMemcpyAsync(s->result_h, src, m * s->kw, hipMemcpyDeviceToHost, s->stream));
+            RSV_HIP_TRY(hipMemcpyAsync(r.host(), src, m * s->kw, hipMemcpyDeviceToHost, s->stream));
         }
     }
-    RSV_HIP_TRY(sync_stream(s));
-    if (m && !device_out && s->cfg.kind != RSV_KIND_DISTINCT) memcpy(out, s->result_h, (size_t)m * s->kw);
+    if (!waited) RSV_HIP_TRY(sync_stream(s));
+    if (m && !device_out && !take) memcpy(out, r.host(), (size_t)m * s->kw);
     *out_n = m;
     if (!s->cfg.reusable) s->open = false;  // SingleUse.close, Sampler.scala:188-191, :345-350
     return RSV_OK;
@@ -1281,18 +1210,10 @@ rsv_status rsv_result_take(rsv_sampler* s, void** buf, int64_t* out_n) {
         DeviceGuard g(s->device);
         if (rsv_status st = ensure_result_buffer(s)) return st;
     }
-    // the published path of rsv_result, with the buffer handed over instead of copied
-    void* h = s->result_h;
-    const int64_t cap = s->k;
-    rsv_status st = result_impl(s, nullptr, cap, out_n, false, /*take=*/true);
-    if (st != RSV_OK) return st;
-    *buf = h;
-    (void)s->result_pub.detach();  // the caller's now (rsv_host_release): a closed single-use handle publishes nothing more
-    s->result_h = nullptr;
-    s->result_dev = nullptr;
-    s->result_flag = nullptr;
-    s->result_flag_dev = nullptr;
-    s->result_publish = false;
+    // the published path of rsv_result, with the block handed over instead of copied: the caller's now
+    // (rsv_host_release); a closed single-use handle publishes nothing more
+    if (rsv_status st = result_impl(s, nullptr, s->k, out_n, false, /*take=*/true)) return st;
+    *buf = s->result.give();
     return RSV_OK;
 }
 
@@ -1307,16 +1228,13 @@ int64_t rsv_count(const rsv_sampler* s) { return s ? s->count + s->stage_n : 0; 
 rsv_status rsv_set_stream(rsv_sampler* s, void* hip_stream) {
     if (rsv_status st = check_no_batch(s)) return st;
     DeviceGuard g(s->device);
-    if (s->side_pending) {  // the hand-over covers the forked resolve too
-        join_side(s);
-        ++s->ops;
-    }
-    if (s->ops != s->ops_done && (hipStream_t)hip_stream != s->stream) {
+    if (s->side.pending) touch(s);  // the hand-over covers the forked resolve too
+    if (!s->clock.idle() && (hipStream_t)hip_stream != s->stream) {
         // stream-ordered hand-over, no host wait: the new stream waits for the work queued so far
         // (e.g. a combine moved to a communication stream while the next batch samples on the
         // first).  The event is the handle's own until rsv_destroy: handed back to the pool at
         // once, its next record elsewhere could land before the wait binds
-        if (!s->handover) RSV_HIP_TRY(pool_event(&s->handover, hipEventDisableTiming));
+        RSV_HIP_TRY(s->handover.ensure(s->device, hipEventDisableTiming));
         RSV_HIP_TRY(hipEventRecord(s->handover, s->stream));
         RSV_HIP_TRY(hipStreamWaitEvent((hipStream_t)hip_stream, s->handover, 0));
     }
@@ -1332,11 +1250,8 @@ rsv_status rsv_set_resolve_stream(rsv_sampler* s, void* hip_stream) {
     if (rsv_status st = check_no_batch(s)) return st;
     if (s->cfg.kind != RSV_KIND_ELEMENTS) return fail(RSV_E_UNSUPPORTED, "rsv_set_resolve_stream: ELEMENTS samplers only");
     DeviceGuard g(s->device);
-    if (s->side_pending) {
-        join_side(s);
-        ++s->ops;
-    }
-    s->rstream = (hipStream_t)hip_stream;
+    if (s->side.pending) touch(s);
+    s->side.rstream = (hipStream_t)hip_stream;
     return RSV_OK;
 }
 
@@ -1417,7 +1332,7 @@ rsv_status rsv_seek(rsv_sampler* s, int64_t index) {
     }
     if (index < s->count) return fail(RSV_E_ILLEGAL_ARGUMENT, "rsv_seek cannot move backwards");
     // a publication holds min(count, k) keys: once the count crosses k it covers too few
-    if (std::min<int64_t>(index, s->k) != std::min<int64_t>(s->count, s->k)) s->pub_valid = false;
+    if (std::min<int64_t>(index, s->k) != std::min<int64_t>(s->count, s->k)) s->clock.invalidate();
     s->count = index;
     return RSV_OK;
 }
@@ -1435,9 +1350,9 @@ rsv_status rsv_export_state(rsv_sampler* s, int64_t* idx_dev, void* keys_dev, in
         *out_n = s->distinct->size();
     } else {
         if (rsv_status st = ensure_slots(s)) return st;
-        if (idx_dev) RSV_HIP_TRY(hipMemcpyAsync(idx_dev, s->slot_idx, s->k * 8ull, hipMemcpyDeviceToDevice, s->stream));
+        if (idx_dev) RSV_HIP_TRY(hipMemcpyAsync(idx_dev, s->slots.sb.slot_idx, s->k * 8ull, hipMemcpyDeviceToDevice, s->stream));
         if (keys_dev)
-            RSV_HIP_TRY(hipMemcpyAsync(keys_dev, s->slot_key, (size_t)s->k * s->kw, hipMemcpyDeviceToDevice, s->stream));
+            RSV_HIP_TRY(hipMemcpyAsync(keys_dev, s->slots.sb.slot_key, (size_t)s->k * s->kw, hipMemcpyDeviceToDevice, s->stream));
         *out_n = s->k;
     }
     // on the handle's private stream the caller cannot order against it: wait; on a caller
@@ -1464,7 +1379,7 @@ rsv_status rsv_merge_state(rsv_sampler* s, const int64_t* idx_dev, const void* k
         if (parts > 0 && !idx_dev) return fail(RSV_E_NULL_POINTER, "idx_dev is NULL");
         if (rsv_status st = ensure_slots(s)) return st;
         RSV_HIP_TRY(launch_merge_slots(idx_dev, keys_dev, parts, part_len, slot_block(s), s->stream));
-        s->pub_valid = false;
+        s->clock.invalidate();
     }
     if (total_count > s->count) s->count = total_count;
     if (s->own_stream) RSV_HIP_TRY(sync_stream(s));
@@ -1516,7 +1431,7 @@ rsv_status rsv_merge_log(rsv_sampler* s, const int64_t* hashes_host, const void*
     if (int rc = s->distinct->log_merge(hashes_host, keys_host, n, total_count, s->stream))
         return (rsv_status)rc;
     if (total_count > s->count) s->count = total_count;
-    s->pub_valid = false;
+    s->clock.invalidate();
     if (s->own_stream) RSV_HIP_TRY(sync_stream(s));
     return RSV_OK;
 }
@@ -1558,7 +1473,7 @@ rsv_status rsv_merge_packed(rsv_sampler* s, const int64_t* rows_dev, int32_t par
         if (rsv_status st = flush_stage(s)) return st;
         if (int rc = s->distinct->merge_rows(rows_dev, parts, row_stride, s->stream)) return (rsv_status)rc;
         if (total_count > s->count) s->count = total_count;
-        s->pub_valid = false;
+        s->clock.invalidate();
         if (s->own_stream) {  // the call returns with its work done: settle now, while the rows are the caller's
             RSV_HIP_TRY(sync_stream(s));
             if (int rc = s->distinct->settle(s->stream)) return (rsv_status)rc;
@@ -1574,7 +1489,7 @@ rsv_status rsv_merge_packed(rsv_sampler* s, const int64_t* rows_dev, int32_t par
     if (rsv_status st = ensure_slots(s)) return st;
     if (total_count > s->count) {
         // a publication holds min(count, k) keys: once the count crosses k it covers too few (rsv_seek)
-        if (std::min<int64_t>(total_count, s->k) != std::min<int64_t>(s->count, s->k)) s->pub_valid = false;
+        if (std::min<int64_t>(total_count, s->k) != std::min<int64_t>(s->count, s->k)) s->clock.invalidate();
         s->count = total_count;
     }
     if (parts > 0) {  // for small reservoirs of Int / Long keys: merge + publish in one dispatch

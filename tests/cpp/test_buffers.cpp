@@ -1,6 +1,8 @@
 // The owning buffers of reservoir_amd/csrc/rsv_buffers.h over stub pool functions (malloc, a live-block
 // count, an allocation that can be told to fail): capacity and pointer change together, a group's capacity
-// never runs ahead of a member, and every block goes back to the pool.  Host only: no HIP library is linked.
+// never runs ahead of a member, and every block goes back to the pool.  Then the sampler handle's types from
+// the same header: the landing zone, the event owner (stub events, counted the same way) and the work clock.
+// Host only: no HIP library is linked.
 #include <assert.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -46,6 +48,18 @@ hipError_t pool_host_alloc_mapped(void** p, void** dev_alias, size_t bytes) {
     return hipSuccess;
 }
 void pool_host_free(void* p) { stub_free(p); }
+// events: a live set like the blocks', with the device and flags each was taken with
+hipError_t pool_event(hipEvent_t* out, unsigned flags) {
+    void* p = nullptr;
+    if (hipError_t e = stub_alloc(&p, sizeof(unsigned))) return e;
+    *(unsigned*)p = flags;
+    *out = (hipEvent_t)p;
+    return hipSuccess;
+}
+void pool_release_event(int device, hipEvent_t e, unsigned flags) {
+    assert(e && device == 3 && *(unsigned*)e == flags);  // returned as taken
+    stub_free(e);
+}
 }  // namespace rsv
 
 using namespace rsv;
@@ -172,6 +186,84 @@ static int run() {
         pool_host_free(gone);
     }
     CHECK(g_live.empty());
+    // The landing zone takes each form once, from a byte size and the caller's "may publish"; with its only
+    // allocation failing it stays empty -- no form, no alias -- and the next ensure chooses again.
+    for (int may = 0; may < 2; ++may) {
+        Landing z;
+        z.gen = 7;
+        arm(1);
+        CHECK(z.ensure(1000, may) == hipErrorOutOfMemory);
+        CHECK(!z.host() && !z.dev() && !z.published() && !z.pub.p && !z.pin.p && z.gen == 7 && g_live.empty());
+        arm(0);
+        CHECK(z.ensure(1000, may) == hipSuccess && z.host() && z.published() == (may == 1) && g_live.size() == 1);
+        void* h = z.host();
+        if (may) {  // the flag line lies behind the entries on a 64-byte boundary, inside the block, and starts at gen
+            CHECK(z.dev() == h && (uint8_t*)z.flag() == (uint8_t*)h + 1024 && z.flag_dev() == z.flag());
+            CHECK(z.pub.cap == 1024 + 64 && *z.flag() == 7);
+            z.flag()[15] = 1;  // the whole line is there (checked by the sanitizer)
+        } else {
+            CHECK(!z.dev() && z.pin.cap == 1000);
+            ((uint8_t*)h)[999] = 1;
+        }
+        CHECK(z.next_gen() == 8 && z.gen == 8);
+        CHECK(z.ensure(1000, !may) == hipSuccess && z.host() == h && z.published() == (may == 1));  // chosen once
+        CHECK(g_allocs == 1);
+        if (may) {  // given away, it holds nothing: the taker frees the block, the generation stays
+            void* gone = z.give();
+            CHECK(gone == h && !z.host() && !z.dev() && !z.published() && z.pub.cap == 0 && z.gen == 8);
+            CHECK(g_live.size() == 1 && g_live.count(gone));
+            pool_host_free(gone);
+        }
+    }
+    CHECK(g_live.empty());
+    {  // the event owner: taken at first use, returned exactly once with its device and flags, moves included
+        PoolEvent a, never;
+        arm(1);
+        CHECK(a.ensure(3, 2) == hipErrorOutOfMemory && !a.e && g_live.empty());
+        arm(0);
+        CHECK(a.ensure(3, 2) == hipSuccess && a.e && g_live.size() == 1);
+        hipEvent_t e = a;
+        CHECK(a.ensure(3, 2) == hipSuccess && a.e == e && g_allocs == 1);
+        PoolEvent b(std::move(a));
+        CHECK(!a.e && b.e == e && b.device == 3 && b.flags == 2);
+        PoolEvent c;
+        CHECK(c.ensure(3, 0) == hipSuccess && g_live.size() == 2);
+        c = std::move(b);  // c's own event goes back to the pool
+        CHECK(c.e == e && !b.e && c.flags == 2 && g_live.size() == 1);
+        c.release();
+        CHECK(!c.e && g_live.empty());
+        c.release();
+        CHECK(c.ensure(3, 2) == hipSuccess);  // and can be taken again; returned by the destructor
+    }
+    CHECK(g_live.empty());
+    {  // the work clock, as rules
+        WorkClock c;
+        CHECK(c.idle() && !c.holds() && !c.current());
+        c.group();
+        CHECK(!c.idle());
+        c.drained();  // (1) drained after a drain ...
+        CHECK(c.idle());
+        c.group();
+        c.published(true, 5);
+        CHECK(c.holds() && c.current() && c.pub_gen == 5 && !c.idle());
+        c.seen(c.pub_ops, 4, 5);  // ... not when the host saw an older generation than the newest issued,
+        CHECK(!c.idle());
+        c.seen(c.pub_ops, 5, 5);  // ... and when it saw the generation of a publication that was the last group
+        CHECK(c.idle());
+        c.group();  // (2) the next group: the publication still has the slots, is no longer current,
+        CHECK(c.holds() && !c.current() && !c.idle());
+        c.seen(c.pub_ops, 5, 5);  // and seeing it again drains nothing
+        CHECK(!c.idle());
+        c.published(true, 6);
+        CHECK(c.current());
+        c.invalidate();  // (2) ... or an invalidation
+        CHECK(!c.holds() && !c.current() && c.pub_gen == 6);
+        c.published(true, 7);
+        c.published(false, 9);  // (3) recording "no publication" invalidates and records nothing
+        CHECK(!c.holds() && !c.current() && c.pub_gen == 7);
+        c.seen(c.ops, 9, 9);  // a landing zone of its own (the index-only offsets), published by the last group
+        CHECK(c.idle());
+    }
     return 0;
 }
 

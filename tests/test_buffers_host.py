@@ -1,8 +1,10 @@
 """The owning buffers over the resource pool (reservoir_amd/csrc/rsv_buffers.h) against stub pool
 functions that count live blocks and fail a chosen allocation: no allocation within the capacity, kept
 contents across growths, a group's capacity never above a member's after any failed allocation, move and
-swap, and no block left behind (tests/cpp/test_buffers.cpp, a stand-alone host program built with
-AddressSanitizer + UndefinedBehaviorSanitizer; CPU only, no HIP library linked)."""
+swap, and no block left behind; then the sampler handle's landing zone (each form, a failed allocation, the
+block given away), its event owner (taken at first use, returned once) and its work clock, as rules
+(tests/cpp/test_buffers.cpp, a stand-alone host program built with AddressSanitizer +
+UndefinedBehaviorSanitizer; CPU only, no HIP library linked)."""
 import os
 import subprocess
 

@@ -283,3 +283,37 @@ def test_count_and_is_open_answer_in_every_state(cuda, oracle, family, state):
     assert c.count() == want and c.is_open() == (0 if state in ("closed", "taken") else 1)
     assert c.L.rsv_get_stream(c.h)
     c.close()
+
+
+@pytest.mark.parametrize("then", ["nothing", "export_state", "merge_state"])
+def test_distinct_serves_a_publication_only_as_the_last_group(cuda, oracle, monkeypatch, then):
+    """A distinct batch may publish its merged set speculatively (forced for every batch here through
+    RSV_SPEC_MIN_BATCH, read at creation), and result() then only waits for that publication -- but only
+    while no group of work came after it.  rsv_export_state opens a group that reads the set, and
+    rsv_merge_state of a distinct sampler changes the set without a word about the publication: after
+    either, result() publishes again, and gives the oracle's set of everything sampled and merged."""
+    import torch
+
+    from reservoir_amd import Sampler
+
+    monkeypatch.setenv("RSV_SPEC_MIN_BATCH", "1")
+    keys = oracle.splitmix_keys(77, 6000)
+    kd = torch.from_numpy(keys).to(cuda)
+    d = Sampler.distinct(K, seed=SEED, reusable=True)(hash="identity")
+    ref = oracle.Distinct(K, SEED, oracle.HASH_IDENTITY)
+    d.sample_all(kd[:4000])
+    ref.sample_all(keys[:4000])
+    if then == "export_state":
+        _, got_keys, _, n = d.export_state(cuda)
+        assert n == K and np.array_equal(np.sort(got_keys.cpu().numpy()), np.sort(ref.result()[0]))
+    elif then == "merge_state":
+        e = Sampler.distinct(K, seed=SEED)(hash="identity")
+        e.sample_all(kd[4000:])
+        _, pk, ph, pn = e.export_state(cuda)
+        d.merge_state(torch.zeros((1, K), dtype=torch.int64, device=cuda), pk[None], ph[None], [pn], keys.size)
+        ref.sample_all(keys[4000:])
+        e.close()
+    want = ref.result()[0]
+    assert np.array_equal(d.result(), want)
+    assert np.array_equal(d.result(), want)  # a reusable sampler: asked twice
+    d.close()
