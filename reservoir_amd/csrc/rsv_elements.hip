@@ -42,27 +42,14 @@ struct K1Lds {
     uint64_t cq[kBlock / 64][kQueue];
 };
 
-// the launch-uniform conditions of k1_body_q's FAST resolve
-__device__ __forceinline__ bool k1_fast(uint64_t lo, uint64_t hi) {
-    return (lo >> 33) == ((hi - 1) >> 33) && hi <= (1ull << 40);
-}
-
-// the work layout of one K1 launch (k1_body_q): sch.A == 0 -- grid-stride windows; else the two-group
-// schedule of half windows
-struct K1Sched {
-    uint32_t W1, A, B;
-};
-
 __global__ __launch_bounds__(kBlock) void k1_last_writer(DrawKey dk, uint32_t k, uint64_t lo,
                                                          uint64_t hi, uint64_t g_begin,
                                                          uint64_t n_groups,
-                                                         unsigned long long* __restrict__ win, K1Sched sch) {
+                                                         unsigned long long* __restrict__ win, K1Launch P) {
     __shared__ K1Lds L;
     const int w = threadIdx.x >> 6;
-    if (k1_fast(lo, hi))
-        k1_body_q<kK1Win, true>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], sch.W1, sch.A, sch.B);
-    else
-        k1_body_q<kK1Win, false>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], sch.W1, sch.A, sch.B);
+    if (P.flags & kK1Fast) k1_body_q<kK1Win, true, kBlock>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
+    else k1_body_q<kK1Win, false, kBlock>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
 }
 
 // ---- the slot rule ----------------------------------------------------------------------------
@@ -156,14 +143,12 @@ __global__ __launch_bounds__(kBlock) void k1_resolve_publish(DrawKey dk, uint32_
                                                              uint32_t* ticket, const KeyT* __restrict__ keys,
                                                              int64_t base, int64_t n, KeyT* __restrict__ slot_key,
                                                              int64_t* __restrict__ slot_idx, int fresh, int64_t m,
-                                                             KeyT* dst, uint32_t* flag, uint32_t gen, K1Sched sch) {
+                                                             KeyT* dst, uint32_t* flag, uint32_t gen, K1Launch P) {
     __shared__ K1Lds L;
     __shared__ uint32_t last;
     const int w = threadIdx.x >> 6;
-    if (k1_fast(lo, hi))
-        k1_body_q<kK1Win, true>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], sch.W1, sch.A, sch.B);
-    else
-        k1_body_q<kK1Win, false>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], sch.W1, sch.A, sch.B);
+    if (P.flags & kK1Fast) k1_body_q<kK1Win, true, kBlock>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
+    else k1_body_q<kK1Win, false, kBlock>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
     // This wave's winner atomics are performed once vmcnt drains: on gfx942/gfx950 a global atomic
     // without return still counts in vmcnt until the memory system acknowledges it (there is no
     // separate vscnt), and an agent-scope atomic is performed at the agent's coherence point (the
@@ -429,26 +414,29 @@ inline unsigned k1_grid(uint64_t n_groups) {
     return (unsigned)std::max<uint64_t>(1, n_groups / (per_window * m));
 }
 
-// The two-group schedule (k1_body_q), for launches of >= 10 half windows per first-group wave: the
-// first kK1W1 waves (one generation of resident waves: 6 four-wave workgroups per CU) take ~75 % of
-// the half windows, the rest go two per wave.  tools/micro_k1o s, 1e9 draws (81 k half windows):
-// (6144, 10, 2) 81.7-81.8 us, (5120, 12, 2) 81.7-82.5, (4096, 16, 1) 82.1-82.7, (6144, 8, 2)
-// 82.9-83.2, (6144, 13, 1) 89.3 (a long first group outlasts the rest) vs 83.0-83.2 us grid-stride.
+// The two-group schedule (k1_body_q): the first kK1W1 waves (one generation of resident waves: 6 four-
+// wave workgroups per CU) take A steady half windows each, the rest go two per wave.  The launch's slow
+// iterations (its dense head, its clipped ends) are no units: the first group's waves take them round-
+// robin ahead of their units (k1_launch).
+// A: the second group keeps kK1Rest .. kK1Rest + kK1W1 units (0.44 .. 0.94 of a generation at two per
+// wave) and the first group takes all the others.  tools/micro_k1o s (K1O_N for the size), best A per
+// size, us: 6e8 7 (48.5; 6: 50.5), 9.5e8 11 (74.0; 10: 74.8, 12: 74.4), 1e9 12 (77.3-77.5; 10: 78.4-78.7,
+// 11: 80.0, 13: 80.3 -- 1.5 k units left for the second group), 1.2e9 15 (91.9; 14: 92.8), 1.5e9 18
+// (114.1; 17: 115.2, 19: 115.4), 2e9 25 (150.0; 24: 151.2, 20: 153.7) -- each the A of this rule; the
+// 75.5 % share it replaces gave 6, 9, 10, 12, 15 and 20.  B = 1 or 3 and 5120 or 4096 first-group waves
+// were no better at 1e9 (profiles/k1_fixed_cost/micro_k1o_sched.jsonl).
+// From kK1MinA units per first-group wave (4.44e8 draws at k = 1024); grid-stride against the schedule,
+// micro_k1o n: 4.5e8 43.4 vs 42.0 us, 6e8 56.4 vs 55.7, 7.5e8 67.2 vs 63.8, 9e8 75.5 vs 72.4 (these
+// four still with the 75.5 % share), 1e9 79.1 vs 78.1, 2e9 153.8 vs 151.9; below 4.5e8 not measured.
 constexpr uint32_t kK1W1 = 256 * 6 * (kBlock / 64);
-inline unsigned k1_plan(uint64_t n_groups, K1Sched& sch) {
-    sch = K1Sched{0, 0, 0};
-    constexpr uint64_t UB = (uint64_t)kK1Unroll * 64 * (kK1Win / 2);  // blocks per half window
-    const uint64_t units = (n_groups + UB - 1) / UB;
-    const uint64_t A = (units * 755 / 1000 + kK1W1 / 2) / kK1W1;
-    // from ~1e9 draws (A >= 10); below, the plan lost to the grid-stride launch (micro_k1o n: 4.5e8
-    // 48.2 vs 44.7 us, 6e8 58.2 vs 55.7; 1e9 81.7 vs 82.8, 2e9 157.5 vs 158.8, 8e9 610.5 vs 616.9)
-    if (n_groups < (uint64_t)kK1Unroll * kBlock * kK1Win * 768 || A < 10) return k1_grid(n_groups);
-    sch.W1 = kK1W1;
-    sch.A = (uint32_t)A;
-    sch.B = 2;
-    const uint64_t rest = units - (uint64_t)kK1W1 * A;  // > 0: A ~ 0.755 units / W1
-    const uint64_t waves = kK1W1 + (rest + sch.B - 1) / sch.B;
-    return (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
+constexpr uint32_t kK1Rest = 5400, kK1MinA = 5;
+inline unsigned k1_plan(uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin, uint64_t n_groups, K1Launch& P) {
+    const unsigned stride_grid = k1_grid(n_groups);
+    P = k1_launch<kK1Win>(k, lo, hi, g_begin, n_groups, stride_grid, kBlock);
+    // a launch with too few steady units (small, or nearly all dense: 256 k near its end) runs grid-stride
+    if (P.units < kK1MinA * kK1W1 + kK1Rest) return stride_grid;
+    const unsigned grid = k1_schedule(P, kK1W1, (P.units - kK1Rest) / kK1W1, 2, kBlock);
+    return grid ? grid : stride_grid;
 }
 
 // f(KeyT{}) with the key type of a 4- / 8-byte key_width (f launches a kernel); the launch's error
@@ -476,10 +464,10 @@ hipError_t launch_k1_last_writer(const DrawParams& dp, uint32_t k, uint64_t lo, 
         // and no launch crosses a multiple of 2^32 blocks: the counter's high word is a scalar
         const uint64_t g_wrap = ((g_begin >> 32) + 1) << 32;
         n_groups = std::min<uint64_t>(std::min<uint64_t>(g_end, g_wrap) - g_begin, kMaxGroups);
-        K1Sched sch;
-        const unsigned grid = k1_plan(n_groups, sch);
+        K1Launch P;
+        const unsigned grid = k1_plan(k, lo, hi, g_begin, n_groups, P);
         hipLaunchKernelGGL(k1_last_writer, dim3(grid), dim3(kBlock), 0, st, make_key(dp), k, lo, hi,
-                           g_begin, n_groups, batch_win, sch);
+                           g_begin, n_groups, batch_win, P);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -497,13 +485,13 @@ hipError_t launch_k1_resolve_publish(const DrawParams& dp, uint64_t lo, uint64_t
                                      uint32_t* ticket, const Batch& b, const Publication& pub, hipStream_t st) {
     if (!k1_fused_ok(lo, hi, sb.k, sb.key_width)) return hipErrorInvalidValue;
     const uint64_t g_begin = lo >> 4, n_groups = ((hi + 15) >> 4) - g_begin;
-    K1Sched sch;
-    const unsigned grid = k1_plan(n_groups, sch);
+    K1Launch P;
+    const unsigned grid = k1_plan(sb.k, lo, hi, g_begin, n_groups, P);
     return with_key_type(sb.key_width, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL(k1_resolve_publish<T>, dim3(grid), dim3(kBlock), 0, st, make_key(dp), sb.k, lo, hi, g_begin,
                            n_groups, sb.win, ticket, (const T*)b.keys, b.base, b.n, (T*)sb.slot_key, sb.slot_idx,
-                           (int)b.fresh, pub.m, (T*)pub.dst, pub.flag, pub.gen, sch);
+                           (int)b.fresh, pub.m, (T*)pub.dst, pub.flag, pub.gen, P);
     });
 }
 

@@ -59,7 +59,9 @@ __device__ __forceinline__ void enqueue_block(const DrawKey& dk, const u32x4& w,
         if (has) {
             const uint32_t e = __builtin_ctz(mask);
             mask &= mask - 1;
-            q[qn + __popcll(bal & lanemask_lt64())] = ((uint64_t)level0_byte(w, e) << 56) | (i0 + e);
+            // (mbcnt, not a lane mask: K1 would set the mask up in every wave's prologue for this rare path)
+            const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+            q[qn + pos] = ((uint64_t)level0_byte(w, e) << 56) | (i0 + e);
         }
         qn += (uint32_t)__popcll(bal);
         if (qn >= 64) {
@@ -160,24 +162,90 @@ constexpr uint32_t k1q_cap() { return 64u * (1u + W / 2); }
 // waves per K1 workgroup (256 threads): the pooled tail's per-wave queue count
 constexpr uint32_t kQueueWaves = 4;
 
-// FAST (launch-uniform, the kernel picks): the level-1 counter's high word is uniform over the
-// launch and every index is below 2^40 -- the resolve then forms the counter's low word with
+// FAST (launch-uniform, the host picks: K1Launch::flags): the level-1 counter's high word is uniform
+// over the launch and every index is below 2^40 -- the resolve then forms the counter's low word with
 // 32-bit ops from the entry's counter word instead of the general 64-bit index arithmetic.
 //
 // Two work layouts (launch-uniform): A == 0 -- grid-stride over whole windows (every wave the same
-// number of iterations); A > 0 -- a static two-group schedule of half windows (units of W/2
-// iterations over 768 contiguous blocks): the first W1 waves take A units each, the rest B each,
-// strided within each group (unit j * group_waves + wave, so the launch's first units -- the dense
-// region, many times a sparse unit's work -- go one per wave to the first-dispatched waves).  The
+// number of iterations); A > 0 -- a static two-group schedule of the launch's steady half windows
+// (units of W/2 iterations over 768 contiguous blocks): the first W1 waves take A units each, the rest
+// B each, strided within each group (unit j * group_waves + wave).  The
 // first generation of resident workgroups then runs long (fewer waves: every wave ends on one or two
 // partial resolve rounds, 4.4 us of an 83 us launch at 20 k waves -- tools/micro_k1o t), the last
 // stays short (the launch's end waits on the last workgroups): tools/micro_k1o s, 1e9 draws:
 // 81.7-81.8 us at (6144, 10, 2) vs 83.0-83.2 for the grid-stride launch (profiles/r05/).
-template <int W = 12, bool FAST = false>
+//
+// The slow iterations -- those holding dense or clipped blocks: the launch's head below off_steady and
+// its last partial unit -- are no units of that schedule: they are dealt one at a time round-robin over
+// the first-group waves, which run theirs first, so no wave takes more than ceil(slow_iters / W1) of
+// them (dealt as whole units, the 21 dense units of a 1e9-draw launch at k = 1024 sat on 21 waves).
+
+// What every wave of a launch would derive alike, derived once on the host (k1_launch) and passed by
+// value: the launch's steady span, its counter words, the form flags and the schedule.
+constexpr uint32_t kK1Fast = 1u, kK1HiUniform = 2u, kK1Below2p40 = 4u;
+struct K1Launch {
+    uint32_t W1, A, B;    // the two-group schedule; A == 0: grid-stride windows
+    uint32_t nB;          // waves of the second group
+    uint32_t units;       // steady units of the schedule: blocks [unit_off, unit_off + units UB)
+    uint32_t unit_off;
+    uint32_t head_iters;  // slow iterations d < head_iters start at block 128 d,
+    uint32_t slow_iters;  // the others at tail_off + 128 (d - head_iters)
+    uint32_t tail_off;
+    uint32_t stride;      // blocks per grid-stride iteration of the whole launch
+    uint32_t off_steady, ng_steady;  // blocks [off_steady, ng_steady) are neither dense nor clipped
+    uint32_t c1u, ghi;    // the level-1 counter's uniform high word; the block counter's high word
+    uint32_t flags;       // kK1Fast | kK1HiUniform | kK1Below2p40
+    uint64_t k24, khi;    // k << 24, k << 32
+};
+
+// the launch-uniform values of a launch over blocks [g_begin, g_begin + n_groups) of indices [lo, hi)
+// with `grid` workgroups of `block` threads (no schedule: k1_schedule sets one)
+template <int W = 12>
+inline K1Launch k1_launch(uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin, uint64_t n_groups, unsigned grid,
+                          unsigned block = 256) {
+    constexpr uint32_t UB = (W / 2) * 2 * 64, IB = 2 * 64;  // blocks per unit, per iteration
+    K1Launch P{};
+    const uint32_t ng = (uint32_t)n_groups;  // < 2^31 per launch (the host splits)
+    const uint64_t g_sparse = (256ull * k + 14) >> 4;
+    const uint32_t off_sparse = g_sparse <= g_begin ? 0u : (uint32_t)std::min<uint64_t>(g_sparse - g_begin, ng);
+    P.off_steady = std::max<uint32_t>(off_sparse, (lo & 15) ? 1u : 0u);
+    P.ng_steady = ng - ((hi & 15) ? 1u : 0u);
+    P.stride = grid * block * 2;
+    P.c1u = (uint32_t)(lo >> 33) | kDomainLevel1;
+    P.ghi = (uint32_t)(g_begin >> 32);
+    const bool hi_uniform = (lo >> 33) == ((hi - 1) >> 33), below = hi <= (1ull << 40);
+    P.flags = (hi_uniform && below ? kK1Fast : 0u) | (hi_uniform ? kK1HiUniform : 0u) | (below ? kK1Below2p40 : 0u);
+    P.k24 = (uint64_t)k << 24;
+    P.khi = (uint64_t)k << 32;
+    // the head in whole iterations, then whole steady units, then the rest in iterations
+    const uint32_t head = (uint32_t)std::min<uint64_t>(((uint64_t)P.off_steady + IB - 1) / IB * IB, ng);
+    P.unit_off = head;
+    P.units = P.ng_steady > head ? (P.ng_steady - head) / UB : 0u;
+    P.tail_off = head + P.units * UB;
+    P.head_iters = (head + IB - 1) / IB;
+    P.slow_iters = P.head_iters + (ng - P.tail_off + IB - 1) / IB;
+    return P;
+}
+
+// the two-group schedule (W1, A, B) for the launch; returns its grid in workgroups of `block` threads, 0
+// when the schedule does not fit the launch (no unit left for the second group)
+inline unsigned k1_schedule(K1Launch& P, uint32_t W1, uint32_t A, uint32_t B, unsigned block = 256) {
+    if (W1 == 0 || A == 0 || B == 0 || (uint64_t)W1 * A >= P.units) return 0;
+    const uint64_t rest = P.units - (uint64_t)W1 * A;
+    const uint64_t wpg = block / 64, waves = W1 + (rest + B - 1) / B;
+    const unsigned grid = (unsigned)((waves + wpg - 1) / wpg);
+    P.W1 = W1;
+    P.A = A;
+    P.B = B;
+    P.nB = (uint32_t)(grid * wpg - W1);
+    P.stride = grid * block * 2;
+    return grid;
+}
+
+template <int W = 12, bool FAST = false, int BS = 256>
 __device__ __forceinline__ void k1_body_q(const DrawKey& dk, uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin,
                                           uint64_t n_groups, unsigned long long* __restrict__ win, uint64_t* q,
-                                          uint64_t* cq, uint32_t W1 = 0, uint32_t A = 0, uint32_t B = 0,
-                                          uint32_t* pool = nullptr) {
+                                          uint64_t* cq, const K1Launch& P, uint32_t* pool = nullptr) {
     static_assert(W % 2 == 0, "half windows");
     constexpr int U = 2;
     const uint32_t lane = threadIdx.x & 63;
@@ -185,21 +253,17 @@ __device__ __forceinline__ void k1_body_q(const DrawKey& dk, uint32_t k, uint64_
     auto hit = [&](uint32_t j, uint64_t i) { atomicMax(&win[j], (unsigned long long)i); };
     const uint64_t dense_lim = 256ull * k;
     const uint32_t ng = (uint32_t)n_groups;  // < 2^31 per launch (host splits)
-    const uint64_t g_sparse = (dense_lim + 14) >> 4;
-    const uint32_t off_sparse = g_sparse <= g_begin ? 0u : (uint32_t)std::min<uint64_t>(g_sparse - g_begin, ng);
-    const uint32_t stride = gridDim.x * blockDim.x * U;
-    const uint32_t c1u = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(lo >> 33) | kDomainLevel1));
-    const bool hi_uniform = (lo >> 33) == ((hi - 1) >> 33);
-    const bool pre_ok = hi <= (1ull << 40);
-    const uint64_t k_hi = (uint64_t)k << 32, k_24 = (uint64_t)k << 24;
+    const uint32_t stride = P.stride;
+    const uint32_t c1u = P.c1u;
+    const bool hi_uniform = P.flags & kK1HiUniform;
+    const bool pre_ok = P.flags & kK1Below2p40;
+    const uint64_t k_hi = P.khi, k_24 = P.k24;
     int32_t dpend = 0;  // dense entries appended and not yet resolved (wave-uniform)
     const uint32_t g0 = (uint32_t)g_begin;
-    uint32_t base = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + (threadIdx.x & ~63u)) * U);
-    const uint32_t ghi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(g_begin >> 32));
+    uint32_t base = __builtin_amdgcn_readfirstlane((blockIdx.x * BS + (threadIdx.x & ~63u)) * U);
+    const uint32_t ghi = P.ghi;
     uint32_t gl = g0 + base + lane;
-    const uint32_t off_steady =
-        __builtin_amdgcn_readfirstlane((int)std::max<uint32_t>(off_sparse, (lo & 15) ? 1u : 0u));
-    const uint32_t ng_steady = __builtin_amdgcn_readfirstlane((int)(ng - ((hi & 15) ? 1u : 0u)));
+    const uint32_t off_steady = P.off_steady, ng_steady = P.ng_steady;
 
     // one queue entry per lane (valid lanes): its pair's first zero byte by level 1; the pair's other
     // zero bytes go back to the queue; a dense / clipped pair (a z half 0) recomputes both blocks.  An
@@ -362,26 +426,27 @@ __device__ __forceinline__ void k1_body_q(const DrawKey& dk, uint32_t k, uint64_
         __builtin_amdgcn_wave_barrier();
         rounds();
     };
-    if (A > 0) {
+    if (P.A > 0) {
         constexpr uint32_t UB = (W / 2) * U * 64;
-        const uint32_t units = (ng + UB - 1) / UB;
-        const uint32_t wg = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-        const uint32_t nB = gridDim.x * (blockDim.x >> 6) - W1;
+        const uint32_t W1 = P.W1;
+        const uint32_t wg = __builtin_amdgcn_readfirstlane((blockIdx.x * BS + threadIdx.x) >> 6);
         const bool ga = wg < W1;
-        const uint32_t cnt = ga ? A : B, u_step = ga ? W1 : nB, u_first = ga ? wg : W1 * A + (wg - W1);
-        for (uint32_t j = 0; j < cnt; ++j) {  // wave-uniform
-            const uint32_t u = u_first + j * u_step;
-            if (u >= units) break;
-            uint32_t ub = u * UB;
-            gl = g0 + ub + lane;
-            if (ub >= off_steady && ub + UB <= ng_steady) {
-#pragma unroll
-                for (int t = 0; t < W / 2; ++t) steady(t * (U * 64));
-                __builtin_amdgcn_wave_barrier();
-                rounds();
-            } else {  // a unit holding dense / clipped blocks or the launch's end
-                for (int t = 0; t < W / 2 && ub < ng; ++t, ub += U * 64, gl += U * 64) partial(ub);
+        if (ga) {  // this wave's share of the slow iterations, before its units
+            for (uint32_t d = wg; d < P.slow_iters; d += W1) {  // wave-uniform
+                const uint32_t b = d < P.head_iters ? d * (U * 64) : P.tail_off + (d - P.head_iters) * (U * 64);
+                gl = g0 + b + lane;
+                partial(b);
             }
+        }
+        const uint32_t cnt = ga ? P.A : P.B, u_step = ga ? W1 : P.nB, u_first = ga ? wg : W1 * P.A + (wg - W1);
+        for (uint32_t j = 0; j < cnt; ++j) {  // wave-uniform; every unit is steady
+            const uint32_t u = u_first + j * u_step;
+            if (u >= P.units) break;
+            gl = g0 + P.unit_off + u * UB + lane;
+#pragma unroll
+            for (int t = 0; t < W / 2; ++t) steady(t * (U * 64));
+            __builtin_amdgcn_wave_barrier();
+            rounds();
         }
         base = ng;  // the grid-stride loop below has nothing left
     }

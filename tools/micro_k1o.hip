@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include <algorithm>
 #include <vector>
@@ -74,10 +75,10 @@ struct K1QLds {
 };
 template <int W, bool FAST = false>
 __global__ __launch_bounds__(256) void k1_q(DrawKey dk, uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin,
-                                            uint64_t n_groups, unsigned long long* __restrict__ win) {
+                                            uint64_t n_groups, unsigned long long* __restrict__ win, K1Launch P) {
     __shared__ K1QLds<W> L;
     const int w = threadIdx.x >> 6;
-    k1_body_q<W, FAST>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w]);
+    k1_body_q<W, FAST>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
 }
 
 // the product body (a copy) with the tail cost probe (tools/k1_dev_bodies.h)
@@ -103,22 +104,20 @@ __global__ __launch_bounds__(256) void k1_qs(DrawKey dk, uint32_t k, uint64_t lo
 // rounds the product then took -- 81.5-82.1 vs 80.6-81.0 us, profiles/r05/micro_k1o_trim.jsonl)
 template <int W, bool FAST, bool TRIM>
 __global__ __launch_bounds__(256) void k1_qp(DrawKey dk, uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin,
-                                             uint64_t n_groups, unsigned long long* __restrict__ win, uint32_t W1,
-                                             uint32_t A, uint32_t B) {
+                                             uint64_t n_groups, unsigned long long* __restrict__ win, K1Launch P) {
     __shared__ K1QLds<W> L;
     const int w = threadIdx.x >> 6;
     (void)TRIM;
-    k1_body_q<W, FAST>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], W1, A, B);
+    k1_body_q<W, FAST>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
 }
 
 // the product body with the workgroup-pooled tail (round 6; k1_qp keeps the per-wave tail)
 template <int W, bool FAST>
 __global__ __launch_bounds__(256) void k1_qpp(DrawKey dk, uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin,
-                                              uint64_t n_groups, unsigned long long* __restrict__ win, uint32_t W1,
-                                              uint32_t A, uint32_t B) {
+                                              uint64_t n_groups, unsigned long long* __restrict__ win, K1Launch P) {
     __shared__ K1QLds<W> L;
     const int w = threadIdx.x >> 6;
-    k1_body_q<W, FAST>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], W1, A, B, L.pool);
+    k1_body_q<W, FAST>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P, L.pool);
 }
 
 // the product body over its plan with each wave's shader clock stamped at entry and exit (a separate
@@ -126,18 +125,60 @@ __global__ __launch_bounds__(256) void k1_qpp(DrawKey dk, uint32_t k, uint64_t l
 // dt = s_memtime ticks (shader cycles), dr = s_memrealtime ticks (100 MHz) -> the in-kernel clock
 template <int W, bool FAST>
 __global__ __launch_bounds__(256) void k1_qclk(DrawKey dk, uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin,
-                                               uint64_t n_groups, unsigned long long* __restrict__ win, uint32_t W1,
-                                               uint32_t A, uint32_t B, unsigned long long* __restrict__ stamps) {
+                                               uint64_t n_groups, unsigned long long* __restrict__ win, K1Launch P,
+                                               unsigned long long* __restrict__ stamps) {
     __shared__ K1QLds<W> L;
     const int w = threadIdx.x >> 6;
     const uint64_t t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-    k1_body_q<W, FAST>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], W1, A, B);
+    k1_body_q<W, FAST>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
     const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if ((threadIdx.x & 63) == 0) {  // vector stores
         stamps[2 * wave] = t1 - t0;
         stamps[2 * wave + 1] = r1 - r0;
     }
+}
+
+// the wave timeline (mode 'T'; a diagnostic kernel like k1_qclk, the product kernels carry no stamps): per wave
+// its first and last s_memrealtime (100 MHz, one counter for the chip), where it ran (HW_ID: SIMD, CU, SE; XCC_ID)
+// and how many units of the plan it took
+struct WaveStamp {
+    unsigned long long t0, t1, where, units;
+};
+template <int W, bool FAST>
+__global__ __launch_bounds__(256) void k1_qtl(DrawKey dk, uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin,
+                                              uint64_t n_groups, unsigned long long* __restrict__ win, K1Launch P,
+                                              WaveStamp* __restrict__ stamps) {
+    __shared__ K1QLds<W> L;
+    const int w = threadIdx.x >> 6;
+    const uint64_t r0 = __builtin_amdgcn_s_memrealtime();
+    k1_body_q<W, FAST>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
+    const uint64_t r1 = __builtin_amdgcn_s_memrealtime();
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t hw = __builtin_amdgcn_s_getreg(4 | (31 << 11));   // HW_REG_HW_ID, 32 bits
+    const uint32_t xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11));  // HW_REG_XCC_ID, bits 3:0
+    if ((threadIdx.x & 63) == 0) {  // vector stores
+        // its steady units, and in the high word its slow iterations (the first group's waves take those)
+        uint32_t cnt = 0, slow = 0;
+        for (uint32_t j = 0; j < (wave < P.W1 ? P.A : P.B); ++j)
+            cnt += (wave < P.W1 ? wave + j * P.W1 : P.W1 * P.A + (wave - P.W1) + j * P.nB) < P.units;
+        for (uint32_t d = wave; wave < P.W1 && d < P.slow_iters; d += P.W1) ++slow;
+        stamps[wave] = WaveStamp{r0, r1, ((unsigned long long)xcc << 32) | hw, ((unsigned long long)slow << 32) | cnt};
+    }
+}
+
+// the launch-uniform values of a launch (rsv_scan.h k1_launch): grid-stride over `grid` workgroups, or the two-group
+// schedule (W1, A, B), whose grid comes back in `grid` (0: the schedule does not fit the launch)
+template <int W = 12>
+static K1Launch stride_vals(uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin, uint64_t ng, int grid) {
+    return k1_launch<W>(k, lo, hi, g_begin, ng, (unsigned)grid);
+}
+template <int W = 12>
+static K1Launch plan_vals(uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin, uint64_t ng, uint32_t W1, uint32_t A,
+                          uint32_t B, int& grid) {
+    K1Launch P = k1_launch<W>(k, lo, hi, g_begin, ng, 1u);
+    grid = (int)k1_schedule(P, W1, A, B);
+    return P;
 }
 
 // a stand-in for a collective running beside K1 (RCCL's all-gather kernel: a few workgroups for tens
@@ -202,7 +243,9 @@ int main(int argc, char** argv) {
         CK(hipFree(di));
         CK(hipFree(dout));
         printf("{\"fold_check_nop\": %d, \"bad\": %d, \"of\": %d}\n", nop, bad, 20 * N);
-    }    const uint64_t n = 1000000000ull, lo = 1024, n_groups = (n + 15) / 16;
+    }
+    // the launch: 1e9 draws, or K1O_N of them (the schedule modes at other sizes)
+    const uint64_t n = getenv("K1O_N") ? (uint64_t)atof(getenv("K1O_N")) : 1000000000ull, lo = 1024, n_groups = (n + 15) / 16;
     const uint32_t k = 1024;
     DrawKey dk{0xC0FFEE, 0, 0x5A5A, 0};
     unsigned long long* win;
@@ -211,24 +254,24 @@ int main(int argc, char** argv) {
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
     std::vector<unsigned long long> ref(k), got(k);
-    auto run = [&](auto kern, int grid, std::vector<unsigned long long>& out) -> int {
+    auto run = [&](auto kern, int grid, std::vector<unsigned long long>& out, auto... more) -> int {
         CK(hipMemset(win, 0, k * 8));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win, more...);
         CK(hipMemcpy(out.data(), win, k * 8, hipMemcpyDeviceToHost));
         return 0;
     };
-    auto time_v = [&](auto kern, const char* name, int grid) -> int {
+    auto time_v = [&](auto kern, const char* name, int grid, auto... more) -> int {
         for (int rep = 0; rep < 3; ++rep)
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win, more...);
         const int reps = 20;
         CK(hipEventRecord(e0));
         for (int rep = 0; rep < reps; ++rep)
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win, more...);
         CK(hipEventRecord(e1));
         CK(hipEventSynchronize(e1));
         float ms;
         CK(hipEventElapsedTime(&ms, e0, e1));
-        if (run(kern, grid, got)) return 1;
+        if (run(kern, grid, got, more...)) return 1;
         printf("{\"kernel\": \"%s\", \"grid\": %d, \"us\": %.2f, \"winners_match\": %s}\n", name, grid,
                ms / reps * 1e3, got == ref ? "true" : "false");
         return 0;
@@ -257,15 +300,14 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (argc > 1 && argv[1][0] == 'c') {  // K1 beside a concurrent occupier kernel: plan vs grid-stride
-        const uint32_t W1 = 6144, A = 10, B = 2;
-        const uint64_t units = (n_groups + 767) / 768, waves = W1 + (units - (uint64_t)W1 * A + 1) / 2;
-        const int pgrid = (int)((waves + 3) / 4);
+        int pgrid;
+        const K1Launch PP = plan_vals(k, lo, n, 0, n_groups, 6144, 10, 2, pgrid), PS = stride_vals(k, lo, n, 0, n_groups, 5086);
         hipStream_t s1, s2;
         CK(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking));
         CK(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
         for (int rep = 0; rep < 3000; ++rep)
             hipLaunchKernelGGL((k1_qp<12, true, false>), dim3(pgrid), dim3(256), 0, s1, dk, k, lo, n, 0ull, n_groups, win,
-                               W1, A, B);
+                               PP);
         CK(hipDeviceSynchronize());
         for (int occ : {0, 16, 64}) {
             for (int p = 0; p < 3; ++p)
@@ -275,10 +317,10 @@ int main(int argc, char** argv) {
                     for (int rep = 0; rep < reps; ++rep) {
                         CK(hipEventRecord(e0, s1));
                         if (v == 0)
-                            hipLaunchKernelGGL((k1_q<12, true>), dim3(5086), dim3(256), 0, s1, dk, k, lo, n, 0ull, n_groups, win);
+                            hipLaunchKernelGGL((k1_q<12, true>), dim3(5086), dim3(256), 0, s1, dk, k, lo, n, 0ull, n_groups, win, PS);
                         else
                             hipLaunchKernelGGL((k1_qp<12, true, false>), dim3(pgrid), dim3(256), 0, s1, dk, k, lo, n, 0ull,
-                                               n_groups, win, W1, A, B);
+                                               n_groups, win, PP);
                         if (occ) hipLaunchKernelGGL(occupy, dim3(occ), dim3(256), 0, s2, 30000ull);
                         CK(hipEventRecord(e1, s1));
                         CK(hipEventSynchronize(e1));
@@ -294,25 +336,24 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (argc > 1 && argv[1][0] == 'k') {  // K1's in-kernel clock (stamped diagnostic kernel, see k1_qclk)
-        const uint32_t W1 = 6144, A = 10, B = 2;
-        const uint64_t units = (n_groups + 767) / 768, waves = W1 + (units - (uint64_t)W1 * A + 1) / 2;
-        const int pgrid = (int)((waves + 3) / 4);
+        int pgrid;
+        const K1Launch PP = plan_vals(k, lo, n, 0, n_groups, 6144, 10, 2, pgrid);
         unsigned long long* stamps;
         CK(hipMalloc(&stamps, (size_t)pgrid * 4 * 16));
         // >= 2 s of back-to-back launches first (the clock settles under load)
         for (int rep = 0; rep < 25000; ++rep)
             hipLaunchKernelGGL((k1_qp<12, true, false>), dim3(pgrid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win,
-                               W1, A, B);
+                               PP);
         CK(hipDeviceSynchronize());
         for (int p = 0; p < 5; ++p) {
             const int reps = 20;
             CK(hipEventRecord(e0));
             for (int rep = 0; rep < reps; ++rep)
                 hipLaunchKernelGGL((k1_qp<12, true, false>), dim3(pgrid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups,
-                                   win, W1, A, B);
+                                   win, PP);
             CK(hipEventRecord(e1));
-            hipLaunchKernelGGL((k1_qclk<12, true>), dim3(pgrid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win, W1, A,
-                               B, stamps);
+            hipLaunchKernelGGL((k1_qclk<12, true>), dim3(pgrid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win, PP,
+                               stamps);
             CK(hipDeviceSynchronize());
             float ms;
             CK(hipEventElapsedTime(&ms, e0, e1));
@@ -330,29 +371,34 @@ int main(int argc, char** argv) {
     }
     if (argc > 1 && argv[1][0] == 'o') {  // round 6: per-wave vs workgroup-pooled tail; argv[2..] "W1:A:B" plans
         // (the r05 schedule body k1_body_q_sched -- round-5 steady and tail -- beside them at 6144:10:2)
-        const uint32_t units = (uint32_t)((n_groups + 767) / 768);
-        for (int rep = 0; rep < 3000; ++rep)
-            hipLaunchKernelGGL((k1_qpp<12, true>), dim3(4024), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win, 6144u,
-                               10u, 2u);
+        {
+            int wgrid;
+            const K1Launch PW = plan_vals(k, lo, n, 0, n_groups, 6144, 10, 2, wgrid);
+            for (int rep = 0; rep < 3000; ++rep)
+                hipLaunchKernelGGL((k1_qpp<12, true>), dim3(wgrid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win, PW);
+        }
         CK(hipDeviceSynchronize());
         for (int p = 0; p < 3; ++p)
             for (int a = 2; a < argc; ++a) {
                 unsigned W1, A, B;
                 if (sscanf(argv[a], "%u:%u:%u", &W1, &A, &B) != 3) return 2;
-                const uint64_t rest = (uint64_t)units > (uint64_t)W1 * A ? units - (uint64_t)W1 * A : 0;
-                const uint64_t waves = std::min<uint64_t>(W1, (units + A - 1) / A) + (rest + B - 1) / B;
-                const int grid = (int)((waves + 3) / 4);
+                int grid;
+                const K1Launch PP = plan_vals(k, lo, n, 0, n_groups, W1, A, B, grid);
+                if (!grid) continue;  // no unit left for the second group
+                // the r05 schedule body deals whole units (dense ones included): its own grid
+                const uint64_t units = (n_groups + 767) / 768, rest = units > (uint64_t)W1 * A ? units - (uint64_t)W1 * A : 0;
+                const int sgrid = (int)((std::min<uint64_t>(W1, (units + A - 1) / A) + (rest + B - 1) / B + 3) / 4);
                 for (int v = 0; v < 3; ++v) {
                     if (v == 2 && !(W1 == 6144 && A == 10 && B == 2)) continue;
                     auto launch = [&]() {
                         if (v == 0)
                             hipLaunchKernelGGL((k1_qp<12, true, false>), dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull,
-                                               n_groups, win, W1, A, B);
+                                               n_groups, win, PP);
                         else if (v == 1)
                             hipLaunchKernelGGL((k1_qpp<12, true>), dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups,
-                                               win, W1, A, B);
+                                               win, PP);
                         else
-                            hipLaunchKernelGGL((k1_qs<12, true>), dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups,
+                            hipLaunchKernelGGL((k1_qs<12, true>), dim3(sgrid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups,
                                                win, W1, A, B);
                     };
                     for (int rep = 0; rep < 3; ++rep) launch();
@@ -375,30 +421,27 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (argc > 1 && argv[1][0] == 'w') {  // window length under the two-group plan: W = 8 / 12 / 16
-        auto plan_for = [&](uint64_t UB, uint32_t& A) {
-            const uint64_t units = (n_groups + UB - 1) / UB;
-            A = (uint32_t)((units * 755 / 1000 + 3072) / 6144);
-            const uint64_t waves = 6144 + (units - 6144ull * A + 1) / 2;
-            return (int)((waves + 3) / 4);
-        };
-        uint32_t A8, A12, A16;
-        const int g8 = plan_for(512, A8), g12 = plan_for(768, A12), g16 = plan_for(1024, A16);
+        auto share = [&](uint64_t UB) { return (uint32_t)(((n_groups + UB - 1) / UB * 755 / 1000 + 3072) / 6144); };
+        int g8, g12, g16;
+        const K1Launch P8 = plan_vals<8>(k, lo, n, 0, n_groups, 6144, share(512), 2, g8);
+        const K1Launch P12 = plan_vals<12>(k, lo, n, 0, n_groups, 6144, share(768), 2, g12);
+        const K1Launch P16 = plan_vals<16>(k, lo, n, 0, n_groups, 6144, share(1024), 2, g16);
         for (int rep = 0; rep < 3000; ++rep)
             hipLaunchKernelGGL((k1_qp<12, true, false>), dim3(g12), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win,
-                               6144u, A12, 2u);
+                               P12);
         CK(hipDeviceSynchronize());
         for (int p = 0; p < 4; ++p)
             for (int v = 0; v < 3; ++v) {
                 auto launch = [&]() {
                     if (v == 0)
                         hipLaunchKernelGGL((k1_qp<8, true, false>), dim3(g8), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups,
-                                           win, 6144u, A8, 2u);
+                                           win, P8);
                     else if (v == 1)
                         hipLaunchKernelGGL((k1_qp<12, true, false>), dim3(g12), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups,
-                                           win, 6144u, A12, 2u);
+                                           win, P12);
                     else
                         hipLaunchKernelGGL((k1_qp<16, true, false>), dim3(g16), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups,
-                                           win, 6144u, A16, 2u);
+                                           win, P16);
                 };
                 for (int rep = 0; rep < 3; ++rep) launch();
                 const int reps = 20;
@@ -428,9 +471,11 @@ int main(int argc, char** argv) {
                 g = std::max<uint64_t>(1, ng / (per_window * mm));
             }
             const uint64_t units = (ng + 767) / 768, A = (units * 755 / 1000 + 3072) / 6144;
-            const bool plan = ng >= per_window * 768 && A >= 4;
-            const uint64_t waves = plan ? 6144 + (units - 6144 * A + 1) / 2 : 0;
-            const int pg = plan ? (int)((waves + 3) / 4) : 0;
+            const K1Launch PS = stride_vals(k, lo, nn, lo / 16, ng, (int)g);
+            // the plan's A: all the steady units but 5400 .. 5400 + 6144 for the second group (k1_plan)
+            int pg = 0;
+            const K1Launch PP = plan_vals(k, lo, nn, lo / 16, ng, 6144, PS.units > 5400 ? (PS.units - 5400) / 6144 : 0, 2, pg);
+            const bool plan = A >= 3 && pg > 0;
             std::vector<unsigned long long> r0(k), r1(k);
             float best0 = 1e9f, best1 = 1e9f;
             for (int p = 0; p < 3; ++p) {
@@ -438,10 +483,10 @@ int main(int argc, char** argv) {
                     if (v == 1 && !plan) continue;
                     auto launch = [&]() {
                         if (v == 0)
-                            hipLaunchKernelGGL((k1_q<12, true>), dim3((unsigned)g), dim3(256), 0, 0, dk, k, lo, nn, lo / 16, ng, win);
+                            hipLaunchKernelGGL((k1_q<12, true>), dim3((unsigned)g), dim3(256), 0, 0, dk, k, lo, nn, lo / 16, ng, win, PS);
                         else
-                            hipLaunchKernelGGL((k1_qs<12, true>), dim3(pg), dim3(256), 0, 0, dk, k, lo, nn, lo / 16, ng, win,
-                                               6144u, (uint32_t)A, 2u);
+                            hipLaunchKernelGGL((k1_qp<12, true, false>), dim3(pg), dim3(256), 0, 0, dk, k, lo, nn, lo / 16, ng,
+                                               win, PP);
                     };
                     for (int rep = 0; rep < 3; ++rep) launch();
                     const int reps = 10;
@@ -459,25 +504,113 @@ int main(int argc, char** argv) {
                 }
             }
             printf("{\"n\": %.3g, \"grid_stride_us\": %.2f, \"grid\": %llu, \"plan_A\": %llu, \"plan_grid\": %d, \"plan_us\": %.2f, "
-                   "\"winners_match\": %s}\n", (double)nn, best0, (unsigned long long)g, plan ? (unsigned long long)A : 0ull,
+                   "\"winners_match\": %s}\n", (double)nn, best0, (unsigned long long)g, plan ? (unsigned long long)PP.A : 0ull,
                    pg, plan ? best1 : 0.0f, plan ? (r0 == r1 ? "true" : "false") : "null");
         }
         return 0;
     }
-    if (argc > 1 && argv[1][0] == 's') {  // static two-group schedules vs the product grid
-        // argv[2..]: "W1:A:B" triples (W1 waves of A half windows, the rest B each)
-        const uint32_t units = (uint32_t)((n_groups + 767) / 768);
+    if (argc > 1 && argv[1][0] == 'T') {  // the wave timeline of one warm launch of the plan; argv[2]: "W1:A:B"
+        unsigned W1 = 6144, A = 10, B = 2;
+        if (argc > 2 && sscanf(argv[2], "%u:%u:%u", &W1, &A, &B) != 3) return 2;
+        int grid;
+        const K1Launch PP = plan_vals(k, lo, n, 0, n_groups, W1, A, B, grid);
+        if (!grid) return 2;
+        const uint32_t nw = (uint32_t)grid * 4;
+        WaveStamp* stamps;
+        CK(hipMalloc(&stamps, (size_t)nw * sizeof(WaveStamp)));
+        auto plain = [&]() {
+            hipLaunchKernelGGL((k1_qp<12, true, false>), dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win, PP);
+        };
+        for (int rep = 0; rep < 25000; ++rep) plain();  // >= 2 s of load: the clock settles
+        CK(hipDeviceSynchronize());
         for (int p = 0; p < 3; ++p) {
-            if (time_v(k1_q<12, true>, "q12fast", 5086)) return 1;
+            const int reps = 20;
+            CK(hipEventRecord(e0));
+            for (int rep = 0; rep < reps; ++rep) plain();
+            CK(hipEventRecord(e1));
+            CK(hipMemset(stamps, 0, (size_t)nw * sizeof(WaveStamp)));
+            hipLaunchKernelGGL((k1_qtl<12, true>), dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win, PP,
+                               stamps);
+            CK(hipDeviceSynchronize());
+            float ms;
+            CK(hipEventElapsedTime(&ms, e0, e1));
+            std::vector<WaveStamp> st(nw);
+            CK(hipMemcpy(st.data(), stamps, (size_t)nw * sizeof(WaveStamp), hipMemcpyDeviceToHost));
+            unsigned long long t0 = ~0ull, tend = 0;
+            for (const WaveStamp& s : st) t0 = std::min(t0, s.t0), tend = std::max(tend, s.t1);
+            auto us = [&](unsigned long long t) { return (double)(t - t0) * 0.01; };
+            // ends per class, and each class's running time (median, max)
+            double end1 = 0, endd = 0, end2 = 0, start2 = 1e9, start2_last = 0;
+            std::vector<double> d1, dd, d2;
+            std::vector<unsigned long long> simds;
+            for (uint32_t w = 0; w < nw; ++w) {
+                const WaveStamp& s = st[w];
+                const double dur = (double)(s.t1 - s.t0) * 0.01;
+                simds.push_back(s.where & 0xF0000FF30ull);  // XCC | SE, SH, CU, SIMD
+                const bool slow = (s.units >> 32) != 0;  // it took dense or clipped iterations
+                if (slow) endd = std::max(endd, us(s.t1)), dd.push_back(dur);
+                if (w < W1) {
+                    end1 = std::max(end1, us(s.t1));
+                    if (!slow) d1.push_back(dur);
+                } else {
+                    end2 = std::max(end2, us(s.t1)), start2 = std::min(start2, us(s.t0));
+                    start2_last = std::max(start2_last, us(s.t0));
+                    if (!slow) d2.push_back(dur);
+                }
+            }
+            std::sort(simds.begin(), simds.end());
+            const size_t n_simd = std::unique(simds.begin(), simds.end()) - simds.begin();
+            auto med = [](std::vector<double>& v) { std::sort(v.begin(), v.end()); return v.empty() ? 0.0 : v[v.size() / 2]; };
+            const double m1 = med(d1), md = med(dd), m2 = med(d2);
+            // resident waves over time: the peak, and how long the launch runs below 95 % of it at either end
+            std::vector<std::pair<unsigned long long, int>> ev;
+            for (const WaveStamp& s : st) ev.push_back({s.t0, +1}), ev.push_back({s.t1, -1});
+            std::sort(ev.begin(), ev.end());
+            int res = 0, peak = 0;
+            for (auto& e : ev) res += e.second, peak = std::max(peak, res);
+            unsigned long long t_full = tend, t_last_full = t0;
+            res = 0;
+            for (auto& e : ev) {
+                res += e.second;
+                if (res * 100 >= peak * 95) t_full = std::min(t_full, e.first), t_last_full = std::max(t_last_full, e.first);
+            }
+            // waves resident at every whole microsecond
+            std::vector<int> per_us((size_t)us(tend) + 1, 0);
+            for (const WaveStamp& s : st)
+                for (size_t u = (size_t)(us(s.t0) + 0.999999); u < per_us.size() && u <= us(s.t1); ++u) ++per_us[u];
+            printf("{\"mode\": \"wave_timeline\", \"W1\": %u, \"A\": %u, \"B\": %u, \"waves\": %u, \"simds_seen\": %zu, "
+                   "\"plain_launch_us\": %.2f, \"stamped_span_us\": %.2f, \"first_group_last_end_us\": %.2f, "
+                   "\"dense_or_clipped_waves\": %zu, \"dense_last_end_us\": %.2f, \"second_group_first_start_us\": %.2f, "
+                   "\"second_group_last_start_us\": %.2f, \"second_group_last_end_us\": %.2f, "
+                   "\"run_us_median\": {\"first_group\": %.2f, \"dense\": %.2f, \"second_group\": %.2f}, "
+                   "\"run_us_max\": {\"first_group\": %.2f, \"dense\": %.2f, \"second_group\": %.2f}, "
+                   "\"peak_resident_waves\": %d, \"ramp_below_95pct_us\": %.2f, \"drain_below_95pct_us\": %.2f, "
+                   "\"resident_per_us\": [",
+                   W1, A, B, nw, n_simd, ms / reps * 1e3, us(tend), end1, dd.size(), endd, start2, start2_last, end2, m1,
+                   md, m2, d1.empty() ? 0.0 : d1.back(), dd.empty() ? 0.0 : dd.back(), d2.empty() ? 0.0 : d2.back(), peak,
+                   us(t_full), (double)(tend - t_last_full) * 0.01);
+            for (size_t u = 0; u < per_us.size(); ++u) printf("%s%d", u ? ", " : "", per_us[u]);
+            printf("]}\n");
+        }
+        return 0;
+    }
+    if (argc > 1 && argv[1][0] == 's') {  // static two-group schedules of the product body vs the product grid
+        // argv[2..]: "W1:A:B" triples (W1 waves of A steady half windows after their slow iterations, the rest B each)
+        for (int rep = 0; rep < 3000; ++rep)  // the clock ramps over the first launches
+            hipLaunchKernelGGL((k1_q<12, true>), dim3(5086), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win,
+                               stride_vals(k, lo, n, 0, n_groups, 5086));
+        CK(hipDeviceSynchronize());
+        for (int p = 0; p < 3; ++p) {
+            if (time_v(k1_q<12, true>, "q12fast", 5086, stride_vals(k, lo, n, 0, n_groups, 5086))) return 1;
             for (int a = 2; a < argc; ++a) {
                 unsigned W1, A, B;
                 if (sscanf(argv[a], "%u:%u:%u", &W1, &A, &B) != 3) return 2;
-                const uint64_t rest = (uint64_t)units > (uint64_t)W1 * A ? units - (uint64_t)W1 * A : 0;
-                const uint64_t waves = std::min<uint64_t>(W1, (units + A - 1) / A) + (rest + B - 1) / B;
-                const int grid = (int)((waves + 3) / 4);
+                int grid;
+                const K1Launch PP = plan_vals(k, lo, n, 0, n_groups, W1, A, B, grid);
+                if (!grid) continue;  // no unit left for the second group
                 auto launch = [&]() {
-                    hipLaunchKernelGGL((k1_qs<12, true>), dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win,
-                                       W1, A, B);
+                    hipLaunchKernelGGL((k1_qp<12, true, false>), dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win,
+                                       PP);
                 };
                 for (int rep = 0; rep < 3; ++rep) launch();
                 const int reps = 20;
@@ -504,8 +637,8 @@ int main(int argc, char** argv) {
         for (int g : grids) {
             if (time_v(k1_base, "base", g)) return 1;
             if (time_v(k1_pair<12>, "pair12", g)) return 1;
-            if (time_v(k1_q<12>, "q12", g)) return 1;
-            if (time_v(k1_q<12, true>, "q12fast", g)) return 1;
+            if (time_v(k1_q<12>, "q12", g, stride_vals(k, lo, n, 0, n_groups, g))) return 1;
+            if (time_v(k1_q<12, true>, "q12fast", g, stride_vals(k, lo, n, 0, n_groups, g))) return 1;
         }
     return 0;
 }
