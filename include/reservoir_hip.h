@@ -446,6 +446,51 @@ rsv_status rsv_sample_segmented_rows_merge(const void* part_rows_dev, const int6
                                            int32_t key_width, int32_t k, void* state_rows_dev,
                                            int64_t* state_idx_dev, int64_t* state_next_dev, void* hip_stream);
 
+/* The grouping pass: a micro-batch in arrival order, each element tagged with its state row, to the dense
+ * CSR the segmented update entry points take.  ids_dev[i] (int64 for id_width 8, the stream_ids convention,
+ * or int32 for id_width 4) is the state row of the batch's i-th element.  offsets_dev[num_states + 1]:
+ * [offsets[r], offsets[r+1]) is row r's range in order_dev, empty for a row the batch does not name;
+ * offsets[0] = 0.  order_dev[n]: order[offsets[r] + p] is the position in the batch of row r's p-th element
+ * in arrival order.  An id outside [0, num_states) is not an error: those elements are dropped,
+ * offsets[num_states] is the number of kept elements, and the dropped positions follow at
+ * order[offsets[num_states] .. n) in arrival order, so order_dev is always a permutation of [0, n).
+ * The result is a function of the input alone (a stable partition: no arrival order is decided by an
+ * atomic).  Because the CSR is dense the number of rows present never reaches the host: the update
+ * entry points take it with stream_ids_dev = NULL and num_segments = num_states, and skip the empty
+ * segments.  Stream-ordered on hip_stream without a host wait; scratch of at most 12.25 bytes per element
+ * comes from the stream-ordered allocator and returns to it.  Checked in this order, before anything
+ * touches the device: offsets_dev NULL, then order_dev / ids_dev NULL with n > 0: RSV_E_NULL_POINTER;
+ * n < 0 or num_states < 1: RSV_E_ILLEGAL_ARGUMENT; id_width not 4 or 8: RSV_E_UNSUPPORTED;
+ * n > 2^31 - 1 (order_dev is int32) or num_states > 2^32 - 2: RSV_E_UNSUPPORTED.  n = 0 writes every
+ * offset as 0. */
+rsv_status rsv_group_by_stream(const void* ids_dev, int32_t id_width, int64_t n, int64_t num_states,
+                               int64_t* offsets_dev, int32_t* order_dev, void* hip_stream);
+
+/* rsv_sample_segmented_update through a permutation: segment b's p-th element is
+ * keys_dev[order_dev[offsets[b] + p]] instead of keys_dev[offsets[b] + p]; everything else -- segments,
+ * stream_ids_dev, bases_dev, the skipped segments, widths, k and the state -- is as there.  keys_dev holds
+ * n_keys keys in arrival order and order_dev n_keys entries in [0, n_keys), what rsv_group_by_stream
+ * writes; with its offsets, stream_ids_dev = NULL, bases_dev = NULL and num_segments = num_states this
+ * is the by-id update.  order_dev is read only for the slots a segment replaces (at most k entries per
+ * segment) and no other key is read or moved.  A slot whose entry lies outside [0, n_keys) is left as it
+ * is, key and idx, rather than dereferenced.  order_dev NULL: RSV_E_NULL_POINTER. */
+rsv_status rsv_sample_segmented_update_indirect(const void* keys_dev, int64_t n_keys, const int32_t* order_dev,
+                                                const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                                const int64_t* bases_dev, int64_t num_segments, int64_t num_states,
+                                                int32_t key_width, int32_t k, uint64_t seed, uint64_t stream_base,
+                                                void* state_keys_dev, int64_t* state_idx_dev, int64_t* state_next_dev,
+                                                void* hip_stream);
+
+/* rsv_sample_segmented_rows_update through a permutation, as rsv_sample_segmented_update_indirect:
+ * segment b's p-th row is row order_dev[offsets[b] + p] of rows_dev (n_rows rows of key_width bytes). */
+rsv_status rsv_sample_segmented_rows_update_indirect(const void* rows_dev, int64_t n_rows, const int32_t* order_dev,
+                                                     const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                                     const int64_t* bases_dev, int64_t num_segments,
+                                                     int64_t num_states, int32_t key_width, int32_t k, uint64_t seed,
+                                                     uint64_t stream_base, void* state_rows_dev,
+                                                     int64_t* state_idx_dev, int64_t* state_next_dev,
+                                                     void* hip_stream);
+
 /* Segmented sampling without keys (Sampler.apply for any B over S streams): the elements stay with the
  * caller, only the streams' lengths reach the device.  Stream s has len = offsets[s+1] - offsets[s]
  * elements (offsets_dev is read for its differences alone) and Philox stream id stream_base + s;

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "rsv_distinct_segmented_ordered_update", "rsv_distinct_segmented_rows_ordered_update",
     "rsv_distinct_segmented_candidates",
     "rsv_sample_segmented_indexed", "rsv_sample_segmented_indexed_update", "rsv_sample_segmented_indexed_merge",
+    "rsv_group_by_stream", "rsv_sample_segmented_update_indirect", "rsv_sample_segmented_rows_update_indirect",
 )
 
 
@@ -145,6 +146,9 @@ def load():
     L.rsv_sample_segmented_indexed.argtypes = [vp, i64, i32, u64, u64, vp, vp, vp]
     L.rsv_sample_segmented_indexed_update.argtypes = [vp, vp, vp, i64, i64, i32, u64, u64, vp, vp, vp, vp, vp]
     L.rsv_sample_segmented_indexed_merge.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp, vp]
+    L.rsv_group_by_stream.argtypes = [vp, i32, i64, i64, vp, vp, vp]
+    L.rsv_sample_segmented_update_indirect.argtypes = [vp, i64, vp, vp, vp, vp, i64, i64, i32, i32, u64, u64, vp, vp, vp, vp]
+    L.rsv_sample_segmented_rows_update_indirect.argtypes = L.rsv_sample_segmented_update_indirect.argtypes
     L.rsv_distinct_segmented.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
     L.rsv_distinct_segmented_ordered.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp, vp]
     L.rsv_distinct_segmented_rows.argtypes = [vp, vp, vp, i64, i32, i32, i32, u64, u64, vp, vp, vp, vp]
@@ -195,7 +199,8 @@ def load():
                  "rsv_distinct_segmented_rows_ordered", "rsv_distinct_segmented_ordered_update",
                  "rsv_distinct_segmented_rows_ordered_update", "rsv_distinct_segmented_candidates",
                  "rsv_sample_segmented_indexed", "rsv_sample_segmented_indexed_update",
-                 "rsv_sample_segmented_indexed_merge"):
+                 "rsv_sample_segmented_indexed_merge", "rsv_group_by_stream",
+                 "rsv_sample_segmented_update_indirect", "rsv_sample_segmented_rows_update_indirect"):
         getattr(L, name).restype = i32
     if L.rsv_abi_version() != 1:
         raise ImportError("libreservoir_hip.so ABI version mismatch")

@@ -25,6 +25,9 @@ libreservoir_hip.so.  Every function raises if the engine is unavailable.
     sample_segmented_objects -- Sampler.apply for any B over S streams: the same launch, the elements picked on the host
     SegmentedObjectSampler -- the same as live state: (idx, next) on the device, a slot list per row on the host,
                          one launch per batch that reports the replaced slots (update), and merge by source part
+    group_by_stream   -- a micro-batch tagged by substream in arrival order to the dense CSR (offsets, order) over
+                         all rows, on the device; update_by_id(data, ids) on the element and distinct states is that
+                         pass and their update in one call (the element samplers read only their winners, through order)
     replay_events     -- K1': apply the reference's Algorithm-L eviction events on the GPU
     export_draws      -- the per-element draw sequence j_i of draw format R2
 """
@@ -115,6 +118,35 @@ def _check_stream_ids(torch, stream_ids, S: int) -> None:
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def group_by_stream(ids, num_streams: int):
+    """Group a micro-batch by substream on the device: ids in arrival order in, the dense CSR out.
+
+    ids: a 1-D int64 or int32 device tensor, ids[i] the state row of the batch's i-th element.  Returns
+    (offsets int64 (num_streams + 1,), order int32 (n,)) on ids' device: order[offsets[r]:offsets[r+1]] are the
+    batch positions of row r's elements in arrival order (empty for a row the batch does not name), ids outside
+    [0, num_streams) are dropped -- offsets[num_streams] elements are kept -- and their positions follow in
+    order[offsets[num_streams]:], in arrival order, so order is a permutation of [0, n).  The same input gives
+    the same tensors.  Runs on torch's current stream without a host wait.
+    """
+    import torch
+
+    L = N.load()
+    if not ids.is_cuda:
+        raise N.IllegalArgumentException("ids must be a device tensor")
+    if ids.dtype not in (torch.int64, torch.int32) or ids.dim() != 1:
+        raise N.IllegalArgumentException("ids must be a 1-D int64/int32 tensor")
+    if num_streams < 1:
+        raise N.IllegalArgumentException("num_streams must be at least 1")
+    ids = ids.contiguous()
+    n = ids.numel()
+    offsets = torch.empty(int(num_streams) + 1, dtype=torch.int64, device=ids.device)
+    order = torch.empty(n, dtype=torch.int32, device=ids.device)
+    with torch.cuda.device(ids.device):  # the pass allocates its scratch on the current device
+        N.check(L.rsv_group_by_stream(_ptr(ids) if n else None, ids.element_size(), n, int(num_streams), _ptr(offsets),
+                                      _ptr(order) if n else None, _stream_ptr(torch, ids.device)))
+    return offsets, order
 
 
 def _segd_kind(hash, precomputed: bool) -> int:
@@ -321,6 +353,23 @@ class _SegmentedState:
             _check_stream_ids(torch, out[1], self.num_streams)
         return out
 
+    def _group(self, torch, data, ids):
+        """The id side of an update_by_id: data (keys or rows in arrival order) and ids checked against the state,
+        then group_by_stream over the state's rows; None if there is nothing to feed."""
+        what = self._TENSORS[0]
+        if not (data.is_cuda and ids.is_cuda):
+            raise N.IllegalArgumentException(f"{what} and ids must be device tensors")
+        if ids.dtype not in (torch.int64, torch.int32) or ids.dim() != 1:
+            raise N.IllegalArgumentException("ids must be a 1-D int64/int32 tensor")
+        dev = self._state()[0].device
+        if data.device != dev or ids.device != dev:
+            raise N.IllegalArgumentException(f"{what} and ids must live on the state's device")
+        if data.dim() < 1 or data.shape[0] != ids.numel():
+            raise N.IllegalArgumentException(f"ids must hold one id per element of {what}")
+        if self.num_streams == 0 or ids.numel() == 0:
+            return None
+        return group_by_stream(ids, self.num_streams)
+
     def _merge(self, torch, fn, cls, parts):
         """merge() of every class: parts = (payload, per-slot, per-row) tensors, stacked (P, ...) or one part
         without the leading axis, or up to three states of class cls; fn is the native merge."""
@@ -391,6 +440,29 @@ class _DistinctState(_SegmentedState):
             _ptr(data), _ptr(hashes), _ptr(offsets), _ptr(stream_ids), B, self.num_streams, self._key_width(), self.k,
             kind, self.seed, self.stream_base, *(_ptr(t) for t in state), _stream_ptr(torch, state[0].device)))
         return self
+
+    def update_by_id(self, data, ids, hashes=None):
+        """The batch in arrival order, element i into row ids[i]: group_by_stream, one gather, then update().
+
+        data: the keys or rows update() takes, in arrival order; ids: int64 or int32, one per element; hashes as
+        update() takes them, one per element in arrival order.  The distinct kernels read every key of a segment,
+        so the keys (and hashes) are moved once, by index_select through the grouping's order; update() then runs
+        over the dense CSR -- every row a segment, the empty ones skipped -- with check_ids=False: nothing can
+        repeat, and elements whose id lies outside [0, num_streams) are dropped (they ride along behind the last
+        offset and are never read).  Within a row the elements keep their arrival order.  No host wait.
+        Returns self.
+        """
+        import torch
+
+        grouped = self._group(torch, data, ids)
+        if grouped is None:
+            return self
+        offsets, order = grouped
+        if hashes is not None:
+            if not hashes.is_cuda or hashes.dim() != 1 or hashes.numel() != ids.numel() or hashes.device != ids.device:
+                raise N.IllegalArgumentException("hashes must be a device tensor on the state's device, one per element")
+            hashes = hashes.index_select(0, order)
+        return self.update(data.index_select(0, order), offsets, None, hashes, check_ids=False)
 
 
 class _DistinctKeysState(_DistinctState):
@@ -964,6 +1036,33 @@ class SegmentedSampler(_SegmentedState):
             _stream_ptr(torch, self.keys.device)))
         return self
 
+    def update_by_id(self, keys, ids):
+        """The batch in arrival order, keys[i] into row ids[i]: group_by_stream, then one update launch.
+
+        keys: a 1-D tensor of the state's dtype; ids: int64 or int32, one per key.  The grouping's order stands
+        between the launch and the keys: only the at most k winning keys per row are read, through it, and no key
+        is moved.  Every row continues at its own next, in arrival order.  There is no host wait and nothing to
+        check: a row cannot repeat, and keys whose id lies outside [0, num_streams) are dropped.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        if not (keys.is_cuda and ids.is_cuda):
+            raise N.IllegalArgumentException("keys and ids must be device tensors")
+        if keys.dtype != self.keys.dtype or keys.dim() != 1:
+            raise N.IllegalArgumentException("keys must be 1-D and have the state's dtype")
+        grouped = self._group(torch, keys, ids)
+        if grouped is None:
+            return self
+        offsets, order = grouped
+        keys = keys.contiguous()
+        S = self.num_streams
+        N.check(L.rsv_sample_segmented_update_indirect(
+            _ptr(keys), keys.numel(), _ptr(order), _ptr(offsets), None, None, S, S, keys.element_size(), self.k,
+            self.seed, self.stream_base, _ptr(self.keys), _ptr(self.idx), _ptr(self.next),
+            _stream_ptr(torch, self.keys.device)))
+        return self
+
     def merge(self, part_keys, part_idx=None, part_next=None):
         """Per slot the largest idx among row s and row s of every part wins; next takes the max.
 
@@ -1254,6 +1353,34 @@ class SegmentedSamplerRows(_SegmentedState):
             C.c_void_p(bases.data_ptr()) if bases is not None else None,
             B, self.num_streams, W, self.k, self.seed, self.stream_base,
             C.c_void_p(self.rows.data_ptr()), C.c_void_p(self.idx.data_ptr()), C.c_void_p(self.next.data_ptr()),
+            _stream_ptr(torch, self.rows.device)))
+        return self
+
+    def update_by_id(self, rows, ids):
+        """The batch in arrival order, rows[i] into row ids[i] of the state: as SegmentedSampler.update_by_id.
+
+        rows: uint8 (n, width) or int64 (n, width / 8), as update() takes them; ids: int64 or int32, one per
+        row.  Only the at most k winning rows per state row are read, through the grouping's order.  No host wait;
+        rows whose id lies outside [0, num_streams) are dropped.  Returns self.
+        """
+        import torch
+
+        L = N.load()
+        if not (rows.is_cuda and ids.is_cuda):
+            raise N.IllegalArgumentException("rows and ids must be device tensors")
+        if rows.dim() != 2 or rows.dtype not in (torch.uint8, torch.int64):
+            raise N.IllegalArgumentException("rows must be 2-D uint8 or int64 (one key per row)")
+        if rows.shape[1] * rows.element_size() != self.width:
+            raise N.IllegalArgumentException(f"rows must hold {self.width} bytes each")
+        grouped = self._group(torch, rows, ids)
+        if grouped is None:
+            return self
+        offsets, order = grouped
+        rows = rows.contiguous()
+        S = self.num_streams
+        N.check(L.rsv_sample_segmented_rows_update_indirect(
+            _ptr(rows), rows.shape[0], _ptr(order), _ptr(offsets), None, None, S, S, self.width, self.k,
+            self.seed, self.stream_base, _ptr(self.rows), _ptr(self.idx), _ptr(self.next),
             _stream_ptr(torch, self.rows.device)))
         return self
 

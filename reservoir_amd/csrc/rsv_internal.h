@@ -164,6 +164,27 @@ hipError_t launch_segmented_rows_update(const void* rows, int key_width, const i
 hipError_t launch_segmented_rows_merge(const void* part_rows, int key_width, const int64_t* part_idx,
                                        const int64_t* part_next, int32_t parts, int64_t num_states, uint32_t k,
                                        void* state_rows, int64_t* state_idx, int64_t* state_next, hipStream_t st);
+// The grouping pass (rsv_group.hip): ids[n] (int64 or int32 by id_width), the state row of each
+// element in arrival order, to the dense CSR over num_states rows -- offsets[num_states + 1] and order[n], a
+// permutation of [0, n): row r's positions in arrival order at order[offsets[r], offsets[r+1]), the positions whose
+// id lies outside [0, num_states) behind offsets[num_states], in arrival order too.  A stable radix partition over
+// the low bits of the id (the width of num_states); stream-ordered, scratch from hipMallocAsync.  n <= kGroupMaxN,
+// num_states <= kGroupMaxStates (the host checks).
+constexpr int64_t kGroupMaxN = 0x7FFFFFFFll, kGroupMaxStates = 0xFFFFFFFEll;
+hipError_t launch_group_by_stream(const void* ids, int id_width, int64_t n, int64_t num_states, int64_t* offsets,
+                                  int32_t* order, hipStream_t st);
+// K2 resumed through a permutation (rsv_segmented.hip): launch_segmented_update / _rows_update with segment b's
+// p-th element at keys[order[offsets[b] + p]] (order: n_keys entries in [0, n_keys)).  Only the write-back reads
+// order, for the slots it replaces; a slot whose entry lies outside the range keeps its key and idx.
+hipError_t launch_segmented_update_indirect(const void* keys, int64_t n_keys, const int32_t* order, int key_width,
+                                            const int64_t* offsets, const int64_t* stream_ids, const int64_t* bases,
+                                            int64_t num_segments, int64_t num_states, uint32_t k, const DrawParams& dp,
+                                            void* state_keys, int64_t* state_idx, int64_t* state_next, hipStream_t st);
+hipError_t launch_segmented_rows_update_indirect(const void* rows, int64_t n_rows, const int32_t* order, int key_width,
+                                                 const int64_t* offsets, const int64_t* stream_ids,
+                                                 const int64_t* bases, int64_t num_segments, int64_t num_states,
+                                                 uint32_t k, const DrawParams& dp, void* state_rows,
+                                                 int64_t* state_idx, int64_t* state_next, hipStream_t st);
 // K2 keyless (rsv_segmented.hip, the same element loops and forms): no element reaches the device.  Stateless:
 // out_idx[S*k] takes each slot's stream-relative source index (-1: empty), streams longer than the split length
 // (RSV_K2_SPLIT_LEN) in pieces over the whole device.  The resumed state is (idx, next) as above; update also

@@ -743,6 +743,99 @@ __global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_update_wg(
     }
 }
 
+// ---- resumed, through a permutation (rsv_sample_segmented_update_indirect) ----------
+// Segment b's p-th element is keys[order[offsets[b] + p]]: the batch stays in arrival order and `order`
+// (rsv_group_by_stream's) groups it.  The element loops never see a key, so only the write-back changes: it
+// reads `order` for the slots it replaces and nothing else.  order has n_keys entries, each in [0, n_keys).
+
+// the batch position of entry p of `order`, or -1 for a p or an entry outside [0, n_keys): such a slot is left
+// as it is rather than dereferenced
+__device__ __forceinline__ int64_t order_at(const int32_t* __restrict__ order, int64_t p, int64_t n_keys) {
+    if (p < 0 || p >= n_keys) return -1;
+    const int64_t q = order[p];
+    return q < n_keys ? q : -1;  // a negative entry is -1 or below already
+}
+
+// update_slot with the segment's elements at keys[order[off ...]]
+template <typename KeyT>
+__device__ __forceinline__ void update_slot_indirect(const KeyT* __restrict__ keys, int64_t n_keys,
+                                                     const int32_t* __restrict__ order, int64_t off, int64_t n0,
+                                                     int64_t nend, uint32_t j, uint64_t w, KeyT* __restrict__ sk,
+                                                     int64_t* __restrict__ si) {
+    int64_t at = (int64_t)w;
+    if (!w) at = ((int64_t)j >= n0 && (int64_t)j < nend) ? (int64_t)j : -1;  // a fill index of this segment
+    if (at < 0) return;
+    if (si[j] < at) {
+        const int64_t q = order_at(order, off + (at - n0), n_keys);
+        if (q < 0) return;
+        sk[j] = keys[q];
+        si[j] = at;
+    }
+}
+
+template <typename KeyT>
+__global__ __launch_bounds__(64 * kWaves) void k2_segmented_update_indirect(
+    const KeyT* __restrict__ keys, int64_t n_keys, const int32_t* __restrict__ order,
+    const int64_t* __restrict__ offsets, const int64_t* __restrict__ ids, const int64_t* __restrict__ bases, int64_t B,
+    int64_t S, uint32_t k, uint32_t k0, uint32_t k1, uint64_t stream_base, KeyT* __restrict__ state_keys,
+    int64_t* __restrict__ state_idx, int64_t* __restrict__ state_next, uint32_t fifo_cap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    build_lut((uint16_t*)lds, 256ull * k);
+    __syncthreads();
+    const Wave W = wave_frame(lds, k, k0, k1, fifo_cap);
+    const uint32_t lane = W.lane;
+    const int64_t wave_stride = (int64_t)gridDim.x * kWaves;
+    for (int64_t b = (int64_t)blockIdx.x * kWaves + W.wave; b < B; b += wave_stride) {
+        Segment g;
+        if (!read_segment(g, offsets, ids, bases, state_next, b, S)) continue;
+        const uint64_t stream = stream_base + (uint64_t)g.r;
+        KeyT* sk = state_keys + g.r * (int64_t)k;
+        int64_t* si = state_idx + g.r * (int64_t)k;
+        if (g.nend < kSmallLen) {
+            k2_stream<KeyT, true, false, true>(W, keys, g.off, g.len, stream, nullptr, g.n0);
+            for (uint32_t j = lane; j < k; j += 64)
+                update_slot_indirect(keys, n_keys, order, g.off, g.n0, g.nend, j, ((const uint32_t*)W.tab)[j], sk, si);
+        } else {
+            k2_stream<KeyT, false, false, true>(W, keys, g.off, g.len, stream, nullptr, g.n0);
+            for (uint32_t j = lane; j < k; j += 64)
+                update_slot_indirect(keys, n_keys, order, g.off, g.n0, g.nend, j, ((const uint64_t*)W.tab)[j], sk, si);
+        }
+        if (lane == 0 && state_next[g.r] < g.nend) state_next[g.r] = g.nend;
+        __builtin_amdgcn_wave_barrier();  // the table is read before the next segment zeroes it
+    }
+}
+
+// the workgroup form (k >= kWGMinK), as k2_segmented_update_wg
+template <typename KeyT>
+__global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_update_indirect_wg(
+    const KeyT* __restrict__ keys, int64_t n_keys, const int32_t* __restrict__ order,
+    const int64_t* __restrict__ offsets, const int64_t* __restrict__ ids, const int64_t* __restrict__ bases, int64_t B,
+    int64_t S, uint32_t k, uint32_t k0, uint32_t k1, uint64_t stream_base, KeyT* __restrict__ state_keys,
+    int64_t* __restrict__ state_idx, int64_t* __restrict__ state_next, uint32_t fifo_cap) {
+    using TabT = unsigned long long;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    build_lut((uint16_t*)lds, 256ull * k);
+    const Wave W = wg_frame(lds, k, k0, k1, fifo_cap);
+    TabT* tab = (TabT*)W.tab;
+    const uint32_t nthr = 64u * kWavesWG;
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        Segment g;
+        if (!read_segment(g, offsets, ids, bases, state_next, b, S)) continue;
+        for (uint32_t j = threadIdx.x; j < k; j += nthr) tab[j] = 0;
+        __syncthreads();  // the table is zero, the lut built, and n0 read by every wave
+        const uint64_t stream = stream_base + (uint64_t)g.r;
+        if (g.nend < kSmallLen) k2_part<TabT, true, false, true>(W, tab, g.len, stream, W.wave, g.n0);
+        else k2_part<TabT, false, false, true>(W, tab, g.len, stream, W.wave, g.n0);
+        __syncthreads();
+        KeyT* sk = state_keys + g.r * (int64_t)k;
+        int64_t* si = state_idx + g.r * (int64_t)k;
+        for (uint32_t j = threadIdx.x; j < k; j += nthr)
+            update_slot_indirect(keys, n_keys, order, g.off, g.n0, g.nend, j, tab[j], sk, si);
+        if (threadIdx.x == 0 && state_next[g.r] < g.nend) state_next[g.r] = g.nend;
+        __syncthreads();  // the write-back has read the table before the next segment zeroes it
+    }
+}
+
 // rsv_sample_segmented_merge: per (row, slot) the part with the largest idx, if it beats the row's;
 // next = the max over the row and the parts.  parts: [P][S][k], [P][S][k], [P][S].
 // The pick for entry t = (row, slot) of S k: the part with the largest idx if it beats the state's (-1:
@@ -1026,6 +1119,106 @@ __global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_rows_update_wg(
             const uint64_t e = tab[j];
             return e ? g.off + (int64_t)e - 1 : -1;
         };
+        gather_rows<G, false>(rows, state_rows + (uint64_t)g.r * k * Wb, k, C, p0, src_of);
+        if (threadIdx.x == 0 && state_next[g.r] < g.nend) state_next[g.r] = g.nend;
+        __syncthreads();  // the write-back has read the table before the next segment zeroes it
+    }
+}
+
+// ---- resumed over byte keys, through a permutation (rsv_sample_segmented_rows_update_indirect) ----
+// update_slot_rows with the segment's rows at rows[order[off ...]]: the entry becomes 1 + the BATCH position
+// of the row the slot takes (an int32 entry of `order`, so it fits the 32-bit table too), read through
+// order_at here, in the first pass, so that a slot whose entry is bad keeps its idx as well as its row.
+template <typename TabT>
+__device__ __forceinline__ void update_slot_rows_indirect(TabT* tab, const int32_t* __restrict__ order, int64_t n_rows,
+                                                          int64_t off, int64_t n0, int64_t nend, uint32_t j,
+                                                          int64_t* __restrict__ si) {
+    const uint64_t w = tab[j];
+    int64_t at = (int64_t)w;
+    if (!w) at = ((int64_t)j >= n0 && (int64_t)j < nend) ? (int64_t)j : -1;  // a fill index of this segment
+    TabT e = 0;
+    if (at >= 0 && si[j] < at) {
+        const int64_t q = order_at(order, off + (at - n0), n_rows);
+        if (q >= 0) {
+            si[j] = at;
+            e = (TabT)(q + 1);
+        }
+    }
+    tab[j] = e;
+}
+
+template <typename G>
+__global__ __launch_bounds__(64 * kWaves) void k2_segmented_rows_update_indirect(
+    const unsigned char* __restrict__ rows, int64_t n_rows, const int32_t* __restrict__ order,
+    const int64_t* __restrict__ offsets, const int64_t* __restrict__ ids, const int64_t* __restrict__ bases, int64_t B,
+    int64_t S, uint32_t k, uint32_t C, uint32_t k0, uint32_t k1, uint64_t stream_base,
+    unsigned char* __restrict__ state_rows, int64_t* __restrict__ state_idx, int64_t* __restrict__ state_next,
+    uint32_t fifo_cap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    build_lut((uint16_t*)lds, 256ull * k);
+    __syncthreads();
+    const Wave W = wave_frame(lds, k, k0, k1, fifo_cap);
+    const uint32_t lane = W.lane;
+    void* tab = W.tab;
+    const uint64_t Wb = (uint64_t)C * sizeof(G);
+    const PairStep p0 = pair_step(lane, 64, C);
+    const int64_t wave_stride = (int64_t)gridDim.x * kWaves;
+    for (int64_t b = (int64_t)blockIdx.x * kWaves + W.wave; b < B; b += wave_stride) {
+        Segment g;
+        if (!read_segment(g, offsets, ids, bases, state_next, b, S)) continue;
+        const uint64_t stream = stream_base + (uint64_t)g.r;
+        int64_t* si = state_idx + g.r * (int64_t)k;
+        const bool small = g.nend < kSmallLen;
+        if (small) {
+            k2_stream<int64_t, true, false, true>(W, nullptr, g.off, g.len, stream, nullptr, g.n0);
+            for (uint32_t j = lane; j < k; j += 64)
+                update_slot_rows_indirect((uint32_t*)tab, order, n_rows, g.off, g.n0, g.nend, j, si);
+        } else {
+            k2_stream<int64_t, false, false, true>(W, nullptr, g.off, g.len, stream, nullptr, g.n0);
+            for (uint32_t j = lane; j < k; j += 64)
+                update_slot_rows_indirect((uint64_t*)tab, order, n_rows, g.off, g.n0, g.nend, j, si);
+        }
+        __builtin_amdgcn_wave_barrier();
+        auto src_of = [&](uint32_t j) -> int64_t {
+            const uint64_t e = small ? (uint64_t)((const uint32_t*)tab)[j] : ((const uint64_t*)tab)[j];
+            return (int64_t)e - 1;
+        };
+        gather_rows<G, false>(rows, state_rows + (uint64_t)g.r * k * Wb, k, C, p0, src_of);
+        if (lane == 0 && state_next[g.r] < g.nend) state_next[g.r] = g.nend;
+        __builtin_amdgcn_wave_barrier();  // the table is read before the next segment zeroes it
+    }
+}
+
+// the workgroup form (k >= kWGMinK), as k2_segmented_rows_update_wg
+template <typename G>
+__global__ __launch_bounds__(64 * kWavesWG) void k2_segmented_rows_update_indirect_wg(
+    const unsigned char* __restrict__ rows, int64_t n_rows, const int32_t* __restrict__ order,
+    const int64_t* __restrict__ offsets, const int64_t* __restrict__ ids, const int64_t* __restrict__ bases, int64_t B,
+    int64_t S, uint32_t k, uint32_t C, uint32_t k0, uint32_t k1, uint64_t stream_base,
+    unsigned char* __restrict__ state_rows, int64_t* __restrict__ state_idx, int64_t* __restrict__ state_next,
+    uint32_t fifo_cap) {
+    using TabT = unsigned long long;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    build_lut((uint16_t*)lds, 256ull * k);
+    const Wave W = wg_frame(lds, k, k0, k1, fifo_cap);
+    TabT* tab = (TabT*)W.tab;
+    const uint32_t nthr = 64u * kWavesWG;
+    const uint64_t Wb = (uint64_t)C * sizeof(G);
+    const PairStep p0 = pair_step(threadIdx.x, nthr, C);
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        Segment g;
+        if (!read_segment(g, offsets, ids, bases, state_next, b, S)) continue;
+        for (uint32_t j = threadIdx.x; j < k; j += nthr) tab[j] = 0;
+        __syncthreads();  // the table is zero, the lut built, and n0 read by every wave
+        const uint64_t stream = stream_base + (uint64_t)g.r;
+        if (g.nend < kSmallLen) k2_part<TabT, true, false, true>(W, tab, g.len, stream, W.wave, g.n0);
+        else k2_part<TabT, false, false, true>(W, tab, g.len, stream, W.wave, g.n0);
+        __syncthreads();
+        int64_t* si = state_idx + g.r * (int64_t)k;
+        for (uint32_t j = threadIdx.x; j < k; j += nthr)
+            update_slot_rows_indirect(tab, order, n_rows, g.off, g.n0, g.nend, j, si);
+        __syncthreads();  // every slot's entry names its row (or none)
+        auto src_of = [&](uint32_t j) -> int64_t { return (int64_t)tab[j] - 1; };
         gather_rows<G, false>(rows, state_rows + (uint64_t)g.r * k * Wb, k, C, p0, src_of);
         if (threadIdx.x == 0 && state_next[g.r] < g.nend) state_next[g.r] = g.nend;
         __syncthreads();  // the write-back has read the table before the next segment zeroes it

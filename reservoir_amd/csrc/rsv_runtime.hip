@@ -1631,6 +1631,69 @@ rsv_status rsv_sample_segmented_rows_merge(const void* part_rows_dev, const int6
     return RSV_OK;
 }
 
+// ---- the by-id front door: the grouping pass and the two updates that read through its permutation ----
+rsv_status rsv_group_by_stream(const void* ids_dev, int32_t id_width, int64_t n, int64_t num_states,
+                               int64_t* offsets_dev, int32_t* order_dev, void* hip_stream) {
+    if (!offsets_dev) return fail(RSV_E_NULL_POINTER, "offsets_dev is NULL");
+    if (n > 0 && !order_dev) return fail(RSV_E_NULL_POINTER, "order_dev is NULL");
+    if (n > 0 && !ids_dev) return fail(RSV_E_NULL_POINTER, "ids_dev is NULL");
+    if (n < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative n");
+    if (num_states < 1) return fail(RSV_E_ILLEGAL_ARGUMENT, "num_states must be at least 1");
+    if (id_width != 4 && id_width != 8) return fail(RSV_E_UNSUPPORTED, "id_width must be 4 (int32) or 8 (int64)");
+    if (n > kGroupMaxN)
+        return fail(RSV_E_UNSUPPORTED, "rsv_group_by_stream takes n <= 2147483647 (2^31 - 1) per call: order_dev is int32");
+    if (num_states > kGroupMaxStates)
+        return fail(RSV_E_UNSUPPORTED, "rsv_group_by_stream takes num_states <= 4294967294 (2^32 - 2): the bins are 32-bit");
+    RSV_HIP_TRY(launch_group_by_stream(ids_dev, id_width, n, num_states, offsets_dev, order_dev,
+                                       (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
+rsv_status rsv_sample_segmented_update_indirect(const void* keys_dev, int64_t n_keys, const int32_t* order_dev,
+                                                const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                                const int64_t* bases_dev, int64_t num_segments, int64_t num_states,
+                                                int32_t key_width, int32_t k, uint64_t seed, uint64_t stream_base,
+                                                void* state_keys_dev, int64_t* state_idx_dev, int64_t* state_next_dev,
+                                                void* hip_stream) {
+    rsv_status st = check_segsample_shape("rsv_sample_segmented_update_indirect", nullptr, k, key_width, true);
+    if (st || segsample_update_done(num_segments, num_states, stream_ids_dev, st)) return st;
+    if (n_keys < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative n_keys");
+    // keys_dev is not checked: a launch whose segments are all empty has no keys
+    if (!order_dev) return fail(RSV_E_NULL_POINTER, "order_dev is NULL");
+    if (!offsets_dev || !state_keys_dev || !state_idx_dev || !state_next_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    const DrawParams dp{seed, stream_base};
+    RSV_HIP_TRY(launch_segmented_update_indirect(keys_dev, n_keys, order_dev, key_width, offsets_dev, stream_ids_dev,
+                                                 bases_dev, num_segments, num_states, (uint32_t)k, dp, state_keys_dev,
+                                                 state_idx_dev, state_next_dev, (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
+rsv_status rsv_sample_segmented_rows_update_indirect(const void* rows_dev, int64_t n_rows, const int32_t* order_dev,
+                                                     const int64_t* offsets_dev, const int64_t* stream_ids_dev,
+                                                     const int64_t* bases_dev, int64_t num_segments,
+                                                     int64_t num_states, int32_t key_width, int32_t k, uint64_t seed,
+                                                     uint64_t stream_base, void* state_rows_dev,
+                                                     int64_t* state_idx_dev, int64_t* state_next_dev,
+                                                     void* hip_stream) {
+    rsv_status st = check_segsample_shape("rsv_sample_segmented_rows_update_indirect",
+                                          "rsv_sample_segmented_update_indirect", k, key_width, true);
+    if (st || segsample_update_done(num_segments, num_states, stream_ids_dev, st)) return st;
+    if (n_rows < 0) return fail(RSV_E_ILLEGAL_ARGUMENT, "negative n_rows");
+    // rows_dev is not checked: a launch whose segments are all empty has no rows
+    if (!order_dev) return fail(RSV_E_NULL_POINTER, "order_dev is NULL");
+    if (!offsets_dev || !state_rows_dev || !state_idx_dev || !state_next_dev)
+        return fail(RSV_E_NULL_POINTER, "NULL buffer");
+    if (((uintptr_t)rows_dev | (uintptr_t)state_rows_dev) & 7)
+        return fail(RSV_E_ILLEGAL_ARGUMENT, "rows_dev and state_rows_dev must be 8-byte aligned");
+    const DrawParams dp{seed, stream_base};
+    RSV_HIP_TRY(launch_segmented_rows_update_indirect(rows_dev, n_rows, order_dev, key_width, offsets_dev,
+                                                      stream_ids_dev, bases_dev, num_segments, num_states, (uint32_t)k,
+                                                      dp, state_rows_dev, state_idx_dev, state_next_dev,
+                                                      (hipStream_t)hip_stream));
+    return RSV_OK;
+}
+
 // the three keyless entry points: the checks of their keyed siblings, in their order, without a key width
 rsv_status rsv_sample_segmented_indexed(const int64_t* offsets_dev, int64_t num_streams, int32_t k, uint64_t seed,
                                         uint64_t stream_base, int64_t* out_idx_dev, int64_t* counts_dev,

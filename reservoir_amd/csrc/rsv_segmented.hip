@@ -39,6 +39,12 @@
 // device and indices come back.  The kernels (rsv_indexed.hip, declared in rsv_k2_indexed.h) run the same element
 // loops and forms; the launchers are at the end of this file, with the split form of the stateless launch.
 //
+// Through a permutation (rsv_sample_segmented_update_indirect / _rows_update_indirect): the two
+// resumed launches with segment b's p-th element at keys[order[offsets[b] + p]], `order` being what
+// rsv_group_by_stream (rsv_group.hip) writes for a batch in arrival order.  Kernels of their own beside the direct
+// ones (k2_segmented_update_indirect*, k2_segmented_rows_update_indirect*), the same two forms over the same
+// element loops; only their write-back reads `order`.
+//
 // What the nine keyed kernels and six launchers share exists once.  Device (rsv_k2.h): build_lut, the frames
 // wave_frame / wg_frame (the Wave over the workgroup's LDS and its winner table), read_segment (an update's
 // segment header and its skip rules), slot_source (the stateless slot rule) and merge_pick.  Host (below):
@@ -274,6 +280,29 @@ hipError_t launch_segmented_update(const void* keys, int key_width, const int64_
     });
 }
 
+hipError_t launch_segmented_update_indirect(const void* keys, int64_t n_keys, const int32_t* order, int key_width,
+                                            const int64_t* offsets, const int64_t* stream_ids, const int64_t* bases,
+                                            int64_t num_segments, int64_t num_states, uint32_t k, const DrawParams& dp,
+                                            void* state_keys, int64_t* state_idx, int64_t* state_next,
+                                            hipStream_t st) {
+    if (num_segments <= 0 || num_states <= 0) return hipSuccess;
+    if (k > kSegSampleStateMaxK) return hipErrorInvalidValue;
+    const SeedWords sw(dp);
+    const uint32_t fifo_cap = env_fifo_cap();
+    return with_key(key_width, [&](auto key) {
+        using KeyT = decltype(key);
+        auto launch = [&](auto kernel, int waves) {
+            return [&, kernel, waves](unsigned grid, size_t lds) {
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, st, (const KeyT*)keys, n_keys, order,
+                                   offsets, stream_ids, bases, num_segments, num_states, k, sw.k0, sw.k1, dp.stream,
+                                   (KeyT*)state_keys, state_idx, state_next, fifo_cap);
+            };
+        };
+        return launch_update(num_segments, k, launch(k2_segmented_update_indirect_wg<KeyT>, kWavesWG),
+                             launch(k2_segmented_update_indirect<KeyT>, kWaves));
+    });
+}
+
 hipError_t launch_segmented_merge(const void* part_keys, int key_width, const int64_t* part_idx,
                                   const int64_t* part_next, int32_t parts, int64_t num_states, uint32_t k,
                                   void* state_keys, int64_t* state_idx, int64_t* state_next, hipStream_t st) {
@@ -344,6 +373,32 @@ hipError_t launch_segmented_rows_update(const void* rows_, int key_width, const 
         };
         return launch_update(num_segments, k, launch(k2_segmented_rows_update_wg<G>, kWavesWG),
                              launch(k2_segmented_rows_update<G>, kWaves));
+    });
+}
+
+hipError_t launch_segmented_rows_update_indirect(const void* rows_, int64_t n_rows, const int32_t* order, int key_width,
+                                                 const int64_t* offsets, const int64_t* stream_ids,
+                                                 const int64_t* bases, int64_t num_segments, int64_t num_states,
+                                                 uint32_t k, const DrawParams& dp, void* state_rows_,
+                                                 int64_t* state_idx, int64_t* state_next, hipStream_t st) {
+    if (num_segments <= 0 || num_states <= 0) return hipSuccess;
+    if (k > kSegSampleStateMaxK) return hipErrorInvalidValue;
+    const unsigned char* rows = (const unsigned char*)rows_;
+    unsigned char* state_rows = (unsigned char*)state_rows_;
+    return with_granule(rows_vec16(key_width, rows, state_rows), [&](auto granule) {
+        using G = decltype(granule);
+        const uint32_t C = (uint32_t)key_width / (uint32_t)sizeof(G);
+        const SeedWords sw(dp);
+        const uint32_t fifo_cap = env_fifo_cap();
+        auto launch = [&](auto kernel, int waves) {
+            return [&, kernel, waves](unsigned grid, size_t lds) {
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, st, rows, n_rows, order, offsets,
+                                   stream_ids, bases, num_segments, num_states, k, C, sw.k0, sw.k1, dp.stream,
+                                   state_rows, state_idx, state_next, fifo_cap);
+            };
+        };
+        return launch_update(num_segments, k, launch(k2_segmented_rows_update_indirect_wg<G>, kWavesWG),
+                             launch(k2_segmented_rows_update_indirect<G>, kWaves));
     });
 }
 
