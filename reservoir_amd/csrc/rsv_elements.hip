@@ -27,29 +27,35 @@ constexpr int kBlock = 256;
 // them) go straight to global atomicMax on the k-slot winner table: 14k atomics per 1e9 indices at k = 1024.
 constexpr int kK1Unroll = 2;  // level-0 blocks per lane per iteration (two Philox chains in flight)
 
-// ~20 four-wave workgroups per CU (6 resident: .sgpr_count 104): tools/micro_k1o r03ae/r03af, 1e9
+// ~20 four-wave workgroups per CU (6 resident: .sgpr_count 104 then, 106 now): tools/micro_k1o r03ae/r03af, 1e9
 // draws, 12-iteration windows: 85.0-85.5 us at 5086 workgroups (2 whole windows per wave) vs
 // 87.5-89 us at 3072, 3390 (3 windows), 4096, 6144, 7629 and 10172 (1 window)
 constexpr unsigned kK1Grid = 256 * 20;
 
 // per-wave LDS of k1_body_q: pair queue (< 64 waiting + half a window of appends), the per-
-// candidate queue.  12 iterations per window: tools/micro_k1o (r05k, 1e9 indices, grid 5086)
+// candidate queue, the append's `top` word.  12 iterations per window: tools/micro_k1o (r05k, 1e9 indices, grid 5086)
 // 83.1-83.6 us vs 83.4-83.8 for 8 and 84.7-84.8 for 16, and 84.9-85.8 for the round-4 body
 // (k1_body_p: window bits pushed in ballot rounds, tools/k1_dev_bodies.h), winners identical.
 constexpr int kK1Win = 12;
 struct K1Lds {
     uint64_t q[kBlock / 64][k1q_cap<kK1Win>()];
     uint64_t cq[kBlock / 64][kQueue];
+    uint32_t top[kBlock / 64];  // per wave: the byte address of its next free queue entry (k1_body_q TOP)
 };
 
+// One kernel per form (FAST: rsv_scan.h): the host picks the instantiation from K1Launch::flags
+// (k1_fast_form), so no kernel tests the flag.  With both bodies behind one launch-uniform branch the
+// kernel spilled 29 SGPRs to VGPR lanes, 8-9 lane moves in every unit of the steady loop; alone the
+// FAST body spills none and the general body 5 (profiles/k1_forms/resources.tsv).
+template <bool FAST>
 __global__ __launch_bounds__(kBlock) void k1_last_writer(DrawKey dk, uint32_t k, uint64_t lo,
                                                          uint64_t hi, uint64_t g_begin,
                                                          uint64_t n_groups,
                                                          unsigned long long* __restrict__ win, K1Launch P) {
     __shared__ K1Lds L;
     const int w = threadIdx.x >> 6;
-    if (P.flags & kK1Fast) k1_body_q<kK1Win, true, kBlock>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
-    else k1_body_q<kK1Win, false, kBlock>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
+    k1_body_q<kK1Win, FAST, kBlock, true>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P, nullptr,
+                                          &L.top[w]);
 }
 
 // ---- the slot rule ----------------------------------------------------------------------------
@@ -136,19 +142,43 @@ __device__ __forceinline__ void resolve_registers_first(const KeyT* __restrict__
 // and the resolve dispatch of the two-kernel form.
 constexpr uint32_t kK1FusedMaxK = 8 * kBlock;
 
+// What the tail takes.  It is the kernel's FIRST argument and the kernel never names it: the tail reads it
+// from the kernarg segment (offset 0) behind K1, through an address the compiler cannot trace to the segment
+// (it waits in the LDS meanwhile).  As plain arguments these 20 SGPRs were loaded at entry and held through
+// K1, which has none to spare: the FAST form spilled 10 of them to VGPR lanes (the K1-only kernel none); the
+// segment's address or gridDim.x held through K1 would be spilled the same way, so the grid is here too.
 template <typename KeyT>
-__global__ __launch_bounds__(kBlock) void k1_resolve_publish(DrawKey dk, uint32_t k, uint64_t lo, uint64_t hi,
-                                                             uint64_t g_begin, uint64_t n_groups,
-                                                             unsigned long long* __restrict__ win,
-                                                             uint32_t* ticket, const KeyT* __restrict__ keys,
-                                                             int64_t base, int64_t n, KeyT* __restrict__ slot_key,
-                                                             int64_t* __restrict__ slot_idx, int fresh, int64_t m,
-                                                             KeyT* dst, uint32_t* flag, uint32_t gen, K1Launch P) {
+struct K1Tail {
+    uint32_t* ticket;
+    const KeyT* keys;
+    int64_t base, n;
+    KeyT* slot_key;
+    int64_t* slot_idx;
+    int64_t m;
+    KeyT* dst;
+    uint32_t* flag;
+    uint32_t gen;
+    int fresh;
+    uint32_t grid;  // workgroups of the launch
+};
+
+template <typename KeyT, bool FAST>
+__global__ __launch_bounds__(kBlock) void k1_resolve_publish(K1Tail<KeyT>, DrawKey dk, uint32_t k, uint64_t lo,
+                                                             uint64_t hi, uint64_t g_begin, uint64_t n_groups,
+                                                             unsigned long long* __restrict__ win, K1Launch P) {
     __shared__ K1Lds L;
     __shared__ uint32_t last;
+    __shared__ uint64_t tail_at;
     const int w = threadIdx.x >> 6;
-    if (P.flags & kK1Fast) k1_body_q<kK1Win, true, kBlock>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
-    else k1_body_q<kK1Win, false, kBlock>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
+    // every wave stores the same address and reads it back behind its own store
+    tail_at = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
+    k1_body_q<kK1Win, FAST, kBlock, true>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P, nullptr,
+                                          &L.top[w]);
+    asm volatile("" ::: "memory");
+    const uint64_t at = tail_at;
+    const uint64_t args = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(at >> 32)) << 32) |
+                          (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
+    const auto* T = (const __attribute__((address_space(4))) K1Tail<KeyT>*)args;  // constant memory: scalar loads
     // This wave's winner atomics are performed once vmcnt drains: on gfx942/gfx950 a global atomic
     // without return still counts in vmcnt until the memory system acknowledges it (there is no
     // separate vscnt), and an agent-scope atomic is performed at the agent's coherence point (the
@@ -162,15 +192,15 @@ __global__ __launch_bounds__(kBlock) void k1_resolve_publish(DrawKey dk, uint32_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
-        const uint32_t prev = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = prev == gridDim.x - 1;
-        if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t prev = __hip_atomic_fetch_add(T->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = prev == T->grid - 1;
+        if (last) __hip_atomic_store(T->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
     if (!last) return;  // workgroup-uniform
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    resolve_registers_first<KeyT, kK1FusedMaxK / kBlock, true>(keys, base, n, k, win, slot_key, slot_idx, fresh, m, dst,
-                                                               flag, gen);
+    resolve_registers_first<KeyT, kK1FusedMaxK / kBlock, true>(T->keys, T->base, T->n, k, win, T->slot_key, T->slot_idx,
+                                                               T->fresh, T->m, T->dst, T->flag, T->gen);
 }
 
 // The batch's resolve of 4- / 8-byte keys: the slot rule per slot j, the keys gathered from the batch.
@@ -439,6 +469,13 @@ inline unsigned k1_plan(uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin, 
     return grid ? grid : stride_grid;
 }
 
+// the instantiation a planned launch runs (tests/cpp/test_k1_forms.cpp pins the choice on both sides of 2^33 and 2^40)
+inline auto k1_last_writer_for(const K1Launch& P) { return k1_fast_form(P) ? k1_last_writer<true> : k1_last_writer<false>; }
+template <typename KeyT>
+inline auto k1_resolve_publish_for(const K1Launch& P) {
+    return k1_fast_form(P) ? k1_resolve_publish<KeyT, true> : k1_resolve_publish<KeyT, false>;
+}
+
 // f(KeyT{}) with the key type of a 4- / 8-byte key_width (f launches a kernel); the launch's error
 template <typename F>
 hipError_t with_key_type(int key_width, F&& f) {
@@ -466,8 +503,9 @@ hipError_t launch_k1_last_writer(const DrawParams& dp, uint32_t k, uint64_t lo, 
         n_groups = std::min<uint64_t>(std::min<uint64_t>(g_end, g_wrap) - g_begin, kMaxGroups);
         K1Launch P;
         const unsigned grid = k1_plan(k, lo, hi, g_begin, n_groups, P);
-        hipLaunchKernelGGL(k1_last_writer, dim3(grid), dim3(kBlock), 0, st, make_key(dp), k, lo, hi,
-                           g_begin, n_groups, batch_win, P);
+        const auto kernel = k1_last_writer_for(P);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, make_key(dp), k, lo, hi, g_begin, n_groups,
+                           batch_win, P);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -489,9 +527,11 @@ hipError_t launch_k1_resolve_publish(const DrawParams& dp, uint64_t lo, uint64_t
     const unsigned grid = k1_plan(sb.k, lo, hi, g_begin, n_groups, P);
     return with_key_type(sb.key_width, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL(k1_resolve_publish<T>, dim3(grid), dim3(kBlock), 0, st, make_key(dp), sb.k, lo, hi, g_begin,
-                           n_groups, sb.win, ticket, (const T*)b.keys, b.base, b.n, (T*)sb.slot_key, sb.slot_idx,
-                           (int)b.fresh, pub.m, (T*)pub.dst, pub.flag, pub.gen, P);
+        const auto kernel = k1_resolve_publish_for<T>(P);
+        const K1Tail<T> tail{ticket, (const T*)b.keys, b.base, b.n,  (T*)sb.slot_key, sb.slot_idx,
+                             pub.m,  (T*)pub.dst,      pub.flag, pub.gen, (int)b.fresh, grid};
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, tail, make_key(dp), sb.k, lo, hi, g_begin, n_groups,
+                           sb.win, P);
     });
 }
 

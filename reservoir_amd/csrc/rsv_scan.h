@@ -7,6 +7,7 @@
 // single active lane -- measured 383 us vs ~120 us for the level-0 work alone at 1e9 indices.
 #pragma once
 #include <algorithm>
+#include <type_traits>
 
 #include "rsv_device.h"
 
@@ -157,6 +158,9 @@ __device__ __forceinline__ uint32_t fold_pair(const u32x4& a, const u32x4& b) {
 // fold.  The queue holds < 64 waiting entries + half a window of appends (k1q_cap): the rounds run
 // after each half window.  The steady append takes no branch (the store runs under exec = the mark
 // inside one asm block), so the unrolled window stays one basic block for the scheduler.
+// TOP (what the product kernels run): the rank comes from the LDS, not from mbcnt -- a returning add on a
+// per-wave word under exec = the mark (see steady_top in k1_body_q); the mbcnt form stays for
+// tools/micro_k1o, which measures one against the other.
 template <int W>
 constexpr uint32_t k1q_cap() { return 64u * (1u + W / 2); }
 // waves per K1 workgroup (256 threads): the pooled tail's per-wave queue count
@@ -227,6 +231,9 @@ inline K1Launch k1_launch(uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin
     return P;
 }
 
+// which body a launch runs (the kernels are instantiated per form; none tests the flag)
+inline bool k1_fast_form(const K1Launch& P) { return (P.flags & kK1Fast) != 0; }
+
 // the two-group schedule (W1, A, B) for the launch; returns its grid in workgroups of `block` threads, 0
 // when the schedule does not fit the launch (no unit left for the second group)
 inline unsigned k1_schedule(K1Launch& P, uint32_t W1, uint32_t A, uint32_t B, unsigned block = 256) {
@@ -242,10 +249,11 @@ inline unsigned k1_schedule(K1Launch& P, uint32_t W1, uint32_t A, uint32_t B, un
     return grid;
 }
 
-template <int W = 12, bool FAST = false, int BS = 256>
+template <int W = 12, bool FAST = false, int BS = 256, bool TOP = false>
 __device__ __forceinline__ void k1_body_q(const DrawKey& dk, uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin,
                                           uint64_t n_groups, unsigned long long* __restrict__ win, uint64_t* q,
-                                          uint64_t* cq, const K1Launch& P, uint32_t* pool = nullptr) {
+                                          uint64_t* cq, const K1Launch& P, uint32_t* pool = nullptr,
+                                          uint32_t* top = nullptr) {
     static_assert(W % 2 == 0, "half windows");
     constexpr int U = 2;
     const uint32_t lane = threadIdx.x & 63;
@@ -392,6 +400,105 @@ __device__ __forceinline__ void k1_body_q(const DrawKey& dk, uint32_t k, uint64_
                      : "memory");
         qn += (uint32_t)__popcll(m);
     };
+    // TOP: the append's rank from the LDS instead of the VALU.  The wave's LDS word `top` holds the byte
+    // address of its next free queue entry while a steady half window runs (top_set: q_s + 8 qn at its
+    // start; qn stays the authoritative count, rounds / resolve / append / partial never read top).  Under
+    // exec = the mark, a returning ds_add of 8 on top hands every marked lane a distinct entry address: no
+    // mbcnt, no address op.  The add of iteration t is issued right behind its mark and its entry is
+    // written behind iteration t + 1's Philox (steady_top takes the pending entry of the iteration before
+    // and returns its own), so the add's latency has an iteration to hide in; the last entry is written by
+    // put_last before the rounds.  Every wait is lgkmcnt(0) behind a whole iteration of VALU work: what is
+    // outstanding there is the entry write of t - 1 and the add of t, and the add is the younger.
+    // The order of an iteration's entries inside the queue is now the order in which the LDS serves the
+    // lanes, not the lane order; the winners do not depend on it (atomicMax is the queue's only consumer).
+    // An iteration with an empty mark runs both LDS operations under exec = 0: no lane, no effect.
+    // `addr` is an add's destination and an ordinary asm output: the compiler takes it for ready when the
+    // issuing block ends, while the LDS still owes it.  Nothing but the listing enforces that no instruction
+    // copies or moves that VGPR before the next block's wait -- re-check it there (each ds_add_rtn's
+    // destination untouched, and no label, up to the following s_waitcnt lgkmcnt(0)) after any change to this
+    // body or to the compiler.  The half window's last add is waited for right behind its issue (put_last):
+    // its latency shows once per half window.
+    struct Pending {
+        uint32_t glo, z, addr;
+        unsigned long long m;
+    };
+    uint32_t top_v = 0, eight_v = 0;  // top's LDS address and the constant 8 in VGPRs, opaque like m0v
+    if constexpr (TOP) {
+        const uint32_t top_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)top);
+        asm volatile("v_mov_b32 %0, %1" : "=v"(top_v) : "s"(top_s));
+        asm volatile("v_mov_b32 %0, 8" : "=v"(eight_v));
+    }
+    auto top_set = [&]() {
+        uint32_t t;
+        asm volatile("v_mov_b32 %0, %2\n\t"
+                     "ds_write_b32 %1, %0"
+                     : "=&v"(t)
+                     : "v"(top_v), "s"(q_s + 8u * qn)
+                     : "memory");
+    };
+    // FIRST: no entry is pending (the half window's first iteration)
+    auto steady_top = [&](uint32_t d, const Pending& prev, auto first) -> Pending {
+        u32x4 w0, w1;
+        Pending cur;
+        philox4x32_10_uniform_hi_x2_at(gl, m0v, (uint64_t)kPhiloxM0 * d, ghi, dk.s0, dk.s1, dk.k0, dk.k1, w0, w1, cur.glo);
+        const uint32_t xa = w0.x | w0.y | w0.z | w0.w, xb = w1.x | w1.y | w1.z | w1.w;
+        asm("v_or_b32_sdwa %0, %2, %2 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_1\n\t"
+            "s_nop 0\n\t"
+            "v_or_b32_sdwa %0, %3, %3 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 src1_sel:WORD_1\n\t"
+            "s_nop 0\n\t"
+            "v_cmp_ne_u32_e64 %1, -1, %0"
+            : "=&v"(cur.z), "=s"(cur.m)
+            : "v"(xa), "v"(xb));
+        unsigned long long sv;
+        if constexpr (decltype(first)::value) {
+            asm volatile("s_mov_b64 %0, exec\n\t"
+                         "s_mov_b64 exec, %2\n\t"
+                         "ds_add_rtn_u32 %1, %3, %4\n\t"
+                         "s_mov_b64 exec, %0"
+                         : "=&s"(sv), "=&v"(cur.addr)
+                         : "s"(cur.m), "v"(top_v), "v"(eight_v)
+                         : "memory");
+        } else {
+            const uint64_t ent = (uint64_t)prev.glo | ((uint64_t)prev.z << 32);
+            asm volatile("s_waitcnt lgkmcnt(0)\n\t"
+                         "s_mov_b64 %0, exec\n\t"
+                         "s_mov_b64 exec, %5\n\t"
+                         "ds_write_b64 %6, %7\n\t"
+                         "s_mov_b64 exec, %2\n\t"
+                         "ds_add_rtn_u32 %1, %3, %4\n\t"
+                         "s_mov_b64 exec, %0"
+                         : "=&s"(sv), "=&v"(cur.addr)
+                         : "s"(cur.m), "v"(top_v), "v"(eight_v), "s"(prev.m), "v"(prev.addr), "v"(ent)
+                         : "memory");
+        }
+        qn += (uint32_t)__popcll(cur.m);
+        return cur;
+    };
+    auto put_last = [&](const Pending& prev) {
+        const uint64_t ent = (uint64_t)prev.glo | ((uint64_t)prev.z << 32);
+        unsigned long long sv;
+        asm volatile("s_waitcnt lgkmcnt(0)\n\t"
+                     "s_mov_b64 %0, exec\n\t"
+                     "s_mov_b64 exec, %1\n\t"
+                     "ds_write_b64 %2, %3\n\t"
+                     "s_mov_b64 exec, %0"
+                     : "=&s"(sv)
+                     : "s"(prev.m), "v"(prev.addr), "v"(ent)
+                     : "memory");
+    };
+    // the W / 2 steady iterations of a half window at counter words gl + t step
+    auto half_window = [&](uint32_t step) {
+        if constexpr (TOP) {
+            top_set();
+            Pending p = steady_top(0, Pending{}, std::true_type{});
+#pragma unroll
+            for (int t = 1; t < W / 2; ++t) p = steady_top(t * step, p, std::false_type{});
+            put_last(p);
+        } else {
+#pragma unroll
+            for (int t = 0; t < W / 2; ++t) steady(t * step);
+        }
+    };
     // one iteration of a partial window (the first, the last, or where dense / clipped blocks lie) at
     // block offset b (wave-uniform) and counter word gl
     auto partial = [&](uint32_t b) {
@@ -443,8 +550,7 @@ __device__ __forceinline__ void k1_body_q(const DrawKey& dk, uint32_t k, uint64_
             const uint32_t u = u_first + j * u_step;
             if (u >= P.units) break;
             gl = g0 + P.unit_off + u * UB + lane;
-#pragma unroll
-            for (int t = 0; t < W / 2; ++t) steady(t * (U * 64));
+            half_window(U * 64);
             __builtin_amdgcn_wave_barrier();
             rounds();
         }
@@ -454,8 +560,7 @@ __device__ __forceinline__ void k1_body_q(const DrawKey& dk, uint32_t k, uint64_
         if (base >= off_steady && (uint64_t)base + (uint64_t)(W - 1) * stride + U * 64 <= ng_steady) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-#pragma unroll
-                for (int t = 0; t < W / 2; ++t) steady(t * stride);
+                half_window(stride);
                 gl += (W / 2) * stride;
                 __builtin_amdgcn_wave_barrier();
                 rounds();

@@ -3,7 +3,8 @@
 // MI355X_MICROARCH.md "Residency") and with amdgpu_num_sgpr limits that admit 8, over a grid sweep.
 // Every variant's winner table is checked against the default's.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../include tools/micro_k1o.hip -o tools/micro_k1o
-//        (+ -DK1O_DEBUG -o tools/micro_k1o_dbg: per-launch counters, mode 'd')
+//        (+ -DK1O_DEBUG -o tools/micro_k1o_dbg: per-launch counters, mode 'd';
+//         + -DK1O_FORM=0|1|3 -o tools/micro_k1o_f0|1|3: mode 'f', one kernel shape per binary, run in alternating processes)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -72,6 +73,7 @@ struct K1QLds {
     uint64_t q[4][k1q_cap<W>()];
     uint64_t cq[4][kQueue];
     uint32_t pool[4];
+    uint32_t top[4];  // per wave: the byte address of its next free queue entry (the LDS-ranked append)
 };
 template <int W, bool FAST = false>
 __global__ __launch_bounds__(256) void k1_q(DrawKey dk, uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin,
@@ -109,6 +111,29 @@ __global__ __launch_bounds__(256) void k1_qp(DrawKey dk, uint32_t k, uint64_t lo
     const int w = threadIdx.x >> 6;
     (void)TRIM;
     k1_body_q<W, FAST>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
+}
+
+// mode 'f': the product kernel's shapes over the product's plan, one per binary (-DK1O_FORM=n, the product's
+// launch bounds): 0 both bodies behind the launch-uniform flag (the kernel before it was instantiated per
+// form), 1 the FAST body alone, 3 the FAST body alone with the append's rank from the LDS (rsv_scan.h TOP: what
+// the product runs).  (2, removed: the FAST body with the schedule layout as a template argument, no grid-stride
+// loop in the kernel -- 43 VGPRs for 45, the same 106 SGPRs, 77.87 / 78.05 / 77.90 us beside 1's 77.81 / 77.89 /
+// 78.24, profiles/k1_forms/micro_k1o_append.jsonl)
+#ifndef K1O_FORM
+#define K1O_FORM 1
+#endif
+__global__ __launch_bounds__(256) void k1_form(DrawKey dk, uint32_t k, uint64_t lo, uint64_t hi, uint64_t g_begin,
+                                               uint64_t n_groups, unsigned long long* __restrict__ win, K1Launch P) {
+    __shared__ K1QLds<12> L;
+    const int w = threadIdx.x >> 6;
+#if K1O_FORM == 0
+    if (P.flags & kK1Fast) k1_body_q<12, true, 256>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
+    else k1_body_q<12, false, 256>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
+#elif K1O_FORM == 1
+    k1_body_q<12, true, 256>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P);
+#else
+    k1_body_q<12, true, 256, true>(dk, k, lo, hi, g_begin, n_groups, win, L.q[w], L.cq[w], P, nullptr, &L.top[w]);
+#endif
 }
 
 // the product body with the workgroup-pooled tail (round 6; k1_qp keeps the per-wave tail)
@@ -591,6 +616,36 @@ int main(int argc, char** argv) {
                    us(t_full), (double)(tend - t_last_full) * 0.01);
             for (size_t u = 0; u < per_us.size(); ++u) printf("%s%d", u ? ", " : "", per_us[u]);
             printf("]}\n");
+        }
+        return 0;
+    }
+    if (argc > 1 && argv[1][0] == 'f') {  // this binary's kernel shape (K1O_FORM) over the product's plan; argv[2]: passes,
+        // argv[3]: launches ahead of them (a counter run needs no clock ramp)
+        static const char* const names[] = {"two_bodies", "fast_body", "", "fast_body_lds_rank"};
+        const int passes = argc > 2 ? atoi(argv[2]) : 3;
+        // k1_plan (rsv_elements.hip): all the steady units but 5400 .. 5400 + 6144 for the second group
+        const K1Launch P0 = stride_vals(k, lo, n, 0, n_groups, 5086);
+        int grid = 0;
+        const K1Launch PP = plan_vals(k, lo, n, 0, n_groups, 6144, P0.units > 5400 ? (P0.units - 5400) / 6144 : 0, 2, grid);
+        if (!grid) return 2;
+        auto launch = [&]() {
+            hipLaunchKernelGGL(k1_form, dim3(grid), dim3(256), 0, 0, dk, k, lo, n, 0ull, n_groups, win, PP);
+        };
+        for (int rep = 0, warm = argc > 3 ? atoi(argv[3]) : 3000; rep < warm; ++rep) launch();  // the clock ramps
+        CK(hipDeviceSynchronize());
+        for (int p = 0; p < passes; ++p) {
+            const int reps = 20;
+            CK(hipEventRecord(e0));
+            for (int rep = 0; rep < reps; ++rep) launch();
+            CK(hipEventRecord(e1));
+            CK(hipEventSynchronize(e1));
+            float ms;
+            CK(hipEventElapsedTime(&ms, e0, e1));
+            CK(hipMemset(win, 0, k * 8));
+            launch();
+            CK(hipMemcpy(got.data(), win, k * 8, hipMemcpyDeviceToHost));
+            printf("{\"mode\": \"forms\", \"form\": \"%s\", \"A\": %u, \"grid\": %d, \"pass\": %d, \"us\": %.2f, "
+                   "\"winners_match\": %s}\n", names[K1O_FORM], PP.A, grid, p, ms / reps * 1e3, got == ref ? "true" : "false");
         }
         return 0;
     }
